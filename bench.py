@@ -12,9 +12,13 @@ MLP/composite loop -> background mix).  Poses, model and occupancy are resident 
       BASELINE configs[4]: the Monte-Carlo rollout, two 800x800 renders through `run` (512 samples per ray) + UQ per simulator step,
       in the arithmetic validate.py's rollout uses (fp32: no autocast on that path) unless --dtype f16.
 
-One JSON line on rank 0; fields per the driver contract plus `roofline` (dominant kernel, HIP-event timed in a
-separate profiled pass), `cpu_baseline` (the CPU oracle on a bounded sample of the same frame, rank 0, N = 1), `parity` and `timing`
-(what the timed region looked like from the inside: per-frame completion intervals, a second repetition, one frame at a time).
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the fields of the driver contract (`ms_per_step`
+= milliseconds per timed step) and `timing` (per-frame completion intervals of the timed region).  `--full` adds the legs that take runs
+of their own: `roofline` (dominant kernel, HIP-event timed in a separate profiled pass), `cpu_baseline` (the CPU oracle on a bounded
+sample of the same frame, rank 0, N = 1), `parity`, `batched`, and under `timing` a second repetition and one frame at a time.
+
+  --dump-outputs DIR writes what the last timed step returned on rank 0 as DIR/<name>.npy (float32 / float64): the frame's image,
+  depth and last-iteration sigmas / rgbs, or the rollout's rows.  Inputs depend only on the arguments, so two builds can be compared.
 """
 import argparse
 import ctypes as C
@@ -68,7 +72,13 @@ def parse():
                    help="fp16 only: model.fused_reference_rounding (1 = the reference's c10::Half corner accumulation in the fused gather, "
                         "0 = fp32 accumulation with one rounding); default: the renderer's own default")
     p.add_argument("--no-extras", action="store_true", help="skip the untimed extra legs (second repetition, one-at-a-time, batched, parity)")
+    p.add_argument("--full", action="store_true", help="also run the untimed legs: roofline, cpu_baseline, parity, batched, repeat, "
+                   "one-at-a-time (off: set up, warm up, time the steps, print the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     if a.in_flight is None:
         a.in_flight = a.sims_per_gpu if a.workload == "rollout" else 3
     if a.dtype is None:
@@ -133,6 +143,24 @@ def host_facts():
     except OSError:
         pass
     return facts
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor / ndarray / None} -> path/<name>.npy in float32 (float64 stays float64).  Should they exceed DUMP_LIMIT_BYTES together,
+    each is replaced by the same fraction of its flattened elements, at positions drawn from a fixed seed (same shape, same positions)."""
+    import numpy as np
+    arrays = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in arrays.items() if v is not None}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = a.size * DUMP_LIMIT_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def init_ranks(args, torch, dist):
@@ -240,9 +268,11 @@ def rollout_main(args):
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         elapsed = float(mx[1])
     frames = float(tot[0])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rows": rows})
 
     # ---- separate passes on rank 0 over the poses of one simulation: how many samples does the kernel evaluate (it stops a ray once
-    #      its transmittance is below 1e-10), and how long does the dominant kernel take (HIP events around it)
+    #      its transmittance is below 1e-10; `value` needs it), and, with --full, how long does the dominant kernel take (HIP events)
     roof = evaluated_fraction = None
     if rank == 0:
         sim = RO.RolloutSimulator(model, sc.intrinsics, H, W, args.steps, seed=0, render_kwargs=kw)
@@ -266,6 +296,7 @@ def rollout_main(args):
         counted = int(stamps[13])                            # samples that carried a running ray (k_render_uniform_x16)
         nominal = len(poses) * H * W * 512
         evaluated_fraction = counted / nominal if counted else None
+    if rank == 0 and args.full:
         lib.ngp_prof_reset()
         lib.ngp_prof_enable(1)
         for p_ in poses:
@@ -291,7 +322,7 @@ def rollout_main(args):
                     "measured_with": f"{len(poses)} frames of simulation 0's poses, one at a time, HIP events around each launch (ngp_prof_*)"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and f32:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and f32:
         arm = cpu_arm_run_f32(np, torch)
         cpu = {"value": arm["all_cores"]["samples_per_s"], "unit": "samples/s", "cores": arm["all_cores"]["threads"], "kind": "port",
                "sample": f"{arm['all_cores']['rays']} of 160000 rays of one 400x400 view x 512 samples ({arm['all_cores']['seconds']} s): oracle/ngp_oracle.c "
@@ -365,6 +396,7 @@ def main():
         return (step * world + rank) % n_views
 
     pending = []
+    kept = {"step": None}                    # --dump-outputs: the render result of step kept["step"] lands in kept["out"]
 
     def render_frame(step):
         """one frame = one drop-in render call; returns (tile to exchange or None, (samples, iterations, slots), completion event)"""
@@ -372,6 +404,8 @@ def main():
         rays = get_rays(poses[v:v + 1], intr, H, W)
         # frame_width: scheduling hint of this build (ngp_render_ctx_set_frame_width); the rendered values do not depend on it
         out = model.render(rays["rays_o"], rays["rays_d"], staged=True, bg_color=1, perturb=False, frame_width=W)
+        if step == kept["step"]:
+            kept["out"] = out
         st = model.last_render_stats
         tile = torch.cat([out["image"], out["depth"].unsqueeze(-1)], -1) if collective else None
         ev = torch.cuda.Event(enable_timing=True)
@@ -456,9 +490,14 @@ def main():
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
         prewarm(pipe)
         render_steps(0, args.warmup, pipe)
+        if args.dump_outputs and rank == 0:
+            kept["step"] = args.warmup + args.steps - 1
         elapsed, (samples, iters, slots), done_ms = timed(args.warmup, args.steps, pipe)          # <- THE timed region: `value`
+        kept["step"] = None
         timing["frame_completion_interval_ms"] = intervals(done_ms)
-        if not args.no_extras:
+        if "out" in kept:
+            dump_outputs(args.dump_outputs, kept.pop("out"))
+        if args.full and not args.no_extras:
             # the same K steps a second time, and one frame at a time: what `value` is made of (not part of it)
             el2, (s2, _, _), done2 = timed(args.warmup + args.steps, args.steps, pipe)
             timing["repeat"] = {"value": round(s2 / el2 * world, 1), "ms_per_step": round(el2 / args.steps * 1e3, 3),
@@ -472,7 +511,7 @@ def main():
 
         # ---- roofline leg: per-launch HIP events around the dominant kernel (k_render_iter), separate pass
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             lib.ngp_prof_reset()
             lib.ngp_prof_enable(1)
             ray_iters = 0
@@ -503,7 +542,7 @@ def main():
 
     # ---- extra leg (rank 0, N = 1, not part of `value`): several cameras per render call, as a camera sweep may hand them over
     batched = None
-    if rank == 0 and world == 1 and args.batched_views > 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.batched_views > 1 and not args.no_extras:
         nv = args.batched_views
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
             def call(i):
@@ -531,7 +570,7 @@ def main():
 
     # ---- cpu baseline leg: the oracle on a bounded sample of view 0 (rank 0, N = 1 only)
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import driver as D
         from oracle import oracle as O
         ro, rd = D.pinhole_rays(sc.poses[view_of(0)], intr, H, W)
