@@ -367,6 +367,18 @@ NGP_API int ngp_network_density(const ngp_model* model, const float* xyzs, uint3
 NGP_API int ngp_network_density_backward(const ngp_model* model, const void* packed_weights_bwd, const float* xyzs, uint32_t M,
                                  const float* grad_sigmas, const float* grad_geo_feat, float* grad_xyzs, ngp_stream_t stream);
 
+/* The trajectory planner's collision term (nav/quad_plot.py:216-241 with validate.py:288's density_fn) in one launch: for every
+ * planned state s, its B body points go to the world (R_s b + p_s), to the NeRF's axes (@ rot), through the density half, and
+ * out[s] = mean_b sigma^2.  rot_matrix [S,3,3], pos [S,3], body [B,3], rot [3,3] (row-major, device memory) -> out [S].
+ * One workgroup per state with fixed-order sums: identical bits on every call.  No workspace. */
+NGP_API int ngp_planner_collision(const ngp_model* model, const float* rot_matrix, const float* pos, const float* body, const float* rot,
+                                  uint32_t S, uint32_t B, float* out, ngp_stream_t stream);
+/* Its vector-Jacobian product, map frozen: grad_out [S] -> grad_pos [S,3], grad_rot_matrix [S,3,3] (overwritten).
+ * packed_weights_bwd as for ngp_network_density_backward. */
+NGP_API int ngp_planner_collision_backward(const ngp_model* model, const void* packed_weights_bwd, const float* rot_matrix, const float* pos,
+                                           const float* body, const float* rot, uint32_t S, uint32_t B, const float* grad_out,
+                                           float* grad_pos, float* grad_rot_matrix, ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

@@ -82,6 +82,27 @@ class NetworkDensity(torch.autograd.Function):
         return None, ctx.fm.network_density_backward(x, g_sigma, g_geo)
 
 
+class PlannerCollision(torch.autograd.Function):
+    """The trajectory planner's collision term mean_b density_fn(body_to_world(body))[s, b] ** 2 (nav/quad_plot.py:216-241 with
+    validate.py:288's density_fn) as ONE launch forward (ngp_planner_collision) and ONE backward (ngp_planner_collision_backward)
+    -- differentiable in the states' rotations and positions, the map and the body frozen."""
+
+    @staticmethod
+    def forward(ctx, fm, rot_matrix, pos, body, rot):
+        rot_matrix, pos = rot_matrix.float().contiguous(), pos.float().contiguous()
+        body, rot = body.float().contiguous(), rot.float().contiguous()
+        out = fm.planner_collision(rot_matrix, pos, body, rot)
+        ctx.fm = fm
+        ctx.save_for_backward(rot_matrix, pos, body, rot)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rot_matrix, pos, body, rot = ctx.saved_tensors
+        g_pos, g_rot = ctx.fm.planner_collision_backward(rot_matrix, pos, body, rot, g)
+        return None, g_rot, g_pos, None, None
+
+
 class FusedModel:
     def __init__(self, net, sigma_blob, sigma_mm, color_blob, color_mm, watched, f32=False):
         from .gridencoder.grid import derived_tables
@@ -262,6 +283,29 @@ class FusedModel:
         _lib.check(_lib.lib().ngp_network_density_backward(C.byref(m), _lib.ptr(packed_bwd), _lib.ptr(xyzs), M, _lib.ptr(f32(g_sigma)),
                                                            _lib.ptr(f32(g_geo)), _lib.ptr(gx), _lib.stream()), "network_density_backward")
         return gx
+
+    def planner_collision(self, rot_matrix, pos, body, rot):
+        """rot_matrix [S,3,3], pos [S,3], body [B,3], rot [3,3] f32 contiguous -> mean_b sigma(((R_s b + p_s) @ rot))^2 [S] f32
+        (ngp_planner_collision)"""
+        self._ensure_packed()
+        S, B = rot_matrix.shape[0], body.shape[0]
+        out = torch.empty(S, dtype=torch.float32, device=rot_matrix.device)
+        _lib.check(_lib.lib().ngp_planner_collision(C.byref(self._struct(None)), _lib.ptr(rot_matrix), _lib.ptr(pos), _lib.ptr(body),
+                                                    _lib.ptr(rot), S, B, _lib.ptr(out), _lib.stream()), "planner_collision")
+        return out
+
+    def planner_collision_backward(self, rot_matrix, pos, body, rot, g):
+        """vector-Jacobian product of planner_collision, map frozen: g [S] -> (grad_pos [S,3], grad_rot_matrix [S,3,3])"""
+        self._ensure_packed()
+        packed_bwd = self._ensure_packed_bwd()
+        S, B = rot_matrix.shape[0], body.shape[0]
+        g = g.float().contiguous()
+        g_pos = torch.empty(S, 3, dtype=torch.float32, device=rot_matrix.device)
+        g_rot = torch.empty(S, 3, 3, dtype=torch.float32, device=rot_matrix.device)
+        _lib.check(_lib.lib().ngp_planner_collision_backward(C.byref(self._struct(None)), _lib.ptr(packed_bwd), _lib.ptr(rot_matrix), _lib.ptr(pos),
+                                                             _lib.ptr(body), _lib.ptr(rot), S, B, _lib.ptr(g), _lib.ptr(g_pos), _lib.ptr(g_rot),
+                                                             _lib.stream()), "planner_collision_backward")
+        return g_pos, g_rot
 
     def _pad_value(self):
         """what the network returns for the reference's zero-filled padding rows (xyz = 0, dir = 0)"""

@@ -105,6 +105,8 @@ SIGNATURES = {
     "ngp_network_forward": [C.POINTER(ModelStruct), _vp, _vp, _u32, _vp, _vp, _vp],
     "ngp_network_density": [C.POINTER(ModelStruct), _vp, _u32, _vp, _vp, _vp],
     "ngp_network_density_backward": [C.POINTER(ModelStruct), _vp, _vp, _u32, _vp, _vp, _vp, _vp],
+    "ngp_planner_collision": [C.POINTER(ModelStruct), _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
+    "ngp_planner_collision_backward": [C.POINTER(ModelStruct), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
     "ngp_render_uniform_backward_lds": [C.POINTER(ModelStruct), _u32],
     "ngp_packed_weights_bwd_bytes": [],
     "ngp_pack_weights_bwd": [C.POINTER(ModelStruct), _vp, _vp],

@@ -1246,6 +1246,159 @@ __global__ void __launch_bounds__(256) k_network_density_bwd(NetArgs na, GridLev
 }
 
 // ------------------------------------------------------------------------------------------
+// The trajectory planner's collision term (nav/quad_plot.py:216-241 through validate.py:288's density_fn): for planned state s the
+// B body points b go to the world (w = R_s b + p_s), to the NeRF's axes (x = w @ rot), through hash grid + sigma net + trunc_exp,
+// and out[s] = mean_b sigma^2.  One workgroup per state; its waves take 16-point tiles in turn, and every sum runs in a fixed order
+// (tiles of a lane, then lanes, then waves through LDS): no atomics, the same bits on every call and on every graph replay.
+// ------------------------------------------------------------------------------------------
+struct PlanArgs {
+    const float* rot_matrix;   // [S,3,3]
+    const float* pos;          // [S,3]
+    const float* body;         // [B,3]
+    const float* rot;          // [3,3]
+    uint32_t S, B;
+};
+
+constexpr uint32_t kPlanThreads = 256;
+
+__device__ __forceinline__ void plan_load_rot(const PlanArgs& pa, float (&rot)[9]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) rot[i] = pa.rot[i];
+}
+
+// body point b of state s: its world point w and the density query's input x = w @ rot
+__device__ __forceinline__ void plan_point(const PlanArgs& pa, const float (&rot)[9], uint32_t s, uint32_t b, float (&bp)[3], float (&x)[3]) {
+    const float* R = pa.rot_matrix + (size_t)s * 9;
+    const float* p = pa.pos + (size_t)s * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) bp[k] = pa.body[(size_t)b * 3 + k];
+    float w[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) w[i] = R[3 * i] * bp[0] + R[3 * i + 1] * bp[1] + R[3 * i + 2] * bp[2] + p[i];
+#pragma unroll
+    for (int j = 0; j < 3; j++) x[j] = w[0] * rot[j] + w[1] * rot[3 + j] + w[2] * rot[6 + j];
+}
+
+// sum of lanes 0..15 (every other lane holds 0), complete in lane 0
+__device__ __forceinline__ float plan_lane_sum(float v) {
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <class NET>
+__global__ void __launch_bounds__(kPlanThreads) k_planner_collision(NetArgs na, GridLevels lv, PlanArgs pa, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t w_bytes = NET::w_bytes(na);
+    const char* Wlds = smem;
+    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes);
+    float* red = reinterpret_cast<float*>(smem + w_bytes + sizeof(LevelTab));          // [waves]
+    stage_block(na, lv, smem, lt, w_bytes);
+    float rot[9];
+    plan_load_rot(pa, rot);
+    const uint32_t s = blockIdx.x;
+    const uint32_t lane = threadIdx.x & 63, c = lane & 15, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const uint32_t n_tiles = (pa.B + 15) / 16;
+    float acc = 0.0f;
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const uint32_t b = tile * 16 + c;
+        const bool valid = b < pa.B;
+        float bp[3], x[3];
+        plan_point(pa, rot, s, valid ? b : pa.B - 1, bp, x);
+        float sg;
+        typename NET::geo_t s16[4];
+        NET::density(na, Wlds, *lt, lane, x[0], x[1], x[2], sg, s16);
+        if (valid && lane < 16) acc += sg * sg;          // (sigma is meaningful in the lanes of quarter 0)
+    }
+    acc = plan_lane_sum(lane < 16 ? acc : 0.0f);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float sum = 0.0f;
+        for (uint32_t w = 0; w < n_waves; w++) sum += red[w];
+        out[s] = sum / (float)pa.B;
+    }
+}
+
+// g [S] = dL/d out -> grad_pos [S,3], grad_rot_matrix [S,3,3] (overwritten).  The forward again with kept activations, then per point
+// dL/d sigma = (g / B) * (2 sigma) (mean, then pow), trunc_exp's backward, the sigma net and hash grid (NET::density_vjp, as
+// k_network_density_bwd), d x / d w = rot^T and d w / d (p, R) = (1, b^T).
+template <class NET>
+__global__ void __launch_bounds__(kPlanThreads) k_planner_collision_bwd(NetArgs na, GridLevels lv, const char* __restrict__ packed_bwd,
+                                                                        PlanArgs pa, const float* __restrict__ g, float* __restrict__ grad_pos,
+                                                                        float* __restrict__ grad_rot_matrix) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t w_bytes = NET::w_bytes(na);
+    const size_t ws_bytes = NET::kF32 ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;   // sigma net's transposed fragments
+    const char* Wlds = smem;
+    char* Wb = smem + w_bytes;
+    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes + ws_bytes);
+    float* red = reinterpret_cast<float*>(smem + w_bytes + ws_bytes + sizeof(LevelTab));   // [waves][12]
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(packed_bwd);
+        uint4* dst = reinterpret_cast<uint4*>(Wb);
+        for (uint32_t i = threadIdx.x; i < ws_bytes / 16; i += blockDim.x) dst[i] = src[i];
+    }
+    stage_block(na, lv, smem, lt, w_bytes);
+    float rot[9];
+    plan_load_rot(pa, rot);
+    const uint32_t s = blockIdx.x;
+    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const uint32_t n_tiles = (pa.B + 15) / 16;
+    const float g_mean = g[s] / (float)pa.B;
+    float acc[12];                                       // d/d p (3), then d/d R row-major (9)
+#pragma unroll
+    for (int i = 0; i < 12; i++) acc[i] = 0.0f;
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const uint32_t b = tile * 16 + c;
+        const bool valid = b < pa.B;
+        float bp[3], x[3];
+        plan_point(pa, rot, s, valid ? b : pa.B - 1, bp, x);
+        typename NET::Tape tape;
+        typename NET::geo_t s16[4];
+        NET::density_tape(na, Wlds, *lt, lane, x[0], x[1], x[2], tape, s16);
+        f32x4 gso = {0, 0, 0, 0};
+        if (valid && q == 0) {
+            const float h = (float)s16[0];
+            const float sigma = expf(h);
+            gso[0] = (g_mean * (2.0f * sigma)) * expf(fminf(15.0f, fmaxf(-15.0f, h)));
+        }
+        float gx[3];
+        NET::density_vjp(na, Wb, lane, tape, gso, gx);
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            gx[d] += __shfl_xor(gx[d], 16, 64);
+            gx[d] += __shfl_xor(gx[d], 32, 64);
+        }
+        if (valid && lane < 16) {
+            float gxr[3], gw[3];
+#pragma unroll
+            for (int d = 0; d < 3; d++) gxr[d] = gx[d] * na.inv_two_bound;
+#pragma unroll
+            for (int i = 0; i < 3; i++) gw[i] = rot[3 * i] * gxr[0] + rot[3 * i + 1] * gxr[1] + rot[3 * i + 2] * gxr[2];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                acc[i] += gw[i];
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc[3 + 3 * i + k] += gw[i] * bp[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const float v = plan_lane_sum(lane < 16 ? acc[i] : 0.0f);
+        if (lane == 0) red[wave * 12 + i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        float sum = 0.0f;
+        for (uint32_t w = 0; w < n_waves; w++) sum += red[w * 12 + threadIdx.x];
+        if (threadIdx.x < 3) grad_pos[(size_t)s * 3 + threadIdx.x] = sum;
+        else grad_rot_matrix[(size_t)s * 9 + threadIdx.x - 3] = sum;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // NeRFRenderer.run, uniform sampling without upsampling (nerf/renderer.py:125-258): the path validate.py -O executes
 // (cuda_ray = False, num_steps = 512).  One wave walks one ray 16 samples at a time: positions from the linspace table,
 // fused hash-grid + sigma net, in-wave transmittance scan (alphas * cumprod(1 - alphas + 1e-15), :206-210), colour net only
@@ -3925,6 +4078,54 @@ int ngp_network_density_backward(const ngp_model* model, const void* packed_weig
         k_network_density_bwd<NET><<<blocks, 256, lds, s>>>(na, lv, (const char*)packed_weights_bwd, xyzs, M, grad_sigmas, grad_geo_feat, grad_xyzs);
     });
     return check_launch("network_density_backward");
+}
+
+int ngp_planner_collision(const ngp_model* model, const float* rot_matrix, const float* pos, const float* body, const float* rot, uint32_t S,
+                          uint32_t B, float* out, ngp_stream_t stream) {
+    if (S == 0) return NGP_OK;
+    NGP_REQUIRE(rot_matrix && pos && body && rot && out, "planner_collision: null pointer");
+    NGP_REQUIRE(B > 0, "planner_collision: no body points");
+    NGP_REQUIRE(model && model->packed_weights, "planner_collision: model->packed_weights is NULL (ngp_pack_weights fills it)");
+    hipStream_t s = (hipStream_t)stream;
+    NetArgs na;
+    GridLevels lv;
+    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
+    if (rc) return rc;
+    const size_t lds = weights_bytes(na) + sizeof(LevelTab) + (kPlanThreads / 64) * sizeof(float);
+    NGP_REQUIRE(lds <= 96 * 1024, "planner_collision: the packed weights need %zu bytes of LDS", lds);
+    const PlanArgs pa{rot_matrix, pos, body, rot, S, B};
+    ProfScope prof("planner_collision", s, (size_t)S * B);
+    NGP_WITH_NET(net_variant(na, lv), {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_planner_collision<NET>), 96 * 1024);
+        k_planner_collision<NET><<<S, kPlanThreads, lds, s>>>(na, lv, pa, out);
+    });
+    return check_launch("planner_collision");
+}
+
+int ngp_planner_collision_backward(const ngp_model* model, const void* packed_weights_bwd, const float* rot_matrix, const float* pos,
+                                   const float* body, const float* rot, uint32_t S, uint32_t B, const float* grad_out, float* grad_pos,
+                                   float* grad_rot_matrix, ngp_stream_t stream) {
+    if (S == 0) return NGP_OK;
+    NGP_REQUIRE(rot_matrix && pos && body && rot && grad_out && grad_pos && grad_rot_matrix, "planner_collision_backward: null pointer");
+    NGP_REQUIRE(B > 0, "planner_collision_backward: no body points");
+    NGP_REQUIRE(model && model->packed_weights && packed_weights_bwd,
+                "planner_collision_backward: packed weights missing (ngp_pack_weights / ngp_pack_weights_bwd)");
+    hipStream_t s = (hipStream_t)stream;
+    NetArgs na;
+    GridLevels lv;
+    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
+    if (rc) return rc;
+    NGP_REQUIRE(bwd_shape_ok(na), "planner_collision_backward: the fp32 form supports at most 1 hidden matmul in the sigma net (got %u)", na.sig_mm);
+    const size_t ws = na.f32() ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;
+    const size_t lds = weights_bytes(na) + ws + sizeof(LevelTab) + (kPlanThreads / 64) * 12 * sizeof(float);
+    NGP_REQUIRE(lds <= 160 * 1024, "planner_collision_backward: LDS budget exceeded (%zu bytes)", lds);
+    const PlanArgs pa{rot_matrix, pos, body, rot, S, B};
+    ProfScope prof("planner_collision_backward", s, (size_t)S * B);
+    NGP_WITH_NET(net_variant(na, lv), {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_planner_collision_bwd<NET>), 160 * 1024);
+        k_planner_collision_bwd<NET><<<S, kPlanThreads, lds, s>>>(na, lv, (const char*)packed_weights_bwd, pa, grad_out, grad_pos, grad_rot_matrix);
+    });
+    return check_launch("planner_collision_backward");
 }
 
 int ngp_network_forward(const ngp_model* model, const float* xyzs, const float* dirs, uint32_t M, float* sigmas, float* rgbs,

@@ -35,7 +35,9 @@ class GraphedStep:
     returns the captured outputs -- the same tensor objects every time: clone what must survive the next call.
     """
 
-    def __init__(self, fn, inputs, warmup=3, device=None):
+    def __init__(self, fn, inputs, warmup=3, device=None, capture_error_mode=None):
+        """capture_error_mode: passed on to torch.cuda.graph when given ("thread_local": other host threads may keep launching and
+        allocating while this one captures -- the simulations a FramePipeline runs side by side)"""
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedStep needs a GPU: a HIP graph is captured from a live stream")
         self.fn = fn
@@ -50,7 +52,8 @@ class GraphedStep:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        kw = {} if capture_error_mode is None else {"capture_error_mode": capture_error_mode}
+        with torch.cuda.graph(self.graph, **kw):
             self.outputs = fn(*self.inputs)
         self.replays = 0
 

@@ -13,10 +13,16 @@ validation/simulators/NerfSimulator.py:66-157), reduced to the part that is this
     one CSV row                                             MonteCarlo.py:58-116
 
 Not here (out of scope): the Blender subprocess that renders the ground-truth image, the SIFT / iNeRF state
-estimator, the A* + Adam planner and the pre-computed SDF file.  Their places are taken by fixed, documented stand-ins so that the
-rollout still produces every column of the reference's CSV: the planner's action is hover thrust (zero torque) with the
-straight-line velocity from `start_pos` to `end_pos` as the initial condition (the path the A* initialisation approximates), and
-the collision check looks the four interpolated states up in the analytic occupancy of the synthetic scene instead of `sdf.npy`.
+estimator and the pre-computed SDF file.  Their places are taken by fixed, documented stand-ins so that the rollout still produces
+every column of the reference's CSV: the collision check looks the four interpolated states up in the analytic occupancy of the
+synthetic scene instead of `sdf.npy`.  The A* + Adam planner (nav.Planner) is opt-in (`planner_cfg`, built by planner_config()):
+    reset      Planner + a_star_init + learn_init under seed_everything(seed) (NerfSimulator.py:182-214), computed ONCE per rollout
+               and copied into every simulation -- the stand-in for the reference's on-disk `cached/` plans;
+    each step  action = get_next_action() (NerfSimulator.py:82); after dynamics and noise update_state(state_est) and
+               learn_update(k) (:126-129), where state_est is the TRUE noisy state as an 18-vector (:120) -- the stand-in for the
+               estimator.  The simulation starts at rest in start_pos (validate.py:224-233) and steps by the plan's dt.
+Without it (`planner_cfg=None`, the default) the planner's action is hover thrust (zero torque) with the straight-line velocity
+from `start_pos` to `end_pos` as the initial condition (the path the A* initialisation approximates).
 
 Simulations are independent given their seed -- the reference's own CEM draws with `manual_seed(noise_seed + simulationNumber)`
 (validation/distributions/SeedableMultivariateNormal.py:19-22) -- so they shard over ranks with no data-path collective; the rows are
@@ -40,6 +46,13 @@ ENV = {
     "start_pos": [-0.75, -0.235, 0.25], "end_pos": [0.2, -0.74, 0.3], "start_R": [0.0, 0.0, 0.0],      # :32-35
     "T_final": 2.0,                                                                                    # :37
 }
+# envConfig.json's agent_cfg / planner_cfg values the planner adds (validate.py:169-256)
+PLANNER_ENV = {
+    "body_lims": [[-0.05, 0.05], [-0.05, 0.05], [-0.02, 0.02]], "body_nbins": [10, 10, 5],                          # :17-22
+    "end_R": [0.0, 0.0, 0.0], "steps": 12, "planner_lr": 0.001, "epochs_init": 1000, "fade_out_epoch": 0,            # :36-45
+    "fade_out_sharpness": 10, "epochs_update": 250,
+}
+PLANNER_ROT = [[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]    # validate.py:283: Blender -> NeRF axes of density_fn
 ROW_WIDTH = 24   # MonteCarlo.py:95-116: sim, step, noise x12, sdf value, xyz, step loglik, cumulative loglik, reward, sigma, collided (+ ever collided)
 PENALTY = 36.0   # NerfSimulator.py:171
 
@@ -54,7 +67,7 @@ def rot_x(phi):
 
 def skew(v):
     """math_utils.py:167-178 (and :92-102): vector [...,3] -> skew-symmetric [...,3,3]"""
-    S = torch.zeros(*v.shape[:-1], 3, 3, dtype=v.dtype)
+    S = torch.zeros(*v.shape[:-1], 3, 3, dtype=v.dtype, device=v.device)
     S[..., 0, 1], S[..., 0, 2] = -v[..., 2], v[..., 1]
     S[..., 1, 0], S[..., 1, 2] = v[..., 2], -v[..., 0]
     S[..., 2, 0], S[..., 2, 1] = -v[..., 1], v[..., 0]
@@ -66,7 +79,7 @@ def vec_to_rot_matrix(rot_vec):
     angle = torch.linalg.vector_norm(rot_vec, dim=-1, keepdim=True)
     S = skew(rot_vec / (1e-10 + angle))
     angle = angle[..., None]
-    return torch.eye(3, dtype=rot_vec.dtype) + torch.sin(angle) * S + (1 - torch.cos(angle)) * (S @ S)
+    return torch.eye(3, dtype=rot_vec.dtype, device=rot_vec.device) + torch.sin(angle) * S + (1 - torch.cos(angle)) * (S @ S)
 
 
 def rot_matrix_to_vec(R, eps=1e-7):
@@ -156,11 +169,56 @@ def initial_state(n_steps):
     return s
 
 
+def planner_config(device, **overrides):
+    """validate.py:224-256's planner_cfg from ENV / PLANNER_ENV: start and end 18-vectors (zero rates, R from vec_to_rot_matrix)
+    on `device`, and the scalars.  `overrides` replace entries (e.g. epochs_init, epochs_update)."""
+    rates = torch.zeros(3)
+    start_R = vec_to_rot_matrix(torch.tensor(ENV["start_R"]))
+    end_R = vec_to_rot_matrix(torch.tensor(PLANNER_ENV["end_R"]))
+    start_state = torch.cat([torch.tensor(ENV["start_pos"]).float(), rates, start_R.reshape(-1), rates], dim=0)
+    end_state = torch.cat([torch.tensor(ENV["end_pos"]).float(), rates, end_R.reshape(-1), rates], dim=0)
+    cfg = {"T_final": ENV["T_final"], "steps": PLANNER_ENV["steps"], "lr": PLANNER_ENV["planner_lr"],
+           "epochs_init": PLANNER_ENV["epochs_init"], "fade_out_epoch": PLANNER_ENV["fade_out_epoch"],
+           "fade_out_sharpness": PLANNER_ENV["fade_out_sharpness"], "epochs_update": PLANNER_ENV["epochs_update"],
+           "start_state": start_state.to(device), "end_state": end_state.to(device),
+           "I": torch.tensor(ENV["I"]).float().to(device), "g": ENV["g"], "mass": ENV["mass"],
+           "body": np.array(PLANNER_ENV["body_lims"]), "nbins": PLANNER_ENV["body_nbins"]}
+    cfg.update(overrides)
+    return cfg
+
+
+def initial_plan(model, planner_cfg, seed):
+    """NerfSimulator.reset's planner (NerfSimulator.py:188-214): seed_everything(seed), Planner, a_star_init, learn_init -- fp32
+    outside autocast, density_fn = validate.py:288's query of `model` (nav.density_query)"""
+    from .nav import Planner, density_query
+    from .nerf.utils import seed_everything
+    device = planner_cfg["start_state"].device
+    seed_everything(seed)
+    with torch.autocast("cuda", enabled=False):
+        plan = Planner(planner_cfg["start_state"], planner_cfg["end_state"], planner_cfg,
+                       density_query(model, torch.tensor(PLANNER_ROT, device=device)))
+        plan.a_star_init()
+        plan.learn_init()
+    return plan
+
+
+def copy_plan(plan):
+    """an independent planner continuing from `plan` (its own states and initial acceleration; the rest is read-only)"""
+    import copy
+    p = copy.copy(plan)
+    p.states = plan.states.detach().clone().requires_grad_(True)
+    p.initial_accel = plan.initial_accel.detach().clone().requires_grad_(True)
+    return p
+
+
 class RolloutSimulator:
     """One simulation = `steps` calls of step(); mirrors NerfSimulator.step's use of the renderer (two full-frame renders and the
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
-    def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2):
+    def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
+                 planner_cfg=None, initial_plan=None):
+        """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
+        initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout)."""
         from .nerf.utils import get_rays
         from .uncertainty.quantification.gaussian_approximation_density_uncertainty import GaussianApproximationDensityUncertainty
         self.model, self.intrinsics, self.H, self.W, self.steps, self.seed = model, intrinsics, H, W, steps, seed
@@ -171,6 +229,9 @@ class RolloutSimulator:
         self.n_interp = num_interpolated_points
         self.renders_per_step = renders_per_step
         self.dt = ENV["T_final"] / steps                       # NerfSimulator.py:40
+        self.planner_cfg, self._initial_plan, self.planner = planner_cfg, initial_plan, None
+        if planner_cfg is not None:
+            self.dt = planner_cfg["T_final"] / planner_cfg["steps"]   # agent_cfg['dt'] (NerfSimulator.py:36)
         self.mean = torch.tensor(ENV["mpc_noise_mean"], dtype=torch.float32)
         self.std = torch.tensor(ENV["mpc_noise_std"], dtype=torch.float32)
         self._get_rays, self._UQ = get_rays, GaussianApproximationDensityUncertainty
@@ -198,8 +259,32 @@ class RolloutSimulator:
         return torch.Generator().manual_seed(self.seed + sim)
 
     def action(self, k, state):
-        """stand-in for Planner.get_next_action (nav/quad_plot.py:211-214): hover thrust, zero torque"""
+        """Planner.get_next_action (nav/quad_plot.py:211-214, NerfSimulator.py:82) with a planner; else the stand-in: hover thrust,
+        zero torque"""
+        if self.planner is not None:
+            with torch.no_grad(), torch.autocast("cuda", enabled=False):      # the plan is fp32 (the render may run under autocast)
+                return self.planner.get_next_action().detach().cpu()
         return torch.tensor([ENV["mass"] * ENV["g"], 0.0, 0.0, 0.0])
+
+    def reset_planner(self):
+        """NerfSimulator.reset's planner (a copy of the rollout's initial plan), or None without planner_cfg"""
+        if self.planner_cfg is None:
+            self.planner = None
+            return
+        if self._initial_plan is None:
+            self._initial_plan = initial_plan(self.model, self.planner_cfg, self.seed)
+        self.planner = copy_plan(self._initial_plan)
+
+    def replan(self, k, state):
+        """NerfSimulator.py:120-129: the state estimate as an 18-vector (stand-in: the true noisy state), update_state, learn_update"""
+        if self.planner is None:
+            return
+        dev = self.planner.device
+        s = state.to(dev)
+        state_est = torch.cat([s[:6], vec_to_rot_matrix(s[6:9]).reshape(-1), s[9:]], dim=-1)
+        with torch.autocast("cuda", enabled=False):
+            self.planner.update_state(state_est)
+            self.planner.learn_update(k)
 
     def observe(self, pose):
         """NerfSimulator.py:100-110: the NeRF render of the true pose, the same frame again for the UQ -> sigma_d_opt"""
@@ -215,18 +300,24 @@ class RolloutSimulator:
     def run(self, sim):
         """-> rows [n_steps_run, ROW_WIDTH] float64 (a collision ends the simulation, MonteCarlo.py:88-93)"""
         gen = self.make_generator(sim)
+        self.reset_planner()
         state = initial_state(self.steps)
+        if self.planner is not None:                           # at rest in start_pos (validate.py:224-233, NerfSimulator.py:30-33)
+            state[3:6] = 0.0
         history = [state.numpy().astype(np.float64)]
         rows, reward, cumulative = [], 0.0, 0.0
-        self.poses = []
+        self.poses, self.actions = [], []
         for k in range(self.steps):
             std = self.std + (0.01 * self.std) * reward        # MonteCarlo.py:49-51
             noise = torch.normal(self.mean, std, generator=gen)
-            state = drone_dynamics(state, self.action(k, state), self.dt) + noise          # agent_helpers.py:47-56
+            action = self.action(k, state)
+            self.actions.append(action)
+            state = drone_dynamics(state, action, self.dt) + noise          # agent_helpers.py:47-56
             history.append(state.numpy().astype(np.float64))
             pose = camera_pose(state)
             self.poses.append(pose)
             sigma_d = self.observe(pose)
+            self.replan(k, state)
             # linear interpolation of the true states, last `n_interp` points checked (NerfSimulator.py:92-97,131-155)
             hist = np.stack(history)
             x = np.arange(hist.shape[0])
@@ -249,16 +340,19 @@ class RolloutSimulator:
 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
-                render_kwargs=None, autocast=True, gather=True, renders_per_step=2):
+                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
-    `gather`, else this rank's -- and a dict of this rank's counters)."""
+    `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
+    reference's planner steers every simulation; its initial plan is computed once here)."""
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
     counters = {"frames": 0, "simulations": len(sims), "steps": 0}
+    plan0 = initial_plan(model, planner_cfg, seed) if planner_cfg is not None and sims else None
 
     def one(sim):
-        sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step)
+        sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
+                                   planner_cfg=planner_cfg, initial_plan=plan0)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
