@@ -379,6 +379,27 @@ NGP_API int ngp_planner_collision_backward(const ngp_model* model, const void* p
                                            const float* body, const float* rot, uint32_t S, uint32_t B, const float* grad_out,
                                            float* grad_pos, float* grad_rot_matrix, ngp_stream_t stream);
 
+/* The density behind the rollout's collision map (nerfsafetyvalidation_amd/collision.py; the reference marks mesh vertices in Blender
+ * instead, validation/utils/createCollisionMap.py).  For cell (i, j, k) of an X x Y x Z box and sub-sample (a, b, c) in [0, s)^3 the
+ * world point is p_x = start_x + ((float)i + ((float)a + 0.5f) / (float)s) / granularity (likewise y, z; fp32, IEEE division, no
+ * contraction), mapped to the NeRF's axes as x[j] = p0 * rot[j] + p1 * rot[3 + j] + p2 * rot[6 + j] (rot [3,3] row-major).
+ * out_max_sigma [X,Y,Z] (C order, device) = the largest raw sigma (trunc_exp output) over the s^3 points, each bit-identical to
+ * ngp_network_density's on the same fp32 point; fp16 or fp32 network (ngp_model::precision).  start_host [3] and rot_host [9] are
+ * host memory.  1 <= s <= 16, X * Y * Z < 2^31.  No workspace. */
+NGP_API int ngp_cell_max_density(const ngp_model* model, const float* start_host, float granularity, uint32_t X, uint32_t Y, uint32_t Z,
+                                 uint32_t s, const float* rot_host, float* out_max_sigma, ngp_stream_t stream);
+
+/* Exact squared Euclidean distance transform of a C-order occupancy map: occupied uint8 [X,Y,Z] (non-zero = occupied) ->
+ * d2 int32 [X,Y,Z] = the squared distance, in cells, from every cell to the nearest occupied cell (0 on occupied cells):
+ * scipy.ndimage.distance_transform_edt(~map) ** 2 of validation/utils/createSDF.py, in integers.  A map with no occupied cell gives
+ * NGP_EDT_INF in every cell (scipy measures from a phantom background outside the array there).  Three separable passes, integer
+ * arithmetic only: the same bits on every call.  Every dimension in [1, 16384], X * Y * Z < 2^31.  workspace:
+ * ngp_edt_sq_workspace(X, Y, Z) bytes, 4-byte aligned (NGP_EWORKSPACE when smaller). */
+#define NGP_EDT_INF 0x7fffffff
+NGP_API size_t ngp_edt_sq_workspace(uint32_t X, uint32_t Y, uint32_t Z);
+NGP_API int ngp_edt_sq(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, int32_t* d2, void* workspace, size_t workspace_bytes,
+                       ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

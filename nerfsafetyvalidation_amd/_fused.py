@@ -258,6 +258,19 @@ class FusedModel:
         _lib.check(_lib.lib().ngp_network_density(C.byref(m), _lib.ptr(xyzs), M, _lib.ptr(sigmas), _lib.ptr(geo), _lib.stream()), "network_density")
         return (sigmas, geo) if want_geo else sigmas
 
+    def cell_max_density(self, start, granularity, shape, samples_per_axis, rot):
+        """the collision map's density (ngp_cell_max_density): the largest raw sigma over samples_per_axis^3 points of every cell of
+        the box start [3] (host floats), granularity (cells per metre), shape (X, Y, Z), the points in the NeRF's axes as p @ rot
+        (rot [3,3], host) -> [X, Y, Z] f32"""
+        self._ensure_packed()
+        X, Y, Z = (int(n) for n in shape)
+        out = torch.empty(X, Y, Z, dtype=torch.float32, device=self.device)
+        st = (C.c_float * 3)(*[float(v) for v in start])
+        r = (C.c_float * 9)(*[float(v) for v in torch.as_tensor(rot, dtype=torch.float32).reshape(9).tolist()])
+        _lib.check(_lib.lib().ngp_cell_max_density(C.byref(self._struct(None)), st, float(granularity), X, Y, Z, int(samples_per_axis), r,
+                                                   _lib.ptr(out), _lib.stream()), "cell_max_density")
+        return out
+
     def _ensure_packed_bwd(self):
         """the transposed weights as MFMA fragments (ngp_pack_weights_bwd), once per snapshot"""
         if self._packed_bwd is None:

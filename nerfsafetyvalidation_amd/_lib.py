@@ -17,6 +17,7 @@ SO_PATH = os.environ.get("NGP_HIP_LIB", os.path.join(_HERE, "libngp_hip.so"))   
 
 NGP_F32, NGP_F16 = 0, 1
 NGP_PREC_F16, NGP_PREC_F32, NGP_PREC_F16_REF = 0, 1, 2          # ngp_model::precision
+NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
 
 _vp, _u32, _f32, _int, _sz = C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_size_t
 
@@ -107,6 +108,9 @@ SIGNATURES = {
     "ngp_network_density_backward": [C.POINTER(ModelStruct), _vp, _vp, _u32, _vp, _vp, _vp, _vp],
     "ngp_planner_collision": [C.POINTER(ModelStruct), _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "ngp_planner_collision_backward": [C.POINTER(ModelStruct), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
+    "ngp_cell_max_density": [C.POINTER(ModelStruct), _vp, C.c_float, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
+    "ngp_edt_sq_workspace": [_u32, _u32, _u32],
+    "ngp_edt_sq": [_vp, _u32, _u32, _u32, _vp, _vp, _sz, _vp],
     "ngp_render_uniform_backward_lds": [C.POINTER(ModelStruct), _u32],
     "ngp_packed_weights_bwd_bytes": [],
     "ngp_pack_weights_bwd": [C.POINTER(ModelStruct), _vp, _vp],
@@ -136,7 +140,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_occupancy_lin_bytes": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz}
 
 _lib = None
 

@@ -1192,6 +1192,58 @@ __global__ void __launch_bounds__(256) k_network_density(NetArgs na, GridLevels 
     }
 }
 
+// The collision map's density (collision.py, occupancy_from_density): for cell (i, j, k) of an X x Y x Z box the s^3 sub-sample points
+// p = start + (cell + (sub + 0.5) / s) / granularity (fp32, IEEE division, no contraction), in the NeRF's axes x = p @ rot as
+// plan_point forms them, through the density half -> out[i, j, k] = the largest raw sigma.  Each lane of a 16-point tile owns one
+// cell and walks its sub-samples with a running max: no cross-lane reduction, no atomics, and every sigma is the one
+// k_network_density computes for the same fp32 point.
+struct CellArgs {
+    float start[3];
+    float granularity;
+    float rot[9];
+    uint32_t X, Y, Z, s;
+};
+
+__device__ __forceinline__ float cell_coord(float start, uint32_t cell, uint32_t sub, float s, float g) {
+    return start + ((float)cell + ((float)sub + 0.5f) / s) / g;
+}
+
+template <class NET>
+__global__ void __launch_bounds__(256) k_cell_max_density(NetArgs na, GridLevels lv, CellArgs ca, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const char* Wlds = smem;
+    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
+    stage_block(na, lv, smem, lt, NET::w_bytes(na));
+    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t M = ca.X * ca.Y * ca.Z;
+    const uint32_t n_tiles = (M + 15) / 16;
+    const float fs = (float)ca.s;
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const uint32_t m = tile * 16 + c;
+        const uint32_t mm = m < M ? m : M - 1;
+        const uint32_t k = mm % ca.Z, j = (mm / ca.Z) % ca.Y, i = mm / (ca.Z * ca.Y);
+        float mx = 0.0f;
+        for (uint32_t a = 0; a < ca.s; a++) {
+            const float w0 = cell_coord(ca.start[0], i, a, fs, ca.granularity);
+            for (uint32_t b = 0; b < ca.s; b++) {
+                const float w1 = cell_coord(ca.start[1], j, b, fs, ca.granularity);
+                for (uint32_t e = 0; e < ca.s; e++) {
+                    const float w2 = cell_coord(ca.start[2], k, e, fs, ca.granularity);
+                    float x[3];
+#pragma unroll
+                    for (int d = 0; d < 3; d++) x[d] = w0 * ca.rot[d] + w1 * ca.rot[3 + d] + w2 * ca.rot[6 + d];
+                    float sg;
+                    typename NET::geo_t s16[4];
+                    NET::density(na, Wlds, *lt, lane, x[0], x[1], x[2], sg, s16);
+                    mx = (a | b | e) == 0 ? sg : fmaxf(mx, sg);
+                }
+            }
+        }
+        if (lane < 16 && m < M) out[m] = mx;
+    }
+}
+
 // Vector-Jacobian product of the density half with respect to the POINTS, map frozen: what the trajectory planner differentiates
 // (nav/quad_plot.py:223-249: density_fn on S x 500 body points, 250 Adam steps per simulator step).  Upstream gradients of sigma [M]
 // and (optional) of the geometry features [M, 15] -> grad_xyzs [M, 3].  One pass: forward with kept activations, trunc_exp backward
@@ -4054,6 +4106,37 @@ int ngp_network_density(const ngp_model* model, const float* xyzs, uint32_t M, f
         k_network_density<NET><<<blocks, 256, lds, s>>>(na, lv, xyzs, M, sigmas, geo_feat);
     });
     return check_launch("network_density");
+}
+
+int ngp_cell_max_density(const ngp_model* model, const float* start_host, float granularity, uint32_t X, uint32_t Y, uint32_t Z, uint32_t s,
+                         const float* rot_host, float* out_max_sigma, ngp_stream_t stream) {
+    NGP_REQUIRE(start_host && rot_host && out_max_sigma, "cell_max_density: null pointer");
+    NGP_REQUIRE(model && model->packed_weights, "cell_max_density: model->packed_weights is NULL (ngp_pack_weights fills it)");
+    NGP_REQUIRE(s >= 1 && s <= 16, "cell_max_density: 1 <= samples per axis <= 16 (got %u)", s);
+    NGP_REQUIRE(granularity > 0.0f, "cell_max_density: granularity must be > 0");
+    const uint64_t M = (uint64_t)X * Y * Z;
+    NGP_REQUIRE(M < ((uint64_t)1 << 31), "cell_max_density: X * Y * Z must be < 2^31");
+    if (M == 0) return NGP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    NetArgs na;
+    GridLevels lv;
+    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
+    if (rc) return rc;
+    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
+    NGP_REQUIRE(lds <= 96 * 1024, "cell_max_density: the packed weights need %zu bytes of LDS", lds);
+    CellArgs ca;
+    for (int d = 0; d < 3; d++) ca.start[d] = start_host[d];
+    for (int d = 0; d < 9; d++) ca.rot[d] = rot_host[d];
+    ca.granularity = granularity;
+    ca.X = X; ca.Y = Y; ca.Z = Z; ca.s = s;
+    uint32_t blocks = div_up(div_up((uint32_t)M, 16), 4);
+    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
+    ProfScope prof("cell_max_density", st, (double)M * s * s * s);
+    NGP_WITH_NET(net_variant(na, lv), {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_cell_max_density<NET>), 96 * 1024);
+        k_cell_max_density<NET><<<blocks, 256, lds, st>>>(na, lv, ca, out_max_sigma);
+    });
+    return check_launch("cell_max_density");
 }
 
 int ngp_network_density_backward(const ngp_model* model, const void* packed_weights_bwd, const float* xyzs, uint32_t M, const float* grad_sigmas,

@@ -12,10 +12,13 @@ validation/simulators/NerfSimulator.py:66-157), reduced to the part that is this
     reward    = clip(loglik(noise) - 36 * sigma_d, -72, 36) NerfSimulator.py:159-181
     one CSV row                                             MonteCarlo.py:58-116
 
-Not here (out of scope): the Blender subprocess that renders the ground-truth image, the SIFT / iNeRF state
-estimator and the pre-computed SDF file.  Their places are taken by fixed, documented stand-ins so that the rollout still produces
-every column of the reference's CSV: the collision check looks the four interpolated states up in the analytic occupancy of the
-synthetic scene instead of `sdf.npy`.  The A* + Adam planner (nav.Planner) is opt-in (`planner_cfg`, built by planner_config()):
+Not here (out of scope): the Blender subprocess that renders the ground-truth image and the SIFT / iNeRF state
+estimator.  Their places are taken by fixed, documented stand-ins so that the rollout still produces every column of the
+reference's CSV.  The signed distance field is opt-in (`sdf`, a collision.SignedDistanceField: built on the GPU from the NeRF's
+density, or the reference's own `sdf.npy` through from_array): each interpolated state is looked up as NerfSimulator.py:131-147
+does -- the value starts at 9999, a point outside the field keeps the previous value, the first collision ends the check.
+Without it (`sdf=None`, the default) the stand-in looks the four interpolated states up in the analytic occupancy of the
+synthetic scene (scene_collision: 0 inside, 9999 outside).  The A* + Adam planner (nav.Planner) is opt-in (`planner_cfg`, built by planner_config()):
     reset      Planner + a_star_init + learn_init under seed_everything(seed) (NerfSimulator.py:182-214), computed ONCE per rollout
                and copied into every simulation -- the stand-in for the reference's on-disk `cached/` plans;
     each step  action = get_next_action() (NerfSimulator.py:82); after dynamics and noise update_state(state_est) and
@@ -216,9 +219,10 @@ class RolloutSimulator:
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
-                 planner_cfg=None, initial_plan=None):
+                 planner_cfg=None, initial_plan=None, sdf=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
-        initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout)."""
+        initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
+        sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up."""
         from .nerf.utils import get_rays
         from .uncertainty.quantification.gaussian_approximation_density_uncertainty import GaussianApproximationDensityUncertainty
         self.model, self.intrinsics, self.H, self.W, self.steps, self.seed = model, intrinsics, H, W, steps, seed
@@ -230,6 +234,7 @@ class RolloutSimulator:
         self.renders_per_step = renders_per_step
         self.dt = ENV["T_final"] / steps                       # NerfSimulator.py:40
         self.planner_cfg, self._initial_plan, self.planner = planner_cfg, initial_plan, None
+        self.sdf = sdf
         if planner_cfg is not None:
             self.dt = planner_cfg["T_final"] / planner_cfg["steps"]   # agent_cfg['dt'] (NerfSimulator.py:36)
         self.mean = torch.tensor(ENV["mpc_noise_mean"], dtype=torch.float32)
@@ -295,6 +300,9 @@ class RolloutSimulator:
             return self.uncertainty(out)[1]
 
     def collision(self, xyz):
+        """-> (collided, value): the SDF lookup (value None: outside the field, keep the previous value) or the analytic stand-in"""
+        if self.sdf is not None:
+            return self.sdf.lookup(xyz)
         return scene_collision(xyz)
 
     def run(self, sim):
@@ -325,7 +333,9 @@ class RolloutSimulator:
             interp = np.stack([np.interp(xn, x, hist[:, i]) for i in range(3)], -1)[-self.n_interp:]
             collided, value, where = False, 9999.0, interp[-1]
             for p in interp:
-                collided, value = self.collision(p)
+                collided, v = self.collision(p)
+                if v is not None:                              # None: NerfSimulator.py:145's IndexError branch keeps the value
+                    value = v
                 where = p
                 if collided:
                     break
@@ -340,10 +350,11 @@ class RolloutSimulator:
 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
-                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None):
+                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
-    reference's planner steers every simulation; its initial plan is computed once here)."""
+    reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
+    a collision.SignedDistanceField every simulation's collision check looks up."""
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -352,7 +363,7 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
 
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
-                                   planner_cfg=planner_cfg, initial_plan=plan0)
+                                   planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
