@@ -524,6 +524,22 @@ NGP_API int ngp_adam_step_dev(float* param, const float* grad, float* exp_avg, f
                       float beta2, float eps, const float* step_dev, const float* grad_scale_dev, const float* found_inf_dev,
                       ngp_stream_t stream);
 
+/* ---------------- keypoint detection (nav/features.py) ---------------- */
+/* SIFT's detection stage with cv2.SIFT_create()'s defaults (3 layers per octave, contrast 0.04, edge 10, sigma 1.6, first octave -1)
+ * on an RGB uint8 frame [H][W][3], and the state estimator's interest mask (nav/estimator_helpers.py:95-107).  Outputs, both uint8
+ * [W][H] (x-major, the reference's interest_regions[x, y]): points = 1 at the truncated position of every accepted keypoint; mask =
+ * points dilated with a kernel_size^2 box dil_iter times (cv2.dilate: anchor at the centre, pixels outside do not contribute).
+ * count [1] device = number of accepted keypoints (before deduplication; 0 is the estimator's failure branch).  H, W in [8, 16384]
+ * and 20 H W < 2^32 (the element counts of octave 0's DoG planes are 32-bit).
+ * The workspace holds the Gaussian and DoG pyramids: ngp_sift_workspace(H, W) bytes (0: unsupported size); octave o's layer
+ * `index` (0..5 Gaussian, 6..10 DoG, float [rows_o][cols_o]) starts at byte ngp_sift_layer_offset(H, W, o, index) and stays
+ * valid until the workspace is reused; ngp_sift_octaves(H, W) octaves, rows_0 = 2 H, cols_0 = 2 W, halved (floor) per octave. */
+NGP_API size_t ngp_sift_workspace(uint32_t H, uint32_t W);
+NGP_API size_t ngp_sift_layer_offset(uint32_t H, uint32_t W, int octave, int index);
+NGP_API int ngp_sift_octaves(uint32_t H, uint32_t W);
+NGP_API int ngp_sift_interest_mask(const uint8_t* rgb, uint32_t H, uint32_t W, uint32_t kernel_size, uint32_t dil_iter, uint8_t* points,
+                                   uint8_t* mask, uint32_t* count, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+
 /* Diagnostics.  ngp_debug_set_stamps / ngp_debug_set_sample_hash / ngp_debug_disable_march_queue set the PROCESS DEFAULT;
  * ngp_render_ctx_set_debug(ctx, 1, flags, stamps, sample_hash) gives one context its own state (enable = 0: back to the default).
  * A render call snapshots the state that applies to it once, at its start: concurrent calls on other threads / streams are not

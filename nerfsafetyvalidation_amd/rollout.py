@@ -24,6 +24,10 @@ synthetic scene (scene_collision: 0 inside, 9999 outside).  The A* + Adam planne
     each step  action = get_next_action() (NerfSimulator.py:82); after dynamics and noise update_state(state_est) and
                learn_update(k) (:126-129), where state_est is the TRUE noisy state as an 18-vector (:120) -- the stand-in for the
                estimator.  The simulation starts at rest in start_pos (validate.py:224-233) and steps by the plan's dt.
+The reference's NeRF state estimator (nav.Estimator) is opt-in on top of the planner (`estimator_cfg`, built by
+nav.estimator_config()): each simulation builds a fresh Estimator at the true start state; every step render #1's image, quantised
+as NerfSimulator.py:102-106 does (* 255, astype(uint8)), is the sensor image of estimate_state (:120), and the planner replans from
+the estimate instead of the true state.  The per-step estimates, covariances and success flags are kept on the simulator.
 Without it (`planner_cfg=None`, the default) the planner's action is hover thrust (zero torque) with the straight-line velocity
 from `start_pos` to `end_pos` as the initial condition (the path the A* initialisation approximates).
 
@@ -219,10 +223,12 @@ class RolloutSimulator:
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
-                 planner_cfg=None, initial_plan=None, sdf=None):
+                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
-        sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up."""
+        sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up.
+        estimator_cfg: None (the planner replans from the true state) or nav.estimator_config()'s dict: the reference's estimator
+        turns render #1 of every step into the state the planner replans from (needs planner_cfg)."""
         from .nerf.utils import get_rays
         from .uncertainty.quantification.gaussian_approximation_density_uncertainty import GaussianApproximationDensityUncertainty
         self.model, self.intrinsics, self.H, self.W, self.steps, self.seed = model, intrinsics, H, W, steps, seed
@@ -235,6 +241,9 @@ class RolloutSimulator:
         self.dt = ENV["T_final"] / steps                       # NerfSimulator.py:40
         self.planner_cfg, self._initial_plan, self.planner = planner_cfg, initial_plan, None
         self.sdf = sdf
+        self.estimator_cfg, self.estimator = estimator_cfg, None
+        if estimator_cfg is not None and planner_cfg is None:
+            raise ValueError("RolloutSimulator: estimator_cfg needs planner_cfg (the estimate is what the planner replans from)")
         if planner_cfg is not None:
             self.dt = planner_cfg["T_final"] / planner_cfg["steps"]   # agent_cfg['dt'] (NerfSimulator.py:36)
         self.mean = torch.tensor(ENV["mpc_noise_mean"], dtype=torch.float32)
@@ -284,6 +293,8 @@ class RolloutSimulator:
         """NerfSimulator.py:120-129: the state estimate as an 18-vector (stand-in: the true noisy state), update_state, learn_update"""
         if self.planner is None:
             return
+        if self.estimator is not None:
+            state = self.estimate(k, state)
         dev = self.planner.device
         s = state.to(dev)
         state_est = torch.cat([s[:6], vec_to_rot_matrix(s[6:9]).reshape(-1), s[9:]], dim=-1)
@@ -291,12 +302,45 @@ class RolloutSimulator:
             self.planner.update_state(state_est)
             self.planner.learn_update(k)
 
+    def reset_estimator(self, sim, start_state):
+        """NerfSimulator.reset's Estimator (:196-197) at the true start state, drawing its pixels from seed + simulation number"""
+        self.estimates, self.covariances, self.estimate_success = [], [], []
+        if self.estimator_cfg is None:
+            self.estimator = None
+            return
+        from .nav.estimator import Estimator
+        from .nerf.utils import get_rays
+        kw = {k: v for k, v in self.render_kwargs.items() if k != "frame_width"}   # (sparse pixels: no frame to schedule by)
+        dev, dt = self.device, self.dt
+
+        class _Agent:
+            @staticmethod
+            def drone_dynamics(x, action):
+                return drone_dynamics(x, action, dt)
+
+        self.estimator = Estimator(self.estimator_cfg, _Agent(), start_state.clone(), seed=self.seed + sim,
+                                   get_rays_fn=lambda pose, inds: get_rays(pose.to(dev), self.intrinsics, self.H, self.W, inds=inds),
+                                   render_fn=lambda o, d: self.model.render(o, d, **kw))
+
+    def estimate(self, k, state):
+        """NerfSimulator.py:120: estimate_state on the quantised render #1 of this step -> the 12-vector the planner replans from"""
+        est = self.estimator.estimate_state(self.sensor_image, self.poses[-1], self.actions[-1]).cpu()
+        self.estimates.append(est.numpy().copy())
+        self.covariances.append(np.asarray(self.estimator.covariance, np.float32))
+        self.estimate_success.append(bool(self.estimator.success))
+        return est
+
     def observe(self, pose):
-        """NerfSimulator.py:100-110: the NeRF render of the true pose, the same frame again for the UQ -> sigma_d_opt"""
+        """NerfSimulator.py:100-110: the NeRF render of the true pose, the same frame again for the UQ -> sigma_d_opt.  With the
+        estimator, render #1's image quantised as :102-106 (* 255, astype(uint8)) becomes self.sensor_image."""
         with torch.no_grad():
             out = None
-            for _ in range(self.renders_per_step):
+            for i in range(self.renders_per_step):
                 out = self.render(pose)
+                if i == 0 and self.estimator is not None:
+                    img = torch.squeeze(out["image"]).float().cpu().numpy().reshape((self.H, self.W, -1))
+                    img *= 255
+                    self.sensor_image = img.astype(np.uint8)
             return self.uncertainty(out)[1]
 
     def collision(self, xyz):
@@ -312,6 +356,7 @@ class RolloutSimulator:
         state = initial_state(self.steps)
         if self.planner is not None:                           # at rest in start_pos (validate.py:224-233, NerfSimulator.py:30-33)
             state[3:6] = 0.0
+        self.reset_estimator(sim, state)
         history = [state.numpy().astype(np.float64)]
         rows, reward, cumulative = [], 0.0, 0.0
         self.poses, self.actions = [], []
@@ -350,11 +395,12 @@ class RolloutSimulator:
 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
-                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None):
+                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
-    a collision.SignedDistanceField every simulation's collision check looks up."""
+    a collision.SignedDistanceField every simulation's collision check looks up.  estimator_cfg: None, or nav.estimator_config()'s
+    dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps)."""
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -363,7 +409,7 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
 
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
-                                   planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf)
+                                   planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
