@@ -299,7 +299,7 @@ typedef struct ngp_model {
  * default accumulates the corners in fp32 and rounds once (closer to the exact value, one instruction per corner instead of three). */
 #define NGP_PREC_F16_REF 2u
 
-/* fragment-major copy of model->sigma_weights / color_weights for the fused kernels (layout: render_fused.hip, k_pack_weights) */
+/* fragment-major copy of model->sigma_weights / color_weights for the fused kernels (layout: fused_net.hpp, k_pack_weights) */
 NGP_API size_t ngp_packed_weights_bytes(void);
 NGP_API int ngp_pack_weights(const ngp_model* model, void* out, ngp_stream_t stream);
 

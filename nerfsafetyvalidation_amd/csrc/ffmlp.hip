@@ -12,7 +12,7 @@
 //
 // One wave = one 16-row batch tile at a time (grid-stride over tiles), 4 waves per workgroup.
 // The register-resident, K=32 specialisation for the 64-wide NeRF networks lives in
-// render_fused.hip; this file is the drop-in general operator.
+// fused_net.hpp; this file is the drop-in general operator.
 //
 // Rounding points (DESIGN.md "Numerics"): fp16 operands, fp32 MFMA accumulation, accumulator
 // rounded to fp16, activation evaluated on that fp16 value, result rounded to fp16.  The CUDA

@@ -58,7 +58,7 @@ struct GridLevels {
 void fill_levels(GridLevels& lv, const int32_t* offsets_host, uint32_t L, float S, uint32_t H, uint32_t D, uint32_t gridtype,
                  bool align_corners);
 
-// derived copies of the occupancy bits (defined in render_fused.hip, shared with march_rays_train): x-fastest re-layout and its
+// derived copies of the occupancy bits (defined in render_fused.hip, launched there and by march_rays_train): x-fastest re-layout and its
 // 1:64 reduction (one bit per 4x4x4 block)
 __global__ void k_build_linear(const uint8_t* __restrict__ bitfield, uint32_t cascade, uint32_t logH, uint32_t* __restrict__ lin);
 __global__ void k_build_coarse_linear(const unsigned long long* __restrict__ bitfield64, uint32_t cascade, uint32_t logH,

@@ -1,5 +1,5 @@
 // render_fused.hip -- the MI355X-native body of NeRFRenderer.run_cuda (eval branch,
-// /root/reference/nerf/renderer.py:329-378): march -> hash-grid encode -> sigma MLP -> SH ->
+// nerf/renderer.py:329-378): march -> hash-grid encode -> sigma MLP -> SH ->
 // colour MLP -> composite -> stable compaction, one fused kernel per reference loop iteration.
 //
 // What the reference does per iteration (6+ launches, 3 zero-filled [M,*] tensors, a host sync
@@ -30,21 +30,18 @@
 //
 // Numerics: the operator kernels' expressions (explicit fmaf, -ffp-contract=off) except the fp32 corner accumulation
 // noted above; DESIGN.md section 5.
+//
+// The network itself (NetArgs, stage_block, net_density / net_color) is fused_net.hpp; the uniform-sample renderer, the point
+// queries and weight packing are units of their own (DESIGN.md "Fused sources").
 #include <hip/hip_fp16.h>
 #include <math.h>
 #include <string.h>
 
 #include <atomic>
-#include <mutex>
 
-#include "ngp_common.hpp"
+#include "fused_net.hpp"
 
 namespace ngp {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWaves = 8;                 // waves per workgroup
 constexpr int kThreads = kWaves * 64;     // 512
@@ -91,2166 +88,6 @@ constexpr uint32_t kDeathWords = 2u * kDeathShards * kSpecK;
 struct QueueHeads { uint32_t head[8][32]; };
 
 constexpr int kStatShards = 64;   // sample counters are sharded: a single hot atomic serialises at ~90 ops/us chip-wide
-
-// per-level table staged in LDS (16 levels)
-struct LevelTab {
-    float scale[16];
-    uint32_t offset[16], size[16];
-    uint32_t a1[16], a2[16];   // per-dimension multipliers: the hash primes for hashed levels, the dense strides otherwise
-    uint32_t mask[16];         // index reduction as an AND: size-1 (power-of-two size), ~0 (dense: already < size)
-    uint32_t flags[16];        // bit0 hashed, bit1 needs a generic modulo (only in the GENERIC kernel variants)
-    uint32_t cell_off[16], cell_res[16];   // per-cell corner records (NetArgs::cells): first record and cells per axis
-};
-
-struct NetArgs {
-    const uint32_t* table;     // fp16 pairs viewed as u32
-    const _Float16* packed;    // fragment-major weights (global)
-    uint32_t sig_mm, col_mm;   // hidden->hidden matmuls
-    float bound, inv_two_bound, density_scale;
-    int align_corners;
-    // per-cell corner records of the first 4 * cell_steps levels (ngp_build_cell_tables), or null: record (level, cx, cy, cz) =
-    // the 8 table entries the cell's corners map to, 32 contiguous bytes instead of 8 gathers from up to 4 cache lines
-    const uint4* cells;
-    uint32_t cell_steps;
-    uint32_t cell_off[16];     // first record of a level
-    // bits 0-3: diagnostics (debug flag bits 4-7): fold hashed levels into size >> n entries (timing only, wrong images);
-    // bit 8: ngp_model::precision == NGP_PREC_F32 (`table` holds float pairs, `packed` float fragments: NetF32 below); bit 9: ... == NGP_PREC_F16_REF
-    // (host side only: selects the HACC kernel instantiations).  (One word: the struct is a kernel argument of the tuned render loop.)
-    uint32_t dbg_shrink;
-    __host__ __device__ bool f32() const { return (dbg_shrink & 256u) != 0; }
-    __host__ __device__ bool hacc() const { return (dbg_shrink & 512u) != 0; }
-    __host__ __device__ uint32_t shrink() const { return dbg_shrink & 15u; }
-};
-
-__host__ __device__ inline uint32_t sig_halfs(uint32_t mm) { return 2048 + mm * 4096 + 1024; }
-__host__ __device__ inline size_t net_w_bytes_f16(const NetArgs& na) { return (size_t)(sig_halfs(na.sig_mm) + sig_halfs(na.col_mm)) * 2; }
-// bytes of the packed forward weights of both nets (the LDS image every fused kernel starts with)
-__host__ __device__ inline size_t net_w_bytes(const NetArgs& na) {
-    return (size_t)(sig_halfs(na.sig_mm) + sig_halfs(na.col_mm)) * (na.f32() ? 4 : 2);
-}
-
-// ------------------------------------------------------------------------------------------
-// weight fragment packing.  Source blobs are FFMLP-layout [64 x 32 | mm x 64 x 64 | 16 x 64].
-// Destination: for every (layer, 16-row block ob, 32-wide k step s, lane) 8 halfs = the lane's
-// A fragment for v_mfma_f32_16x16x32_f16 (row = 16*ob + (lane & 15), k index permuted):
-//   first sigma layer : k(q, j) = 2*(q + 4*(j >> 1)) + (j & 1)      (lane q gathers levels q, q+4, q+8, q+12)
-//   first colour layer: k(q, j) = j < 4 ? 4q + j                      (SH 4q..4q+3)
-//                                : (q == 0 && j == 4) ? 31           (the zero pad feature sits where lane 0 holds sigma)
-//                                : 15 + 4q + (j - 4)                  (geo_feat = sigma-net outputs 4q..4q+3, shifted by 15)
-//   hidden / output   : k(q, j, s) = 32 s + 16*(j >> 2) + 4q + (j & 3)  (accumulators of row blocks 2s, 2s+1)
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t perm_grid(uint32_t q, uint32_t j) { return 2 * (q + 4 * (j >> 1)) + (j & 1); }
-__device__ __forceinline__ uint32_t perm_color(uint32_t q, uint32_t j) {
-    return j < 4 ? 4 * q + j : ((q == 0 && j == 4) ? 31u : 15 + 4 * q + (j - 4));
-}
-__device__ __forceinline__ uint32_t perm_hidden(uint32_t q, uint32_t j, uint32_t s) { return 32 * s + 16 * (j >> 2) + 4 * q + (j & 3); }
-
-__global__ void k_pack_weights(const _Float16* __restrict__ sig, uint32_t sig_mm, const _Float16* __restrict__ col, uint32_t col_mm,
-                               _Float16* __restrict__ packed) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n_sig = sig_halfs(sig_mm), n_col = sig_halfs(col_mm);
-    if (e >= n_sig + n_col) return;
-    const bool is_col = e >= n_sig;
-    const uint32_t r = is_col ? e - n_sig : e;
-    const uint32_t mm = is_col ? col_mm : sig_mm;
-    const _Float16* src = is_col ? col : sig;
-    const uint32_t j = r & 7, lane = (r >> 3) & 63, c = lane & 15, q = lane >> 4;
-    uint32_t src_idx;
-    if (r < 2048) {                                   // input layer [ob][lane][8]
-        const uint32_t ob = r >> 9;
-        const uint32_t k = is_col ? perm_color(q, j) : perm_grid(q, j);
-        src_idx = (16 * ob + c) * 32 + k;
-    } else if (r < 2048 + mm * 4096) {                // hidden layers [k][ob][s][lane][8]
-        const uint32_t rr = r - 2048, layer = rr >> 12, in = rr & 4095;
-        const uint32_t ob = in >> 10, s = (in >> 9) & 1;
-        src_idx = 2048 + layer * 4096 + (16 * ob + c) * 64 + perm_hidden(q, j, s);
-    } else {                                          // output layer [s][lane][8]
-        const uint32_t in = r - 2048 - mm * 4096, s = in >> 9;
-        src_idx = 2048 + mm * 4096 + c * 64 + perm_hidden(q, j, s);
-    }
-    packed[e] = src[src_idx];
-}
-
-// ------------------------------------------------------------------------------------------
-// the network on one 16-sample tile.  All 64 lanes participate; lane = (c = sample, q = quarter).
-// Returns in lanes with q == 0: sigma (trunc_exp output, unscaled) and rgb (fp16-rounded sigmoid).
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ half8 relu_pack(const f32x4& a, const f32x4& b) {
-    half8 h;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const _Float16 x = (_Float16)a[r], y = (_Float16)b[r];
-        h[r] = x > (_Float16)0 ? x : (_Float16)0;
-        h[4 + r] = y > (_Float16)0 ? y : (_Float16)0;
-    }
-    return h;
-}
-
-__device__ __forceinline__ void mlp_in(const half8* W, uint32_t lane, half8 x, half8 (&h)[2]) {
-    f32x4 acc[4];
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[ob * 64 + lane], x, (f32x4){0, 0, 0, 0}, 0, 0, 0);
-    h[0] = relu_pack(acc[0], acc[1]);
-    h[1] = relu_pack(acc[2], acc[3]);
-}
-__device__ __forceinline__ void mlp_hidden(const half8* W, uint32_t lane, half8 (&h)[2]) {
-    f32x4 acc[4];
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) {
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[(ob * 2 + 0) * 64 + lane], h[0], (f32x4){0, 0, 0, 0}, 0, 0, 0);
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[(ob * 2 + 1) * 64 + lane], h[1], acc[ob], 0, 0, 0);
-    }
-    h[0] = relu_pack(acc[0], acc[1]);
-    h[1] = relu_pack(acc[2], acc[3]);
-}
-__device__ __forceinline__ f32x4 mlp_out(const half8* W, uint32_t lane, const half8 (&h)[2]) {
-    f32x4 o = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[lane], h[0], (f32x4){0, 0, 0, 0}, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(W[64 + lane], h[1], o, 0, 0, 0);
-}
-
-// degree-4 real SH of a direction, the 4 values index 4q..4q+3 (shencoder.cu:51-70 as products, see shencoder.hip)
-__device__ __forceinline__ void sh4_quarter(uint32_t q, float x, float y, float z, float (&o)[4]) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    if (q == 0) {
-        o[0] = 0.28209479177387814f;
-        o[1] = -0.48860251190291987f * y;
-        o[2] = 0.48860251190291987f * z;
-        o[3] = -0.48860251190291987f * x;
-    } else if (q == 1) {
-        o[0] = 1.0925484305920792f * xy;
-        o[1] = -1.0925484305920792f * yz;
-        o[2] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-        o[3] = -1.0925484305920792f * xz;
-    } else if (q == 2) {
-        o[0] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-        o[1] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-        o[2] = 2.8906114426405538f * xy * z;
-        o[3] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    } else {
-        o[0] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-        o[1] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-        o[2] = 1.4453057213202769f * z * (x2 - y2);
-        o[3] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-    }
-}
-
-// fmaf(w, (float)half, acc) with the half taken from the low / high 16 bits of a packed table entry: one v_fma_mix_f32
-// (fp32 arithmetic, the conversion is part of the instruction).  hipcc otherwise converts both halves and uses v_pk_fma_f32.
-__device__ __forceinline__ float fma_mix_lo(float w, uint32_t packed, float acc) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(r) : "v"(w), "v"(packed), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ float fma_mix_hi(float w, uint32_t packed, float acc) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(w), "v"(packed), "v"(acc));
-    return r;
-}
-
-// HALF_ACC (ngp_model::precision == NGP_PREC_F16_REF, `model.fused_reference_rounding`): the grid_encode operator's arithmetic instead --
-// every product rounded to fp16, fp16 running sum (c10::Half, gridencoder.cu:169-172): the features are then bit-identical to the
-// reference's, at three VALU instructions per corner and feature instead of one.
-template <bool HALF_ACC = false>
-__device__ __forceinline__ void corners_to_feature(const float (&fr)[3], const uint32_t (&raw)[8], bool oob, _Float16& f0, _Float16& f1) {
-    float a0 = 0.0f, a1 = 0.0f;
-    half2v hs = {(_Float16)0, (_Float16)0};
-#pragma unroll
-    for (int idx = 0; idx < 8; idx++) {
-        const float wx = (idx & 1) ? fr[0] : 1 - fr[0];
-        const float wy = (idx & 2) ? fr[1] : 1 - fr[1];
-        const float wz = (idx & 4) ? fr[2] : 1 - fr[2];
-        const float w = (wx * wy) * wz;
-        if (HALF_ACC) {
-            // w * (float)entry in fp32 (x + (-0) = x: the fma with a -0 addend IS the fp32 product, signed zeros included; the
-            // conversion of the entry is part of the instruction), rounded to half -- two roundings, as c10::Half's operator* gives,
-            // not the single one of v_fma_mixlo_f16 -- then the half running sum of both channels in one packed add
-            half2v pr = {(_Float16)fma_mix_lo(w, raw[idx], -0.0f), (_Float16)fma_mix_hi(w, raw[idx], -0.0f)};
-            hs = hs + pr;
-        } else {
-            a0 = fma_mix_lo(w, raw[idx], a0);
-            a1 = fma_mix_hi(w, raw[idx], a1);
-        }
-    }
-    f0 = oob ? (_Float16)0 : (HALF_ACC ? hs[0] : (_Float16)a0);
-    f1 = oob ? (_Float16)0 : (HALF_ACC ? hs[1] : (_Float16)a1);
-}
-
-// density half: hash-grid encode + sigma net.  Returns sigma (meaningful in q == 0) and the sigma-net outputs 4q..4q+3 as fp16.
-template <int MODE, bool HACC = false>
-__device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* Wlds, const LevelTab& lt, uint32_t lane, float x, float y, float z,
-                                            float& sigma, _Float16 (&s16)[4]) {
-    const uint32_t q = lane >> 4;
-    // encoder input: (x + bound) / (2 bound)  (gridencoder/grid.py:144).  torch evaluates a division by a Python scalar on
-    // the GPU as a multiplication with the fp32 reciprocal; identical to the division whenever 2*bound is a power of two.
-    float u0 = (x + na.bound) * na.inv_two_bound, u1 = (y + na.bound) * na.inv_two_bound, u2 = (z + na.bound) * na.inv_two_bound;
-    const bool oob = (u0 < 0 || u0 > 1) || (u1 < 0 || u1 > 1) || (u2 < 0 || u2 > 1);
-    if (oob) { u0 = 0.5f; u1 = 0.5f; u2 = 0.5f; }  // keep the gathers in range; the features are zeroed below (gridencoder.cu:107-123)
-    const float half_off = na.align_corners ? 0.0f : 0.5f;
-
-    // ---- 4 levels x 8 corners: issue all 32 gathers, then interpolate (gridencoder.cu:139-175).
-    // Index recipe of get_grid_index (:54-72), branch-free: hashed and dense candidates are both formed from the
-    // same two products and selected per level; the modulo is an AND (see LevelTab).
-    uint32_t raw[4][8];
-    float fr[4][3];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t level = q + 4 * i;
-        const float scale = lt.scale[level];
-        const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], fl = lt.flags[level];
-        const bool hashed = (fl & 1u) != 0;
-        float p[3] = {fmaf(u0, scale, half_off), fmaf(u1, scale, half_off), fmaf(u2, scale, half_off)};
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float fl_ = floorf(p[d]);
-            g[d] = (uint32_t)fl_;
-            fr[i][d] = p[d] - (float)g[d];
-        }
-        if (MODE == 2 && i < 3) {   // levels 0..11 from the per-cell records (compile-time: no second code path in the other kernels)
-            const uint32_t S = lt.cell_res[level];
-            const uint32_t ci = lt.cell_off[level] + g[0] + S * (g[1] + S * g[2]);
-            const uint4* rec = na.cells + (size_t)ci * 2;
-            const uint4 lo = rec[0], hi = rec[1];
-            raw[i][0] = lo.x; raw[i][1] = lo.y; raw[i][2] = lo.z; raw[i][3] = lo.w;
-            raw[i][4] = hi.x; raw[i][5] = hi.y; raw[i][6] = hi.z; raw[i][7] = hi.w;
-            continue;
-        }
-        const uint32_t* tab = na.table + lt.offset[level];
-        const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1};
-        const uint32_t t2[2] = {g[2] * a2, g[2] * a2 + a2};
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const uint32_t px = g[0] + (idx & 1), ty = t1[(idx >> 1) & 1], tz = t2[(idx >> 2) & 1];
-            uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
-            e &= mask;
-            if (MODE == 1) {
-                if (fl & 2u) e %= lt.size[level];
-            }
-            raw[i][idx] = tab[e];
-        }
-    }
-    half8 feat;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        // The fused path accumulates the 8 corners in fp32 (one v_fma_mix_f32 per corner and feature) and rounds the feature
-        // to fp16 once; the grid_encode operator keeps the reference's c10::Half accumulation (8 roundings, :169-172) bit for
-        // bit.  The difference is below one fp16 ulp of the feature and inside the fused path's documented tolerance.
-        if constexpr (HACC) {        // the reference's c10::Half accumulation (NGP_PREC_F16_REF)
-            _Float16 f0, f1;
-            corners_to_feature<true>(fr[i], raw[i], oob, f0, f1);
-            feat[2 * i] = f0; feat[2 * i + 1] = f1;
-            continue;
-        }
-        float a0 = 0.0f, a1 = 0.0f;
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            // w = ((1 * wx) * wy) * wz in the reference's order (:150-160); 1 * wx is exact
-            const float wx = (idx & 1) ? fr[i][0] : 1 - fr[i][0];
-            const float wy = (idx & 2) ? fr[i][1] : 1 - fr[i][1];
-            const float wz = (idx & 4) ? fr[i][2] : 1 - fr[i][2];
-            const float w = (wx * wy) * wz;
-            a0 = fma_mix_lo(w, raw[i][idx], a0);
-            a1 = fma_mix_hi(w, raw[i][idx], a1);
-        }
-        feat[2 * i] = oob ? (_Float16)0 : (_Float16)a0;
-        feat[2 * i + 1] = oob ? (_Float16)0 : (_Float16)a1;
-    }
-
-    // ---- sigma net: 32 -> 64 (-> 64)* -> 16
-    const half8* Ws = reinterpret_cast<const half8*>(Wlds);
-    half8 h[2];
-    mlp_in(Ws, lane, feat, h);
-    for (uint32_t k = 0; k < na.sig_mm; k++) mlp_hidden(Ws + 256 + k * 512, lane, h);
-    const f32x4 so = mlp_out(Ws + 256 + na.sig_mm * 512, lane, h);
-#pragma unroll
-    for (int r = 0; r < 4; r++) s16[r] = (_Float16)so[r];
-    sigma = expf((float)s16[0]);  // trunc_exp forward (activation.py:8-10), meaningful in q == 0
-}
-
-// ---- MODE 2 inside the render loop: the hashed level of a lane (12 + q) is gathered ONE TILE AHEAD --------------------------------
-// With the per-cell records the only loads that still miss far are the 8 gathers of the lane's hashed level.  They are issued for
-// the NEXT tile's sample while this tile's records are in flight and its MLPs run, and consumed a tile later from registers
-// (`pre`).  Order inside a tile: issue this tile's record loads; interpolate the hashed level from `pre` (loaded a tile ago);
-// issue the next tile's hashed gathers into the freed registers; then wait for the records only (vector-memory loads return
-// in order, so the younger gathers stay in flight behind them).
-__device__ __forceinline__ void encoder_unit(const NetArgs& na, float x, float y, float z, float (&u)[3], bool& oob) {
-    u[0] = (x + na.bound) * na.inv_two_bound; u[1] = (y + na.bound) * na.inv_two_bound; u[2] = (z + na.bound) * na.inv_two_bound;
-    oob = (u[0] < 0 || u[0] > 1) || (u[1] < 0 || u[1] > 1) || (u[2] < 0 || u[2] > 1);
-    if (oob) { u[0] = 0.5f; u[1] = 0.5f; u[2] = 0.5f; }
-}
-
-__device__ __forceinline__ void hashed_gather(const NetArgs& na, const LevelTab& lt, uint32_t level, float x, float y, float z, uint32_t (&out)[8]) {
-    float u[3];
-    bool oob;
-    encoder_unit(na, x, y, z, u, oob);
-    const float half_off = na.align_corners ? 0.0f : 0.5f, scale = lt.scale[level];
-    const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level];
-    const uint32_t g0 = (uint32_t)floorf(fmaf(u[0], scale, half_off)), g1 = (uint32_t)floorf(fmaf(u[1], scale, half_off)),
-                   g2 = (uint32_t)floorf(fmaf(u[2], scale, half_off));
-    const uint32_t* tab = na.table + lt.offset[level];
-    const bool hashed = (lt.flags[level] & 1u) != 0;     // (a tiled grid's fine levels are sums wrapped by the mask, not hashes)
-    const uint32_t t1[2] = {g1 * a1, g1 * a1 + a1};
-    const uint32_t t2[2] = {g2 * a2, g2 * a2 + a2};
-#pragma unroll
-    for (int idx = 0; idx < 8; idx++) {
-        const uint32_t px = g0 + (idx & 1), ty = t1[(idx >> 1) & 1], tz = t2[(idx >> 2) & 1];
-        out[idx] = tab[(hashed ? (px ^ ty ^ tz) : (px + ty + tz)) & mask];
-    }
-}
-
-// same values and arithmetic as net_density<2>; `pre` holds this tile's hashed-level entries on entry and the next tile's on exit
-template <bool HACC = false>
-__device__ __forceinline__ void net_density_piped(const NetArgs& na, const _Float16* Wlds, const LevelTab& lt, uint32_t lane, float x, float y,
-                                                  float z, float nx, float ny, float nz, uint32_t (&pre)[8], float& sigma,
-                                                  _Float16 (&s16)[4]) {
-    const uint32_t q = lane >> 4;
-    float u[3];
-    bool oob;
-    encoder_unit(na, x, y, z, u, oob);
-    const float half_off = na.align_corners ? 0.0f : 0.5f;
-    uint4 rec[3][2];
-    float fr[4][3];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t level = q + 4 * i;
-        const float scale = lt.scale[level];
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
-        if (i < 3) {
-            const uint32_t S = lt.cell_res[level];
-            const uint4* r = na.cells + (size_t)(lt.cell_off[level] + g[0] + S * (g[1] + S * g[2])) * 2;
-            rec[i][0] = r[0];
-            rec[i][1] = r[1];
-        }
-    }
-    half8 feat;
-    {
-        _Float16 f0, f1;
-        corners_to_feature<HACC>(fr[3], pre, oob, f0, f1);
-        feat[6] = f0; feat[7] = f1;
-    }
-    // (unconditional: a branch here makes the compiler wait for ALL outstanding loads at the join; the last tile re-gathers its own entries)
-    hashed_gather(na, lt, q + 12, nx, ny, nz, pre);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const uint32_t raw[8] = {rec[i][0].x, rec[i][0].y, rec[i][0].z, rec[i][0].w, rec[i][1].x, rec[i][1].y, rec[i][1].z, rec[i][1].w};
-        _Float16 f0, f1;
-        corners_to_feature<HACC>(fr[i], raw, oob, f0, f1);
-        feat[2 * i] = f0; feat[2 * i + 1] = f1;
-    }
-    const half8* Ws = reinterpret_cast<const half8*>(Wlds);
-    half8 h[2];
-    mlp_in(Ws, lane, feat, h);
-    for (uint32_t k = 0; k < na.sig_mm; k++) mlp_hidden(Ws + 256 + k * 512, lane, h);
-    const f32x4 so = mlp_out(Ws + 256 + na.sig_mm * 512, lane, h);
-#pragma unroll
-    for (int r = 0; r < 4; r++) s16[r] = (_Float16)so[r];
-    sigma = expf((float)s16[0]);
-}
-
-// The gather of net_density on its own: a lane's four levels (q, q+4, q+8, q+12) -> 32 raw corner entries, the interpolation
-// fractions and the out-of-range flag.  (net_density keeps its own copy of these lines: its instruction schedule is tuned.)
-template <int MODE>
-__device__ __forceinline__ void fused_gather(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, uint32_t (&raw)[4][8],
-                                             float (&fr)[4][3], bool& oob) {
-    float u[3];
-    encoder_unit(na, x, y, z, u, oob);
-    const float half_off = na.align_corners ? 0.0f : 0.5f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t level = q + 4 * i;
-        const float scale = lt.scale[level];
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
-        if (MODE == 2 && i < 3) {
-            const uint32_t S = lt.cell_res[level];
-            const uint4* rec = na.cells + (size_t)(lt.cell_off[level] + g[0] + S * (g[1] + S * g[2])) * 2;
-            const uint4 lo = rec[0], hi = rec[1];
-            raw[i][0] = lo.x; raw[i][1] = lo.y; raw[i][2] = lo.z; raw[i][3] = lo.w;
-            raw[i][4] = hi.x; raw[i][5] = hi.y; raw[i][6] = hi.z; raw[i][7] = hi.w;
-            continue;
-        }
-        const uint32_t* tab = na.table + lt.offset[level];
-        const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], fl = lt.flags[level];
-        const bool hashed = (fl & 1u) != 0;
-        const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1}, t2[2] = {g[2] * a2, g[2] * a2 + a2};
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const uint32_t px = g[0] + (idx & 1), ty = t1[(idx >> 1) & 1], tz = t2[(idx >> 2) & 1];
-            uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
-            e &= mask;
-            if (MODE == 1) { if (fl & 2u) e %= lt.size[level]; }
-            raw[i][idx] = tab[e];
-        }
-    }
-}
-
-// colour half: SH degree 4 + geo_feat -> colour net -> fp16 sigmoid (results in q == 0)
-__device__ __forceinline__ void net_color(const NetArgs& na, const _Float16* Wlds, uint32_t lane, float dx, float dy, float dz,
-                                          const _Float16 (&s16)[4], float& cr, float& cg, float& cb) {
-    const uint32_t q = lane >> 4;
-    half8 h[2];
-    // ---- colour net input: [SH(16) | geo_feat(15) | 0] in the permuted k order of perm_color
-    float sh[4];
-    sh4_quarter(q, dx, dy, dz, sh);
-    half8 cin;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        cin[r] = (_Float16)sh[r];
-        cin[4 + r] = s16[r];
-    }
-    if (q == 0) cin[4] = (_Float16)0;  // lane 0's accumulator row 0 is sigma, not a feature: this slot carries the zero pad
-    const half8* Wc = reinterpret_cast<const half8*>(Wlds + sig_halfs(na.sig_mm));
-    mlp_in(Wc, lane, cin, h);
-    for (uint32_t k = 0; k < na.col_mm; k++) mlp_hidden(Wc + 256 + k * 512, lane, h);
-    const f32x4 co = mlp_out(Wc + 256 + na.col_mm * 512, lane, h);
-    // torch.sigmoid on a half tensor: evaluate in fp32, round to fp16
-    cr = (float)(_Float16)(1.0f / (1.0f + expf(-(float)(_Float16)co[0])));
-    cg = (float)(_Float16)(1.0f / (1.0f + expf(-(float)(_Float16)co[1])));
-    cb = (float)(_Float16)(1.0f / (1.0f + expf(-(float)(_Float16)co[2])));
-}
-
-template <int MODE>
-__device__ __forceinline__ void net_tile(const NetArgs& na, const _Float16* Wlds, const LevelTab& lt, uint32_t lane, float x, float y, float z,
-                                         float dx, float dy, float dz, float& sigma, float& cr, float& cg, float& cb) {
-    _Float16 s16[4];
-    net_density<MODE>(na, Wlds, lt, lane, x, y, z, sigma, s16);
-    net_color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-}
-
-// ==========================================================================================
-// The same network in fp32 (ngp_model::precision == NGP_PREC_F32): what validate.py's rollout evaluates.  Its render_fn is a bare
-// model.render(...) (validate.py:288-291) -- no autocast context is ever entered on that path (the only ones are inside Trainer
-// methods, nerf/utils.py:544-864) -- so the table is read as fp32 (gridencoder/grid.py:36-39 casts only under autocast) and the
-// nn.Linear layers of nerf/network.py:33-47 run as fp32 GEMMs.
-//
-// Same lane mapping as the fp16 form: lane = (sample c, quarter q), a lane gathers levels q, q+4, q+8, q+12 as 8-byte (float2)
-// entries and interpolates them with the operator's arithmetic (fmaf(w, entry, acc) over the corners in index order,
-// gridencoder.cu:139-175: the features are bit-identical to grid_encode's fp32 output).  The MLPs run on v_mfma_f32_16x16x4_f32
-// (f32 in, f32 accumulate: bit for bit a k-ordered fmaf chain, at the fp32 vector rate): H^T = W X^T again, so an accumulator
-// (units 16 ob + 4 q + r of sample c) is directly the B operand of the next layer's k-steps -- step (ob, r) takes register r of
-// block ob from every lane, i.e. k = q <-> unit 16 ob + 4 q + r -- and the A fragments are stored in that order:
-//   in layer  [ob 4][g 2][lane][4]: W_in[16 ob + c][phi(q, 4 g + r)],  phi = perm_grid / perm_color (the lane's own 8 inputs)
-//   hidden    [ob 4][g 4][lane][4]: W[16 ob + c][16 g + 4 q + r]
-//   out layer        [g 4][lane][4]: W_out[c][16 g + 4 q + r]
-// one ds_read_b128 per lane and four MFMAs.  The summation order over k is therefore a permutation of the natural one (fp32
-// round-off level, like any GEMM library's).  Source blobs: the FFMLP layout in fp32.
-// ==========================================================================================
-__global__ void k_pack_weights_f32(const float* __restrict__ sig, uint32_t sig_mm, const float* __restrict__ col, uint32_t col_mm,
-                                   float* __restrict__ packed) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n_sig = sig_halfs(sig_mm), n_col = sig_halfs(col_mm);
-    if (e >= n_sig + n_col) return;
-    const bool is_col = e >= n_sig;
-    const uint32_t r = is_col ? e - n_sig : e;
-    const uint32_t mm = is_col ? col_mm : sig_mm;
-    const float* src = is_col ? col : sig;
-    const uint32_t r4 = r & 3, lane = (r >> 2) & 63, c = lane & 15, q = lane >> 4;
-    uint32_t src_idx;
-    if (r < 2048) {                                   // input layer [ob][g][lane][4]
-        const uint32_t blk = r >> 8, ob = blk >> 1, g = blk & 1, j = 4 * g + r4;
-        src_idx = (16 * ob + c) * 32 + (is_col ? perm_color(q, j) : perm_grid(q, j));
-    } else if (r < 2048 + mm * 4096) {                // hidden layers [k][ob][g][lane][4]
-        const uint32_t rr = r - 2048, layer = rr >> 12, blk = (rr & 4095) >> 8, ob = blk >> 2, g = blk & 3;
-        src_idx = 2048 + layer * 4096 + (16 * ob + c) * 64 + 16 * g + 4 * q + r4;
-    } else {                                          // output layer [g][lane][4]
-        const uint32_t g = (r - 2048 - mm * 4096) >> 8;
-        src_idx = 2048 + mm * 4096 + c * 64 + 16 * g + 4 * q + r4;
-    }
-    packed[e] = src[src_idx];
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void relu4(f32x4 (&h)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) h[ob][r] = h[ob][r] > 0.0f ? h[ob][r] : 0.0f;
-}
-__device__ __forceinline__ void mlp32_in(const f32x4* W, uint32_t lane, const float (&x)[8], f32x4 (&h)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) h[ob] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < 2; g++) {
-        f32x4 a[4];
-#pragma unroll
-        for (int ob = 0; ob < 4; ob++) a[ob] = W[(ob * 2 + g) * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int ob = 0; ob < 4; ob++) h[ob] = mfma4(a[ob][r], x[4 * g + r], h[ob]);
-    }
-    relu4(h);
-}
-__device__ __forceinline__ void mlp32_hidden_raw(const f32x4* W, uint32_t lane, const f32x4 (&h)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) acc[ob] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        f32x4 a[4];
-#pragma unroll
-        for (int ob = 0; ob < 4; ob++) a[ob] = W[(ob * 4 + g) * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int ob = 0; ob < 4; ob++) acc[ob] = mfma4(a[ob][r], h[g][r], acc[ob]);
-    }
-}
-__device__ __forceinline__ void mlp32_hidden(const f32x4* W, uint32_t lane, f32x4 (&h)[4]) {
-    f32x4 acc[4];
-    mlp32_hidden_raw(W, lane, h, acc);
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) h[ob] = acc[ob];
-    relu4(h);
-}
-__device__ __forceinline__ f32x4 mlp32_out(const f32x4* W, uint32_t lane, const f32x4 (&h)[4]) {
-    f32x4 o = {0, 0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const f32x4 a = W[g * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < 4; r++) o = mfma4(a[r], h[g][r], o);
-    }
-    return o;
-}
-
-// a lane's four levels from the fp32 table: 32 eight-byte corner entries, the interpolation fractions, the out-of-range flag
-template <int MODE>
-__device__ __forceinline__ void fused_gather32(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, float2 (&raw)[4][8],
-                                               float (&fr)[4][3], bool& oob) {
-    float u[3];
-    encoder_unit(na, x, y, z, u, oob);
-    const float half_off = na.align_corners ? 0.0f : 0.5f;
-    const float2* table = reinterpret_cast<const float2*>(na.table);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t level = q + 4 * i;
-        const float scale = lt.scale[level];
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
-        const float2* tab = table + lt.offset[level];
-        const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], fl = lt.flags[level];
-        const bool hashed = (fl & 1u) != 0;
-        const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1}, t2[2] = {g[2] * a2, g[2] * a2 + a2};
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-            const uint32_t px = g[0] + (idx & 1), ty = t1[(idx >> 1) & 1], tz = t2[(idx >> 2) & 1];
-            uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
-            e &= mask;
-            if (MODE == 1) { if (fl & 2u) e %= lt.size[level]; }
-            raw[i][idx] = tab[e];
-        }
-    }
-}
-// gridencoder.cu:139-175 in fp32: results[ch] += w * grid[index + ch] over the corners in index order (one fma each under nvcc's
-// -fmad; the operator and the oracle write it as fmaf) -- bit-identical to grid_encode's fp32 features
-__device__ __forceinline__ void corners_to_feature32(const float (&fr)[3], const float2 (&raw)[8], bool oob, float& f0, float& f1) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc = {0.0f, 0.0f};                           // both features of a corner in one v_pk_fma_f32 (an IEEE fma per component)
-#pragma unroll
-    for (int idx = 0; idx < 8; idx++) {
-        const float wx = (idx & 1) ? fr[0] : 1 - fr[0];
-        const float wy = (idx & 2) ? fr[1] : 1 - fr[1];
-        const float wz = (idx & 4) ? fr[2] : 1 - fr[2];
-        const float w = (wx * wy) * wz;
-        acc = __builtin_elementwise_fma((f32x2){w, w}, (f32x2){raw[idx].x, raw[idx].y}, acc);
-    }
-    const float a0 = acc[0], a1 = acc[1];
-    f0 = oob ? 0.0f : a0;
-    f1 = oob ? 0.0f : a1;
-}
-// d feature / d u_gd of one level (gridencoder.cu:177-222) contracted with the feature gradients (g0, g1): += into gx[3]
-__device__ __forceinline__ void level_input_grad32(float scale, const float (&fr)[3], const float2 (&raw)[8], float g0, float g1, float (&gx)[3]) {
-#pragma unroll
-    for (int gd = 0; gd < 3; gd++) {
-        float d0 = 0.0f, d1 = 0.0f;
-#pragma unroll
-        for (int k4 = 0; k4 < 4; k4++) {
-            float w = scale;
-            int left = 0;
-#pragma unroll
-            for (int nd = 0; nd < 2; nd++) {
-                const int d = (nd >= gd) ? (nd + 1) : nd;
-                const int bit = (k4 >> nd) & 1;
-                w *= bit ? fr[d] : 1 - fr[d];
-                left |= bit << d;
-            }
-            const int right = left | (1 << gd);
-            d0 = fmaf(w, raw[right].x - raw[left].x, d0);
-            d1 = fmaf(w, raw[right].y - raw[left].y, d1);
-        }
-        gx[gd] = fmaf(g0, d0, fmaf(g1, d1, gx[gd]));
-    }
-}
-
-// backward fragments, fp32.  Per net: [out layer: ob 4][lane][4] | [hidden layers, LAST first: ob 4][g 4][lane][4] | [in layer: ob 2][g 4][lane][4]
-//   out layer   : A[row = unit 16 ob + c][k = q] of step r = W_out[4 q + r][unit]            (B operand = the lane's output gradient r)
-//   hidden layer: A[row = unit 16 ob + c of the layer BELOW][k = q] of step (g, r) = W[16 g + 4 q + r][that unit]
-//   in layer    : accumulator (ob, r) of lane (c, q') = gradient of the lane's own input 4 ob + r, i.e. of feature phi(q', 4 ob + r):
-//                 A[row i][k = q] of step (g, r) = W_in[16 g + 4 q + r][phi(i >> 2, 4 ob + (i & 3))]
-__host__ __device__ inline uint32_t bwd_floats(uint32_t mm) { return 1024 + mm * 4096 + 2048; }
-__global__ void k_pack_weights_bwd_f32(const float* __restrict__ sig, uint32_t sig_mm, const float* __restrict__ col, uint32_t col_mm,
-                                       float* __restrict__ packed) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n_sig = bwd_floats(sig_mm), n_col = bwd_floats(col_mm);
-    if (e >= n_sig + n_col) return;
-    const bool is_col = e >= n_sig;
-    const uint32_t r = is_col ? e - n_sig : e;
-    const uint32_t mm = is_col ? col_mm : sig_mm;
-    const float* src = is_col ? col : sig;
-    const uint32_t r4 = r & 3, lane = (r >> 2) & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t w_hid = 2048, w_out = 2048 + mm * 4096;
-    float v;
-    if (r < 1024) {                                                   // out layer [ob][lane][4]
-        const uint32_t ob = r >> 8;
-        v = src[w_out + (4 * q + r4) * 64 + 16 * ob + c];
-    } else if (r < 1024 + mm * 4096) {                                // hidden layers, last first
-        const uint32_t rr = r - 1024, slot = rr >> 12, blk = (rr & 4095) >> 8, ob = blk >> 2, g = blk & 3;
-        const uint32_t layer = mm - 1 - slot;
-        v = src[w_hid + layer * 4096 + (16 * g + 4 * q + r4) * 64 + 16 * ob + c];
-    } else {                                                          // in layer [ob 2][g 4][lane][4]
-        const uint32_t blk = (r - 1024 - mm * 4096) >> 8, ob = blk >> 2, g = blk & 3;
-        const uint32_t qq = c >> 2, jj = 4 * ob + (c & 3);
-        v = src[(16 * g + 4 * q + r4) * 32 + (is_col ? perm_color(qq, jj) : perm_grid(qq, jj))];
-    }
-    packed[e] = v;
-}
-__device__ __forceinline__ void mlp32_out_bwd(const f32x4* Wt, uint32_t lane, const f32x4& g, f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) {
-        const f32x4 a = Wt[ob * 64 + lane];
-        acc[ob] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 4; r++) acc[ob] = mfma4(a[r], g[r], acc[ob]);
-    }
-}
-__device__ __forceinline__ void mlp32_in_bwd(const f32x4* Wt, uint32_t lane, const f32x4 (&g)[4], f32x4 (&acc)[2]) {
-#pragma unroll
-    for (int ob = 0; ob < 2; ob++) acc[ob] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int gg = 0; gg < 4; gg++)
-#pragma unroll
-        for (int ob = 0; ob < 2; ob++) {
-            const f32x4 a = Wt[(ob * 4 + gg) * 64 + lane];
-#pragma unroll
-            for (int r = 0; r < 4; r++) acc[ob] = mfma4(a[r], g[gg][r], acc[ob]);
-        }
-}
-// gradient through ReLU at the layer whose post-activation forward values are h
-__device__ __forceinline__ void relu_mask32(const f32x4 (&acc)[4], const f32x4 (&h)[4], f32x4 (&g)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) g[ob][r] = h[ob][r] > 0.0f ? acc[ob][r] : 0.0f;
-}
-
-// stage packed weights + level table into LDS (all threads of the block)
-// (w_bytes: the caller's net_w_bytes(na), or the fp16 constant expression in the kernels that only exist for fp16)
-__device__ __forceinline__ void stage_block(const NetArgs& na, const GridLevels& lv, void* Wlds, LevelTab* lt, size_t w_bytes) {
-    const uint32_t n16 = (uint32_t)(w_bytes / 16);  // 16-byte chunks
-    const uint4* src = reinterpret_cast<const uint4*>(na.packed);
-    uint4* dst = reinterpret_cast<uint4*>(Wlds);
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-    if (threadIdx.x < 16) {
-        const uint32_t l = threadIdx.x;
-        const uint32_t size = lv.offset[l + 1] - lv.offset[l];
-        lt->scale[l] = lv.scale[l];
-        lt->offset[l] = lv.offset[l];
-        lt->size[l] = size;
-        lt->a1[l] = lv.hashed[l] ? 2654435761u : lv.mul1[l];
-        lt->a2[l] = lv.hashed[l] ? 805459861u : lv.mul2[l];
-        lt->mask[l] = lv.mode[l] == 1 ? (size >> na.shrink()) - 1 : 0xFFFFFFFFu;
-        lt->flags[l] = (uint32_t)lv.hashed[l] | (lv.mode[l] == 2 ? 2u : 0u);
-        lt->cell_off[l] = na.cell_off[l];
-        lt->cell_res[l] = lv.resolution[l];
-    }
-    __syncthreads();
-}
-
-// ------------------------------------------------------------------------------------------
-// Network policies: what a fused kernel needs of the network, for the two precisions.  `W` is the LDS image of the packed forward
-// weights (sigma net, then colour net), `Wb` that of the transposed ones (backward kernels only).
-//   density      hash grid + sigma net of the lane's sample -> sigma (trunc_exp output, meaningful in q == 0) and the sigma net's
-//                outputs 4q..4q+3 (`geo_t`: fp16 / fp32)
-//   color        SH + colour net -> rgb in q == 0
-//   density_tape the same forward keeping what its backward needs;  density_vjp: dL/d(sigma-net outputs) -> this lane's part of
-//                dL/d(encoder input in [0,1]) (the sample's is the sum over its four lanes)
-//   color_vjp    colour net forward + backward for one tile: dL/d rgb = G * wsc * sigmoid' -> this lane's part of dL/d dir (through
-//                SH) and dL/d(sigma-net outputs) (through the geometry features)
-// ------------------------------------------------------------------------------------------
-__host__ __device__ inline uint32_t bwd_halfs(uint32_t mm);
-__device__ __forceinline__ void mlp_out_bwd(const half8* Wt, uint32_t lane, half8 g, f32x4 (&acc)[4]);
-__device__ __forceinline__ void mlp_hidden_bwd(const half8* Wt, uint32_t lane, const half8 (&g)[2], f32x4 (&acc)[4]);
-__device__ __forceinline__ void mlp_in_bwd(const half8* Wt, uint32_t lane, const half8 (&g)[2], f32x4 (&acc)[2]);
-__device__ __forceinline__ void relu_mask_pack(const f32x4 (&acc)[4], const half8 (&h)[2], half8 (&g)[2]);
-__device__ __forceinline__ void sh4_quarter_vjp(uint32_t q, float x, float y, float z, const float (&g)[4], float (&o)[3]);
-
-template <int MODE_, bool HACC_ = false>
-struct NetF16 {
-    static constexpr int MODE = MODE_;
-    static constexpr bool HACC = HACC_;        // the reference's c10::Half corner accumulation (NGP_PREC_F16_REF)
-    static constexpr bool kF32 = false;
-    typedef _Float16 geo_t;
-    static __host__ __device__ size_t w_bytes(const NetArgs& na) { return net_w_bytes_f16(na); }
-    static __device__ __forceinline__ void density(const NetArgs& na, const char* W, const LevelTab& lt, uint32_t lane, float x, float y, float z,
-                                                   float& sigma, geo_t (&s)[4]) {
-        net_density<MODE, HACC>(na, reinterpret_cast<const _Float16*>(W), lt, lane, x, y, z, sigma, s);
-    }
-    static __device__ __forceinline__ void color(const NetArgs& na, const char* W, uint32_t lane, float dx, float dy, float dz, const geo_t (&s)[4],
-                                                 float& cr, float& cg, float& cb) {
-        net_color(na, reinterpret_cast<const _Float16*>(W), lane, dx, dy, dz, s, cr, cg, cb);
-    }
-    static __host__ __device__ size_t wb_bytes(const NetArgs& na) { return (size_t)(bwd_halfs(na.sig_mm) + bwd_halfs(na.col_mm)) * 2; }
-
-    struct Tape {
-        bool oob;
-        uint32_t raw[4][8];
-        float fr[4][3], scl[4];
-        half8 hs[3][2], hs_last[2];        // sigma net: post-activations of the input layer and of each hidden layer
-    };
-    static __device__ __forceinline__ void density_tape(const NetArgs& na, const char* W, const LevelTab& lt, uint32_t lane, float x, float y,
-                                                        float z, Tape& t, geo_t (&s)[4]) {
-        const uint32_t q = lane >> 4;
-        const half8* Ws = reinterpret_cast<const half8*>(W);
-        fused_gather<MODE>(na, lt, q, x, y, z, t.raw, t.fr, t.oob);
-#pragma unroll
-        for (int i = 0; i < 4; i++) t.scl[i] = lt.scale[q + 4 * i];
-        half8 feat;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            _Float16 f0, f1;
-            corners_to_feature<HACC>(t.fr[i], t.raw[i], t.oob, f0, f1);
-            feat[2 * i] = f0; feat[2 * i + 1] = f1;
-        }
-        mlp_in(Ws, lane, feat, t.hs[0]);                   // (indices stay compile-time constants: register arrays)
-        t.hs_last[0] = t.hs[0][0]; t.hs_last[1] = t.hs[0][1];
-#pragma unroll
-        for (int k = 0; k < 2; k++)
-            if ((uint32_t)k < na.sig_mm) {
-                mlp_hidden(Ws + 256 + k * 512, lane, t.hs_last);
-                t.hs[k + 1][0] = t.hs_last[0]; t.hs[k + 1][1] = t.hs_last[1];
-            }
-        const f32x4 so = mlp_out(Ws + 256 + na.sig_mm * 512, lane, t.hs_last);
-#pragma unroll
-        for (int r = 0; r < 4; r++) s[r] = (_Float16)so[r];
-    }
-    static __device__ __forceinline__ void density_vjp(const NetArgs& na, const char* Wb, uint32_t lane, const Tape& t, const f32x4& gso,
-                                                       float (&gx)[3]) {
-        const half8* Bs = reinterpret_cast<const half8*>(Wb);
-        half8 gs_out = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 4; r++) gs_out[r] = (_Float16)gso[r];
-        f32x4 acc[4];
-        half8 gsn[2];
-        mlp_out_bwd(Bs, lane, gs_out, acc);
-        relu_mask_pack(acc, t.hs_last, gsn);
-#pragma unroll
-        for (int l = 1; l >= 0; l--)
-            if ((uint32_t)l < na.sig_mm) {
-                mlp_hidden_bwd(Bs + 256 + (na.sig_mm - 1 - l) * 512, lane, gsn, acc);
-                relu_mask_pack(acc, t.hs[l], gsn);
-            }
-        f32x4 gfe[2];
-        mlp_in_bwd(Bs + 256 + na.sig_mm * 512, lane, gsn, gfe);
-        // accumulator (ob, r) = gradient of feature perm_grid(q, 4 ob + r) = level q + 4 (2 ob + (r >> 1)), channel r & 1
-        gx[0] = 0; gx[1] = 0; gx[2] = 0;
-        if (!t.oob) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const float g0 = (float)(_Float16)gfe[i >> 1][2 * (i & 1)], g1 = (float)(_Float16)gfe[i >> 1][2 * (i & 1) + 1];
-#pragma unroll
-                for (int gd = 0; gd < 3; gd++) {              // gridencoder.cu:177-222: d feature / d u_gd = scale * sum_4 w (right - left)
-                    float d0 = 0.0f, d1 = 0.0f;
-#pragma unroll
-                    for (int k4 = 0; k4 < 4; k4++) {
-                        float w = t.scl[i];
-                        int left = 0;
-#pragma unroll
-                        for (int nd = 0; nd < 2; nd++) {
-                            const int d = (nd >= gd) ? (nd + 1) : nd;
-                            const int bit = (k4 >> nd) & 1;
-                            w *= bit ? t.fr[i][d] : 1 - t.fr[i][d];
-                            left |= bit << d;
-                        }
-                        const int right = left | (1 << gd);
-                        const uint32_t rl = t.raw[i][left], rr = t.raw[i][right];
-                        d0 = fmaf(w, (float)__builtin_bit_cast(_Float16, (uint16_t)(rr & 0xffffu)) - (float)__builtin_bit_cast(_Float16, (uint16_t)(rl & 0xffffu)), d0);
-                        d1 = fmaf(w, (float)__builtin_bit_cast(_Float16, (uint16_t)(rr >> 16)) - (float)__builtin_bit_cast(_Float16, (uint16_t)(rl >> 16)), d1);
-                    }
-                    gx[gd] = fmaf(g0, d0, fmaf(g1, d1, gx[gd]));
-                }
-            }
-        }
-    }
-    static __device__ __forceinline__ void color_vjp(const NetArgs& na, const char* W, const char* Wb, uint32_t lane, float dx, float dy, float dz,
-                                                     const geo_t (&s)[4], float wsc, const float (&G)[3], float (&gdir)[3], f32x4& gso) {
-        const uint32_t q = lane >> 4;
-        const half8* Wc = reinterpret_cast<const half8*>(reinterpret_cast<const _Float16*>(W) + sig_halfs(na.sig_mm));
-        const half8* Bc = reinterpret_cast<const half8*>(reinterpret_cast<const _Float16*>(Wb) + bwd_halfs(na.sig_mm));
-        // ---- colour net forward with kept activations
-        float sh[4];
-        sh4_quarter(q, dx, dy, dz, sh);
-        half8 cin;
-#pragma unroll
-        for (int r = 0; r < 4; r++) { cin[r] = (_Float16)sh[r]; cin[4 + r] = s[r]; }
-        if (q == 0) cin[4] = (_Float16)0;
-        half8 hc[4][2], hc_last[2];
-        mlp_in(Wc, lane, cin, hc[0]);
-        hc_last[0] = hc[0][0]; hc_last[1] = hc[0][1];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            if ((uint32_t)k < na.col_mm) {
-                mlp_hidden(Wc + 256 + k * 512, lane, hc_last);
-                hc[k + 1][0] = hc_last[0]; hc[k + 1][1] = hc_last[1];
-            }
-        const f32x4 co = mlp_out(Wc + 256 + na.col_mm * 512, lane, hc_last);
-        // ---- backward: sigmoid (on the fp16-rounded value, as torch.sigmoid's backward does), out layer, hidden, in
-        half8 gco = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q == 0) {
-#pragma unroll
-            for (int k3 = 0; k3 < 3; k3++) {
-                const float yv = (float)(_Float16)(1.0f / (1.0f + expf(-(float)(_Float16)co[k3])));
-                gco[k3] = (_Float16)(G[k3] * wsc * (yv * (1.0f - yv)));
-            }
-        }
-        f32x4 acc[4];
-        half8 gc[2];
-        mlp_out_bwd(Bc, lane, gco, acc);
-        relu_mask_pack(acc, hc_last, gc);
-#pragma unroll
-        for (int l = 2; l >= 0; l--)                        // through hidden matmul l (input activations hc[l]), last first
-            if ((uint32_t)l < na.col_mm) {
-                mlp_hidden_bwd(Bc + 256 + (na.col_mm - 1 - l) * 512, lane, gc, acc);
-                relu_mask_pack(acc, hc[l], gc);
-            }
-        f32x4 gin[2];
-        mlp_in_bwd(Bc + 256 + na.col_mm * 512, lane, gc, gin);
-        // accumulator (ob, r) = gradient of colour input perm_color(q, 4 ob + r): ob 0 -> SH 4q + r, ob 1 -> sigma-net output 4q + r
-        const float gsh[4] = {(float)(_Float16)gin[0][0], (float)(_Float16)gin[0][1], (float)(_Float16)gin[0][2], (float)(_Float16)gin[0][3]};
-        sh4_quarter_vjp(q, dx, dy, dz, gsh, gdir);
-#pragma unroll
-        for (int r = 0; r < 4; r++) gso[r] = (float)(_Float16)gin[1][r];
-        if (q == 0) gso[0] = 0.0f;                          // that slot was the zero pad, not sigma
-    }
-};
-
-template <int MODE_>
-struct NetF32 {
-    static constexpr int MODE = MODE_;
-    static constexpr bool kF32 = true;
-    typedef float geo_t;
-    static __host__ __device__ size_t w_bytes(const NetArgs& na) { return 2 * net_w_bytes_f16(na); }
-    static __device__ __forceinline__ void features(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, float (&feat)[8]) {
-        float2 raw[4][8];
-        float fr[4][3];
-        bool oob;
-        fused_gather32<MODE>(na, lt, q, x, y, z, raw, fr, oob);
-#pragma unroll
-        for (int i = 0; i < 4; i++) corners_to_feature32(fr[i], raw[i], oob, feat[2 * i], feat[2 * i + 1]);
-    }
-    static __device__ __forceinline__ void density(const NetArgs& na, const char* W, const LevelTab& lt, uint32_t lane, float x, float y, float z,
-                                                   float& sigma, geo_t (&s)[4]) {
-        const f32x4* Ws = reinterpret_cast<const f32x4*>(W);
-        float feat[8];
-        features(na, lt, lane >> 4, x, y, z, feat);
-        f32x4 h[4];
-        mlp32_in(Ws, lane, feat, h);
-        for (uint32_t k = 0; k < na.sig_mm; k++) mlp32_hidden(Ws + 512 + k * 1024, lane, h);
-        const f32x4 so = mlp32_out(Ws + 512 + na.sig_mm * 1024, lane, h);
-#pragma unroll
-        for (int r = 0; r < 4; r++) s[r] = so[r];
-        sigma = expf(so[0]);              // trunc_exp forward (activation.py:8-10), meaningful in q == 0
-    }
-    static __device__ __forceinline__ void color_input(uint32_t q, float dx, float dy, float dz, const geo_t (&s)[4], float (&cin)[8]) {
-        float sh[4];
-        sh4_quarter(q, dx, dy, dz, sh);
-#pragma unroll
-        for (int r = 0; r < 4; r++) { cin[r] = sh[r]; cin[4 + r] = s[r]; }
-        if (q == 0) cin[4] = 0.0f;        // lane 0's accumulator row 0 is sigma, not a feature: this slot meets the zero-padded weight column
-    }
-    static __device__ __forceinline__ void color(const NetArgs& na, const char* W, uint32_t lane, float dx, float dy, float dz, const geo_t (&s)[4],
-                                                 float& cr, float& cg, float& cb) {
-        const f32x4* Wc = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(W) + sig_halfs(na.sig_mm));
-        float cin[8];
-        color_input(lane >> 4, dx, dy, dz, s, cin);
-        f32x4 h[4];
-        mlp32_in(Wc, lane, cin, h);
-        for (uint32_t k = 0; k < na.col_mm; k++) mlp32_hidden(Wc + 512 + k * 1024, lane, h);
-        const f32x4 co = mlp32_out(Wc + 512 + na.col_mm * 1024, lane, h);
-        cr = 1.0f / (1.0f + expf(-co[0]));                 // torch.sigmoid (nerf/network.py:122)
-        cg = 1.0f / (1.0f + expf(-co[1]));
-        cb = 1.0f / (1.0f + expf(-co[2]));
-    }
-    static __host__ __device__ size_t wb_bytes(const NetArgs& na) { return (size_t)(bwd_floats(na.sig_mm) + bwd_floats(na.col_mm)) * 4; }
-
-    // backward kernels: at most 1 hidden matmul in the sigma net and 2 in the colour net (nerf/network.py has 0 and 1)
-    static constexpr uint32_t kMaxSigMM = 1, kMaxColMM = 2;
-    struct Tape {
-        bool oob;
-        float2 raw[4][8];
-        float fr[4][3], scl[4];
-        f32x4 hs[2][4], hs_last[4];
-    };
-    static __device__ __forceinline__ void density_tape(const NetArgs& na, const char* W, const LevelTab& lt, uint32_t lane, float x, float y,
-                                                        float z, Tape& t, geo_t (&s)[4]) {
-        const uint32_t q = lane >> 4;
-        const f32x4* Ws = reinterpret_cast<const f32x4*>(W);
-        fused_gather32<MODE>(na, lt, q, x, y, z, t.raw, t.fr, t.oob);
-        float feat[8];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            t.scl[i] = lt.scale[q + 4 * i];
-            corners_to_feature32(t.fr[i], t.raw[i], t.oob, feat[2 * i], feat[2 * i + 1]);
-        }
-        mlp32_in(Ws, lane, feat, t.hs[0]);
-#pragma unroll
-        for (int ob = 0; ob < 4; ob++) t.hs_last[ob] = t.hs[0][ob];
-        if (na.sig_mm > 0) {
-            mlp32_hidden(Ws + 512, lane, t.hs_last);
-#pragma unroll
-            for (int ob = 0; ob < 4; ob++) t.hs[1][ob] = t.hs_last[ob];
-        }
-        const f32x4 so = mlp32_out(Ws + 512 + na.sig_mm * 1024, lane, t.hs_last);
-#pragma unroll
-        for (int r = 0; r < 4; r++) s[r] = so[r];
-    }
-    static __device__ __forceinline__ void density_vjp(const NetArgs& na, const char* Wb, uint32_t lane, const Tape& t, const f32x4& gso,
-                                                       float (&gx)[3]) {
-        const f32x4* Bs = reinterpret_cast<const f32x4*>(Wb);
-        f32x4 acc[4], g[4];
-        mlp32_out_bwd(Bs, lane, gso, acc);
-        relu_mask32(acc, t.hs_last, g);
-        if (na.sig_mm > 0) {
-            mlp32_hidden_raw(Bs + 256, lane, g, acc);      // (the transposed fragments have the forward layout: rows = units of the layer below)
-            relu_mask32(acc, t.hs[0], g);
-        }
-        f32x4 gfe[2];
-        mlp32_in_bwd(Bs + 256 + na.sig_mm * 1024, lane, g, gfe);
-        gx[0] = 0; gx[1] = 0; gx[2] = 0;
-        if (!t.oob) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) level_input_grad32(t.scl[i], t.fr[i], t.raw[i], gfe[i >> 1][2 * (i & 1)], gfe[i >> 1][2 * (i & 1) + 1], gx);
-        }
-    }
-    static __device__ __forceinline__ void color_vjp(const NetArgs& na, const char* W, const char* Wb, uint32_t lane, float dx, float dy, float dz,
-                                                     const geo_t (&s)[4], float wsc, const float (&G)[3], float (&gdir)[3], f32x4& gso) {
-        const uint32_t q = lane >> 4;
-        const f32x4* Wc = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(W) + sig_halfs(na.sig_mm));
-        const f32x4* Bc = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Wb) + bwd_floats(na.sig_mm));
-        float cin[8];
-        color_input(q, dx, dy, dz, s, cin);
-        f32x4 hc[3][4], hc_last[4];
-        mlp32_in(Wc, lane, cin, hc[0]);
-#pragma unroll
-        for (int ob = 0; ob < 4; ob++) hc_last[ob] = hc[0][ob];
-#pragma unroll
-        for (int k = 0; k < 2; k++)
-            if ((uint32_t)k < na.col_mm) {
-                mlp32_hidden(Wc + 512 + k * 1024, lane, hc_last);
-#pragma unroll
-                for (int ob = 0; ob < 4; ob++) hc[k + 1][ob] = hc_last[ob];
-            }
-        const f32x4 co = mlp32_out(Wc + 512 + na.col_mm * 1024, lane, hc_last);
-        f32x4 gco = {0, 0, 0, 0};
-        if (q == 0) {
-#pragma unroll
-            for (int k3 = 0; k3 < 3; k3++) {
-                const float yv = 1.0f / (1.0f + expf(-co[k3]));
-                gco[k3] = G[k3] * wsc * (yv * (1.0f - yv));
-            }
-        }
-        f32x4 acc[4], gc[4];
-        mlp32_out_bwd(Bc, lane, gco, acc);
-        relu_mask32(acc, hc_last, gc);
-#pragma unroll
-        for (int l = 1; l >= 0; l--)
-            if ((uint32_t)l < na.col_mm) {
-                mlp32_hidden_raw(Bc + 256 + (na.col_mm - 1 - l) * 1024, lane, gc, acc);
-                relu_mask32(acc, hc[l], gc);
-            }
-        f32x4 gin[2];
-        mlp32_in_bwd(Bc + 256 + na.col_mm * 1024, lane, gc, gin);
-        const float gsh[4] = {gin[0][0], gin[0][1], gin[0][2], gin[0][3]};
-        sh4_quarter_vjp(q, dx, dy, dz, gsh, gdir);
-        gso = gin[1];
-        if (q == 0) gso[0] = 0.0f;                          // that slot was the zero pad, not sigma
-    }
-};
-
-// Diagnostics: the 32 hash-grid features as the fused kernels form them ([M, 32] fp16 in the operator's order 2 * level + channel),
-// with the default arithmetic or with the operator's (HALF_ACC)
-template <int MODE, bool HALF_ACC>
-__global__ void __launch_bounds__(256) k_debug_features(NetArgs na, GridLevels lv, const float* __restrict__ xyzs, uint32_t M, _Float16* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* Wlds = reinterpret_cast<_Float16*>(smem);
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + net_w_bytes_f16(na));
-    stage_block(na, lv, Wlds, lt, net_w_bytes_f16(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t tile = wave; tile < (M + 15) / 16; tile += n_waves) {
-        const uint32_t m = tile * 16 + c, mm = m < M ? m : M - 1;
-        uint32_t raw[4][8];
-        float fr[4][3];
-        bool oob;
-        fused_gather<MODE>(na, *lt, q, xyzs[(size_t)mm * 3], xyzs[(size_t)mm * 3 + 1], xyzs[(size_t)mm * 3 + 2], raw, fr, oob);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            _Float16 f0, f1;
-            corners_to_feature<HALF_ACC>(fr[i], raw[i], oob, f0, f1);
-            if (m < M) { out[(size_t)m * 32 + 2 * (q + 4 * i)] = f0; out[(size_t)m * 32 + 2 * (q + 4 * i) + 1] = f1; }
-        }
-    }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) k_debug_features32(NetArgs na, GridLevels lv, const float* __restrict__ xyzs, uint32_t M, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + net_w_bytes(na));
-    stage_block(na, lv, smem, lt, net_w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t tile = wave; tile < (M + 15) / 16; tile += n_waves) {
-        const uint32_t m = tile * 16 + c, mm = m < M ? m : M - 1;
-        float feat[8];
-        NetF32<MODE>::features(na, *lt, q, xyzs[(size_t)mm * 3], xyzs[(size_t)mm * 3 + 1], xyzs[(size_t)mm * 3 + 2], feat);
-        if (m < M) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) { out[(size_t)m * 32 + 2 * (q + 4 * i)] = feat[2 * i]; out[(size_t)m * 32 + 2 * (q + 4 * i) + 1] = feat[2 * i + 1]; }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// NeRFNetwork.forward on an explicit point list (network_ff.py:51-75)
-// ------------------------------------------------------------------------------------------
-template <class NET>
-__global__ void __launch_bounds__(256) k_network_forward(NetArgs na, GridLevels lv, const float* __restrict__ xyzs,
-                                                         const float* __restrict__ dirs, uint32_t M, float* __restrict__ sigmas,
-                                                         float* __restrict__ rgbs) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
-    stage_block(na, lv, smem, lt, NET::w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t n_tiles = (M + 15) / 16;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t m = tile * 16 + c;
-        const uint32_t mm = m < M ? m : M - 1;
-        float sg, r, g, b;
-        typename NET::geo_t s16[4];
-        NET::density(na, Wlds, *lt, lane, xyzs[(size_t)mm * 3], xyzs[(size_t)mm * 3 + 1], xyzs[(size_t)mm * 3 + 2], sg, s16);
-        NET::color(na, Wlds, lane, dirs[(size_t)mm * 3], dirs[(size_t)mm * 3 + 1], dirs[(size_t)mm * 3 + 2], s16, r, g, b);
-        if (lane < 16 && m < M) {
-            sigmas[m] = sg;
-            rgbs[(size_t)m * 3] = r;
-            rgbs[(size_t)m * 3 + 1] = g;
-            rgbs[(size_t)m * 3 + 2] = b;
-        }
-    }
-}
-
-// the density half alone (NeRFNetwork.density, network_ff.py:77-90): what the density-grid maintenance queries (renderer.py:487,526)
-// geo (optional, [M, 15] f32): the geometry features = the sigma net's outputs 1..15 (what density() returns next to sigma)
-template <class NET>
-__global__ void __launch_bounds__(256) k_network_density(NetArgs na, GridLevels lv, const float* __restrict__ xyzs, uint32_t M,
-                                                         float* __restrict__ sigmas, float* __restrict__ geo) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
-    stage_block(na, lv, smem, lt, NET::w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t n_tiles = (M + 15) / 16;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t m = tile * 16 + c;
-        const uint32_t mm = m < M ? m : M - 1;
-        float sg;
-        typename NET::geo_t s16[4];
-        NET::density(na, Wlds, *lt, lane, xyzs[(size_t)mm * 3], xyzs[(size_t)mm * 3 + 1], xyzs[(size_t)mm * 3 + 2], sg, s16);
-        if (lane < 16 && m < M) sigmas[m] = sg;
-        if (geo && m < M) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (4 * q + r > 0) geo[(size_t)m * 15 + 4 * q + r - 1] = (float)s16[r];
-        }
-    }
-}
-
-// The collision map's density (collision.py, occupancy_from_density): for cell (i, j, k) of an X x Y x Z box the s^3 sub-sample points
-// p = start + (cell + (sub + 0.5) / s) / granularity (fp32, IEEE division, no contraction), in the NeRF's axes x = p @ rot as
-// plan_point forms them, through the density half -> out[i, j, k] = the largest raw sigma.  Each lane of a 16-point tile owns one
-// cell and walks its sub-samples with a running max: no cross-lane reduction, no atomics, and every sigma is the one
-// k_network_density computes for the same fp32 point.
-struct CellArgs {
-    float start[3];
-    float granularity;
-    float rot[9];
-    uint32_t X, Y, Z, s;
-};
-
-__device__ __forceinline__ float cell_coord(float start, uint32_t cell, uint32_t sub, float s, float g) {
-    return start + ((float)cell + ((float)sub + 0.5f) / s) / g;
-}
-
-template <class NET>
-__global__ void __launch_bounds__(256) k_cell_max_density(NetArgs na, GridLevels lv, CellArgs ca, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
-    stage_block(na, lv, smem, lt, NET::w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t M = ca.X * ca.Y * ca.Z;
-    const uint32_t n_tiles = (M + 15) / 16;
-    const float fs = (float)ca.s;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t m = tile * 16 + c;
-        const uint32_t mm = m < M ? m : M - 1;
-        const uint32_t k = mm % ca.Z, j = (mm / ca.Z) % ca.Y, i = mm / (ca.Z * ca.Y);
-        float mx = 0.0f;
-        for (uint32_t a = 0; a < ca.s; a++) {
-            const float w0 = cell_coord(ca.start[0], i, a, fs, ca.granularity);
-            for (uint32_t b = 0; b < ca.s; b++) {
-                const float w1 = cell_coord(ca.start[1], j, b, fs, ca.granularity);
-                for (uint32_t e = 0; e < ca.s; e++) {
-                    const float w2 = cell_coord(ca.start[2], k, e, fs, ca.granularity);
-                    float x[3];
-#pragma unroll
-                    for (int d = 0; d < 3; d++) x[d] = w0 * ca.rot[d] + w1 * ca.rot[3 + d] + w2 * ca.rot[6 + d];
-                    float sg;
-                    typename NET::geo_t s16[4];
-                    NET::density(na, Wlds, *lt, lane, x[0], x[1], x[2], sg, s16);
-                    mx = (a | b | e) == 0 ? sg : fmaxf(mx, sg);
-                }
-            }
-        }
-        if (lane < 16 && m < M) out[m] = mx;
-    }
-}
-
-// Vector-Jacobian product of the density half with respect to the POINTS, map frozen: what the trajectory planner differentiates
-// (nav/quad_plot.py:223-249: density_fn on S x 500 body points, 250 Adam steps per simulator step).  Upstream gradients of sigma [M]
-// and (optional) of the geometry features [M, 15] -> grad_xyzs [M, 3].  One pass: forward with kept activations, trunc_exp backward
-// (activation.py:12-17), the transposed sigma net, the hash grid's input derivative, d u / d x = 1 / (2 bound).
-template <class NET>
-__global__ void __launch_bounds__(256) k_network_density_bwd(NetArgs na, GridLevels lv, const char* __restrict__ packed_bwd,
-                                                             const float* __restrict__ xyzs, uint32_t M, const float* __restrict__ g_sigma,
-                                                             const float* __restrict__ g_geo, float* __restrict__ grad_xyzs) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t w_bytes = NET::w_bytes(na);
-    const size_t ws_bytes = NET::kF32 ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;   // the sigma net's transposed fragments only
-    const char* Wlds = smem;
-    char* Wb = smem + w_bytes;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes + ws_bytes);
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(packed_bwd);
-        uint4* dst = reinterpret_cast<uint4*>(Wb);
-        for (uint32_t i = threadIdx.x; i < ws_bytes / 16; i += blockDim.x) dst[i] = src[i];
-    }
-    stage_block(na, lv, smem, lt, w_bytes);
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t n_tiles = (M + 15) / 16;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t m = tile * 16 + c;
-        const bool valid = m < M;
-        const uint32_t mm = valid ? m : M - 1;
-        typename NET::Tape tape;
-        typename NET::geo_t s16[4];
-        NET::density_tape(na, Wlds, *lt, lane, xyzs[(size_t)mm * 3], xyzs[(size_t)mm * 3 + 1], xyzs[(size_t)mm * 3 + 2], tape, s16);
-        f32x4 gso = {0, 0, 0, 0};
-        if (valid) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t o = 4 * q + r;
-                if (o == 0) gso[r] = g_sigma ? g_sigma[m] * expf(fminf(15.0f, fmaxf(-15.0f, (float)s16[0]))) : 0.0f;
-                else gso[r] = g_geo ? g_geo[(size_t)m * 15 + o - 1] : 0.0f;
-            }
-        }
-        float gx[3];
-        NET::density_vjp(na, Wb, lane, tape, gso, gx);
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            gx[d] += __shfl_xor(gx[d], 16, 64);
-            gx[d] += __shfl_xor(gx[d], 32, 64);
-        }
-        if (lane < 16 && valid) {
-#pragma unroll
-            for (int d = 0; d < 3; d++) grad_xyzs[(size_t)m * 3 + d] = gx[d] * na.inv_two_bound;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// The trajectory planner's collision term (nav/quad_plot.py:216-241 through validate.py:288's density_fn): for planned state s the
-// B body points b go to the world (w = R_s b + p_s), to the NeRF's axes (x = w @ rot), through hash grid + sigma net + trunc_exp,
-// and out[s] = mean_b sigma^2.  One workgroup per state; its waves take 16-point tiles in turn, and every sum runs in a fixed order
-// (tiles of a lane, then lanes, then waves through LDS): no atomics, the same bits on every call and on every graph replay.
-// ------------------------------------------------------------------------------------------
-struct PlanArgs {
-    const float* rot_matrix;   // [S,3,3]
-    const float* pos;          // [S,3]
-    const float* body;         // [B,3]
-    const float* rot;          // [3,3]
-    uint32_t S, B;
-};
-
-constexpr uint32_t kPlanThreads = 256;
-
-__device__ __forceinline__ void plan_load_rot(const PlanArgs& pa, float (&rot)[9]) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) rot[i] = pa.rot[i];
-}
-
-// body point b of state s: its world point w and the density query's input x = w @ rot
-__device__ __forceinline__ void plan_point(const PlanArgs& pa, const float (&rot)[9], uint32_t s, uint32_t b, float (&bp)[3], float (&x)[3]) {
-    const float* R = pa.rot_matrix + (size_t)s * 9;
-    const float* p = pa.pos + (size_t)s * 3;
-#pragma unroll
-    for (int k = 0; k < 3; k++) bp[k] = pa.body[(size_t)b * 3 + k];
-    float w[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) w[i] = R[3 * i] * bp[0] + R[3 * i + 1] * bp[1] + R[3 * i + 2] * bp[2] + p[i];
-#pragma unroll
-    for (int j = 0; j < 3; j++) x[j] = w[0] * rot[j] + w[1] * rot[3 + j] + w[2] * rot[6 + j];
-}
-
-// sum of lanes 0..15 (every other lane holds 0), complete in lane 0
-__device__ __forceinline__ float plan_lane_sum(float v) {
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-template <class NET>
-__global__ void __launch_bounds__(kPlanThreads) k_planner_collision(NetArgs na, GridLevels lv, PlanArgs pa, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t w_bytes = NET::w_bytes(na);
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes);
-    float* red = reinterpret_cast<float*>(smem + w_bytes + sizeof(LevelTab));          // [waves]
-    stage_block(na, lv, smem, lt, w_bytes);
-    float rot[9];
-    plan_load_rot(pa, rot);
-    const uint32_t s = blockIdx.x;
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const uint32_t n_tiles = (pa.B + 15) / 16;
-    float acc = 0.0f;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t b = tile * 16 + c;
-        const bool valid = b < pa.B;
-        float bp[3], x[3];
-        plan_point(pa, rot, s, valid ? b : pa.B - 1, bp, x);
-        float sg;
-        typename NET::geo_t s16[4];
-        NET::density(na, Wlds, *lt, lane, x[0], x[1], x[2], sg, s16);
-        if (valid && lane < 16) acc += sg * sg;          // (sigma is meaningful in the lanes of quarter 0)
-    }
-    acc = plan_lane_sum(lane < 16 ? acc : 0.0f);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sum = 0.0f;
-        for (uint32_t w = 0; w < n_waves; w++) sum += red[w];
-        out[s] = sum / (float)pa.B;
-    }
-}
-
-// g [S] = dL/d out -> grad_pos [S,3], grad_rot_matrix [S,3,3] (overwritten).  The forward again with kept activations, then per point
-// dL/d sigma = (g / B) * (2 sigma) (mean, then pow), trunc_exp's backward, the sigma net and hash grid (NET::density_vjp, as
-// k_network_density_bwd), d x / d w = rot^T and d w / d (p, R) = (1, b^T).
-template <class NET>
-__global__ void __launch_bounds__(kPlanThreads) k_planner_collision_bwd(NetArgs na, GridLevels lv, const char* __restrict__ packed_bwd,
-                                                                        PlanArgs pa, const float* __restrict__ g, float* __restrict__ grad_pos,
-                                                                        float* __restrict__ grad_rot_matrix) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t w_bytes = NET::w_bytes(na);
-    const size_t ws_bytes = NET::kF32 ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;   // sigma net's transposed fragments
-    const char* Wlds = smem;
-    char* Wb = smem + w_bytes;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes + ws_bytes);
-    float* red = reinterpret_cast<float*>(smem + w_bytes + ws_bytes + sizeof(LevelTab));   // [waves][12]
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(packed_bwd);
-        uint4* dst = reinterpret_cast<uint4*>(Wb);
-        for (uint32_t i = threadIdx.x; i < ws_bytes / 16; i += blockDim.x) dst[i] = src[i];
-    }
-    stage_block(na, lv, smem, lt, w_bytes);
-    float rot[9];
-    plan_load_rot(pa, rot);
-    const uint32_t s = blockIdx.x;
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const uint32_t n_tiles = (pa.B + 15) / 16;
-    const float g_mean = g[s] / (float)pa.B;
-    float acc[12];                                       // d/d p (3), then d/d R row-major (9)
-#pragma unroll
-    for (int i = 0; i < 12; i++) acc[i] = 0.0f;
-    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
-        const uint32_t b = tile * 16 + c;
-        const bool valid = b < pa.B;
-        float bp[3], x[3];
-        plan_point(pa, rot, s, valid ? b : pa.B - 1, bp, x);
-        typename NET::Tape tape;
-        typename NET::geo_t s16[4];
-        NET::density_tape(na, Wlds, *lt, lane, x[0], x[1], x[2], tape, s16);
-        f32x4 gso = {0, 0, 0, 0};
-        if (valid && q == 0) {
-            const float h = (float)s16[0];
-            const float sigma = expf(h);
-            gso[0] = (g_mean * (2.0f * sigma)) * expf(fminf(15.0f, fmaxf(-15.0f, h)));
-        }
-        float gx[3];
-        NET::density_vjp(na, Wb, lane, tape, gso, gx);
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            gx[d] += __shfl_xor(gx[d], 16, 64);
-            gx[d] += __shfl_xor(gx[d], 32, 64);
-        }
-        if (valid && lane < 16) {
-            float gxr[3], gw[3];
-#pragma unroll
-            for (int d = 0; d < 3; d++) gxr[d] = gx[d] * na.inv_two_bound;
-#pragma unroll
-            for (int i = 0; i < 3; i++) gw[i] = rot[3 * i] * gxr[0] + rot[3 * i + 1] * gxr[1] + rot[3 * i + 2] * gxr[2];
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                acc[i] += gw[i];
-#pragma unroll
-                for (int k = 0; k < 3; k++) acc[3 + 3 * i + k] += gw[i] * bp[k];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        const float v = plan_lane_sum(lane < 16 ? acc[i] : 0.0f);
-        if (lane == 0) red[wave * 12 + i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        float sum = 0.0f;
-        for (uint32_t w = 0; w < n_waves; w++) sum += red[w * 12 + threadIdx.x];
-        if (threadIdx.x < 3) grad_pos[(size_t)s * 3 + threadIdx.x] = sum;
-        else grad_rot_matrix[(size_t)s * 9 + threadIdx.x - 3] = sum;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// NeRFRenderer.run, uniform sampling without upsampling (nerf/renderer.py:125-258): the path validate.py -O executes
-// (cuda_ray = False, num_steps = 512).  One wave walks one ray 16 samples at a time: positions from the linspace table,
-// fused hash-grid + sigma net, in-wave transmittance scan (alphas * cumprod(1 - alphas + 1e-15), :206-210), colour net only
-// for tiles that contain a sample with weight > 1e-4 (the reference's masked colour query, :216-218), running sums of
-// weights, depth, colour and weights * sigma.  None of the reference's [N, T, *] intermediates exists in memory; the
-// per-sample sigmas / rgbs it returns for the LAST ray chunk are written only for rays >= dump_begin.
-// ------------------------------------------------------------------------------------------
-template <class NET>
-__global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform(NetArgs na, GridLevels lv, const float* __restrict__ rays_o,
-                                                           const float* __restrict__ rays_d, const float* __restrict__ nears,
-                                                           const float* __restrict__ fars, uint32_t N, uint32_t T,
-                                                           const float* __restrict__ lin, float* __restrict__ weights_sum,
-                                                           float* __restrict__ depth, float* __restrict__ image,
-                                                           float* __restrict__ aggregated_density, uint32_t dump_begin,
-                                                           float* __restrict__ sigmas, float* __restrict__ rgbs, float aabb_lo, float aabb_hi) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
-    stage_block(na, lv, smem, lt, NET::w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t ray = wave; ray < N; ray += n_waves) {
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153 (tensor / Python scalar on the GPU = multiplication with the fp32 reciprocal)
-        const bool dump = sigmas != nullptr && ray >= dump_begin;
-        float carry = 1.0f;                                                          // cumprod of (1 - alpha + 1e-15) over earlier tiles
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;             // per-lane partial sums (lanes 0..15)
-        for (uint32_t i0 = 0; i0 < T; i0 += 16) {
-            const uint32_t idx = i0 + c;
-            const bool valid = idx < T;
-            const uint32_t ii = valid ? idx : T - 1;
-            const float zv = near + span * lin[ii];                                  // :150 (mul, then add: eager torch does not fuse)
-            const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);                  // :159-160
-            const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-            const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
-            float sigma;
-            typename NET::geo_t s16[4];
-            NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-            // ---- lanes 0..15 hold sigma of samples i0..i0+15 (the other quarters compute along with them; only lane < 16 results are used)
-            const float z_next = (ii + 1 < T) ? near + span * lin[ii + 1] : 0.0f;
-            const float delta = (ii + 1 < T) ? z_next - zv : sample_dist;           // :206-207
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;   // :208
-            const float p = (1.0f - alpha) + 1e-15f;                                 // :209
-            float incl = p;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl_in_tile = __shfl_up(incl, 1, 16);
-            const float Tr = carry * (c == 0 ? 1.0f : excl_in_tile);
-            const float w = alpha * Tr;                                              // :210
-            const bool masked = valid && w > 1e-4f;                                  // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked && lane < 16) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (lane < 16 && valid) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227; 0/0 = NaN for rays that miss the box and
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));         // torch.clamp keeps the NaN, as the reference does
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;                         // :231
-                a_agg += w * sigma;                                                  // :244
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * T + idx;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-            }
-            // (lanes 16..63 evaluate other rows of the sigma net in `sigma`: only quarter 0's transmittance is the ray's.  The exit
-            //  below must be taken by the WHOLE wave at once -- a quarter that left early would stop gathering its levels -- hence
-            //  the broadcast of lane 0's value)
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));
-            // everything further down the ray is weighted by <= carry: below fp32 resolution of the O(1) sums
-            if (!dump && carry < 1e-10f) break;
-        }
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            a_ws += __shfl_xor(a_ws, off, 16); a_dep += __shfl_xor(a_dep, off, 16); a_agg += __shfl_xor(a_agg, off, 16);
-            a_r += __shfl_xor(a_r, off, 16); a_g += __shfl_xor(a_g, off, 16); a_b += __shfl_xor(a_b, off, 16);
-        }
-        if (lane == 0) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
-    }
-}
-
-// The same computation with the samples of a tile taken ACROSS sixteen neighbouring rays (consecutive pixels of a row) at one
-// depth index instead of along one ray: neighbouring pixels at equal depth are ~4x closer than consecutive samples of a ray
-// (d / 1111 against span / 512), so the sixteen samples of a tile share cells -- and cache lines -- down to finer levels, as the
-// tiles of k_render_iter do; and the transmittance becomes a per-lane running product (no in-tile scan).  Lane c of every quarter
-// walks ray 16 g + c; a ray whose transmittance is spent idles until the last ray of its group is (neighbouring pixels end at
-// similar depths).  Per-sample granularity of the stop: a ray ends after the first sample that leaves carry < 1e-10.
-constexpr uint32_t kUniformX16MinRays = 65536;      // (measured: section 4 of DESIGN.md)
-// DENS: the density pass alone -- sigma of every uniform sample of every ray into sigmas [N, T], no colour, no sums, no early stop
-// (the coarse pass of the importance resampling, ngp_density_uniform).
-template <class NET, bool DENS = false>
-__global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(NetArgs na, GridLevels lv, const float* __restrict__ rays_o,
-                                                               const float* __restrict__ rays_d, const float* __restrict__ nears,
-                                                               const float* __restrict__ fars, uint32_t N, uint32_t T,
-                                                               const float* __restrict__ lin, float* __restrict__ weights_sum,
-                                                               float* __restrict__ depth, float* __restrict__ image,
-                                                               float* __restrict__ aggregated_density, uint32_t dump_begin,
-                                                               float* __restrict__ sigmas, float* __restrict__ rgbs, float aabb_lo, float aabb_hi,
-                                                               uint32_t frame_w, unsigned long long* __restrict__ stamps,
-                                                               const float* __restrict__ z_in, _Float16* __restrict__ geo_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const char* Wlds = smem;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
-    stage_block(na, lv, smem, lt, NET::w_bytes(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t n_groups = (N + 15) / 16;
-    for (uint32_t grp = wave; grp < n_groups; grp += n_waves) {
-        uint32_t ray_raw = grp * 16 + c;
-        if (frame_w) {      // 4x4-pixel blocks of row-major frames `frame_w` wide (frame_w % 4 == 0, N % (4 * frame_w) == 0: checked on the host)
-            const uint32_t bpr = frame_w >> 2, by = grp / bpr, bx = grp - by * bpr;
-            ray_raw = (by * 4 + (c >> 2)) * frame_w + bx * 4 + (c & 3);
-        }
-        const bool live = ray_raw < N;
-        const uint32_t ray = live ? ray_raw : N - 1;
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
-        const bool dump = live && sigmas != nullptr && ray >= dump_begin;
-        float carry = 1.0f;
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
-        bool running = live;
-        uint32_t n_iter = 0, n_counted = 0;
-        if constexpr (DENS && !NET::kF32) {      // z_in: the depths come from the resampling instead of the uniform table.  Scratch arrays are GROUP-major,
-            // [group][sample][ray of the group]: the sixteen rays' values of one sample are 64 (sigma, depth) or 512 (geo) contiguous bytes
-            for (uint32_t i = 0; i < T; i++) {
-                const size_t at = ((size_t)grp * T + i) * 16 + c;
-                const float zs = z_in ? (live ? z_in[at] : 0.0f) : near + span * lin[i];    // (slots past the last ray were never written)
-                const float x = clampf(ox + dx * zs, aabb_lo, aabb_hi), y = clampf(oy + dy * zs, aabb_lo, aabb_hi), z = clampf(oz + dz * zs, aabb_lo, aabb_hi);
-                float sigma;
-                _Float16 s16[4];
-                NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-                if (lane < 16) sigmas[at] = sigma;
-                // the sigma net's sixteen outputs (sigma's pre-activation + the 15 geometry features), 4 per quarter: what the colour
-                // net of the compositing launch needs of this sample
-                if (geo_out) {
-                    half4 h4 = {s16[0], s16[1], s16[2], s16[3]};
-                    *reinterpret_cast<half4*>(geo_out + at * 16 + (lane >> 4) * 4) = h4;
-                }
-            }
-            continue;
-        }
-        float zv = near + span * lin[0];                                             // :150
-        for (uint32_t i = 0; i < T; i++) {
-            n_iter++;
-            const float z_next = (i + 1 < T) ? near + span * lin[i + 1] : 0.0f;
-            const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);                  // :159-160
-            const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-            const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
-            float sigma;
-            typename NET::geo_t s16[4];
-            NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-            // (quarter 0 holds sigma; the other quarters evaluate other rows of the sigma net in `sigma` and follow quarter 0's
-            //  decisions through the ballots below)
-            const float delta = (i + 1 < T) ? z_next - zv : sample_dist;             // :206-207
-            const float alpha = 1.0f - expf(((-delta) * na.density_scale) * sigma);  // :208
-            const float w = alpha * carry;                                           // :210
-            const bool counted = running && lane < 16;
-            const bool masked = counted && w > 1e-4f;                                // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (counted) {
-                n_counted++;
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;                         // :231
-                a_agg += w * sigma;                                                  // :244
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * T + i;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-                carry *= (1.0f - alpha) + 1e-15f;                                    // :209
-                if (!dump && carry < 1e-10f) running = false;                        // what follows is weighted by <= carry
-            }
-            if (__ballot(running && lane < 16) == 0ull) break;
-            zv = z_next;
-        }
-        if (lane < 16 && live) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
-        if (stamps) {    // diagnostics (ngp_debug_set_stamps): depth indices walked by the group x 16 lanes, and those that carried a running ray
-            uint32_t mine = lane < 16 ? n_counted : 0u;
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 16);
-            if (lane == 0) { atomicAdd(stamps + 12, (unsigned long long)n_iter * 16ull); atomicAdd(stamps + 13, (unsigned long long)mine); }
-        }
-    }
-}
-
-// ray -> (group of sixteen, slot in the group) as k_render_uniform_x16 forms its groups: 1x16 strips, or 4x4-pixel blocks of frames
-// `frame_w` wide
-__device__ __forceinline__ void ray_slot(uint32_t ray, uint32_t frame_w, uint32_t& grp, uint32_t& c) {
-    if (frame_w) {
-        const uint32_t row = ray / frame_w, col = ray - row * frame_w;
-        grp = (row >> 2) * (frame_w >> 2) + (col >> 2);
-        c = (row & 3u) * 4u + (col & 3u);
-    } else {
-        grp = ray >> 4;
-        c = ray & 15u;
-    }
-}
-
-// The last launch of the large-batch importance resampling: merge + compositing ACROSS the sixteen rays of a group.  Every lane walks
-// its ray's two ascending runs -- the T uniform depths (computed) and the U resampled ones (group-major scratch) -- with two
-// pointers (coarse first on ties: the order k_merge_sorted / torch.sort of the concatenation give), so the merge costs no search and
-// no LDS; sigma and, for tiles that hold a sample with weight > 1e-4, the sigma net's outputs come from the density launches'
-// scratch, and only the colour net is evaluated here.  Transmittance is a per-lane running product, as in k_render_uniform_x16.
-template <int MODE>
-__global__ void __launch_bounds__(256, 4) k_composite_merged_x16(NetArgs na, GridLevels lv, const float* __restrict__ rays_d,
-                                                                 const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N,
-                                                                 uint32_t T, uint32_t U, const float* __restrict__ lin,
-                                                                 const float* __restrict__ sc, const float* __restrict__ zf,
-                                                                 const float* __restrict__ sf, const _Float16* __restrict__ geo_c,
-                                                                 const _Float16* __restrict__ geo_f, float* __restrict__ weights_sum,
-                                                                 float* __restrict__ depth, float* __restrict__ image,
-                                                                 float* __restrict__ aggregated_density, uint32_t dump_begin,
-                                                                 float* __restrict__ sigmas, float* __restrict__ rgbs, uint32_t frame_w) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* Wlds = reinterpret_cast<_Float16*>(smem);
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + net_w_bytes_f16(na));
-    stage_block(na, lv, Wlds, lt, net_w_bytes_f16(na));
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t n_groups = (N + 15) / 16, Tm = T + U;
-    const float inf = __builtin_huge_valf();
-    for (uint32_t grp = wave; grp < n_groups; grp += n_waves) {
-        uint32_t ray_raw = grp * 16 + c;
-        if (frame_w) {
-            const uint32_t bpr = frame_w >> 2, by = grp / bpr, bx = grp - by * bpr;
-            ray_raw = (by * 4 + (c >> 2)) * frame_w + bx * 4 + (c & 3);
-        }
-        const bool live = ray_raw < N;
-        const uint32_t ray = live ? ray_raw : N - 1;
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
-        const bool dump = live && sigmas != nullptr && ray >= dump_begin;
-        const size_t cbase = (size_t)grp * T * 16 + c, fbase = (size_t)grp * U * 16 + c;
-        uint32_t i = 0, j = 0;                                                       // next coarse / fine sample of this lane's ray
-        float zci = near + span * lin[0], zfj = live ? zf[fbase] : 0.0f;                 // (slots past the last ray were never written)
-        float carry = 1.0f, a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
-        bool running = live;
-        for (uint32_t m = 0; m < Tm; m++) {
-            const bool from_c = zci <= zfj;                                          // (an exhausted run holds +inf; both cannot be)
-            const float zv = from_c ? zci : zfj;
-            const size_t at = from_c ? cbase + (size_t)i * 16 : fbase + (size_t)j * 16;
-            const float sigma = (from_c ? sc : sf)[at];
-            const _Float16* gp = (from_c ? geo_c : geo_f) + at * 16 + q * 4;
-            if (from_c) { i++; zci = i < T ? near + span * lin[i] : inf; }
-            else { j++; zfj = j < U ? (live ? zf[fbase + (size_t)j * 16] : 0.0f) : inf; }
-            const float z_next = zci <= zfj ? zci : zfj;
-            const float delta = (m + 1 < Tm) ? z_next - zv : sample_dist;            // :206-207
-            const float alpha = 1.0f - expf(((-delta) * na.density_scale) * sigma);  // :208
-            const float w = alpha * carry;                                           // :210
-            const bool counted = running && lane < 16;
-            const bool masked = counted && w > 1e-4f;                                // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
-                const half4 h4 = *reinterpret_cast<const half4*>(gp);
-                const _Float16 s16[4] = {h4[0], h4[1], h4[2], h4[3]};
-                net_color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (counted) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;
-                a_agg += w * sigma;
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * Tm + m;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-                carry *= (1.0f - alpha) + 1e-15f;                                    // :209
-                if (!dump && carry < 1e-10f) running = false;
-            }
-            if (__ballot(running && lane < 16) == 0ull) break;
-        }
-        if (lane < 16 && live) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// NeRFRenderer.run WITH the NeRF-style importance resampling (nerf/renderer.py:172-204, sample_pdf :12-46), evaluation mode
-// (`det`: the u of the inverse-CDF draw are the fixed linspace of :26).  One wave walks one ray; everything the reference keeps
-// in [N, T, *] / [N, T + U, *] tensors -- coarse depths and densities, their weights, the CDF, the U resampled depths, the
-// merged order -- lives in a few KB of LDS per wave:
-//   1. coarse pass: T uniform samples, fused hash grid + sigma net                                   (:148-170)
-//   2. weights of the coarse samples (:176-180), CDF over the T - 1 mid points of weights[1:-1] + 1e-5 (:17-22), U inverse-CDF
-//      samples by binary search (:29-44)
-//   3. fine pass: sigma at the U new depths                                                          (:181-184)
-//   4. merge of the two ascending runs (the sort + gathers of :187-193; coarse first on ties)
-//   5. compositing over the T + U merged samples exactly as k_render_uniform does; a tile that holds a sample with weight > 1e-4
-//      re-evaluates the sigma net for its geometry features (bit-identical to the first evaluation) and runs the colour net.
-// ------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels lv, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                         const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N, uint32_t T,
-                                                         uint32_t U, const float* __restrict__ lin, const float* __restrict__ u_det,
-                                                         float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image,
-                                                         float* __restrict__ aggregated_density, uint32_t dump_begin, float* __restrict__ sigmas,
-                                                         float* __restrict__ rgbs, float aabb_lo, float aabb_hi,
-                                                         const float* __restrict__ sc_in, float* __restrict__ zf_out, uint32_t frame_w) {
-    // sc_in: sigma of the uniform samples, evaluated by k_render_uniform_x16<DENS> (tiles across rays);  zf_out: stop after the resampling
-    // and hand the new depths over.  Both group-major (frame_w as in that launch): the middle launch of the large-batch form.
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t w_bytes = net_w_bytes_f16(na);
-    _Float16* Wlds = reinterpret_cast<_Float16*>(smem);
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes);
-    stage_block(na, lv, Wlds, lt, w_bytes);
-    const uint32_t lane = threadIdx.x & 63, c = lane & 15, wid = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    const uint32_t Tm = T + U;
-    float* zc = reinterpret_cast<float*>(smem + w_bytes + sizeof(LevelTab)) + (size_t)wid * (5 * T + 4 * U);
-    float* sc = zc + T;
-    float* cdf = sc + T;          // first the coarse weights, then (in place) the CDF
-    float* zf = cdf + T;
-    float* sf = zf + U;
-    float* zm = sf + U;
-    float* sm = zm + Tm;
-#define NGP_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-    for (uint32_t ray = blockIdx.x * wpb + wid; ray < N; ray += gridDim.x * wpb) {
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
-        const bool dump = sigmas != nullptr && ray >= dump_begin;
-        uint32_t g_grp, g_c;
-        ray_slot(ray, frame_w, g_grp, g_c);
-        // ---- 1. / 3. sigma along the ray: the T uniform depths, then (after the resampling below) the U new ones
-        for (int phase = 0; phase < 2; phase++) {
-            const uint32_t n = phase ? U : T;
-            float* zdst = phase ? zf : zc;
-            float* sdst = phase ? sf : sc;
-            if (!phase && sc_in) {  // the coarse pass was evaluated across rays: take its sigma
-                for (uint32_t i = lane; i < n; i += 64) {
-                    zdst[i] = near + span * lin[i];
-                    sdst[i] = sc_in[((size_t)g_grp * T + i) * 16 + g_c];
-                }
-            } else
-            for (uint32_t i0 = 0; i0 < n; i0 += 16) {
-                const uint32_t idx = i0 + c;
-                const bool valid = idx < n;
-                const uint32_t ii = valid ? idx : n - 1;
-                const float zv = phase ? zf[ii] : near + span * lin[ii];             // :150
-                const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);              // :159-160, :181-182
-                const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-                const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
-                float sigma;
-                _Float16 s16[4];
-                net_density<MODE>(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-                if (lane < 16 && valid) { zdst[idx] = zv; sdst[idx] = sigma; }
-            }
-            NGP_WAVE_SYNC();
-            if (phase) break;
-            // ---- 2. coarse weights (:176-180), lane = sample
-            float carry = 1.0f;
-            for (uint32_t t0 = 0; t0 < T; t0 += 64) {
-                const uint32_t t = t0 + lane;
-                const bool on = t < T;
-                const uint32_t tt = on ? t : T - 1;
-                const float delta = tt + 1 < T ? zc[tt + 1] - zc[tt] : sample_dist;
-                const float alpha = on ? 1.0f - expf(((-delta) * na.density_scale) * sc[tt]) : 0.0f;
-                float incl = on ? (1.0f - alpha) + 1e-15f : 1.0f;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const float o = __shfl_up(incl, off, 64);
-                    if (lane >= (uint32_t)off) incl *= o;
-                }
-                const float excl = __shfl_up(incl, 1, 64);
-                if (on) cdf[t] = alpha * (carry * (lane == 0 ? 1.0f : excl));
-                carry *= __shfl(incl, 63, 64);
-            }
-            NGP_WAVE_SYNC();
-            // sample_pdf(bins = mid points [T - 1], weights[1:-1] [T - 2]) (:12-46): cdf[k], k = 0 .. T - 2, in place of weights[k]
-            const uint32_t Tb = T - 1, Tw = T - 2;
-            float sum = 0.0f;
-            for (uint32_t t = lane; t < Tw; t += 64) sum += cdf[t + 1] + 1e-5f;      // :19-20
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-            float run = 0.0f;
-            for (uint32_t t0 = 0; t0 < Tw; t0 += 64) {
-                const uint32_t t = t0 + lane;
-                const float pdf = t < Tw ? (cdf[t + 1] + 1e-5f) / sum : 0.0f;
-                float incl = pdf;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const float o = __shfl_up(incl, off, 64);
-                    if (lane >= (uint32_t)off) incl += o;
-                }
-                if (t < Tw) cdf[t + 1] = run + incl;                                 // :21
-                run += __shfl(incl, 63, 64);
-            }
-            if (lane == 0) cdf[0] = 0.0f;                                            // :22
-            NGP_WAVE_SYNC();
-            for (uint32_t sI = lane; sI < U; sI += 64) {
-                const float us = u_det[sI];
-                uint32_t lo = 0, hi = Tb;                                            // searchsorted(cdf, u, right=True)
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (cdf[mid] > us) hi = mid; else lo = mid + 1;
-                }
-                const uint32_t below = lo > 0 ? lo - 1 : 0, above = lo < Tb - 1 ? lo : Tb - 1;   // :33-34
-                float denom = cdf[above] - cdf[below];                               // :41
-                if (denom < 1e-5f) denom = 1.0f;                                     // :42
-                const float tq = (us - cdf[below]) / denom;                          // :43
-                const float b0 = zc[below] + 0.5f * (zc[below + 1] - zc[below]);     // :174 mid points
-                const float b1 = zc[above] + 0.5f * (zc[above + 1] - zc[above]);
-                zf[sI] = b0 + tq * (b1 - b0);                                        // :44
-                if (zf_out) zf_out[((size_t)g_grp * U + sI) * 16 + g_c] = zf[sI];
-            }
-            NGP_WAVE_SYNC();
-            if (zf_out) break;
-        }
-        if (zf_out) { NGP_WAVE_SYNC(); continue; }
-        // ---- 4. merge: rank of every element in the other run (coarse first on ties)
-        for (uint32_t k = lane; k < Tm; k += 64) {
-            float v, sg;
-            uint32_t pos;
-            if (k < T) {
-                v = zc[k]; sg = sc[k];
-                uint32_t lo = 0, hi = U;
-                while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (zf[mid] < v) lo = mid + 1; else hi = mid; }
-                pos = k + lo;
-            } else {
-                v = zf[k - T]; sg = sf[k - T];
-                uint32_t lo = 0, hi = T;
-                while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (zc[mid] <= v) lo = mid + 1; else hi = mid; }
-                pos = (k - T) + lo;
-            }
-            zm[pos] = v; sm[pos] = sg;
-        }
-        NGP_WAVE_SYNC();
-        // ---- 5. compositing over the merged samples (:206-244)
-        float carry = 1.0f;
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
-        for (uint32_t i0 = 0; i0 < Tm; i0 += 16) {
-            const uint32_t idx = i0 + c;
-            const bool valid = idx < Tm;
-            const uint32_t ii = valid ? idx : Tm - 1;
-            const float zv = zm[ii], sigma = sm[ii];
-            const float delta = (ii + 1 < Tm) ? zm[ii + 1] - zv : sample_dist;       // :206-207
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;
-            float incl = (1.0f - alpha) + 1e-15f;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl_in_tile = __shfl_up(incl, 1, 16);
-            const float w = alpha * (carry * (c == 0 ? 1.0f : excl_in_tile));        // :210
-            const bool masked = valid && w > 1e-4f;                                  // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
-                const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);
-                const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-                const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
-                float s_again;
-                _Float16 s16[4];
-                net_density<MODE>(na, Wlds, *lt, lane, x, y, z, s_again, s16);
-                net_color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (lane < 16 && valid) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;
-                a_agg += w * sigma;
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * Tm + idx;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-            }
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));
-            if (!dump && carry < 1e-10f) break;
-        }
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            a_ws += __shfl_xor(a_ws, off, 16); a_dep += __shfl_xor(a_dep, off, 16); a_agg += __shfl_xor(a_agg, off, 16);
-            a_r += __shfl_xor(a_r, off, 16); a_g += __shfl_xor(a_g, off, 16); a_b += __shfl_xor(a_b, off, 16);
-        }
-        if (lane == 0) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
-        NGP_WAVE_SYNC();      // the next ray overwrites the arrays
-    }
-#undef NGP_WAVE_SYNC
-}
-
-// ==========================================================================================
-// Differentiable `run`: the vector-Jacobian product of k_render_uniform with respect to the RAYS, map frozen.
-// What nav/estimator_helpers.py:191-225 (measurement_fn) differentiates -- <= 1024 chosen pixels x 512 samples, 100 Adam steps per
-// simulator step -- is d(image, depth) / d(rays_o, rays_d) through sampling -> hash grid -> sigma net -> SH -> colour net ->
-// compositing, with table and weights constant.  The reference (and this package's operator path) gets it from autograd over
-// ~60 kernels and [N, T, *] saved tensors; here it is ONE launch, one wave per ray, nothing saved by the forward pass:
-//
-//   pass 1  forward over the ray's tiles (as k_render_uniform): per sample sigma, transmittance T_i and the upstream gradient
-//           of its weight, g_i = dL/dw_i = G_img . rgb_i [w_i > 1e-4] + G_depth rel_i + G_ws + G_agg sigma_i, into LDS;
-//   scan    reverse scan over the samples: dL/dalpha_j = g_j T_j - (sum_{i>j} g_i w_i) / p_j  ->  dL/dsigma_j, in place;
-//   pass 2  per tile, recompute the network keeping every layer's activations in registers and walk it backwards with the
-//           TRANSPOSED weights (packed as MFMA A fragments by k_pack_weights_bwd: dH_prev^T = W^T dH^T, the same accumulator ->
-//           B-fragment trick as forward, so gradients never leave registers either): colour net -> (SH', geo) -> sigma net ->
-//           hash-grid input derivative from the corners already gathered -> clip -> (grad o, grad d), reduced over the ray.
-//
-// Rounding points follow the operator path: fp16 activations and activation gradients, fp32 MFMA accumulation, fp32 everywhere
-// outside the MLPs.
-// ==========================================================================================
-__host__ __device__ inline uint32_t bwd_halfs(uint32_t mm) { return 2048 + mm * 4096 + 2048; }
-
-// Transposed fragments.  Per net: [out layer: ob 4][lane][8] | [hidden layers, LAST first: ob 4][s 2][lane][8] | [in layer: ob 2][s 2][lane][8]
-//   out layer   : A[row = unit 16 ob + c][k(q, j)] = j < 4 ? W_out[4q + j][unit] : 0      (B fragment = the lane's own 4 output gradients)
-//   hidden layer: A[row = unit 16 ob + c of the layer BELOW][k = perm_hidden(q, j, s)] = W[perm_hidden(q, j, s)][that unit]
-//   in layer    : accumulator row 4 q' + r of block ob is the gradient of input feature phi(q', 4 ob + r), phi = perm_grid / perm_color:
-//                 A[row i][k = perm_hidden(q, j, s)] = W_in[perm_hidden(q, j, s)][phi(i >> 2, 4 ob + (i & 3))]
-__global__ void k_pack_weights_bwd(const _Float16* __restrict__ sig, uint32_t sig_mm, const _Float16* __restrict__ col, uint32_t col_mm,
-                                   _Float16* __restrict__ packed) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n_sig = bwd_halfs(sig_mm), n_col = bwd_halfs(col_mm);
-    if (e >= n_sig + n_col) return;
-    const bool is_col = e >= n_sig;
-    const uint32_t r = is_col ? e - n_sig : e;
-    const uint32_t mm = is_col ? col_mm : sig_mm;
-    const _Float16* src = is_col ? col : sig;
-    const uint32_t j = r & 7, lane = (r >> 3) & 63, c = lane & 15, q = lane >> 4;
-    const uint32_t w_hid = 2048, w_out = 2048 + mm * 4096;           // offsets inside the FFMLP-layout source blob
-    _Float16 v;
-    if (r < 2048) {                                                   // out layer [ob][lane][8]
-        const uint32_t ob = r >> 9;
-        v = j < 4 ? src[w_out + (4 * q + j) * 64 + 16 * ob + c] : (_Float16)0;
-    } else if (r < 2048 + mm * 4096) {                                // hidden layers, last first
-        const uint32_t rr = r - 2048, slot = rr >> 12, in = rr & 4095;
-        const uint32_t layer = mm - 1 - slot;
-        const uint32_t ob = in >> 10, st = (in >> 9) & 1;
-        v = src[w_hid + layer * 4096 + perm_hidden(q, j, st) * 64 + 16 * ob + c];
-    } else {                                                          // in layer [ob 2][s 2][lane][8]
-        const uint32_t in = r - 2048 - mm * 4096, ob = in >> 10, st = (in >> 9) & 1;
-        const uint32_t i = c, qq = i >> 2, jj = 4 * ob + (i & 3);
-        const uint32_t feat = is_col ? perm_color(qq, jj) : perm_grid(qq, jj);
-        v = src[perm_hidden(q, j, st) * 32 + feat];
-    }
-    packed[e] = v;
-}
-
-__device__ __forceinline__ void mlp_out_bwd(const half8* Wt, uint32_t lane, half8 g, f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wt[ob * 64 + lane], g, (f32x4){0, 0, 0, 0}, 0, 0, 0);
-}
-__device__ __forceinline__ void mlp_hidden_bwd(const half8* Wt, uint32_t lane, const half8 (&g)[2], f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int ob = 0; ob < 4; ob++) {
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wt[(ob * 2 + 0) * 64 + lane], g[0], (f32x4){0, 0, 0, 0}, 0, 0, 0);
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wt[(ob * 2 + 1) * 64 + lane], g[1], acc[ob], 0, 0, 0);
-    }
-}
-__device__ __forceinline__ void mlp_in_bwd(const half8* Wt, uint32_t lane, const half8 (&g)[2], f32x4 (&acc)[2]) {
-#pragma unroll
-    for (int ob = 0; ob < 2; ob++) {
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wt[(ob * 2 + 0) * 64 + lane], g[0], (f32x4){0, 0, 0, 0}, 0, 0, 0);
-        acc[ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wt[(ob * 2 + 1) * 64 + lane], g[1], acc[ob], 0, 0, 0);
-    }
-}
-// gradient through ReLU at the layer whose (post-activation) forward values are h: pass where h > 0; fp16 like the operator's buffers
-__device__ __forceinline__ void relu_mask_pack(const f32x4 (&acc)[4], const half8 (&h)[2], half8 (&g)[2]) {
-#pragma unroll
-    for (int st = 0; st < 2; st++)
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const _Float16 v = (_Float16)acc[2 * st + (jj >> 2)][jj & 3];
-            g[st][jj] = h[st][jj] > (_Float16)0 ? v : (_Float16)0;
-        }
-}
-
-// d SH_k / d (x, y, z) for k = 4q .. 4q + 3 contracted with g[4] (the closed forms of sh4_quarter differentiated)
-__device__ __forceinline__ void sh4_quarter_vjp(uint32_t q, float x, float y, float z, const float (&g)[4], float (&o)[3]) {
-    const float a = 0.48860251190291987f, b = 1.0925484305920792f, c2 = 2.0f * 0.94617469575755997f, e = 0.54627421529603959f,
-                f = 0.59004358992664352f, gg = 2.8906114426405538f, h = 0.45704579946446572f, k = 0.3731763325901154f, m = 1.4453057213202769f;
-    const float x2 = x * x, y2 = y * y, z2 = z * z;
-    if (q == 0) {
-        o[0] = -a * g[3]; o[1] = -a * g[1]; o[2] = a * g[2];
-    } else if (q == 1) {
-        o[0] = b * y * g[0] - b * z * g[3];
-        o[1] = b * x * g[0] - b * z * g[1];
-        o[2] = -b * y * g[1] + c2 * z * g[2] - b * x * g[3];
-    } else if (q == 2) {
-        o[0] = 2 * e * x * g[0] - 6 * f * x * y * g[1] + gg * y * z * g[2];
-        o[1] = -2 * e * y * g[0] + f * (-3 * x2 + 3 * y2) * g[1] + gg * x * z * g[2] + h * (1 - 5 * z2) * g[3];
-        o[2] = gg * x * y * g[2] - 10 * h * y * z * g[3];
-    } else {
-        o[0] = h * (1 - 5 * z2) * g[1] + 2 * m * x * z * g[2] + f * (-3 * x2 + 3 * y2) * g[3];
-        o[1] = -2 * m * y * z * g[2] + 6 * f * x * y * g[3];
-        o[2] = k * (15 * z2 - 3) * g[0] - 10 * h * x * z * g[1] + m * (x2 - y2) * g[2];
-    }
-}
-
-struct GradArgs {
-    const float *rays_o, *rays_d, *nears, *fars, *lin;
-    const float *g_image, *g_depth, *g_ws, *g_agg;      // upstream gradients of the four per-ray outputs (g_depth / g_ws / g_agg may be NULL)
-    float *grad_o, *grad_d;
-    const void* packed_bwd;
-    uint32_t N, T;
-    float aabb_lo, aabb_hi;
-    float* dump;    // diagnostics (ngp_debug_set_grad_dump): [N][T][4] = sigma, transmittance, dL/dw, dL/dsigma per sample; NULL = off
-};
-
-constexpr int kGradWaves = 8;
-constexpr uint32_t kGradMaxT = 1024;
-
-// GW waves (= rays in flight) per workgroup, one workgroup per CU: 8, or 4 -- one wave per SIMD with the whole register file, which the
-// fp32 form needs (its tape is twice the size) and which also spreads a small batch over all CUs (the pose estimator's 1024 rays are
-// 128 workgroups of 8 but 256 of 4)
-template <class NET, int GW>
-__global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, GridLevels lv, GradArgs ga) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t w_bytes = NET::w_bytes(na);
-    const size_t wb_bytes = NET::wb_bytes(na);
-    const char* Wlds = smem;
-    char* Wb = smem + w_bytes;
-    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + w_bytes + wb_bytes);
-    float* store = reinterpret_cast<float*>(smem + w_bytes + wb_bytes + sizeof(LevelTab));
-    {   // transposed fragments next to the forward ones
-        const uint4* src = reinterpret_cast<const uint4*>(ga.packed_bwd);
-        uint4* dst = reinterpret_cast<uint4*>(Wb);
-        for (uint32_t i = threadIdx.x; i < wb_bytes / 16; i += blockDim.x) dst[i] = src[i];
-    }
-    stage_block(na, lv, smem, lt, w_bytes);
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const uint32_t T = ga.T;
-    float* s_sig = store + (size_t)wid * 3 * T;      // pass 1: sigma (raw);  after the scan: dL/dsigma
-    float* s_g = s_sig + T;                          // pass 1: dL/dw;        after the scan: w [w > 1e-4] (the scale of dL/drgb)
-    float* s_T = s_g + T;                            // transmittance before the sample
-
-    for (uint32_t ray = blockIdx.x * GW + wid; ray < ga.N; ray += gridDim.x * GW) {
-        const float ox = ga.rays_o[(size_t)ray * 3], oy = ga.rays_o[(size_t)ray * 3 + 1], oz = ga.rays_o[(size_t)ray * 3 + 2];
-        const float dx = ga.rays_d[(size_t)ray * 3], dy = ga.rays_d[(size_t)ray * 3 + 1], dz = ga.rays_d[(size_t)ray * 3 + 2];
-        const float near = ga.nears[ray], far = ga.fars[ray], span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);
-        const float Gi0 = ga.g_image[(size_t)ray * 3], Gi1 = ga.g_image[(size_t)ray * 3 + 1], Gi2 = ga.g_image[(size_t)ray * 3 + 2];
-        const float Gd = ga.g_depth ? ga.g_depth[ray] : 0.0f, Gw = ga.g_ws ? ga.g_ws[ray] : 0.0f, Ga = ga.g_agg ? ga.g_agg[ray] : 0.0f;
-        // ---------------- pass 1: forward, exactly k_render_uniform's arithmetic ----------------
-        float carry = 1.0f;
-        uint32_t t_end = T;                                           // samples >= t_end carry no weight (transmittance below 1e-10)
-        for (uint32_t i0 = 0; i0 < T; i0 += 16) {
-            const uint32_t idx = i0 + c;
-            const bool valid = idx < T;
-            const uint32_t ii = valid ? idx : T - 1;
-            const float zv = near + span * ga.lin[ii];
-            const float x = clampf(ox + dx * zv, ga.aabb_lo, ga.aabb_hi), y = clampf(oy + dy * zv, ga.aabb_lo, ga.aabb_hi),
-                        z = clampf(oz + dz * zv, ga.aabb_lo, ga.aabb_hi);
-            float sigma;
-            typename NET::geo_t s16[4];
-            NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-            const float z_next = (ii + 1 < T) ? near + span * ga.lin[ii + 1] : 0.0f;
-            const float delta = (ii + 1 < T) ? z_next - zv : sample_dist;
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;
-            const float p = (1.0f - alpha) + 1e-15f;
-            float incl = p;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl = __shfl_up(incl, 1, 16);
-            const float Tr = carry * (c == 0 ? 1.0f : excl);
-            const float w = alpha * Tr;
-            const bool masked = valid && w > 1e-4f;
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked && lane < 16) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (lane < 16 && valid) {
-                const float qz = (zv - near) / span;
-                const float rel = qz != qz ? 0.0f : fminf(1.0f, fmaxf(0.0f, qz));
-                s_sig[idx] = sigma;
-                s_T[idx] = Tr;
-                s_g[idx] = fmaf(Gi0, cr, fmaf(Gi1, cg, Gi2 * cb)) + Gd * rel + Gw + Ga * sigma;
-            }
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));   // quarter 0's value, for the whole wave
-            if (carry < 1e-10f) { t_end = (i0 + 16 < T) ? i0 + 16 : T; break; }
-        }
-        __builtin_amdgcn_wave_barrier();
-        // ---------------- reverse scan: dL/dsigma_j and the colour scale w_j [w_j > 1e-4] ----------------
-        float suffix = 0.0f;
-        for (uint32_t c0 = ((t_end + 63) / 64) * 64; c0 > 0; c0 -= 64) {
-            const uint32_t t = c0 - 64 + lane;
-            const bool on = t < t_end;
-            const uint32_t tt = on ? t : t_end - 1;
-            const float zv = near + span * ga.lin[tt];
-            const float delta = (tt + 1 < T) ? (near + span * ga.lin[tt + 1]) - zv : sample_dist;
-            const float sg = s_sig[tt], Tr = s_T[tt];
-            const float e = expf(((-delta) * na.density_scale) * sg);
-            const float alpha = 1.0f - e, p = (1.0f - alpha) + 1e-15f, w = alpha * Tr;
-            const float g = on ? s_g[tt] : 0.0f;
-            const float gw = on ? g * w : 0.0f;
-            float inc = gw;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float o = __shfl_down(inc, off, 64);
-                if (lane + (uint32_t)off < 64) inc += o;
-            }
-            const float later = suffix + (inc - gw);
-            suffix += __shfl(inc, 0, 64);
-            __builtin_amdgcn_wave_barrier();
-            if (on) {
-                const float dsg = (g * Tr - later / p) * ((delta * na.density_scale) * e) + Ga * w;
-                if (ga.dump) {
-                    float* o4 = ga.dump + ((size_t)ray * T + t) * 4;
-                    o4[0] = sg; o4[1] = Tr; o4[2] = g; o4[3] = dsg;
-                }
-                s_sig[t] = dsg;
-                s_g[t] = w > 1e-4f ? w : 0.0f;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        // ---------------- pass 2: network backward per tile ----------------
-        float a_o[3] = {0, 0, 0}, a_d[3] = {0, 0, 0};
-        const float G[3] = {Gi0, Gi1, Gi2};
-        for (uint32_t i0 = 0; i0 < t_end; i0 += 16) {
-            const uint32_t idx = i0 + c;
-            const bool valid = idx < t_end;
-            const uint32_t ii = valid ? idx : t_end - 1;
-            const float zv = near + span * ga.lin[ii];
-            const float ux = ox + dx * zv, uy = oy + dy * zv, uz = oz + dz * zv;          // before the clip (for its derivative)
-            const float x = clampf(ux, ga.aabb_lo, ga.aabb_hi), y = clampf(uy, ga.aabb_lo, ga.aabb_hi), z = clampf(uz, ga.aabb_lo, ga.aabb_hi);
-            // ---- forward recompute, keeping corners and activations
-            typename NET::Tape tape;
-            typename NET::geo_t s16[4];
-            NET::density_tape(na, Wlds, *lt, lane, x, y, z, tape, s16);
-            const float wscale = valid ? s_g[ii] : 0.0f;            // w [w > 1e-4]: zero when the reference does not evaluate the colour
-            const float dsig = valid ? s_sig[ii] : 0.0f;
-            f32x4 gso = {0, 0, 0, 0};                               // dL/d(sigma-net outputs 4q .. 4q+3) of sample c
-            float gdir[3] = {0, 0, 0};
-            if (__ballot(wscale != 0.0f && lane < 16) != 0ull) {
-                const float wsc = __shfl(wscale, c, 64);             // lanes 0..15 hold the per-sample values: broadcast to the sample's 4 lanes
-                NET::color_vjp(na, Wlds, Wb, lane, dx, dy, dz, s16, wsc, G, gdir, gso);
-            }
-            // ---- sigma: trunc_exp backward (activation.py:12-17) on output 0
-            {
-                const float ds = __shfl(dsig, c, 64);
-                if (q == 0) gso[0] = ds * expf(fminf(15.0f, fmaxf(-15.0f, (float)s16[0])));
-            }
-            float gx[3];
-            NET::density_vjp(na, Wb, lane, tape, gso, gx);
-            // reduce the four level groups of a sample, then x = clip(o + d z): (x + bound) / (2 bound) upstream
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                gx[d] += __shfl_xor(gx[d], 16, 64);
-                gx[d] += __shfl_xor(gx[d], 32, 64);
-                gdir[d] += __shfl_xor(gdir[d], 16, 64);
-                gdir[d] += __shfl_xor(gdir[d], 32, 64);
-            }
-            if (lane < 16 && valid) {
-                const float uu[3] = {ux, uy, uz};
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    const float a = uu[d] > ga.aabb_lo ? 1.0f : (uu[d] == ga.aabb_lo ? 0.5f : 0.0f);
-                    const float v = fmaxf(uu[d], ga.aabb_lo);
-                    const float b = v < ga.aabb_hi ? 1.0f : (v == ga.aabb_hi ? 0.5f : 0.0f);
-                    const float gxd = gx[d] * na.inv_two_bound * (a * b);
-                    a_o[d] += gxd;
-                    a_d[d] = fmaf(gxd, zv, a_d[d]) + gdir[d];       // the direction also enters through SH (dirs = rays_d per sample)
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) { a_o[d] += __shfl_xor(a_o[d], off, 16); a_d[d] += __shfl_xor(a_d[d], off, 16); }
-            if (lane == 0) { ga.grad_o[(size_t)ray * 3 + d] = a_o[d]; ga.grad_d[(size_t)ray * 3 + d] = a_d[d]; }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
 
 // one bit per aligned 8-byte word (= 64 Morton-consecutive cells = one 4x4x4 block) of the occupancy bitfield
 __global__ void __launch_bounds__(256) k_build_coarse(const unsigned long long* __restrict__ bitfield64, uint32_t n_words,
@@ -3273,167 +1110,17 @@ struct ngp_render_ctx {
     uint32_t* debug_sample_hash = nullptr;
 };
 
-// Diagnostics state.  The process-wide setters (ngp_debug_*) only change the DEFAULT; a context can carry its own
-// (ngp_render_ctx_set_debug), and every render call takes ONE snapshot when it starts, so concurrent calls on other host threads /
-// streams (pipeline.py) never see a half-changed set and never change under a running call.
-struct DebugState {
-    int flags = 0;
-    unsigned long long* stamps = nullptr;
-    uint32_t* sample_hash = nullptr;
-    bool coarse_off() const { return (flags & 2) != 0; }
-    bool sort_off() const { return (flags & 4) != 0; }
-    bool lin_off() const { return (flags & 8) != 0; }
-    bool jump_off() const { return (flags & 1) != 0; }
-    bool spec_off() const { return (flags & 256) != 0; }
-    bool tile_off() const { return (flags & 8192) != 0; }
-    bool pre_verdict_off() const { return (flags & 16384) != 0; }
-    bool narrow_items_off() const { return (flags & 32768) != 0; }
-    bool prefix_replay_off() const { return (flags & 65536) != 0; }
-    bool wave_march_off() const { return (flags & 131072) != 0; }
-    bool cell_runs_off() const { return (flags & 262144) != 0; }
-    uint32_t spec_safety_x2() const { return ((uint32_t)flags >> 9) & 15u; }   // 0: kSpecSafetyX2
-    uint32_t shrink() const { return ((uint32_t)flags >> 4) & 15u; }
-};
-static std::mutex g_debug_mu;
-static DebugState g_debug_default;
-static float* g_grad_dump = nullptr;     // ngp_debug_set_grad_dump
+// this context's own diagnostics state (ngp_render_ctx_set_debug), else the process default
 static DebugState debug_snapshot(const ngp_render_ctx* ctx) {
     if (ctx && ctx->has_debug) {
         DebugState d;
         d.flags = ctx->debug_flags; d.stamps = ctx->debug_stamps; d.sample_hash = ctx->debug_sample_hash;
         return d;
     }
-    std::lock_guard<std::mutex> lk(g_debug_mu);
-    return g_debug_default;
+    return ngp::debug_snapshot();
 }
-
-// per-cell corner records: record r of level l (cells x-fastest, `res` per axis) = the table entries of the cell's 8 corners in
-// the gather's corner order (bit 0 of the corner index = x).  One thread per record.
-__global__ void __launch_bounds__(256) k_build_cells(const uint32_t* __restrict__ table, GridLevels lv, uint32_t level, uint32_t n_cells,
-                                                     uint4* __restrict__ out) {
-    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_cells) return;
-    const uint32_t S = lv.resolution[level];
-    const uint32_t cx = r % S, cy = (r / S) % S, cz = r / (S * S);
-    const uint32_t size = lv.offset[level + 1] - lv.offset[level];
-    const bool hashed = lv.hashed[level] != 0;
-    const uint32_t a1 = hashed ? 2654435761u : lv.mul1[level], a2 = hashed ? 805459861u : lv.mul2[level];
-    const uint32_t* tab = table + lv.offset[level];
-    uint32_t v[8];
-#pragma unroll
-    for (int idx = 0; idx < 8; idx++) {
-        const uint32_t px = cx + (idx & 1), ty = (cy + ((idx >> 1) & 1)) * a1, tz = (cz + ((idx >> 2) & 1)) * a2;
-        uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
-        if (lv.mode[level] == 1) e &= size - 1;
-        else if (lv.mode[level] == 2) e %= size;
-        v[idx] = tab[e];
-    }
-    out[(size_t)r * 2] = make_uint4(v[0], v[1], v[2], v[3]);
-    out[(size_t)r * 2 + 1] = make_uint4(v[4], v[5], v[6], v[7]);
-}
-
-// records needed for the first n_levels levels (0 when they do not fit 32-bit record indices)
-static uint64_t cell_records(const GridLevels& lv, uint32_t n_levels, uint32_t* off) {
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n_levels; l++) {
-        if (off) off[l] = (uint32_t)total;
-        const uint64_t S = lv.resolution[l];
-        total += S * S * S;
-    }
-    return total < (1ull << 32) ? total : 0;
-}
-
-static bool needs_generic(const GridLevels& lv) {
-    for (int l = 0; l < 16; l++)
-        if (lv.mode[l] == 2) return true;
-    return false;
-}
-
-static int fill_net(const ngp_model* m, const DebugState& dbg, const _Float16* packed, NetArgs& na, GridLevels& lv) {
-    NGP_REQUIRE(m && m->embeddings && m->offsets_host && m->sigma_weights && m->color_weights, "ngp_model: null pointer");
-    NGP_REQUIRE(m->L == 16, "fused renderer: the hash grid must have 16 levels with 2 features (got L=%u)", m->L);
-    NGP_REQUIRE(m->sigma_hidden_mm <= 2 && m->color_hidden_mm <= 3, "fused renderer: at most 2 / 3 hidden matmuls (got %u / %u)",
-                m->sigma_hidden_mm, m->color_hidden_mm);
-    fill_levels(lv, m->offsets_host, 16, m->S, m->H_base, 3, m->gridtype, m->align_corners != 0);
-    na.table = reinterpret_cast<const uint32_t*>(m->embeddings);
-    na.packed = packed;
-    na.sig_mm = m->sigma_hidden_mm;
-    na.col_mm = m->color_hidden_mm;
-    na.bound = m->bound;
-    na.inv_two_bound = 1.0f / (2 * m->bound);
-    na.density_scale = m->density_scale;
-    na.align_corners = m->align_corners;
-    NGP_REQUIRE(m->precision <= NGP_PREC_F16_REF, "ngp_model: unknown precision %u", m->precision);
-    na.dbg_shrink = dbg.shrink() | (m->precision == NGP_PREC_F32 ? 256u : 0u) | (m->precision == NGP_PREC_F16_REF ? 512u : 0u);
-    na.cells = nullptr;
-    na.cell_steps = 0;
-    for (int l = 0; l < 16; l++) na.cell_off[l] = 0;
-    if (m->cell_tables && m->cell_levels) {
-        NGP_REQUIRE(m->cell_levels % 4 == 0 && m->cell_levels <= 16, "ngp_model: cell_levels must be 0, 4, 8, 12 or 16 (got %u)", m->cell_levels);
-        NGP_REQUIRE(cell_records(lv, m->cell_levels, na.cell_off) != 0, "ngp_model: the cell tables of %u levels exceed 2^32 records", m->cell_levels);
-        NGP_REQUIRE(((uintptr_t)m->cell_tables & 15) == 0, "ngp_model: cell_tables must be 16-byte aligned");
-        NGP_REQUIRE(!na.f32(), "ngp_model: per-cell records exist for the fp16 table only");
-        if (m->cell_levels == 12 && !needs_generic(lv)) {   // the kernels are specialised for exactly 12 expanded levels
-            na.cells = reinterpret_cast<const uint4*>(m->cell_tables);
-            na.cell_steps = 3;
-        }
-    }
-    return NGP_OK;
-}
-
-static size_t weights_bytes(const NetArgs& na) { return net_w_bytes(na); }
-// Workgroups of a grid-strided launch: as many as are RESIDENT at once -- four 256-thread workgroups per CU, or what the LDS holds (the
-// fp32 weights take 40 KB per workgroup: three).  With more, the surplus of every CU runs as a second round at a fraction of the occupancy.
-static uint32_t resident_blocks(size_t lds) {
-    const uint32_t fit = (uint32_t)((160 * 1024) / (lds ? lds : 1));
-    return 256u * (fit > 4 ? 4u : (fit < 1 ? 1u : fit));
-}
-
-// kernel variant of a model: 0 / 1 / 2 = fp16 (AND-reduced indices, generic modulo, per-cell records), 3 / 4 = fp32 (AND, generic),
-// 5 / 6 / 7 = fp16 with the reference's corner rounding
-static int net_variant(const NetArgs& na, const GridLevels& lv) {
-    const bool gen = needs_generic(lv);
-    if (na.f32()) return gen ? 4 : 3;
-    return (gen ? 1 : (na.cells ? 2 : 0)) + (na.hacc() ? 5 : 0);
-}
-// runs STMT with NET bound to the policy class of `variant`
-#define NGP_WITH_NET(variant, ...)                                           \
-    switch (variant) {                                                       \
-        case 0: { using NET = NetF16<0>; __VA_ARGS__; } break;               \
-        case 1: { using NET = NetF16<1>; __VA_ARGS__; } break;               \
-        case 2: { using NET = NetF16<2>; __VA_ARGS__; } break;               \
-        case 3: { using NET = NetF32<0>; __VA_ARGS__; } break;               \
-        case 4: { using NET = NetF32<1>; __VA_ARGS__; } break;               \
-        case 5: { using NET = NetF16<0, true>; __VA_ARGS__; } break;         \
-        case 6: { using NET = NetF16<1, true>; __VA_ARGS__; } break;         \
-        default: { using NET = NetF16<2, true>; __VA_ARGS__; } break;        \
-    }
 
 extern "C" {
-
-size_t ngp_cell_tables_bytes(const ngp_model* model, uint32_t n_levels) {
-    if (!model || !model->offsets_host || model->L != 16 || n_levels > 16) return 0;
-    GridLevels lv;
-    fill_levels(lv, model->offsets_host, 16, model->S, model->H_base, 3, model->gridtype, model->align_corners != 0);
-    return (size_t)cell_records(lv, n_levels, nullptr) * 32;
-}
-
-int ngp_build_cell_tables(const ngp_model* model, uint32_t n_levels, void* out, ngp_stream_t stream) {
-    NGP_REQUIRE(model && model->embeddings && model->offsets_host && out, "build_cell_tables: null pointer");
-    NGP_REQUIRE(model->L == 16 && n_levels % 4 == 0 && n_levels >= 4 && n_levels <= 16, "build_cell_tables: n_levels must be 4, 8, 12 or 16");
-    NGP_REQUIRE(((uintptr_t)out & 15) == 0, "build_cell_tables: the buffer must be 16-byte aligned");
-    GridLevels lv;
-    fill_levels(lv, model->offsets_host, 16, model->S, model->H_base, 3, model->gridtype, model->align_corners != 0);
-    uint32_t off[16];
-    NGP_REQUIRE(cell_records(lv, n_levels, off) != 0, "build_cell_tables: %u levels exceed 2^32 records", n_levels);
-    for (uint32_t l = 0; l < n_levels; l++) {
-        const uint64_t S = lv.resolution[l];
-        const uint32_t n = (uint32_t)(S * S * S);
-        k_build_cells<<<div_up(n, 256), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const uint32_t*>(model->embeddings), lv, l, n,
-                                                                       reinterpret_cast<uint4*>(out) + (size_t)off[l] * 2);
-    }
-    return check_launch("build_cell_tables");
-}
 
 int ngp_render_ctx_create(uint32_t max_rays, ngp_render_ctx** out) {
     NGP_REQUIRE(out, "render_ctx_create: null out pointer");
@@ -3784,59 +1471,6 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     return NGP_OK;
 }
 
-int ngp_debug_set_stamps(unsigned long long* device_buf) {
-    std::lock_guard<std::mutex> lk(g_debug_mu);
-    g_debug_default.stamps = device_buf;
-    return NGP_OK;
-}
-
-int ngp_debug_set_sample_hash(uint32_t* device_buf) {
-    std::lock_guard<std::mutex> lk(g_debug_mu);
-    g_debug_default.sample_hash = device_buf;
-    return NGP_OK;
-}
-
-int ngp_debug_disable_march_queue(int off) {
-    std::lock_guard<std::mutex> lk(g_debug_mu);
-    g_debug_default.flags = off;
-    return NGP_OK;
-}
-
-int ngp_debug_fused_features(const ngp_model* model, const float* xyzs, uint32_t M, int operator_rounding, uint16_t* features, ngp_stream_t stream) {
-    if (M == 0) return NGP_OK;
-    NGP_REQUIRE(xyzs && features, "debug_fused_features: null pointer");
-    NGP_REQUIRE(model && model->packed_weights, "debug_fused_features: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
-    uint32_t blocks = div_up(div_up(M, 16), 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
-    if (na.f32()) {   // `features` is float [M, 32] then; one arithmetic only (the operator's)
-        if (needs_generic(lv)) k_debug_features32<1><<<blocks, 256, lds, s>>>(na, lv, xyzs, M, (float*)features);
-        else k_debug_features32<0><<<blocks, 256, lds, s>>>(na, lv, xyzs, M, (float*)features);
-        return check_launch("debug_fused_features");
-    }
-    const int mode = needs_generic(lv) ? 1 : (na.cells ? 2 : 0);
-#define NGP_DBG_FEAT(MODE_, HA_)                                                                              \
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_debug_features<MODE_, HA_>), 96 * 1024);               \
-    k_debug_features<MODE_, HA_><<<blocks, 256, lds, s>>>(na, lv, xyzs, M, (_Float16*)features)
-    if (operator_rounding) {
-        if (mode == 1) { NGP_DBG_FEAT(1, true); } else if (mode == 2) { NGP_DBG_FEAT(2, true); } else { NGP_DBG_FEAT(0, true); }
-    } else {
-        if (mode == 1) { NGP_DBG_FEAT(1, false); } else if (mode == 2) { NGP_DBG_FEAT(2, false); } else { NGP_DBG_FEAT(0, false); }
-    }
-#undef NGP_DBG_FEAT
-    return check_launch("debug_fused_features");
-}
-
-int ngp_debug_set_grad_dump(float* device_buf) {
-    g_grad_dump = device_buf;
-    return NGP_OK;
-}
-
 int ngp_render_ctx_set_debug(ngp_render_ctx* ctx, int enable, int flags, unsigned long long* stamps, uint32_t* sample_hash) {
     NGP_REQUIRE(ctx, "render_ctx_set_debug: null context");
     ctx->has_debug = enable != 0;
@@ -3844,396 +1478,6 @@ int ngp_render_ctx_set_debug(ngp_render_ctx* ctx, int enable, int flags, unsigne
     ctx->debug_stamps = stamps;
     ctx->debug_sample_hash = sample_hash;
     return NGP_OK;
-}
-
-size_t ngp_packed_weights_bytes(void) { return (size_t)(sig_halfs(2) + sig_halfs(3)) * 4; }   // (sized for the fp32 form; fp16 uses half of it)
-
-int ngp_pack_weights(const ngp_model* model, void* out, ngp_stream_t stream) {
-    NGP_REQUIRE(model && model->sigma_weights && model->color_weights && out, "pack_weights: null pointer");
-    NGP_REQUIRE(model->sigma_hidden_mm <= 2 && model->color_hidden_mm <= 3, "pack_weights: at most 2 / 3 hidden matmuls (got %u / %u)",
-                model->sigma_hidden_mm, model->color_hidden_mm);
-    NGP_REQUIRE(((uintptr_t)out & 15) == 0, "pack_weights: the buffer must be 16-byte aligned");
-    const uint32_t n_packed = sig_halfs(model->sigma_hidden_mm) + sig_halfs(model->color_hidden_mm);
-    if (model->precision == NGP_PREC_F32)
-        k_pack_weights_f32<<<div_up(n_packed, 256), 256, 0, (hipStream_t)stream>>>((const float*)model->sigma_weights, model->sigma_hidden_mm,
-                                                                                   (const float*)model->color_weights, model->color_hidden_mm,
-                                                                                   (float*)out);
-    else
-        k_pack_weights<<<div_up(n_packed, 256), 256, 0, (hipStream_t)stream>>>((const _Float16*)model->sigma_weights, model->sigma_hidden_mm,
-                                                                               (const _Float16*)model->color_weights, model->color_hidden_mm,
-                                                                               (_Float16*)out);
-    return check_launch("pack_weights");
-}
-
-int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t N,
-                       uint32_t T, const float* lin, float* weights_sum, float* depth, float* image, float* aggregated_density,
-                       uint32_t dump_begin, float* sigmas, float* rgbs, uint32_t frame_width, ngp_stream_t stream) {
-    if (N == 0) return NGP_OK;
-    NGP_REQUIRE(rays_o && rays_d && nears && fars && lin && weights_sum && depth && image && aggregated_density, "render_uniform: null pointer");
-    NGP_REQUIRE((sigmas == nullptr) == (rgbs == nullptr), "render_uniform: sigmas and rgbs must both be given or both NULL");
-    NGP_REQUIRE(T >= 1, "render_uniform: num_steps must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    // No scratch of the library's own: the fragment-major weights are the caller's, packed once per parameter version
-    // (a process-wide buffer here would be shared by calls that run concurrently on different streams with different models)
-    NGP_REQUIRE(model && model->packed_weights, "render_uniform: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    NetArgs na;
-    GridLevels lv;
-    const DebugState dbg = debug_snapshot(nullptr);
-    int rc = fill_net(model, dbg, (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
-    NGP_REQUIRE(lds <= 96 * 1024, "render_uniform: the packed weights need %zu bytes of LDS", lds);
-    const int variant = net_variant(na, lv);
-    uint32_t blocks = div_up(N, 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);   // each wave strides over rays
-    ProfScope prof("render_uniform", s, (double)N * T);
-    // tiles across sixteen neighbouring rays (twice the per-sample rate) once there are enough groups of sixteen to occupy the chip;
-    // a pose-estimator batch (1024 scattered pixels, every ray dumped) keeps one ray per wave
-    const bool per_ray = getenv("NGP_UNIFORM_PER_RAY") != nullptr;            // diagnostics (read per call: tests switch it): tiles along one ray for every size
-    const uint32_t x16_min = getenv("NGP_UNIFORM_X16_MIN") ? (uint32_t)atoi(getenv("NGP_UNIFORM_X16_MIN")) : kUniformX16MinRays;
-    if (!per_ray && N >= x16_min) {
-        // frame_width (scheduling hint, results do not depend on it): the rays are the pixels of row-major frames this wide -> a
-        // group is a 4x4-pixel block instead of a 1x16 strip (its sixteen rays are closer together and end at more similar depths)
-        uint32_t fw = frame_width;
-        if (fw && (fw % 4 != 0 || N % (4 * fw) != 0)) fw = 0;
-        uint32_t gb = div_up(div_up(N, 16), 4);
-        // as many workgroups as are RESIDENT at once (each strides over the groups): four per CU, or what the LDS holds -- the fp32
-        // weights take 40 KB per workgroup, three fit, and with 1024 workgroups the fourth of every CU ran as a second round at a third
-        // of the occupancy (800x800 x 512 samples, fp32: 8.01 -> 7.56 ms; NGP_UNIFORM_BLOCKS fixes the count for an A/B)
-        static const uint32_t gb_env = getenv("NGP_UNIFORM_BLOCKS") ? (uint32_t)atoi(getenv("NGP_UNIFORM_BLOCKS")) : 0u;
-        const uint32_t gb_cap = gb_env ? gb_env : resident_blocks(lds);
-        if (gb > gb_cap) gb = gb_cap;
-        NGP_WITH_NET(variant, {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NET>), 96 * 1024);
-            k_render_uniform_x16<NET><<<gb, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density,
-                                                           dump_begin, sigmas, rgbs, -model->bound, model->bound, fw, dbg.stamps, nullptr, nullptr);
-        });
-        return check_launch("render_uniform");
-    }
-    NGP_WITH_NET(variant, {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform<NET>), 96 * 1024);
-        k_render_uniform<NET><<<blocks, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density,
-                                                       dump_begin, sigmas, rgbs, -model->bound, model->bound);
-    });
-    return check_launch("render_uniform");
-}
-
-// sigma of the coarse pass [N, T], depths and sigma of the fine pass [N, U] x 2 (fp32), the sigma net's outputs of both [N, T + U, 16] (fp16)
-static size_t upsample_workspace_bytes(uint32_t N, uint32_t T, uint32_t U) {
-    const size_t Np = ((size_t)N + 15) / 16 * 16;          // whole groups of sixteen rays
-    return Np * (((size_t)T + 2 * (size_t)U) * sizeof(float) + ((size_t)T + U) * 16 * sizeof(_Float16));
-}
-size_t ngp_render_upsample_workspace(uint32_t N, uint32_t T, uint32_t U) {
-    return N >= kUniformX16MinRays ? upsample_workspace_bytes(N, T, U) : 0;
-}
-
-int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t N,
-                        uint32_t T, uint32_t U, const float* lin, const float* u, float* weights_sum, float* depth, float* image,
-                        float* aggregated_density, uint32_t dump_begin, float* sigmas, float* rgbs, uint32_t frame_width, void* workspace,
-                        size_t workspace_bytes, ngp_stream_t stream) {
-    if (N == 0) return NGP_OK;
-    NGP_REQUIRE(rays_o && rays_d && nears && fars && lin && u && weights_sum && depth && image && aggregated_density, "render_upsample: null pointer");
-    NGP_REQUIRE((sigmas == nullptr) == (rgbs == nullptr), "render_upsample: sigmas and rgbs must both be given or both NULL");
-    NGP_REQUIRE(T >= 3 && U >= 1, "render_upsample: num_steps >= 3 and upsample_steps >= 1 (got %u, %u)", T, U);
-    hipStream_t s = (hipStream_t)stream;
-    NGP_REQUIRE(model && model->packed_weights, "render_upsample: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    NGP_REQUIRE(!na.f32(), "render_upsample: built for the fp16 network (ngp_model::precision == NGP_PREC_F16)");
-    const size_t fixed = weights_bytes(na) + sizeof(LevelTab), per_wave = ((size_t)5 * T + (size_t)4 * U) * sizeof(float);
-    const size_t budget = 160 * 1024 - 1024;
-    NGP_REQUIRE(fixed + per_wave <= budget, "render_upsample: num_steps %u + upsample_steps %u need %zu bytes of LDS per ray, %zu are available", T, U,
-                per_wave, budget - fixed);
-    uint32_t waves = (uint32_t)((budget - fixed) / per_wave);
-    waves = waves > 4 ? 4 : waves;
-    const size_t lds = fixed + waves * per_wave;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<0>), 160 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<1>), 160 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<2>), 160 * 1024);
-    uint32_t blocks = div_up(N, waves);
-    if (blocks > 1024) blocks = 1024;
-    ProfScope prof("render_upsample", s, (double)N * (T + U));
-    const int mode = needs_generic(lv) ? 1 : (na.cells ? 2 : 0);
-    uint32_t fw = frame_width;
-    if (fw && (fw % 4 != 0 || N % (4 * fw) != 0)) fw = 0;
-    auto per_ray = [&](const float* sc_in, float* zf_out) {
-        if (mode == 1)
-            k_render_upsample<1><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-        else if (mode == 2)
-            k_render_upsample<2><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-        else
-            k_render_upsample<0><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-    };
-    const size_t need = upsample_workspace_bytes(N, T, U);
-    if (!(workspace && workspace_bytes >= need && N >= kUniformX16MinRays && getenv("NGP_UPSAMPLE_PER_RAY") == nullptr)) {
-        per_ray(nullptr, nullptr);      // everything along the ray in one launch
-        return check_launch("render_upsample");
-    }
-    // Large batches: four launches through the caller's scratch (group-major arrays, see k_render_uniform_x16<DENS>).  The two density
-    // passes take their tiles ACROSS sixteen neighbouring rays (twice the per-sample rate of tiles along a ray) and keep the sigma
-    // net's outputs; the per-ray kernel resamples between them; merge + compositing run across the rays as well, colour net only.
-    const size_t Np = ((size_t)N + 15) / 16 * 16;
-    float* sc = reinterpret_cast<float*>(workspace);
-    float* zf = sc + Np * T;
-    float* sf = zf + Np * U;
-    _Float16* gc = reinterpret_cast<_Float16*>(sf + Np * U);
-    _Float16* gf = gc + Np * T * 16;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<0>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<1>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<2>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<0>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<1>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<2>), 96 * 1024);
-    uint32_t gb = div_up(div_up(N, 16), 4);
-    if (gb > 1024) gb = 1024;
-    auto density = [&](uint32_t n, const float* z_in, float* out, _Float16* geo) {
-        if (mode == 1)
-            k_render_uniform_x16<NetF16<1>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
-        else if (mode == 2)
-            k_render_uniform_x16<NetF16<2>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
-        else
-            k_render_uniform_x16<NetF16<0>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
-    };
-    density(T, nullptr, sc, gc);
-    per_ray(sc, zf);
-    density(U, zf, sf, gf);
-    if (mode == 1)
-        k_composite_merged_x16<1><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
-    else if (mode == 2)
-        k_composite_merged_x16<2><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
-    else
-        k_composite_merged_x16<0><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
-    return check_launch("render_upsample");
-}
-
-size_t ngp_packed_weights_bwd_bytes(void) {      // (sized for whichever form is larger)
-    const size_t h = (size_t)(bwd_halfs(2) + bwd_halfs(3)) * 2, f = (size_t)(bwd_floats(2) + bwd_floats(3)) * 4;
-    return h > f ? h : f;
-}
-
-int ngp_pack_weights_bwd(const ngp_model* model, void* out, ngp_stream_t stream) {
-    NGP_REQUIRE(model && model->sigma_weights && model->color_weights && out, "pack_weights_bwd: null pointer");
-    NGP_REQUIRE(model->sigma_hidden_mm <= 2 && model->color_hidden_mm <= 3, "pack_weights_bwd: at most 2 / 3 hidden matmuls (got %u / %u)",
-                model->sigma_hidden_mm, model->color_hidden_mm);
-    NGP_REQUIRE(((uintptr_t)out & 15) == 0, "pack_weights_bwd: the buffer must be 16-byte aligned");
-    if (model->precision == NGP_PREC_F32) {
-        const uint32_t n = bwd_floats(model->sigma_hidden_mm) + bwd_floats(model->color_hidden_mm);
-        k_pack_weights_bwd_f32<<<div_up(n, 256), 256, 0, (hipStream_t)stream>>>((const float*)model->sigma_weights, model->sigma_hidden_mm,
-                                                                                (const float*)model->color_weights, model->color_hidden_mm, (float*)out);
-    } else {
-        const uint32_t n = bwd_halfs(model->sigma_hidden_mm) + bwd_halfs(model->color_hidden_mm);
-        k_pack_weights_bwd<<<div_up(n, 256), 256, 0, (hipStream_t)stream>>>((const _Float16*)model->sigma_weights, model->sigma_hidden_mm,
-                                                                            (const _Float16*)model->color_weights, model->color_hidden_mm, (_Float16*)out);
-    }
-    return check_launch("pack_weights_bwd");
-}
-
-// the fp32 backward kernels keep at most 1 / 2 hidden layers' activations (NetF32::Tape; nerf/network.py has 0 / 1)
-static bool bwd_shape_ok(const NetArgs& na) { return !na.f32() || (na.sig_mm <= NetF32<0>::kMaxSigMM && na.col_mm <= NetF32<0>::kMaxColMM); }
-
-size_t ngp_render_uniform_backward_lds(const ngp_model* model, uint32_t T) {
-    if (!model) return 0;
-    NetArgs na = {};
-    na.sig_mm = model->sigma_hidden_mm; na.col_mm = model->color_hidden_mm; na.dbg_shrink = model->precision == NGP_PREC_F32 ? 256u : 0u;
-    if (!bwd_shape_ok(na)) return (size_t)-1;
-    const size_t wb = na.f32() ? NetF32<0>::wb_bytes(na) : NetF16<0>::wb_bytes(na);
-    return net_w_bytes(na) + wb + sizeof(LevelTab) + (size_t)(na.f32() ? 4 : kGradWaves) * 3 * T * 4;
-}
-
-int ngp_render_uniform_backward(const ngp_model* model, const void* packed_weights_bwd, const float* rays_o, const float* rays_d, const float* nears,
-                                const float* fars, uint32_t N, uint32_t T, const float* lin, const float* grad_image, const float* grad_depth,
-                                const float* grad_weights_sum, const float* grad_aggregated_density, float* grad_rays_o, float* grad_rays_d,
-                                ngp_stream_t stream) {
-    if (N == 0) return NGP_OK;
-    NGP_REQUIRE(rays_o && rays_d && nears && fars && lin && grad_image && grad_rays_o && grad_rays_d, "render_uniform_backward: null pointer");
-    NGP_REQUIRE(model && model->packed_weights && packed_weights_bwd, "render_uniform_backward: packed weights missing (ngp_pack_weights / ngp_pack_weights_bwd)");
-    NGP_REQUIRE(T >= 1 && T <= kGradMaxT, "render_uniform_backward: 1 <= num_steps <= %u (got %u)", kGradMaxT, T);
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    NGP_REQUIRE(bwd_shape_ok(na), "render_uniform_backward: the fp32 form supports at most 1 / 2 hidden matmuls (got %u / %u)", na.sig_mm, na.col_mm);
-    GradArgs ga = {rays_o, rays_d, nears, fars, lin, grad_image, grad_depth, grad_weights_sum, grad_aggregated_density, grad_rays_o, grad_rays_d,
-                   packed_weights_bwd, N, T, -model->bound, model->bound, g_grad_dump};
-    const size_t lds = ngp_render_uniform_backward_lds(model, T);
-    NGP_REQUIRE(lds <= 160 * 1024, "render_uniform_backward: LDS budget exceeded (%zu bytes: at most %u samples per ray with this network)", lds, T);
-    ProfScope prof("render_uniform_backward", s, (double)N * T);
-    // four rays per workgroup: always in fp32; in fp16 while that still gives every CU at most two rounds of work
-    static const int force_gw = getenv("NGP_GRAD_WAVES") ? atoi(getenv("NGP_GRAD_WAVES")) : 0;     // diagnostics
-    const bool four = na.f32() || (force_gw ? force_gw == 4 : N <= 2048);
-    uint32_t blocks = div_up(N, four ? 4 : kGradWaves);
-    if (blocks > 512) blocks = 512;
-    NGP_WITH_NET(net_variant(na, lv), {
-        if (four) {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_bwd<NET, 4>), 160 * 1024);
-            k_render_uniform_bwd<NET, 4><<<blocks, 4 * 64, lds, s>>>(na, lv, ga);
-        } else {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_bwd<NET, kGradWaves>), 160 * 1024);
-            k_render_uniform_bwd<NET, kGradWaves><<<blocks, kGradWaves * 64, lds, s>>>(na, lv, ga);
-        }
-    });
-    return check_launch("render_uniform_backward");
-}
-
-int ngp_network_density(const ngp_model* model, const float* xyzs, uint32_t M, float* sigmas, float* geo_feat, ngp_stream_t stream) {
-    if (M == 0) return NGP_OK;
-    NGP_REQUIRE(xyzs && sigmas, "network_density: null pointer");
-    NGP_REQUIRE(model && model->packed_weights, "network_density: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
-    NGP_REQUIRE(lds <= 96 * 1024, "network_density: the packed weights need %zu bytes of LDS", lds);
-    uint32_t blocks = div_up(div_up(M, 16), 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
-    ProfScope prof("network_density", s, M);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_network_density<NET>), 96 * 1024);
-        k_network_density<NET><<<blocks, 256, lds, s>>>(na, lv, xyzs, M, sigmas, geo_feat);
-    });
-    return check_launch("network_density");
-}
-
-int ngp_cell_max_density(const ngp_model* model, const float* start_host, float granularity, uint32_t X, uint32_t Y, uint32_t Z, uint32_t s,
-                         const float* rot_host, float* out_max_sigma, ngp_stream_t stream) {
-    NGP_REQUIRE(start_host && rot_host && out_max_sigma, "cell_max_density: null pointer");
-    NGP_REQUIRE(model && model->packed_weights, "cell_max_density: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    NGP_REQUIRE(s >= 1 && s <= 16, "cell_max_density: 1 <= samples per axis <= 16 (got %u)", s);
-    NGP_REQUIRE(granularity > 0.0f, "cell_max_density: granularity must be > 0");
-    const uint64_t M = (uint64_t)X * Y * Z;
-    NGP_REQUIRE(M < ((uint64_t)1 << 31), "cell_max_density: X * Y * Z must be < 2^31");
-    if (M == 0) return NGP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
-    NGP_REQUIRE(lds <= 96 * 1024, "cell_max_density: the packed weights need %zu bytes of LDS", lds);
-    CellArgs ca;
-    for (int d = 0; d < 3; d++) ca.start[d] = start_host[d];
-    for (int d = 0; d < 9; d++) ca.rot[d] = rot_host[d];
-    ca.granularity = granularity;
-    ca.X = X; ca.Y = Y; ca.Z = Z; ca.s = s;
-    uint32_t blocks = div_up(div_up((uint32_t)M, 16), 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
-    ProfScope prof("cell_max_density", st, (double)M * s * s * s);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_cell_max_density<NET>), 96 * 1024);
-        k_cell_max_density<NET><<<blocks, 256, lds, st>>>(na, lv, ca, out_max_sigma);
-    });
-    return check_launch("cell_max_density");
-}
-
-int ngp_network_density_backward(const ngp_model* model, const void* packed_weights_bwd, const float* xyzs, uint32_t M, const float* grad_sigmas,
-                                 const float* grad_geo_feat, float* grad_xyzs, ngp_stream_t stream) {
-    if (M == 0) return NGP_OK;
-    NGP_REQUIRE(xyzs && grad_xyzs && (grad_sigmas || grad_geo_feat), "network_density_backward: null pointer");
-    NGP_REQUIRE(model && model->packed_weights && packed_weights_bwd, "network_density_backward: packed weights missing (ngp_pack_weights / ngp_pack_weights_bwd)");
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    NGP_REQUIRE(bwd_shape_ok(na), "network_density_backward: the fp32 form supports at most 1 hidden matmul in the sigma net (got %u)", na.sig_mm);
-    const size_t ws = na.f32() ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;
-    const size_t lds = weights_bytes(na) + ws + sizeof(LevelTab);
-    NGP_REQUIRE(lds <= 160 * 1024, "network_density_backward: LDS budget exceeded (%zu bytes)", lds);
-    uint32_t blocks = div_up(div_up(M, 16), 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
-    ProfScope prof("network_density_backward", s, M);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_network_density_bwd<NET>), 160 * 1024);
-        k_network_density_bwd<NET><<<blocks, 256, lds, s>>>(na, lv, (const char*)packed_weights_bwd, xyzs, M, grad_sigmas, grad_geo_feat, grad_xyzs);
-    });
-    return check_launch("network_density_backward");
-}
-
-int ngp_planner_collision(const ngp_model* model, const float* rot_matrix, const float* pos, const float* body, const float* rot, uint32_t S,
-                          uint32_t B, float* out, ngp_stream_t stream) {
-    if (S == 0) return NGP_OK;
-    NGP_REQUIRE(rot_matrix && pos && body && rot && out, "planner_collision: null pointer");
-    NGP_REQUIRE(B > 0, "planner_collision: no body points");
-    NGP_REQUIRE(model && model->packed_weights, "planner_collision: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab) + (kPlanThreads / 64) * sizeof(float);
-    NGP_REQUIRE(lds <= 96 * 1024, "planner_collision: the packed weights need %zu bytes of LDS", lds);
-    const PlanArgs pa{rot_matrix, pos, body, rot, S, B};
-    ProfScope prof("planner_collision", s, (size_t)S * B);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_planner_collision<NET>), 96 * 1024);
-        k_planner_collision<NET><<<S, kPlanThreads, lds, s>>>(na, lv, pa, out);
-    });
-    return check_launch("planner_collision");
-}
-
-int ngp_planner_collision_backward(const ngp_model* model, const void* packed_weights_bwd, const float* rot_matrix, const float* pos,
-                                   const float* body, const float* rot, uint32_t S, uint32_t B, const float* grad_out, float* grad_pos,
-                                   float* grad_rot_matrix, ngp_stream_t stream) {
-    if (S == 0) return NGP_OK;
-    NGP_REQUIRE(rot_matrix && pos && body && rot && grad_out && grad_pos && grad_rot_matrix, "planner_collision_backward: null pointer");
-    NGP_REQUIRE(B > 0, "planner_collision_backward: no body points");
-    NGP_REQUIRE(model && model->packed_weights && packed_weights_bwd,
-                "planner_collision_backward: packed weights missing (ngp_pack_weights / ngp_pack_weights_bwd)");
-    hipStream_t s = (hipStream_t)stream;
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    NGP_REQUIRE(bwd_shape_ok(na), "planner_collision_backward: the fp32 form supports at most 1 hidden matmul in the sigma net (got %u)", na.sig_mm);
-    const size_t ws = na.f32() ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;
-    const size_t lds = weights_bytes(na) + ws + sizeof(LevelTab) + (kPlanThreads / 64) * 12 * sizeof(float);
-    NGP_REQUIRE(lds <= 160 * 1024, "planner_collision_backward: LDS budget exceeded (%zu bytes)", lds);
-    const PlanArgs pa{rot_matrix, pos, body, rot, S, B};
-    ProfScope prof("planner_collision_backward", s, (size_t)S * B);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_planner_collision_bwd<NET>), 160 * 1024);
-        k_planner_collision_bwd<NET><<<S, kPlanThreads, lds, s>>>(na, lv, (const char*)packed_weights_bwd, pa, grad_out, grad_pos, grad_rot_matrix);
-    });
-    return check_launch("planner_collision_backward");
-}
-
-int ngp_network_forward(const ngp_model* model, const float* xyzs, const float* dirs, uint32_t M, float* sigmas, float* rgbs,
-                        ngp_stream_t stream) {
-    if (M == 0) return NGP_OK;
-    NGP_REQUIRE(xyzs && dirs && sigmas && rgbs, "network_forward: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    // No scratch of the library's own: the fragment-major weights are the caller's, packed once per parameter version
-    // (a process-wide buffer here would be shared by calls that run concurrently on different streams with different models)
-    NGP_REQUIRE(model && model->packed_weights, "network_forward: model->packed_weights is NULL (ngp_pack_weights fills it)");
-    NetArgs na;
-    GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(nullptr), (const _Float16*)model->packed_weights, na, lv);
-    if (rc) return rc;
-    const size_t lds = weights_bytes(na) + sizeof(LevelTab);
-    NGP_REQUIRE(lds <= 96 * 1024, "network_forward: the packed weights need %zu bytes of LDS", lds);
-    const uint32_t n_tiles = div_up(M, 16);
-    uint32_t blocks = div_up(n_tiles, 4);
-    if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);
-    ProfScope prof("network_forward", s, M);
-    NGP_WITH_NET(net_variant(na, lv), {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_network_forward<NET>), 96 * 1024);
-        k_network_forward<NET><<<blocks, 256, lds, s>>>(na, lv, xyzs, dirs, M, sigmas, rgbs);
-    });
-    return check_launch("network_forward");
 }
 
 }  // extern "C"

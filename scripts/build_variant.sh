@@ -1,10 +1,16 @@
 #!/bin/bash
-# A/B builds of render_fused.hip with experiment macros: scripts/build_variant.sh <name> "<-D flags>" -> nerfsafetyvalidation_amd/libngp_hip_<name>.so
-# (select at run time with NGP_HIP_LIB=$PWD/nerfsafetyvalidation_amd/libngp_hip_<name>.so)
+# A/B builds of fused units with experiment macros:
+#   scripts/build_variant.sh <name> "<-D flags>" [unit ...]   -> nerfsafetyvalidation_amd/libngp_hip_<name>.so
+# rebuilds the named units of csrc/ (default: render_fused; e.g. render_uniform fused_query) with the flags and links them with
+# the other objects of the last `make`.  Select at run time with NGP_HIP_LIB=$PWD/nerfsafetyvalidation_amd/libngp_hip_<name>.so
 set -e
 cd "$(dirname "$0")/../nerfsafetyvalidation_amd/csrc"
-name=$1; shift
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function -DNGP_BUILD $@ -c render_fused.hip -o /tmp/render_fused_$name.o
-objs=$(ls *.o | grep -v render_fused.o)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libngp_hip_$name.so $objs /tmp/render_fused_$name.o
+name=$1; flags=$2; shift 2 || { echo "usage: $0 <name> \"<-D flags>\" [unit ...]" >&2; exit 2; }
+units=${@:-render_fused}
+objs=$(ls *.o)
+for u in $units; do
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function -DNGP_BUILD $flags -c $u.hip -o /tmp/${u}_$name.o
+    objs="$(echo "$objs" | grep -vx $u.o) /tmp/${u}_$name.o"
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libngp_hip_$name.so $objs
 echo built ../libngp_hip_$name.so

@@ -1,4 +1,4 @@
-"""The collision field's GPU kernels (collision.hip ngp_edt_sq, render_fused.hip ngp_cell_max_density) and the rollout with a field:
+"""The collision field's GPU kernels (collision.hip ngp_edt_sq, fused_query.hip ngp_cell_max_density) and the rollout with a field:
 the distance transform against brute force and scipy, the reference's own createSDF.py output (tests/golden/sdf_henge.npz, made by
 make_golden_sdf.py), the cell density against ngp_network_density bit for bit, and a GPU rollout looked up in the henge field."""
 import hashlib
