@@ -400,6 +400,25 @@ NGP_API size_t ngp_edt_sq_workspace(uint32_t X, uint32_t Y, uint32_t Z);
 NGP_API int ngp_edt_sq(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, int32_t* d2, void* workspace, size_t workspace_bytes,
                        ngp_stream_t stream);
 
+/* Isosurface of a C-order scalar lattice u float [X,Y,Z] as an indexed, welded triangle mesh: marching tetrahedra on the Kuhn split
+ * (six tetrahedra around every cell's (0,0,0)-(1,1,1) diagonal; DESIGN.md "Mesh export" fixes the rule and the output order).  A
+ * lattice point is inside iff u > threshold (NaN is outside); every lattice edge (3 axis edges, 3 face diagonals, 1 body diagonal per
+ * point, owned by the lower end) whose ends differ carries one vertex at pa + (thr - ua) / (ub - ua) * (pb - pa), in index units.
+ * Two calls with one host read between them:
+ *   ngp_isosurface_count  fills the workspace (edge masks, triangle counts, their exclusive scans) and writes totals[0] = V and
+ *                         totals[1] = F (device memory, two uint64);
+ *   ngp_isosurface_emit   with the SAME u, sizes, threshold and workspace, and the V and F read back: vertices float [V,3] ordered by
+ *                         (owner in C order, edge type), faces int32 [F,3] ordered by (cell in C order, tetrahedron, triangle),
+ *                         normals from inside to outside.  V == F == 0 launches nothing (the outputs may be null).
+ * Every axis >= 2, X * Y * Z < 2^31, V < 2^31 and F < 2^31 (NGP_EINVAL otherwise, nothing launched).  workspace:
+ * ngp_isosurface_workspace(X, Y, Z) bytes (0 for sizes it refuses), 8-byte aligned (NGP_EWORKSPACE when smaller).  No atomics and
+ * no global state: the same bits on every call, and calls on different streams with their own workspaces do not interact. */
+NGP_API size_t ngp_isosurface_workspace(uint32_t X, uint32_t Y, uint32_t Z);
+NGP_API int ngp_isosurface_count(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, void* workspace, size_t workspace_bytes,
+                                 uint64_t* totals, ngp_stream_t stream);
+NGP_API int ngp_isosurface_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, const void* workspace,
+                                size_t workspace_bytes, uint64_t V, uint64_t F, float* vertices, int32_t* faces, ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

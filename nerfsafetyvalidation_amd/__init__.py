@@ -8,6 +8,7 @@ Sub-packages mirror the reference's operator packages one to one:
     nerfsafetyvalidation_amd.ffmlp         <->  ffmlp/
     nerfsafetyvalidation_amd.nerf          <->  nerf/ (renderer, network, network_ff, utils.get_rays)
     nerfsafetyvalidation_amd.encoding / .activation
+    nerfsafetyvalidation_amd.mesh          <->  nerf/utils.py's extract_fields / extract_geometry / Trainer.save_mesh
 
 `install_dropin()` registers them under the reference's TOP-LEVEL module names so that
 `import raymarching`, `from gridencoder import GridEncoder`, `from nerf.network import NeRFNetwork` ...
@@ -17,6 +18,8 @@ import importlib
 import sys
 
 __version__ = "0.1.0"
+
+from . import mesh  # noqa: E402,F401  (save_mesh, extract_geometry, isosurface)
 
 _DROPIN = ["raymarching", "gridencoder", "shencoder", "ffmlp", "encoding", "activation"]
 

@@ -111,6 +111,9 @@ SIGNATURES = {
     "ngp_cell_max_density": [C.POINTER(ModelStruct), _vp, C.c_float, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
     "ngp_edt_sq_workspace": [_u32, _u32, _u32],
     "ngp_edt_sq": [_vp, _u32, _u32, _u32, _vp, _vp, _sz, _vp],
+    "ngp_isosurface_workspace": [_u32, _u32, _u32],
+    "ngp_isosurface_count": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, _vp, _vp],
+    "ngp_isosurface_emit": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _vp],
     "ngp_sift_workspace": [_u32, _u32],
     "ngp_sift_layer_offset": [_u32, _u32, _int, _int],
     "ngp_sift_octaves": [_u32, _u32],
@@ -144,7 +147,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz}
 
 _lib = None
 
