@@ -3,7 +3,7 @@
 // One 64-lane wave handles 64 rays; blocks are 256 threads (4 waves, one per SIMD).
 // All kernels are streaming / latency-bound integer+fp32 work: no LDS tiling, no MFMA.
 // References are to /root/reference/raymarching/src/raymarching.cu.
-#include "ngp_common.hpp"
+#include "occupancy.hpp"
 
 namespace ngp {
 
@@ -100,12 +100,8 @@ __global__ void __launch_bounds__(kBlock) k_packbits(const float* __restrict__ g
 // ------------------------------------------------------------------ march_rays_train :313-484
 // Phase A: count occupied steps per ray (the reference's first pass) + per-block sums.
 // LIN: power-of-two grid with the derived copies of the occupancy bits in the workspace (x-fastest layout read through
-// Dda::probe_lin, its 4x4x4-block reduction staged in LDS): the same probes and the same t, cheaper (see ngp_common.hpp)
-struct TrainLin {
-    const uint32_t* lin;
-    const uint32_t* coarse;
-    uint32_t coarse_words, logH;
-};
+// Dda::probe_lin, its 4x4x4-block reduction staged in LDS): the same probes and the same t, cheaper (see occupancy.hpp)
+constexpr size_t kTrainLinBytes = 1u << 20;      // march_rays_train keeps the copies in its workspace when C * H^3 / 8 fits this; march_rays likewise
 
 // TRACE (small batches, where a launch is a few dozen waves and the march is a latency chain): the count pass records (t, dt) of
 // every sample it finds, so the write pass replays them instead of marching the ray a second time.
@@ -115,17 +111,17 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count(const float* __res
                                                               uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
                                                               const float* __restrict__ nears, const float* __restrict__ fars,
                                                               uint32_t perturb, Pcg32 rng, uint32_t* __restrict__ counts,
-                                                              uint32_t* __restrict__ block_sums, TrainLin tl, float2* __restrict__ trace) {
+                                                              uint32_t* __restrict__ block_sums, OccupancyLin tl, float2* __restrict__ trace) {
     __shared__ uint32_t wave_sums[kBlock / 64];
-    __shared__ uint32_t coarse_lds[LIN ? kTrainCoarseBytes / 4 : 1];
+    __shared__ uint32_t coarse_lds[LIN ? kCoarseMaxBytes / 4 : 1];
     if (LIN) {
-        for (uint32_t i = threadIdx.x; i < tl.coarse_words; i += kBlock) coarse_lds[i] = tl.coarse[i];
+        stage_coarse(tl, coarse_lds, kBlock);
         __syncthreads();
     }
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     uint32_t num_steps = 0;
     if (n < N) {
-        Dda s;
+        Dda s;      // (open-coded on purpose, not Dda::start: `far` is loaded between init and jitter -- DESIGN.md "Occupancy sources")
         s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, grid, bound, dt_gamma, max_steps, C, H);
         if (LIN) s.init_lin(tl.lin, tl.logH, true);
         const float far = fars[n];
@@ -158,28 +154,22 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count(const float* __res
 }
 
 // The count pass of a SMALL batch (the reference's 4096 rays per step: 64 waves, each the latency chain of its slowest ray -- hundreds of
-// dependent probes; 0.35 ms of a 1.6 ms training step) with one WAVE per ray.  With dt_gamma == 0 every t the march visits lies on the
-// lattice t0, t0 + dt, (t0 + dt) + dt, ... of the sequential additions, and inside one binade (above Dda::t_fast_min) those additions
-// are exact: point k is fmaf(k, d, t) with d = fl(t + dt) - t (skip_const_dt's argument).  Lane l therefore evaluates the probe AT
-// lattice point l of the current window -- the same pure function of t the sequential march evaluates, returning whether the cell is
-// occupied and where the march goes next from there (one step for a sample, the cell / block exit for an empty cell) -- and the wave
-// then follows the chain 0 -> next(0) -> next(next(0)) ... through the window from registers: the points on it are exactly the ones
-// the sequential march visits, the occupied ones among them its samples, in order.  Windows end at the binade (the step d changes
-// there: the point after it is evaluated alone, as the sequential march would), at `far`, and at the step budget.  Same (t, dt) trace,
-// same counts, bit for bit; the write pass replays the trace.
+// dependent probes; 0.35 ms of a 1.6 ms training step) with one WAVE per ray: the lanes probe the 64 lattice points of a window at once
+// and the wave follows the march's chain through them (probe_window, occupancy.hpp).  Windows also end at the step budget.  Same
+// (t, dt) trace, same counts, bit for bit; the write pass replays the trace.
 __global__ void __launch_bounds__(kBlock) k_march_train_count_wave(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                                    const uint8_t* __restrict__ grid, float bound, uint32_t max_steps,
                                                                    uint32_t N, uint32_t C, uint32_t H, const float* __restrict__ nears,
                                                                    const float* __restrict__ fars, uint32_t perturb, Pcg32 rng,
-                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ block_sums, TrainLin tl,
+                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ block_sums, OccupancyLin tl,
                                                                    float2* __restrict__ trace) {
-    __shared__ uint32_t coarse_lds[kTrainCoarseBytes / 4];
-    for (uint32_t i = threadIdx.x; i < tl.coarse_words; i += kBlock) coarse_lds[i] = tl.coarse[i];
+    __shared__ uint32_t coarse_lds[kCoarseMaxBytes / 4];
+    stage_coarse(tl, coarse_lds, kBlock);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);      // one wave per ray
     if (n >= N) return;
-    Dda s;
+    Dda s;      // (open-coded on purpose, not Dda::start: see k_march_train_count)
     s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, grid, bound, 0.0f, max_steps, C, H);
     s.init_lin(tl.lin, tl.logH, true);
     const float far = fars[n];
@@ -191,39 +181,22 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count_wave(const float* 
     uint32_t num_steps = 0;
     float2* out = trace + (size_t)n * max_steps;
     while (t < far && num_steps < max_steps) {
-        // lattice point `lane` of this window; valid while it stays in t's binade (and the exact regime) and before `far`
-        const float t1 = t + s.dt_c, d = t1 - t;
-        const float p = lane == 0 ? t : fmaf((float)lane, d, t);
-        const bool exact = t >= s.t_fast_min && ((__float_as_uint(p) ^ __float_as_uint(t)) >> 23) == 0;
-        const bool valid = lane == 0 || (exact && p < far);
-        float nxt = p, x, y, z, dt;
-        bool occ = false;
-        if (valid) {
-            occ = s.probe_lin(nxt, x, y, z, dt, coarse_lds);      // empty: nxt moves on to where the march continues
-            if (occ) nxt = p + dt;
-        }
-        // index of `nxt` in the window (64: it leaves the window, or is not one of its points): exact when it is a lattice point
-        uint32_t j = 64;
-        if (valid) {
-            const float q = rintf((nxt - t) * __builtin_amdgcn_rcpf(d));
-            if (q >= 1.0f && q < 64.0f && fmaf(q, d, t) == nxt) j = (uint32_t)q;
-        }
-        const unsigned long long vmask = __ballot(valid), omask = __ballot(occ);
+        const LatticeWindow w = probe_window(s, t, far, lane, coarse_lds);
         // follow the chain from point 0 (registers only: one v_readlane per visited point)
         unsigned long long visited = 0ull;
         uint32_t cur = 0;
         float t_exit = t;
         for (int guard = 0; guard < 64; guard++) {        // (the chain is strictly increasing: at most 64 points)
             visited |= 1ull << cur;
-            const uint32_t jn = (uint32_t)__builtin_amdgcn_readlane((int)j, (int)cur);
-            if (jn >= 64u || !((vmask >> jn) & 1ull)) {
-                t_exit = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(nxt), (int)cur));
+            const uint32_t jn = (uint32_t)__builtin_amdgcn_readlane((int)w.j, (int)cur);
+            if (jn >= 64u || !((w.vmask >> jn) & 1ull)) {
+                t_exit = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(w.nxt), (int)cur));
                 break;
             }
             cur = jn;
         }
         // the samples of the window, in order, up to the step budget (the march stops after the sample that fills it)
-        unsigned long long emit = visited & omask;
+        unsigned long long emit = visited & w.omask;
         const uint32_t room = max_steps - num_steps;
         uint32_t cnt = (uint32_t)__popcll(emit);
         if (cnt > room) {
@@ -233,7 +206,7 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count_wave(const float* 
             emit &= ~e;
             cnt = room;
         }
-        if ((emit >> lane) & 1ull) out[num_steps + (uint32_t)__popcll(emit & ((1ull << lane) - 1ull))] = make_float2(p, dt);
+        if ((emit >> lane) & 1ull) out[num_steps + (uint32_t)__popcll(emit & ((1ull << lane) - 1ull))] = make_float2(w.p, w.dt);
         num_steps += cnt;
         t = t_exit;
         if (cnt == room) break;
@@ -249,34 +222,11 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count_wave(const float* 
 // counter values BEFORE this call (the slot / row bases).
 __global__ void __launch_bounds__(1024) k_march_train_scan(uint32_t* __restrict__ block_sums, uint32_t nblocks, uint32_t N,
                                                             int32_t* __restrict__ counter, uint32_t* __restrict__ base) {
-    __shared__ uint32_t wave_tot[16];
-    __shared__ uint32_t carry_s;
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t start = 0; start < nblocks; start += 1024) {
-        const uint32_t i = start + threadIdx.x;
-        const uint32_t v = i < nblocks ? block_sums[i] : 0;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += o;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (uint32_t w = 0; w < wid; w++) wave_off += wave_tot[w];
-        const uint32_t carry = carry_s;
-        if (i < nblocks) block_sums[i] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wave_off + incl;
-        __syncthreads();
-    }
+    const uint32_t total = scan_in_place_1024(block_sums, nblocks);
     if (threadIdx.x == 0) {
         base[0] = (uint32_t)counter[0];
         base[1] = (uint32_t)counter[1];
-        counter[0] += (int32_t)carry_s;
+        counter[0] += (int32_t)total;
         counter[1] += (int32_t)N;
     }
 }
@@ -290,26 +240,15 @@ __global__ void __launch_bounds__(kBlock) k_march_train_write(const float* __res
                                                               uint32_t perturb, Pcg32 rng, const uint32_t* __restrict__ counts,
                                                               const uint32_t* __restrict__ block_offsets, const uint32_t* __restrict__ base,
                                                               float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas,
-                                                              int32_t* __restrict__ rays, TrainLin tl, const float2* __restrict__ trace) {
+                                                              int32_t* __restrict__ rays, OccupancyLin tl, const float2* __restrict__ trace) {
     __shared__ uint32_t wave_tot[kBlock / 64];
-    __shared__ uint32_t coarse_lds[LIN ? kTrainCoarseBytes / 4 : 1];
-    if (LIN)
-        for (uint32_t i = threadIdx.x; i < tl.coarse_words; i += kBlock) coarse_lds[i] = tl.coarse[i];
+    __shared__ uint32_t coarse_lds[LIN ? kCoarseMaxBytes / 4 : 1];
+    if (LIN) stage_coarse(tl, coarse_lds, kBlock);
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint32_t num_steps = n < N ? counts[n] : 0;
-    uint32_t incl = num_steps;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += o;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (uint32_t w = 0; w < wid; w++) wave_off += wave_tot[w];
+    const uint32_t before = block_exclusive_scan<kBlock>(num_steps, wave_tot);      // (its barrier also covers the staged coarse bits)
     if (n >= N) return;
-    const uint32_t point_index = base[0] + block_offsets[blockIdx.x] + wave_off + incl - num_steps;
+    const uint32_t point_index = base[0] + block_offsets[blockIdx.x] + before;
     const uint32_t ray_index = base[1] + n;
     if (ray_index < N) {
         rays[ray_index * 3] = (int32_t)n;
@@ -320,14 +259,9 @@ __global__ void __launch_bounds__(kBlock) k_march_train_write(const float* __res
     if (point_index + num_steps >= M) return;
 
     Dda s;
-    s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, grid, bound, dt_gamma, max_steps, C, H);
-    if (LIN) s.init_lin(tl.lin, tl.logH, true);
     const float far = fars[n];
-    float t = nears[n];
-    if (perturb) {
-        rng.advance((int64_t)n);
-        t += s.dt_min * rng.next_float();
-    }
+    float t = s.start(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, grid, bound, dt_gamma, max_steps, C, H, LIN ? &tl : nullptr, true, nears[n],
+                      perturb, rng, n);
     float* pxyz = xyzs + (size_t)point_index * 3;
     float* pdir = dirs + (size_t)point_index * 3;
     float* pdel = deltas + (size_t)point_index * 2;
@@ -576,10 +510,10 @@ __global__ void __launch_bounds__(kBlock) k_march_rays(uint32_t n_alive, uint32_
                                                        uint32_t C, uint32_t H, const uint8_t* __restrict__ grid,
                                                        const float* __restrict__ fars, float* __restrict__ xyzs,
                                                        float* __restrict__ dirs, float* __restrict__ deltas, uint32_t perturb, Pcg32 rng,
-                                                       uint32_t n_rows /* padded rows / n_step, rounded up */, uint32_t M_padded, TrainLin tl) {
-    __shared__ uint32_t coarse_lds[LIN ? kTrainCoarseBytes / 4 : 1];
+                                                       uint32_t n_rows /* padded rows / n_step, rounded up */, uint32_t M_padded, OccupancyLin tl) {
+    __shared__ uint32_t coarse_lds[LIN ? kCoarseMaxBytes / 4 : 1];
     if (LIN) {
-        for (uint32_t i = threadIdx.x; i < tl.coarse_words; i += kBlock) coarse_lds[i] = tl.coarse[i];
+        stage_coarse(tl, coarse_lds, kBlock);
         __syncthreads();
     }
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
@@ -590,7 +524,7 @@ __global__ void __launch_bounds__(kBlock) k_march_rays(uint32_t n_alive, uint32_
     uint32_t step = 0;
     if (n < n_alive) {
         const int32_t index = rays_alive[n];
-        Dda s;
+        Dda s;      // (open-coded on purpose, not Dda::start: see k_march_train_count)
         s.init(rays_o + (size_t)index * 3, rays_d + (size_t)index * 3, grid, bound, dt_gamma, max_steps, C, H);
         if (LIN) s.init_lin(tl.lin, tl.logH, true);
         float t = rays_t[index];
@@ -818,7 +752,7 @@ constexpr uint32_t kTraceMaxRays = 16384, kTraceMaxSteps = 1024;   // (t, dt) tr
 static size_t train_trace_bytes(uint32_t N) { return N <= kTraceMaxRays ? (size_t)N * kTraceMaxSteps * sizeof(float2) : 0; }
 
 size_t ngp_march_rays_train_workspace(uint32_t N) {
-    return train_counts_bytes(N) + kTrainLinBytes + kTrainCoarseBytes + train_trace_bytes(N);
+    return train_counts_bytes(N) + kTrainLinBytes + kCoarseMaxBytes + train_trace_bytes(N);
 }
 
 int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma, uint32_t max_steps,
@@ -841,54 +775,43 @@ int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t
     rng.seed(42u);  // raymarching.cu:489 hard-coded seed
     ProfScope prof("march_rays_train", s, N);
     // power-of-two grid whose bits fit the workspace: derived copies of the occupancy bits (a few microseconds) and the cheaper probes
-    const size_t cells = (size_t)C * H * H * H;
-    uint32_t logH = 0;
-    while ((1u << logH) < H) logH++;
-    TrainLin tl = {};
-    const bool lin = (1u << logH) == H && H >= 8 && cells % 4096 == 0 && cells / 8 <= kTrainLinBytes && cells / 64 / 8 <= kTrainCoarseBytes &&
-                     ((uintptr_t)grid & 7) == 0 && N >= 1024;
+    OccupancyLin tl = {};
+    const bool lin = N >= 1024 && occupancy_lin_fits(C, H, grid, kTrainLinBytes, kCoarseMaxBytes);
+    char* extra = (char*)workspace + train_counts_bytes(N);      // the two copies, then the trace
     float2* trace = nullptr;
-    if (lin && train_trace_bytes(N) && max_steps <= kTraceMaxSteps)
-        trace = (float2*)((char*)workspace + train_counts_bytes(N) + kTrainLinBytes + kTrainCoarseBytes);
-    if (lin) {
-        char* extra = (char*)workspace + train_counts_bytes(N);
-        uint32_t* lin_bits = (uint32_t*)extra;
-        unsigned long long* coarse = (unsigned long long*)(extra + kTrainLinBytes);
-        k_build_linear<<<div_up((uint32_t)(cells / 32), 256), 256, 0, s>>>(grid, C, logH, lin_bits);
-        k_build_coarse_linear<<<div_up((uint32_t)(cells / 64), 256), 256, 0, s>>>((const unsigned long long*)grid, C, logH, coarse);
-        tl.lin = lin_bits;
-        tl.coarse = (const uint32_t*)coarse;
-        tl.coarse_words = (uint32_t)(cells / 64 / 32);
-        tl.logH = logH;
-        static const bool wave_off = getenv("NGP_MARCH_TRAIN_NO_WAVE") != nullptr;      // diagnostics: the one-lane-per-ray count pass
-        if (trace && dt_gamma == 0.0f && !wave_off) {
+    if (lin && train_trace_bytes(N) && max_steps <= kTraceMaxSteps) trace = (float2*)(extra + kTrainLinBytes + kCoarseMaxBytes);
+    // both passes: a wave per ray on the step lattice (NGP_MARCH_TRAIN_NO_WAVE: never), a lane per ray with the trace replayed, or marching twice
+    static const bool wave_off = getenv("NGP_MARCH_TRAIN_NO_WAVE") != nullptr;
+    enum { kWave, kTraced, kLin, kPlain } const form = !lin ? kPlain : (!trace ? kLin : ((dt_gamma == 0.0f && !wave_off) ? kWave : kTraced));
+    if (lin) tl = build_occupancy_lin(grid, C, H, extra, extra + kTrainLinBytes, s);
+#define NGP_COUNT(LIN_, TRACE_)                                                                                                                   \
+    k_march_train_count<LIN_, TRACE_><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb, rng, \
+                                                                 counts, block_sums, tl, trace)
+#define NGP_WRITE(LIN_, TRACE_)                                                                                                                      \
+    k_march_train_write<LIN_, TRACE_><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, perturb, rng, \
+                                                                 counts, block_sums, base, xyzs, dirs, deltas, rays, tl, trace)
+    switch (form) {
+        case kWave:
             (void)hipMemsetAsync(block_sums, 0, (size_t)nblocks * sizeof(uint32_t), s);
-            k_march_train_count_wave<<<div_up(N, kBlock / 64), kBlock, 0, s>>>(rays_o, rays_d, grid, bound, max_steps, N, C, H, nears, fars, perturb, rng,
-                                                                              counts, block_sums, tl, trace);
-        } else if (trace)
-            k_march_train_count<true, true><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb,
-                                                                       rng, counts, block_sums, tl, trace);
-        else
-            k_march_train_count<true, false><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb,
-                                                                        rng, counts, block_sums, tl, nullptr);
-    } else {
-        k_march_train_count<false, false><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb, rng,
-                                                                     counts, block_sums, tl, nullptr);
+            k_march_train_count_wave<<<div_up(N, kBlock / 64), kBlock, 0, s>>>(rays_o, rays_d, grid, bound, max_steps, N, C, H, nears, fars, perturb,
+                                                                              rng, counts, block_sums, tl, trace);
+            break;
+        case kTraced: NGP_COUNT(true, true); break;
+        case kLin: NGP_COUNT(true, false); break;
+        case kPlain: NGP_COUNT(false, false); break;
     }
     k_march_train_scan<<<1, 1024, 0, s>>>(block_sums, nblocks, N, counter, base);
-    static const bool wave_off2 = getenv("NGP_MARCH_TRAIN_NO_WAVE") != nullptr;
-    if (lin && trace && dt_gamma == 0.0f && !wave_off2)
-        k_march_train_write_wave<<<div_up(N, kBlock / 64), kBlock, 0, s>>>(rays_o, rays_d, bound, max_steps, N, M, nears, perturb, rng, counts, block_sums,
-                                                                          base, xyzs, dirs, deltas, rays, trace);
-    else if (lin && trace)
-        k_march_train_write<true, true><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, perturb, rng,
-                                                                   counts, block_sums, base, xyzs, dirs, deltas, rays, tl, trace);
-    else if (lin)
-        k_march_train_write<true, false><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, perturb, rng,
-                                                                    counts, block_sums, base, xyzs, dirs, deltas, rays, tl, nullptr);
-    else
-        k_march_train_write<false, false><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, perturb, rng,
-                                                                     counts, block_sums, base, xyzs, dirs, deltas, rays, tl, nullptr);
+    switch (form) {
+        case kWave:
+            k_march_train_write_wave<<<div_up(N, kBlock / 64), kBlock, 0, s>>>(rays_o, rays_d, bound, max_steps, N, M, nears, perturb, rng, counts,
+                                                                              block_sums, base, xyzs, dirs, deltas, rays, trace);
+            break;
+        case kTraced: NGP_WRITE(true, true); break;
+        case kLin: NGP_WRITE(true, false); break;
+        case kPlain: NGP_WRITE(false, false); break;
+    }
+#undef NGP_COUNT
+#undef NGP_WRITE
     return check_launch("march_rays_train");
 }
 
@@ -916,28 +839,17 @@ int ngp_composite_rays_train_backward(const float* grad_weights_sum, const float
 
 // Derived copies of the occupancy bits for ngp_march_rays_lin: `out` receives the x-fastest re-layout (C * H^3 / 8 bytes) followed, at the
 // next multiple of 256 bytes, by its 1:64 reduction (C * H^3 / 512 bytes).  0 bytes: this grid takes the plain entry point.
-static bool occupancy_lin_ok(uint32_t C, uint32_t H) {
-    if (C < 1 || C > 8 || H < 8 || H > 1024 || (H & (H - 1))) return false;
-    const size_t cells = (size_t)C * H * H * H;
-    return cells % 4096 == 0 && cells / 8 <= kTrainLinBytes && cells / 64 / 8 <= kTrainCoarseBytes;
-}
+static size_t lin_coarse_offset(uint32_t C, uint32_t H) { return ((size_t)C * H * H * H / 8 + 255) / 256 * 256; }
 size_t ngp_occupancy_lin_bytes(uint32_t C, uint32_t H) {
-    if (!occupancy_lin_ok(C, H)) return 0;
-    const size_t cells = (size_t)C * H * H * H;
-    return (cells / 8 + 255) / 256 * 256 + cells / 512;
+    if (!occupancy_lin_fits(C, H, nullptr, kTrainLinBytes, kCoarseMaxBytes)) return 0;
+    return lin_coarse_offset(C, H) + (size_t)C * H * H * H / 512;
 }
 int ngp_build_occupancy_lin(const uint8_t* grid, uint32_t C, uint32_t H, void* out, size_t out_bytes, ngp_stream_t stream) {
     NGP_REQUIRE(grid && out, "build_occupancy_lin: null pointer");
     const size_t need = ngp_occupancy_lin_bytes(C, H);
     NGP_REQUIRE(need && out_bytes >= need, "build_occupancy_lin: C=%u H=%u needs %zu bytes (0 = not supported), %zu given", C, H, need, out_bytes);
     NGP_REQUIRE(((uintptr_t)grid & 7) == 0 && ((uintptr_t)out & 255) == 0, "build_occupancy_lin: grid must be 8-byte aligned, out 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t cells = (size_t)C * H * H * H;
-    uint32_t logH = 0;
-    while ((1u << logH) < H) logH++;
-    k_build_linear<<<div_up((uint32_t)(cells / 32), 256), 256, 0, s>>>(grid, C, logH, (uint32_t*)out);
-    k_build_coarse_linear<<<div_up((uint32_t)(cells / 64), 256), 256, 0, s>>>((const unsigned long long*)grid, C, logH,
-                                                                             (unsigned long long*)((char*)out + (cells / 8 + 255) / 256 * 256));
+    build_occupancy_lin(grid, C, H, out, (char*)out + lin_coarse_offset(C, H), (hipStream_t)stream);
     return check_launch("build_occupancy_lin");
 }
 
@@ -954,14 +866,10 @@ static int march_rays_impl(uint32_t n_alive, uint32_t n_step, const int32_t* ray
     rng.seed((uint64_t)perturb);  // raymarching.cu:819
     const uint32_t n_rows = div_up(M_padded, n_step);
     ProfScope prof("march_rays", s, (double)n_alive * n_step);
-    TrainLin tl = {};
+    OccupancyLin tl = {};
     if (occupancy_lin) {
-        NGP_REQUIRE(occupancy_lin_ok(C, H), "march_rays_lin: C=%u H=%u has no derived occupancy copies (ngp_occupancy_lin_bytes is 0)", C, H);
-        const size_t cells = (size_t)C * H * H * H;
-        tl.lin = (const uint32_t*)occupancy_lin;
-        tl.coarse = (const uint32_t*)((const char*)occupancy_lin + (cells / 8 + 255) / 256 * 256);
-        tl.coarse_words = (uint32_t)(cells / 64 / 32);
-        while ((1u << tl.logH) < H) tl.logH++;
+        NGP_REQUIRE(occupancy_lin_fits(C, H, nullptr, kTrainLinBytes, kCoarseMaxBytes), "march_rays_lin: C=%u H=%u has no derived occupancy copies (ngp_occupancy_lin_bytes is 0)", C, H);
+        tl = occupancy_lin_view(C, H, occupancy_lin, (const char*)occupancy_lin + lin_coarse_offset(C, H));
         k_march_rays<true><<<div_up(n_rows, kBlock), kBlock, 0, s>>>(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps,
                                                                      C, H, grid, fars, xyzs, dirs, deltas, perturb, rng, n_rows, M_padded, tl);
     } else {

@@ -7,7 +7,7 @@
 //
 //   k_render_iter   512-thread workgroups (8 waves).  A wave owns 64 alive rays:
 //     1. lane = ray: occupancy-grid DDA (ngp::Dda; same sample sequence as march_rays, reached with the exact
-//        shortcuts of Dda::probe_lin / skip_const_dt / jump_block) emits up to kCh sample parameters (t, dt)
+//        shortcuts of Dda::probe_lin / skip_const_dt / jump_block, occupancy.hpp) emits up to kCh sample parameters (t, dt)
 //        per sub-pass into the wave's LDS slab -- no [M,3] xyzs/dirs/deltas;
 //     2. the wave's valid samples are compacted (wave prefix sum) and processed 16 at a time:
 //        lane = (sample c = lane & 15, quarter q = lane >> 4).  Each lane gathers 4 of the 16
@@ -40,6 +40,7 @@
 #include <atomic>
 
 #include "fused_net.hpp"
+#include "occupancy.hpp"
 
 namespace ngp {
 
@@ -49,7 +50,6 @@ constexpr int kWavesPerSimd = 4;          // two 512-thread workgroups per CU (L
 constexpr int kCh = 2;                    // march steps handled per sub-pass (n_step <= 8 is processed in chunks of kCh)
 constexpr int kSlots = 64 * kCh;          // sample slots per wave and sub-pass
 constexpr size_t kLinMaxBytes = 4u << 20;  // linear copy of the occupancy bitfield (C * H^3 / 8 bytes)
-constexpr size_t kCoarseMaxBytes = 8192;  // LDS budget for the coarse occupancy filter (C * H^3 / 64 bits)
 constexpr int kLookahead = 4;             // iterations the host may enqueue beyond the last status it has seen
 constexpr int kRing = 8;
 
@@ -89,51 +89,6 @@ struct QueueHeads { uint32_t head[8][32]; };
 
 constexpr int kStatShards = 64;   // sample counters are sharded: a single hot atomic serialises at ~90 ops/us chip-wide
 
-// one bit per aligned 8-byte word (= 64 Morton-consecutive cells = one 4x4x4 block) of the occupancy bitfield
-__global__ void __launch_bounds__(256) k_build_coarse(const unsigned long long* __restrict__ bitfield64, uint32_t n_words,
-                                                       unsigned long long* __restrict__ coarse) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const bool any = i < n_words && bitfield64[i] != 0ull;
-    const unsigned long long m = __ballot(any);
-    if ((threadIdx.x & 63) == 0 && i < n_words) coarse[i >> 6] = m;
-}
-
-// Linear re-layout of the occupancy bits (power-of-two H): bit (level, z, y, x) of `lin` = bit level*H^3 + morton3D(x, y, z)
-// of the bitfield (raymarching.cu:381).  One thread per output word (32 consecutive x).
-__global__ void __launch_bounds__(256) k_build_linear(const uint8_t* __restrict__ bitfield, uint32_t cascade, uint32_t logH,
-                                                      uint32_t* __restrict__ lin) {
-    const uint32_t w = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t words_per_level = 1u << (3 * logH - 5);
-    if (w >= cascade * words_per_level) return;
-    const uint32_t level = w / words_per_level, c0 = (w % words_per_level) * 32;
-    const uint32_t H1 = (1u << logH) - 1;
-    const uint32_t x0 = c0 & H1, y = (c0 >> logH) & H1, z = c0 >> (2 * logH);
-    const uint32_t n = H1 + 1 < 32 ? H1 + 1 : 32;   // H < 32: a word spans several rows
-    uint32_t out = 0;
-    for (uint32_t i = 0; i < 32; i++) {
-        const uint32_t c = c0 + i;
-        const uint32_t xi = n == 32 ? x0 + i : (c & H1), yi = n == 32 ? y : ((c >> logH) & H1), zi = n == 32 ? z : (c >> (2 * logH));
-        const uint32_t m = (level << (3 * logH)) + morton3D_cell(xi, yi, zi);
-        out |= (uint32_t)((bitfield[m >> 3] >> (m & 7u)) & 1u) << i;
-    }
-    lin[w] = out;
-}
-
-// coarse bits in the same x-fastest order: bit (level, bz, by, bx) = any cell of the 4x4x4 block set
-__global__ void __launch_bounds__(256) k_build_coarse_linear(const unsigned long long* __restrict__ bitfield64, uint32_t cascade, uint32_t logH,
-                                                             unsigned long long* __restrict__ coarse) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t lb = logH - 2, per_level = 1u << (3 * lb), B1 = (1u << lb) - 1;
-    bool any = false;
-    if (i < cascade * per_level) {
-        const uint32_t level = i / per_level, r = i % per_level;
-        const uint32_t bx = r & B1, by = (r >> lb) & B1, bz = r >> (2 * lb);
-        any = bitfield64[(size_t)level * per_level + morton3D_cell(bx, by, bz)] != 0ull;   // 64 Morton-consecutive cells = one block
-    }
-    const unsigned long long m = __ballot(any);
-    if ((threadIdx.x & 63) == 0 && i < cascade * per_level) coarse[i >> 6] = m;
-}
-
 // ------------------------------------------------------------------------------------------
 // render iteration
 // ------------------------------------------------------------------------------------------
@@ -158,10 +113,9 @@ struct RenderArgs {
     uint32_t cascade, grid_size, max_steps, perturb;
     float dt_gamma;
     Pcg32 rng;
-    const uint32_t* coarse;           // coarse occupancy (k_build_coarse), staged into LDS; NULL = unfiltered probes
-    uint32_t coarse_words;            // its size in 32-bit words
-    const uint32_t* bitfield_lin;     // LIN kernels: x-fastest copy of the bitfield (k_build_linear) and log2(grid_size)
-    uint32_t log_grid;
+    // coarse occupancy bits, staged into LDS (coarse_words == 0: unfiltered probes).  LIN kernels: with the x-fastest copy of the bitfield
+    // and log2(grid_size), both in x-fastest order; otherwise `coarse` alone, in the bitfield's Morton order (k_build_coarse)
+    OccupancyLin occ;
     uint32_t block_jump;              // LIN kernels: leave empty 4x4x4 blocks in one step (Dda::jump_block)
     uint32_t* sample_hash;            // diagnostics (ngp_debug_set_sample_hash): per-ray FNV hash of the marched (dt, delta1) bit patterns
     unsigned long long* stamps;       // diagnostics only (ngp_debug_set_stamps): per-phase cycle sums; NULL in normal runs
@@ -248,12 +202,10 @@ __device__ __forceinline__ void dump_row(const RenderArgs& ra, uint32_t entry, i
 // ------------------------------------------------------------------------------------------
 // The same march with one WAVE per ray, for the launches of a frame's tail: a few thousand rays, up to 32 samples each -- a lane per ray
 // leaves the chip empty and the launch lasts as long as one ray's chain of dependent probes (60-80 us).  With a constant step
-// (dt_gamma == 0) the march's positions inside one binade of t are the lattice t + k * d, d = fl(t + dt) - t (Dda::skip_const_dt): lane k
-// probes lattice point k of a 64-point window at once, each probe says where the march goes from there (the next point if the cell is
-// occupied -- a sample -- or the first point beyond the empty cell / block), and the wave follows that chain from point 0 through
-// registers (v_readlane), collecting the samples it visits.  Points the chain cannot vouch for (another binade, t below the exact regime,
-// a continuation that is not a lattice point) end the window: the march continues from the exact t the lane-per-ray form would have.
-// Same samples, same (t, dt) bits, same deltas -- k_render_iter cannot tell the two forms apart.
+// (dt_gamma == 0) the lanes probe the 64 lattice points of a window at once and the wave follows the march's chain through them from
+// registers, collecting the samples it visits (probe_window, occupancy.hpp, where the argument for its exactness is written); windows
+// also end at the iteration boundaries inside the launch.  Same samples, same (t, dt) bits, same deltas -- k_render_iter cannot tell
+// the two forms apart.
 __device__ __forceinline__ void march_ahead_wave(const RenderArgs& ra, float bound, const Ctl& ctl, const uint32_t* coarse) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t entry = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -261,55 +213,34 @@ __device__ __forceinline__ void march_ahead_wave(const RenderArgs& ra, float bou
     const uint32_t n_step = ctl.n_step, spec = ctl.spec;
     const int32_t ray = ra.alive_in[entry];
     Dda dda;
-    dda.init(ra.rays_o + (size_t)ray * 3, ra.rays_d + (size_t)ray * 3, ra.bitfield, bound, 0.0f, ra.max_steps, ra.cascade, ra.grid_size);
-    dda.init_lin(ra.bitfield_lin, ra.log_grid, ra.block_jump != 0);
     const float t_c = ra.rays_t[ray], far = ra.fars[ray];
-    float t_march = t_c;
-    if (ra.perturb) {
-        Pcg32 rng = ra.rng;
-        rng.advance((int64_t)entry);
-        t_march += dda.dt_min * rng.next_float();
-    }
+    float t_march = dda.start(ra.rays_o + (size_t)ray * 3, ra.rays_d + (size_t)ray * 3, ra.bitfield, bound, 0.0f, ra.max_steps, ra.cascade,
+                              ra.grid_size, &ra.occ, ra.block_jump != 0, t_c, ra.perturb, ra.rng, entry);
     float last_m = t_march, geo_tc = t_c;
     uint32_t emitted = 0, rounds = 0;
     float2* out = ra.march_samples + ((size_t)(entry >> 6) * n_step) * 64 + (entry & 63u);
     while (t_march < far && emitted < n_step) {
         rounds++;
-        const float t1 = t_march + dda.dt_c, d = t1 - t_march;
-        const float p = lane == 0 ? t_march : fmaf((float)lane, d, t_march);
-        const bool exact = t_march >= dda.t_fast_min && ((__float_as_uint(p) ^ __float_as_uint(t_march)) >> 23) == 0;
-        const bool valid = lane == 0 || (exact && p < far);
-        float nxt = p, x, y, z, dt = 0.0f;
-        bool occ = false;
-        if (valid) {
-            occ = dda.probe_lin(nxt, x, y, z, dt, coarse);     // empty: nxt moves on to where the march continues
-            if (occ) nxt = p + dt;
-        }
-        uint32_t j = 64;                                       // index of `nxt` in the window, if it is one of its points
-        if (valid) {
-            const float q = rintf((nxt - t_march) * __builtin_amdgcn_rcpf(d));
-            if (q >= 1.0f && q < 64.0f && fmaf(q, d, t_march) == nxt) j = (uint32_t)q;
-        }
-        const unsigned long long vmask = __ballot(valid), omask = __ballot(occ);
+        const LatticeWindow w = probe_window(dda, t_march, far, lane, coarse);
         // samples until the iteration boundary inside the launch (march_rays starts again from rays_t there), or the end of the launch
         const uint32_t room = spec ? spec - emitted % spec : n_step - emitted;
         unsigned long long emit = 0ull;
         uint32_t cur = 0, cnt = 0;
         float t_next = t_march;
         for (int guard = 0; guard < 64; guard++) {             // (the chain is strictly increasing: at most 64 points)
-            const float to = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(nxt), (int)cur));
-            if ((omask >> cur) & 1ull) {
+            const float to = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(w.nxt), (int)cur));
+            if ((w.omask >> cur) & 1ull) {
                 emit |= 1ull << cur;
                 const float d1 = to - last_m;                  // deltas[1] of this sample (:791-793)
                 last_m = to;
                 geo_tc += d1;
                 if (++cnt == room) { t_next = to; break; }
             }
-            const uint32_t jn = (uint32_t)__builtin_amdgcn_readlane((int)j, (int)cur);
-            if (jn >= 64u || !((vmask >> jn) & 1ull)) { t_next = to; break; }
+            const uint32_t jn = (uint32_t)__builtin_amdgcn_readlane((int)w.j, (int)cur);
+            if (jn >= 64u || !((w.vmask >> jn) & 1ull)) { t_next = to; break; }
             cur = jn;
         }
-        if ((emit >> lane) & 1ull) out[(size_t)(emitted + (uint32_t)__popcll(emit & ((1ull << lane) - 1ull))) * 64] = make_float2(p, dt);
+        if ((emit >> lane) & 1ull) out[(size_t)(emitted + (uint32_t)__popcll(emit & ((1ull << lane) - 1ull))) * 64] = make_float2(w.p, w.dt);
         emitted += cnt;
         t_march = t_next;
         if (spec && cnt == room) {                             // iteration boundary: from the re-accumulated rays_t, with last_t = t
@@ -339,9 +270,9 @@ __global__ void __launch_bounds__(256) k_march_ahead(RenderArgs ra, float bound)
     const bool by_wave = LIN && n_alive <= ra.wave_march_max;
     if (blockIdx.x * (by_wave ? 4u : 256u) >= n_alive) return;
     __shared__ uint32_t coarse_lds[kCoarseMaxBytes / 4];
-    for (uint32_t i = threadIdx.x; i < ra.coarse_words; i += blockDim.x) coarse_lds[i] = ra.coarse[i];
+    stage_coarse(ra.occ, coarse_lds, blockDim.x);
     __syncthreads();
-    const uint32_t* coarse = ra.coarse_words ? coarse_lds : nullptr;
+    const uint32_t* coarse = ra.occ.coarse_words ? coarse_lds : nullptr;
     if (LIN && by_wave) {
         march_ahead_wave(ra, bound, ctl, coarse);
         return;
@@ -350,15 +281,9 @@ __global__ void __launch_bounds__(256) k_march_ahead(RenderArgs ra, float bound)
     if (entry >= n_alive) return;
     const int32_t ray = ra.alive_in[entry];
     Dda dda;
-    dda.init(ra.rays_o + (size_t)ray * 3, ra.rays_d + (size_t)ray * 3, ra.bitfield, bound, ra.dt_gamma, ra.max_steps, ra.cascade, ra.grid_size);
-    if (LIN) dda.init_lin(ra.bitfield_lin, ra.log_grid, ra.block_jump != 0);
     const float t_c = ra.rays_t[ray], far = ra.fars[ray];
-    float t_march = t_c;
-    if (ra.perturb) {
-        Pcg32 rng = ra.rng;
-        rng.advance((int64_t)entry);
-        t_march += dda.dt_min * rng.next_float();
-    }
+    float t_march = dda.start(ra.rays_o + (size_t)ray * 3, ra.rays_d + (size_t)ray * 3, ra.bitfield, bound, ra.dt_gamma, ra.max_steps, ra.cascade,
+                              ra.grid_size, LIN ? &ra.occ : nullptr, ra.block_jump != 0, t_c, ra.perturb, ra.rng, entry);
     float last_m = t_march;              // the march's last_t (:727-731)
     float geo_tc = t_c;                  // rays_t as composite_rays re-accumulates it (:848): where the next iteration's march restarts
     uint32_t emitted = 0;
@@ -1018,30 +943,7 @@ __global__ void __launch_bounds__(256) k_dump_count(const uint32_t* __restrict__
     if (threadIdx.x == 0) block_sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 __global__ void __launch_bounds__(1024) k_dump_scan(uint32_t* __restrict__ block_sums, uint32_t nblocks) {
-    __shared__ uint32_t wave_tot[16];
-    __shared__ uint32_t carry_s;
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t start = 0; start < nblocks; start += 1024) {
-        const uint32_t i = start + threadIdx.x;
-        const uint32_t v = i < nblocks ? block_sums[i] : 0;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += o;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (uint32_t w = 0; w < wid; w++) wave_off += wave_tot[w];
-        const uint32_t carry = carry_s;
-        if (i < nblocks) block_sums[i] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wave_off + incl;
-        __syncthreads();
-    }
+    scan_in_place_1024(block_sums, nblocks);
 }
 __global__ void __launch_bounds__(256) k_dump_gather(const uint32_t* __restrict__ dump_iter, const float4* __restrict__ rec, uint32_t N,
                                                       const Ctl* __restrict__ fin_state, const uint32_t* __restrict__ block_off,
@@ -1129,13 +1031,10 @@ int ngp_render_ctx_create(uint32_t max_rays, ngp_render_ctx** out) {
     c->max_rays = max_rays;
     const size_t chunks = div_up(max_rays, 64);
     bool ok = true;
-    int cus = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    }
-    const size_t max_items = items_bound(max_rays, (uint32_t)cus * 16u) + 8;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) c->num_cu = prop.multiProcessorCount;
+    const size_t max_items = items_bound(max_rays, (uint32_t)c->num_cu * 16u) + 8;
     ok &= hipMalloc(&c->alive[0], (size_t)max_rays * 4) == hipSuccess;
     ok &= hipMalloc(&c->alive[1], (size_t)max_rays * 4) == hipSuccess;
     ok &= hipMalloc(&c->staging, chunks * 64 * 4) == hipSuccess;
@@ -1162,9 +1061,6 @@ int ngp_render_ctx_create(uint32_t max_rays, ngp_render_ctx** out) {
         ok &= hipHostGetDevicePointer((void**)&c->fin_dev, c->fin, 0) == hipSuccess;
     }
     for (int i = 0; i < kRing; i++) ok &= hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming) == hipSuccess;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) c->num_cu = prop.multiProcessorCount;
     if (!ok) {
         set_error("render_ctx_create: allocation failed: %s", hipGetErrorString(hipGetLastError()));
         ngp_render_ctx_destroy(c);
@@ -1198,6 +1094,31 @@ struct ActiveRender {
     ActiveRender() { g_active_renders.fetch_add(1, std::memory_order_relaxed); }
     ~ActiveRender() { g_active_renders.fetch_sub(1, std::memory_order_relaxed); }
 };
+
+// The occupancy bits the march probes through: the linear copies (LIN kernels) when the grid has them and they fit this context's
+// buffers, else the Morton-order coarse filter when the bitfield is 8-byte aligned and its 1:64 reduction fits the LDS budget, else the
+// plain probes -- and then no regrouping of slow rays, which needs the coarse bits.  Returns whether the LIN kernels run.
+static bool choose_occupancy(ngp_render_ctx* ctx, const ngp_model* model, const DebugState& dbg, hipStream_t s, RenderArgs& ra) {
+    const uint32_t C = model->cascade, H = model->grid_size;
+    const size_t cells = (size_t)C * H * H * H;
+    // bit 3 of the debug flags turns the linear re-layout off; without the coarse filter there is none either
+    bool lin = !dbg.coarse_off() && !dbg.lin_off() && occupancy_lin_fits(C, H, model->density_bitfield, kLinMaxBytes, kCoarseMaxBytes);
+    // (the Morton-order filter asks less of the grid: any H whose block bits fit)
+    const bool use_coarse = !dbg.coarse_off() && cells % 4096 == 0 && cells / 64 / 8 <= kCoarseMaxBytes && ((uintptr_t)model->density_bitfield & 7) == 0;
+    if (lin && !ctx->grid_lin && hipMalloc(&ctx->grid_lin, kLinMaxBytes) != hipSuccess) lin = false;
+    if (lin) {
+        ra.occ = build_occupancy_lin(model->density_bitfield, C, H, ctx->grid_lin, ctx->coarse, s);
+        ra.block_jump = dbg.jump_off() ? 0u : 1u;
+    } else if (use_coarse) {
+        const uint32_t n_words = (uint32_t)(cells / 64);
+        k_build_coarse<<<div_up(n_words, 256), 256, 0, s>>>((const unsigned long long*)model->density_bitfield, n_words, ctx->coarse);
+        ra.occ.coarse = (const uint32_t*)ctx->coarse;
+        ra.occ.coarse_words = n_words / 32;
+    } else {
+        ra.sort_slow = 0;
+    }
+    return lin;
+}
 
 int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* rays_o, const float* rays_d, const float* nears,
                     const float* fars, uint32_t N, float dt_gamma, uint32_t max_steps, uint32_t perturb, float* weights_sum, float* depth,
@@ -1268,34 +1189,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     ra.sort_slow = (perturb == 0 && !dbg.sort_off()) ? 1u : 0u;   // needs the coarse filter; checked below
     ra.sample_hash = dbg.sample_hash;
 
-    // coarse occupancy filter: usable when the bitfield is 8-byte aligned and its 1:64 reduction fits the LDS budget
-    const size_t cells = (size_t)model->cascade * model->grid_size * model->grid_size * model->grid_size;
-    const size_t coarse_bytes = cells / 64 / 8;
-    const bool use_coarse = !dbg.coarse_off() && cells % 4096 == 0 && coarse_bytes <= kCoarseMaxBytes && ((uintptr_t)model->density_bitfield & 7) == 0;
-    // linear re-layout (cheaper DDA probes): power-of-two grid of at least 8^3 cells; bit 3 of the debug flags turns it off
-    const uint32_t Hg = model->grid_size;
-    uint32_t logH = 0;
-    while ((1u << logH) < Hg) logH++;
-    bool lin = use_coarse && !dbg.lin_off() && (1u << logH) == Hg && Hg >= 8 && cells / 8 <= kLinMaxBytes;
-    if (lin && !ctx->grid_lin && hipMalloc(&ctx->grid_lin, kLinMaxBytes) != hipSuccess) lin = false;
-    if (lin) {
-        const uint32_t n_words = (uint32_t)(cells / 32), n_coarse = (uint32_t)(cells / 64);
-        k_build_linear<<<div_up(n_words, 256), 256, 0, s>>>(model->density_bitfield, model->cascade, logH, ctx->grid_lin);
-        k_build_coarse_linear<<<div_up(n_coarse, 256), 256, 0, s>>>((const unsigned long long*)model->density_bitfield, model->cascade, logH,
-                                                                     ctx->coarse);
-        ra.coarse = (const uint32_t*)ctx->coarse;
-        ra.coarse_words = (uint32_t)(coarse_bytes / 4);
-        ra.bitfield_lin = ctx->grid_lin;
-        ra.log_grid = logH;
-        ra.block_jump = dbg.jump_off() ? 0u : 1u;
-    } else if (use_coarse) {
-        const uint32_t n_words = (uint32_t)(cells / 64);
-        k_build_coarse<<<div_up(n_words, 256), 256, 0, s>>>((const unsigned long long*)model->density_bitfield, n_words, ctx->coarse);
-        ra.coarse = (const uint32_t*)ctx->coarse;
-        ra.coarse_words = (uint32_t)(coarse_bytes / 4);
-    } else {
-        ra.sort_slow = 0;
-    }
+    const bool lin = choose_occupancy(ctx, model, dbg, s, ra);
     if ((ra.sort_slow || tile_w) && last_sigmas) {
         // regrouped alive list + last-iteration tensors requested: collect per-ray records, restore the row order afterwards
         if (!ctx->dump_rec) {

@@ -246,6 +246,48 @@ def test_march_rays_train_bit_exact(device, perturb, edge):
     np.testing.assert_allclose(ts.grad.cpu().numpy(), gs, rtol=1e-3, atol=2e-5)
 
 
+def test_march_rays_train_slot_scan_carries_across_rounds(device):
+    """513 x 513 = 263 169 rays are 1029 blocks of 256: the one-block scan of the per-block sample counts takes 1024 of them per round,
+    so this is the smallest frame whose slots depend on the carry into a second round.  max_steps = 32 keeps the oracle's M = N *
+    max_steps rows within a few hundred MB.  Same assertions as test_march_rays_train_bit_exact."""
+    import time
+    from nerfsafetyvalidation_amd import raymarching
+    sc = _scene(H=513, W=513)
+    rays_o, rays_d = _rays(sc, view=33)
+    N = rays_o.shape[0]
+    assert N > 1024 * 256
+    bitfield = sc.bitfield()
+    aabb = np.array([-sc.bound] * 3 + [sc.bound] * 3, np.float32)
+    nears, fars = np.empty(N, np.float32), np.empty(N, np.float32)
+    O.near_far_from_aabb(rays_o, rays_d, aabb, N, 0.2, nears, fars)
+    max_steps = 32
+    M = N * max_steps
+    xyzs, dirs, deltas = np.zeros((M, 3), np.float32), np.zeros((M, 3), np.float32), np.zeros((M, 2), np.float32)
+    rays = np.zeros((N, 3), np.int32)
+    counter = np.zeros(2, np.int32)
+    t0 = time.perf_counter()
+    O.march_rays_train(rays_o, rays_d, bitfield, sc.bound, 0.0, max_steps, N, sc.cascade, 128, M, nears, fars, xyzs, dirs, deltas, rays,
+                       counter, 0)
+    t1 = time.perf_counter()
+    m = int(counter[0])
+    assert counter[1] == N
+    assert rays[1024 * 256:, 2].any() and rays[1024 * 256, 1] > 0      # rays of the second round hold samples, at offsets past the first's
+    counter_gpu = torch.zeros(2, dtype=torch.int32, device=device)
+    gx, gd, gdl, grays = raymarching.march_rays_train(_t(rays_o, device), _t(rays_d, device), sc.bound, _t(bitfield, device), sc.cascade,
+                                                      128, _t(nears, device), _t(fars, device), counter_gpu, -1, False, 128, True, 0.0,
+                                                      max_steps)
+    got_counter = counter_gpu.cpu().numpy()
+    t2 = time.perf_counter()
+    print("oracle %.2f s, GPU call and read-back %.2f s, %d samples" % (t1 - t0, t2 - t1, m))
+    assert np.array_equal(got_counter, counter)
+    assert np.array_equal(grays.cpu().numpy(), rays)
+    m_pad = m + 128 - m % 128
+    assert gx.shape[0] == m_pad
+    assert np.array_equal(gx.cpu().numpy().view(np.uint32), xyzs[:m_pad].view(np.uint32))
+    assert np.array_equal(gd.cpu().numpy().view(np.uint32), dirs[:m_pad].view(np.uint32))
+    assert np.array_equal(gdl.cpu().numpy().view(np.uint32), deltas[:m_pad].view(np.uint32))
+
+
 def test_composite_rays_inplace(device):
     from nerfsafetyvalidation_amd import raymarching
     rng = np.random.default_rng(4)
