@@ -526,6 +526,30 @@ NGP_API size_t ngp_uq_stats_workspace(void);
 NGP_API int ngp_uq_stats(const void* c, int c_dtype, const float* d, uint64_t n, const float* r, uint64_t m, double* stats,
                  void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 
+/* ---------------- uncertainty/quantification/bayesian_laplace.py:38-91 (the Bayesian-Laplace fit's objective) ---------------- */
+
+/* Negative log posterior of the fp32 linear sigma net (32 -> 64 -> 16, no bias) on CACHED encoder features:
+ *   L(theta) = 0.5 sum_j (theta_j - prior_mean)^2 / prior_var + 0.5 sum_i (y_i - exp(h_i0))^2,   h_i = W2 relu(W1 f_i)
+ * features float [n,32] (16-byte aligned; the grid encoder's output, zero rows for points outside the box), y float [n],
+ * theta float [3072] = [W1 64x32 | W2 16x64] in nn.Linear order.  mode 0: *loss (double) only; 1: + grad float [3072] = the prior term
+ * alone, exactly (theta - prior_mean) / (float)prior_var (what the reference's detached likelihood leaves of the gradient);
+ * 2: + the likelihood's gradient, with trunc_exp's backward d sigma / d h = exp(clamp(h, -15, 15)) (rows 1..15 of W2: prior only).
+ * Persistent workgroups over 64-point tiles, at most max_workgroups of them (0 = default, <= 4096), one partial each in `workspace`
+ * (ngp_sigma_fit_workspace(n, max_workgroups) bytes, 8-byte aligned; NGP_EWORKSPACE when smaller), summed in a fixed order with the
+ * loss in double: no atomics, the same bits on every call with the same arguments. */
+NGP_API size_t ngp_sigma_fit_workspace(uint32_t n, uint32_t max_workgroups);
+NGP_API int ngp_sigma_fit_eval(const float* features, const float* y, uint32_t n, const float* theta, float prior_mean, double prior_var,
+                       int mode, uint32_t max_workgroups, void* workspace, size_t workspace_bytes, double* loss, float* grad,
+                       ngp_stream_t stream);
+/* One step of the fit without a host read-back (mode 1 or 2): the evaluation above at theta, history[history_index] = (float)loss,
+ * `if loss < *min_loss: *min_loss = loss, *improved = 1` on that float (before the update, bayesian_laplace.py:75-81), then
+ * ngp_adam_step on theta with torch.optim.Adam's defaults (betas 0.9 / 0.999, eps 1e-8), learning rate lr and step count `step` >= 1.
+ * grad, exp_avg, exp_avg_sq: float [3072] device buffers the caller keeps between steps (the moments zeroed before step 1). */
+NGP_API int ngp_sigma_fit_step(const float* features, const float* y, uint32_t n, float* theta, float prior_mean, double prior_var, int mode,
+                       uint32_t max_workgroups, void* workspace, size_t workspace_bytes, float* grad, float* exp_avg, float* exp_avg_sq,
+                       float lr, uint32_t step, float* min_loss, int32_t* improved, float* history, uint32_t history_index,
+                       ngp_stream_t stream);
+
 /* ---------------- optimiser step of Trainer.train_step (nerf/utils.py:404-487; main_nerf.py:116) ---------------- */
 
 /* torch.optim.Adam(betas, eps) without weight decay / amsgrad on one fp32 tensor, in place: exp_avg and exp_avg_sq are the

@@ -62,6 +62,8 @@ PLANNER_ENV = {
 PLANNER_ROT = [[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]    # validate.py:283: Blender -> NeRF axes of density_fn
 ROW_WIDTH = 24   # MonteCarlo.py:95-116: sim, step, noise x12, sdf value, xyz, step loglik, cumulative loglik, reward, sigma, collided (+ ever collided)
 PENALTY = 36.0   # NerfSimulator.py:171
+UQ_GAUSSIAN, UQ_LAPLACE = "Gaussian Approximation", "Bayesian Laplace Approximation"     # envConfig.json's uq_method
+NUM_PERTURBATIONS = 3   # NerfSimulator.py:172
 
 
 # ------------------------------------------------------------------ SO(3) helpers (nav/math_utils.py), float32 on the host
@@ -158,6 +160,12 @@ def reward_fn(likelihood, sigma_d_opt):
     return float(np.clip(likelihood - PENALTY * sigma_d_opt, -PENALTY * 2, PENALTY))
 
 
+def reward_fn_laplace(likelihood, rmv, trace):
+    """NerfSimulator.py:177-179, uq_method == 'Bayesian Laplace Approximation': step() unpacks uncertainty()'s (trace, rmv) as
+    `trace, sigma` and returns `sigma, trace` (:110,148), so sigma_d_opt is the root mean variance and `trace` the trace"""
+    return float(np.clip(likelihood - PENALTY * rmv * trace * NUM_PERTURBATIONS, -PENALTY * 2, PENALTY))
+
+
 def scene_collision(state_xyz):
     """Stand-in for the sdf.npy lookup of NerfSimulator.py:131-155: is the (drone-frame) position inside the analytic occupancy
     of the synthetic scene (scene.henge_occupancy, in the NeRF's axes)?  Returns (collided, value) with value 0 inside, 9999 free."""
@@ -223,12 +231,19 @@ class RolloutSimulator:
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
-                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None):
+                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
         sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up.
         estimator_cfg: None (the planner replans from the true state) or nav.estimator_config()'s dict: the reference's estimator
-        turns render #1 of every step into the state the planner replans from (needs planner_cfg)."""
+        turns render #1 of every step into the state the planner replans from (needs planner_cfg).
+        uq_method: envConfig.json's key.  The default, 'Gaussian Approximation', is the path described above.  'Bayesian Laplace
+        Approximation': uncertain.uncertainty on render #2 and its rays (NerfSimulator.py:110), the row's uncertainty column holds the
+        root mean variance and the reward is reward_fn_laplace.  uq_kwargs: its keywords (lr -- the reference passes filter.lrate,
+        1e-3 -- and BayesianLaplace.fit's, e.g. n_steps, likelihood_gradient, lm_solver)."""
+        if uq_method not in (UQ_GAUSSIAN, UQ_LAPLACE):
+            raise ValueError(f"Unrecognized uncertainty quantification method {uq_method}")
+        self.uq_method, self.uq_kwargs, self.last_trace = uq_method, dict(uq_kwargs or {}), None
         from .nerf.utils import get_rays
         from .uncertainty.quantification.gaussian_approximation_density_uncertainty import GaussianApproximationDensityUncertainty
         self.model, self.intrinsics, self.H, self.W, self.steps, self.seed = model, intrinsics, H, W, steps, seed
@@ -256,7 +271,21 @@ class RolloutSimulator:
         rays = self._get_rays(pose.reshape(1, 4, 4).to(self.device), self.intrinsics, self.H, self.W)
         out = self.model.render(rays["rays_o"], rays["rays_d"], **self.render_kwargs)
         self.frames += 1
+        self.last_rays = rays
         return out
+
+    def uncertainty_laplace(self, out, rays):
+        """uncertain.py:181-231 on a render and its rays -> (trace, rmv)"""
+        from .uncertain import LAPLACE, uncertainty
+        kw = dict(self.uq_kwargs)
+        lr = kw.pop("lr", (self.estimator_cfg or {}).get("lrate", 1e-3))
+        return uncertainty(LAPLACE, rendered_output=(out, rays["rays_o"], rays["rays_d"]), model_to_use=self.model, lr=lr, **kw)
+
+    def reward(self, loglik, sigma_d):
+        """NerfSimulator.reward (:159-181) for this simulator's uq_method"""
+        if self.uq_method == UQ_LAPLACE:
+            return reward_fn_laplace(loglik, sigma_d, self.last_trace)
+        return reward_fn(loglik, sigma_d)
 
     def uncertainty(self, out):
         """uncertain.py:78-91: c = rgbs, d = sigmas, r = image of the render"""
@@ -341,6 +370,9 @@ class RolloutSimulator:
                     img = torch.squeeze(out["image"]).float().cpu().numpy().reshape((self.H, self.W, -1))
                     img *= 255
                     self.sensor_image = img.astype(np.uint8)
+            if self.uq_method == UQ_LAPLACE:
+                self.last_trace, rmv = self.uncertainty_laplace(out, self.last_rays)
+                return rmv
             return self.uncertainty(out)[1]
 
     def collision(self, xyz):
@@ -387,7 +419,7 @@ class RolloutSimulator:
             loglik = trajectory_log_likelihood(noise.numpy(), self.mean.numpy(), self.std.numpy())
             cumulative += loglik
             rows.append([sim, k, *noise.tolist(), value, *where.tolist(), loglik, cumulative, reward, sigma_d, float(collided)])
-            reward = reward_fn(loglik, sigma_d)                # applies to the NEXT step (MonteCarlo.py:81-83)
+            reward = self.reward(loglik, sigma_d)              # applies to the NEXT step (MonteCarlo.py:81-83)
             if collided:
                 break
         rows = np.asarray(rows, np.float64)
@@ -395,12 +427,14 @@ class RolloutSimulator:
 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
-                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None):
+                render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None,
+                uq_method=UQ_GAUSSIAN, uq_kwargs=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
     a collision.SignedDistanceField every simulation's collision check looks up.  estimator_cfg: None, or nav.estimator_config()'s
-    dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps)."""
+    dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps).
+    uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged)."""
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -409,7 +443,8 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
 
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
-                                   planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg)
+                                   planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg,
+                                   uq_method=uq_method, uq_kwargs=uq_kwargs)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
