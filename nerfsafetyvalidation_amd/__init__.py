@@ -20,6 +20,7 @@ import sys
 __version__ = "0.1.0"
 
 from . import mesh  # noqa: E402,F401  (save_mesh, extract_geometry, isosurface)
+from . import cem  # noqa: E402,F401  (run_cem, refit, failure_probability, SeedableMultivariateNormal; rollout.run_validation dispatches to it)
 
 _DROPIN = ["raymarching", "gridencoder", "shencoder", "ffmlp", "encoding", "activation"]
 

@@ -35,7 +35,8 @@ Simulations are independent given their seed -- the reference's own CEM draws wi
 (validation/distributions/SeedableMultivariateNormal.py:19-22) -- so they shard over ranks with no data-path collective; the rows are
 gathered once at the end (dist.gather_views).  Within a rank several simulations advance concurrently, each on its own host thread
 and HIP stream (pipeline.FramePipeline): a simulation's steps are sequential (the reward feeds the next step's noise), the
-simulations are not.
+simulations are not.  The Cross Entropy Method stress test (cem.py) runs its populations through the same step (RolloutSimulator.run
+with another noise source and row writer) and the same machinery (run_simulations, gather_rows); run_validation picks between the two.
 """
 import math
 
@@ -381,20 +382,40 @@ class RolloutSimulator:
             return self.sdf.lookup(xyz)
         return scene_collision(xyz)
 
+    # ---- the two places where the stress tests differ (cem.CEMSimulator overrides them): where a step's noise comes from and what
+    # ---- a step writes
+    def begin(self, sim):
+        """start simulation `sim`'s noise source and bookkeeping (MonteCarlo.py:41-47)"""
+        self._gen = self.make_generator(sim)
+        self._reward, self._cumulative = 0.0, 0.0
+
+    def draw_noise(self, sim, k):
+        """MonteCarlo.py:49-53: the std widened by the previous step's reward"""
+        std = self.std + (0.01 * self.std) * self._reward
+        return torch.normal(self.mean, std, generator=self._gen)
+
+    def write_row(self, sim, k, noise, value, where, sigma_d, collided):
+        """MonteCarlo.py:58-116: one CSV row; the reward it computes applies to the NEXT step (:81-83)"""
+        loglik = trajectory_log_likelihood(noise.numpy(), self.mean.numpy(), self.std.numpy())
+        self._cumulative += loglik
+        row = [sim, k, *noise.tolist(), value, *where.tolist(), loglik, self._cumulative, self._reward, sigma_d, float(collided)]
+        self._reward = self.reward(loglik, sigma_d)
+        return row
+
     def run(self, sim):
-        """-> rows [n_steps_run, ROW_WIDTH] float64 (a collision ends the simulation, MonteCarlo.py:88-93)"""
-        gen = self.make_generator(sim)
+        """-> rows [n_steps_run, row width] float64 (a collision ends the simulation, MonteCarlo.py:88-93); the last column,
+        "ever collided", is added once the simulation is over (MonteCarlo.py:112)"""
+        self.begin(sim)
         self.reset_planner()
         state = initial_state(self.steps)
         if self.planner is not None:                           # at rest in start_pos (validate.py:224-233, NerfSimulator.py:30-33)
             state[3:6] = 0.0
         self.reset_estimator(sim, state)
         history = [state.numpy().astype(np.float64)]
-        rows, reward, cumulative = [], 0.0, 0.0
+        rows = []
         self.poses, self.actions = [], []
         for k in range(self.steps):
-            std = self.std + (0.01 * self.std) * reward        # MonteCarlo.py:49-51
-            noise = torch.normal(self.mean, std, generator=gen)
+            noise = self.draw_noise(sim, k)
             action = self.action(k, state)
             self.actions.append(action)
             state = drone_dynamics(state, action, self.dt) + noise          # agent_helpers.py:47-56
@@ -416,14 +437,51 @@ class RolloutSimulator:
                 where = p
                 if collided:
                     break
-            loglik = trajectory_log_likelihood(noise.numpy(), self.mean.numpy(), self.std.numpy())
-            cumulative += loglik
-            rows.append([sim, k, *noise.tolist(), value, *where.tolist(), loglik, cumulative, reward, sigma_d, float(collided)])
-            reward = self.reward(loglik, sigma_d)              # applies to the NEXT step (MonteCarlo.py:81-83)
+            rows.append(self.write_row(sim, k, noise, value, where, sigma_d, collided))
             if collided:
                 break
         rows = np.asarray(rows, np.float64)
         return np.concatenate([rows, np.full((rows.shape[0], 1), float(rows[:, -1].any()))], 1)   # "ever collided", MonteCarlo.py:112
+
+
+def simulation_pipeline(sims, in_flight, device):
+    """the pipeline.FramePipeline run_simulations runs `sims` on (a context manager), or None when they run one after the other"""
+    if in_flight > 1 and len(sims) > 1:
+        from .pipeline import FramePipeline
+        return FramePipeline(None, in_flight=in_flight, device=device)
+    return None
+
+
+def run_simulations(one, sims, in_flight, device, pipe=None):
+    """one(sim) -> (rows, frames) for every simulation of `sims`, `in_flight` at a time, each on its own host thread and HIP stream
+    (pipeline.FramePipeline) -> the results in `sims` order.  pipe: a simulation_pipeline() the caller keeps open over several calls
+    (cem.run_cem: one for all populations); without it one is opened for this call."""
+    if pipe is None:
+        pipe = simulation_pipeline(sims, in_flight, device)
+        if pipe is not None:
+            with pipe:
+                return run_simulations(one, sims, in_flight, device, pipe)
+        return [one(s) for s in sims]
+    futures = [pipe.submit_fn(one, s) for s in sims]
+    return [f.result()[0] for f in futures]
+
+
+def gather_rows(results, n_simulations, steps, width, world_size=1, group=None, device=None, gather=True):
+    """this rank's (rows, frames) results -> every simulation's rows [total, width] in simulation order with ONE collective.  Ragged
+    (a collision ends a simulation early): every simulation is padded to `steps` rows with NaN for the gather."""
+    local = np.full((len(results), steps, width), np.nan, np.float64)
+    for i, (rows, _) in enumerate(results):
+        local[i, :rows.shape[0]] = rows
+    if gather and world_size > 1:
+        import torch.distributed as dist
+        t = torch.from_numpy(local)
+        if dist.get_backend(group) == "nccl":
+            t = t.to(device)
+        allr = gather_views(t, n_simulations, group).cpu().numpy()
+    else:
+        allr = local
+    flat = allr.reshape(-1, width)
+    return flat[~np.isnan(flat[:, 0])]
 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
@@ -449,28 +507,22 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
 
-    results = []
-    if in_flight > 1 and len(sims) > 1:
-        from .pipeline import FramePipeline
-        with FramePipeline(None, in_flight=in_flight, device=device) as pipe:
-            futures = [pipe.submit_fn(one, s) for s in sims]
-            results = [f.result()[0] for f in futures]
-    else:
-        results = [one(s) for s in sims]
+    results = run_simulations(one, sims, in_flight, device)
     for rows, frames in results:
         counters["frames"] += frames
         counters["steps"] += rows.shape[0]
-    # ragged (a collision ends a simulation early): pad every simulation to `steps` rows with NaN for the one collective
-    local = np.full((len(sims), steps, ROW_WIDTH), np.nan, np.float64)
-    for i, (rows, _) in enumerate(results):
-        local[i, :rows.shape[0]] = rows
-    if gather and world_size > 1:
-        import torch.distributed as dist
-        t = torch.from_numpy(local)
-        if dist.get_backend(group) == "nccl":
-            t = t.to(device)
-        allr = gather_views(t, n_simulations, group).cpu().numpy()
-    else:
-        allr = local
-    flat = allr.reshape(-1, ROW_WIDTH)
-    return flat[~np.isnan(flat[:, 0])], counters
+    return gather_rows(results, n_simulations, steps, ROW_WIDTH, world_size, group, device, gather), counters
+
+
+STRESS_MONTE_CARLO, STRESS_CEM = "Monte Carlo", "Cross Entropy Method"     # envConfig.json's stress_test
+
+
+def run_validation(stress_test, *args, **kwargs):
+    """validate.py:23-49: envConfig.json's `stress_test` picks the loop -- 'Monte Carlo' -> run_rollout(*args, **kwargs),
+    'Cross Entropy Method' -> cem.run_cem(*args, **kwargs); anything else is an error (the reference prints and exits)"""
+    if stress_test == STRESS_MONTE_CARLO:
+        return run_rollout(*args, **kwargs)
+    if stress_test == STRESS_CEM:
+        from . import cem
+        return cem.run_cem(*args, **kwargs)
+    raise ValueError(f"Unrecognized stress test {stress_test}")
