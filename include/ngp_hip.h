@@ -584,7 +584,8 @@ NGP_API int ngp_sift_interest_mask(const uint8_t* rgb, uint32_t H, uint32_t W, u
                                    uint8_t* mask, uint32_t* count, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 
 /* Diagnostics.  ngp_debug_set_stamps / ngp_debug_set_sample_hash / ngp_debug_disable_march_queue set the PROCESS DEFAULT;
- * ngp_render_ctx_set_debug(ctx, 1, flags, stamps, sample_hash) gives one context its own state (enable = 0: back to the default).
+ * ngp_render_ctx_set_debug(ctx, 1, flags, stamps, sample_hash) gives one context its own state (enable = 0: back to the default);
+ * `flags` is a word of enum ngp_debug_flag below.
  * A render call snapshots the state that applies to it once, at its start: concurrent calls on other threads / streams are not
  * affected by a change made while they run.
  * When a device buffer of >= 16 uint64 is set, k_render_iter adds per-phase wave-cycle sums
@@ -593,10 +594,26 @@ NGP_API int ngp_sift_interest_mask(const uint8_t* rgb, uint32_t H, uint32_t W, u
 NGP_API int ngp_debug_set_stamps(unsigned long long* device_buf);
 /* Diagnostics: uint32[N] device buffer receiving, per ray, an FNV-1a hash over the bit patterns of (dt, deltas[1]) of every
  * sample the fused renderer marched, in order (NULL = off).  Lets a test prove the fused path's sample sequence equal to
- * march_rays' bit for bit.  ngp_debug_disable_march_queue(flags): bit 0 / bit 1 disable the coarse occupancy filter, bit 2 the
- * slow-ray grouping of the alive list, bit 3 the linear re-layout of the occupancy bits, bit 8 the launches that cover several reference iterations, bits 9-12 replace the safety factor those launches are sized with (value / 2; 0 = built-in), bit 13 ignores the frame-width hint, bit 14 runs every multi-iteration launch as planned (no cut before the network from the march's own counts), bit 15 keeps the work items of k_render_iter at 64 list entries, bit 16 replays a launch that failed its verification as one iteration instead of its verified prefix, bits 4-7 fold the hashed levels into size >> n entries (timing only, wrong images) (A/B experiments; bit 0 disables the one-step exit from empty 4x4x4 blocks, Dda::jump_block). */
+ * march_rays' bit for bit. */
 NGP_API int ngp_debug_set_sample_hash(uint32_t* device_buf);
-NGP_API int ngp_debug_disable_march_queue(int off);
+/* The debug flag word of the fused render loop (ngp_render_rays): every bit switches one scheduling device off.  Results do not
+ * depend on any of them (the tests compare images and sample hashes bit for bit across them).  The numeric values are frozen. */
+enum ngp_debug_flag {
+    NGP_DBG_NO_BLOCK_JUMP = 1 << 0,        /* no one-step exit from empty 4x4x4 blocks (Dda::jump_block) */
+    NGP_DBG_NO_COARSE = 1 << 1,            /* no coarse occupancy filter: plain probes (and then no linear re-layout, no slow-ray grouping) */
+    NGP_DBG_NO_SLOW_SORT = 1 << 2,         /* no grouping of the slow rays at the end of the alive list */
+    NGP_DBG_NO_LIN = 1 << 3,               /* no linear (x-fastest) re-layout of the occupancy bits */
+    NGP_DBG_ONE_ITER_PER_LAUNCH = 1 << 8,  /* no launch covers several reference iterations */
+    NGP_DBG_NO_TILES = 1 << 13,            /* the frame-width hint is ignored: no 4x4-pixel tiles in the alive list */
+    NGP_DBG_NO_PRE_VERDICT = 1 << 14,      /* every multi-iteration launch runs as planned (no cut before the network from the march's counts) */
+    NGP_DBG_WIDE_ITEMS = 1 << 15,          /* the work items of k_render_iter stay 64 list entries wide */
+    NGP_DBG_REPLAY_ONE_ITER = 1 << 16,     /* a launch that failed its verification is replayed as one iteration, not as its verified prefix */
+    NGP_DBG_LANE_MARCH = 1 << 17,          /* k_march_ahead marches a lane per ray always (never a wave per ray) */
+    NGP_DBG_PROBE_PER_SAMPLE = 1 << 18,    /* k_march_ahead probes the occupancy bits for every sample (no runs inside an occupied cell) */
+    NGP_DBG_ALL = 0x7E10F                  /* every bit above; a flag word with any other bit set is refused with NGP_EINVAL */
+};
+/* Sets the WHOLE flag word of the process default (the name is historic: the first flag switched a march queue off). */
+NGP_API int ngp_debug_disable_march_queue(int flags);
 /* Diagnostics: the 32 hash-grid features of xyzs [M,3] (positions in [-bound, bound]) exactly as the fused kernels' gather forms them
  * -> features [M,32] fp16 in the operator's order (2 * level + channel).  operator_rounding = 0: the fused kernels' arithmetic (fp32
  * accumulation of the 8 corners, one rounding); 1: the grid_encode operator's (c10::Half product and running sum,

@@ -17,6 +17,11 @@ SO_PATH = os.environ.get("NGP_HIP_LIB", os.path.join(_HERE, "libngp_hip.so"))   
 
 NGP_F32, NGP_F16 = 0, 1
 NGP_PREC_F16, NGP_PREC_F32, NGP_PREC_F16_REF = 0, 1, 2          # ngp_model::precision
+# enum ngp_debug_flag: the flag word of ngp_debug_disable_march_queue / ngp_render_ctx_set_debug (each bit switches one device off)
+NGP_DBG_NO_BLOCK_JUMP, NGP_DBG_NO_COARSE, NGP_DBG_NO_SLOW_SORT, NGP_DBG_NO_LIN = 1 << 0, 1 << 1, 1 << 2, 1 << 3
+NGP_DBG_ONE_ITER_PER_LAUNCH, NGP_DBG_NO_TILES = 1 << 8, 1 << 13
+NGP_DBG_NO_PRE_VERDICT, NGP_DBG_WIDE_ITEMS, NGP_DBG_REPLAY_ONE_ITER = 1 << 14, 1 << 15, 1 << 16
+NGP_DBG_LANE_MARCH, NGP_DBG_PROBE_PER_SAMPLE = 1 << 17, 1 << 18
 NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
 
 _vp, _u32, _f32, _int, _sz = C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_size_t

@@ -1,6 +1,7 @@
 // capi.hip -- error plumbing, version and the optional per-kernel event timing of libngp_hip.
 #include <math.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -26,6 +27,13 @@ int check_launch(const char* what) {
         return NGP_ELAUNCH;
     }
     return NGP_OK;
+}
+
+// the library's only reads of the environment (INTEGRATION.md lists the switches): per call, nothing cached
+bool env_set(const char* name) { return getenv(name) != nullptr; }
+uint32_t env_u32(const char* name, uint32_t dflt) {
+    const char* e = getenv(name);
+    return e ? (uint32_t)atoll(e) : dflt;
 }
 
 static std::mutex g_attr_mu;

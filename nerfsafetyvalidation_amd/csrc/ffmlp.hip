@@ -837,8 +837,7 @@ static uint32_t fused_bwd_blocks(uint32_t B, uint32_t in_dim, uint32_t NL) {
     return n_groups < 256 * per_cu ? n_groups : 256 * per_cu;
 }
 static bool fused_bwd_applies(uint32_t in_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    static const bool off = getenv("NGP_FFMLP_NO_FUSED_BWD") != nullptr;     // diagnostics: the two-kernel form for every shape
-    return !off && hidden_dim == 64 && num_layers >= 2 && num_layers <= 4 && in_dim <= 64;
+    return hidden_dim == 64 && num_layers >= 2 && num_layers <= 4 && in_dim <= 64;
 }
 template <int NL, bool PLANES = false>
 static void launch_bwd_fused(const uint16_t* grad, const uint16_t* inputs, const uint16_t* w, const uint16_t* fwd, uint32_t B, uint32_t in_dim,

@@ -166,6 +166,12 @@ DebugState debug_snapshot() {
     return g_debug_default;
 }
 
+bool debug_flags_valid(int flags, const char* who) {
+    if ((flags & ~NGP_DBG_ALL) == 0) return true;
+    set_error("%s: unknown debug flag bits 0x%x (the NGP_DBG_* constants are all there are)", who, (unsigned)(flags & ~NGP_DBG_ALL));
+    return false;
+}
+
 float* grad_dump() { return g_grad_dump; }
 
 // records needed for the first n_levels levels (0 when they do not fit 32-bit record indices)
@@ -185,7 +191,7 @@ bool needs_generic(const GridLevels& lv) {
     return false;
 }
 
-int fill_net(const ngp_model* m, const DebugState& dbg, const _Float16* packed, NetArgs& na, GridLevels& lv) {
+int fill_net(const ngp_model* m, const _Float16* packed, NetArgs& na, GridLevels& lv) {
     NGP_REQUIRE(m && m->embeddings && m->offsets_host && m->sigma_weights && m->color_weights, "ngp_model: null pointer");
     NGP_REQUIRE(m->L == 16, "fused renderer: the hash grid must have 16 levels with 2 features (got L=%u)", m->L);
     NGP_REQUIRE(m->sigma_hidden_mm <= 2 && m->color_hidden_mm <= 3, "fused renderer: at most 2 / 3 hidden matmuls (got %u / %u)",
@@ -200,7 +206,7 @@ int fill_net(const ngp_model* m, const DebugState& dbg, const _Float16* packed, 
     na.density_scale = m->density_scale;
     na.align_corners = m->align_corners;
     NGP_REQUIRE(m->precision <= NGP_PREC_F16_REF, "ngp_model: unknown precision %u", m->precision);
-    na.dbg_shrink = dbg.shrink() | (m->precision == NGP_PREC_F32 ? 256u : 0u) | (m->precision == NGP_PREC_F16_REF ? 512u : 0u);
+    na.prec_bits = (m->precision == NGP_PREC_F32 ? 256u : 0u) | (m->precision == NGP_PREC_F16_REF ? 512u : 0u);
     na.cells = nullptr;
     na.cell_steps = 0;
     for (int l = 0; l < 16; l++) na.cell_off[l] = 0;
@@ -303,9 +309,10 @@ int ngp_debug_set_sample_hash(uint32_t* device_buf) {
     return NGP_OK;
 }
 
-int ngp_debug_disable_march_queue(int off) {
+int ngp_debug_disable_march_queue(int flags) {
+    if (!debug_flags_valid(flags, "debug_disable_march_queue")) return NGP_EINVAL;
     std::lock_guard<std::mutex> lk(g_debug_mu);
-    g_debug_default.flags = off;
+    g_debug_default.flags = flags;
     return NGP_OK;
 }
 
@@ -316,7 +323,7 @@ int ngp_debug_fused_features(const ngp_model* model, const float* xyzs, uint32_t
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     uint32_t blocks = div_up(div_up(M, 16), 4);

@@ -38,13 +38,11 @@ struct NetArgs {
     const uint4* cells;
     uint32_t cell_steps;
     uint32_t cell_off[16];     // first record of a level
-    // bits 0-3: diagnostics (debug flag bits 4-7): fold hashed levels into size >> n entries (timing only, wrong images);
     // bit 8: ngp_model::precision == NGP_PREC_F32 (`table` holds float pairs, `packed` float fragments: NetF32 below); bit 9: ... == NGP_PREC_F16_REF
     // (host side only: selects the HACC kernel instantiations).  (One word: the struct is a kernel argument of the tuned render loop.)
-    uint32_t dbg_shrink;
-    __host__ __device__ bool f32() const { return (dbg_shrink & 256u) != 0; }
-    __host__ __device__ bool hacc() const { return (dbg_shrink & 512u) != 0; }
-    __host__ __device__ uint32_t shrink() const { return dbg_shrink & 15u; }
+    uint32_t prec_bits;
+    __host__ __device__ bool f32() const { return (prec_bits & 256u) != 0; }
+    __host__ __device__ bool hacc() const { return (prec_bits & 512u) != 0; }
 };
 
 __host__ __device__ inline uint32_t sig_halfs(uint32_t mm) { return 2048 + mm * 4096 + 1024; }
@@ -686,7 +684,7 @@ __device__ __forceinline__ void stage_block(const NetArgs& na, const GridLevels&
         lt->size[l] = size;
         lt->a1[l] = lv.hashed[l] ? 2654435761u : lv.mul1[l];
         lt->a2[l] = lv.hashed[l] ? 805459861u : lv.mul2[l];
-        lt->mask[l] = lv.mode[l] == 1 ? (size >> na.shrink()) - 1 : 0xFFFFFFFFu;
+        lt->mask[l] = lv.mode[l] == 1 ? size - 1 : 0xFFFFFFFFu;
         lt->flags[l] = (uint32_t)lv.hashed[l] | (lv.mode[l] == 2 ? 2u : 0u);
         lt->cell_off[l] = na.cell_off[l];
         lt->cell_res[l] = lv.resolution[l];
@@ -1005,24 +1003,23 @@ struct DebugState {
     int flags = 0;
     unsigned long long* stamps = nullptr;
     uint32_t* sample_hash = nullptr;
-    bool coarse_off() const { return (flags & 2) != 0; }
-    bool sort_off() const { return (flags & 4) != 0; }
-    bool lin_off() const { return (flags & 8) != 0; }
-    bool jump_off() const { return (flags & 1) != 0; }
-    bool spec_off() const { return (flags & 256) != 0; }
-    bool tile_off() const { return (flags & 8192) != 0; }
-    bool pre_verdict_off() const { return (flags & 16384) != 0; }
-    bool narrow_items_off() const { return (flags & 32768) != 0; }
-    bool prefix_replay_off() const { return (flags & 65536) != 0; }
-    bool wave_march_off() const { return (flags & 131072) != 0; }
-    bool cell_runs_off() const { return (flags & 262144) != 0; }
-    uint32_t spec_safety_x2() const { return ((uint32_t)flags >> 9) & 15u; }   // 0: kSpecSafetyX2
-    uint32_t shrink() const { return ((uint32_t)flags >> 4) & 15u; }
+    bool jump_off() const { return (flags & NGP_DBG_NO_BLOCK_JUMP) != 0; }
+    bool coarse_off() const { return (flags & NGP_DBG_NO_COARSE) != 0; }
+    bool sort_off() const { return (flags & NGP_DBG_NO_SLOW_SORT) != 0; }
+    bool lin_off() const { return (flags & NGP_DBG_NO_LIN) != 0; }
+    bool spec_off() const { return (flags & NGP_DBG_ONE_ITER_PER_LAUNCH) != 0; }
+    bool tile_off() const { return (flags & NGP_DBG_NO_TILES) != 0; }
+    bool pre_verdict_off() const { return (flags & NGP_DBG_NO_PRE_VERDICT) != 0; }
+    bool narrow_items_off() const { return (flags & NGP_DBG_WIDE_ITEMS) != 0; }
+    bool prefix_replay_off() const { return (flags & NGP_DBG_REPLAY_ONE_ITER) != 0; }
+    bool wave_march_off() const { return (flags & NGP_DBG_LANE_MARCH) != 0; }
+    bool cell_runs_off() const { return (flags & NGP_DBG_PROBE_PER_SAMPLE) != 0; }
 };
 DebugState debug_snapshot();   // the process default; a render context may carry its own (render_fused.hip)
+bool debug_flags_valid(int flags, const char* who);   // only NGP_DBG_* bits set; else the error text is set (the setters return NGP_EINVAL)
 float* grad_dump();             // ngp_debug_set_grad_dump
 bool needs_generic(const GridLevels& lv);
-int fill_net(const ngp_model* m, const DebugState& dbg, const _Float16* packed, NetArgs& na, GridLevels& lv);
+int fill_net(const ngp_model* m, const _Float16* packed, NetArgs& na, GridLevels& lv);
 size_t weights_bytes(const NetArgs& na);
 uint32_t resident_blocks(size_t lds);
 int net_variant(const NetArgs& na, const GridLevels& lv);

@@ -334,7 +334,7 @@ int ngp_network_density(const ngp_model* model, const float* xyzs, uint32_t M, f
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     NGP_REQUIRE(lds <= 96 * 1024, "network_density: the packed weights need %zu bytes of LDS", lds);
@@ -360,7 +360,7 @@ int ngp_cell_max_density(const ngp_model* model, const float* start_host, float 
     hipStream_t st = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     NGP_REQUIRE(lds <= 96 * 1024, "cell_max_density: the packed weights need %zu bytes of LDS", lds);
@@ -387,7 +387,7 @@ int ngp_network_density_backward(const ngp_model* model, const void* packed_weig
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     NGP_REQUIRE(bwd_shape_ok(na), "network_density_backward: the fp32 form supports at most 1 hidden matmul in the sigma net (got %u)", na.sig_mm);
     const size_t ws = na.f32() ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;
@@ -412,7 +412,7 @@ int ngp_planner_collision(const ngp_model* model, const float* rot_matrix, const
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab) + (kPlanThreads / 64) * sizeof(float);
     NGP_REQUIRE(lds <= 96 * 1024, "planner_collision: the packed weights need %zu bytes of LDS", lds);
@@ -436,7 +436,7 @@ int ngp_planner_collision_backward(const ngp_model* model, const void* packed_we
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     NGP_REQUIRE(bwd_shape_ok(na), "planner_collision_backward: the fp32 form supports at most 1 hidden matmul in the sigma net (got %u)", na.sig_mm);
     const size_t ws = na.f32() ? (size_t)bwd_floats(na.sig_mm) * 4 : (size_t)bwd_halfs(na.sig_mm) * 2;
@@ -461,7 +461,7 @@ int ngp_network_forward(const ngp_model* model, const float* xyzs, const float* 
     NGP_REQUIRE(model && model->packed_weights, "network_forward: model->packed_weights is NULL (ngp_pack_weights fills it)");
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     NGP_REQUIRE(lds <= 96 * 1024, "network_forward: the packed weights need %zu bytes of LDS", lds);

@@ -692,7 +692,7 @@ constexpr float kMergeScale = 0x1p26f, kMergeInvScale = 0x1p-26f;
 template <int D, int NT, bool MERGE>
 __global__ void __launch_bounds__(NT) k_grid_bwd_bin(const _Float16* __restrict__ grad, const float* __restrict__ inputs,
                                                      _Float16* __restrict__ grad_grid, uint32_t B, GridLevels lv, uint32_t gridtype,
-                                                     bool align_corners, BinLevels bl, uint32_t first, BinPlan plan, GridIo io, uint32_t dbg_skip = 0) {
+                                                     bool align_corners, BinLevels bl, uint32_t first, BinPlan plan, GridIo io) {
     constexpr int C = 2, NC = 1 << D;
     constexpr uint32_t RC = MERGE ? NT * NC / 2 : NT * NC;          // staged records
     constexpr int TPS = MERGE ? (int)((kMergeSlots + NT - 1) / NT) : 1;     // table slots per thread
@@ -736,7 +736,7 @@ __global__ void __launch_bounds__(NT) k_grid_bwd_bin(const _Float16* __restrict_
         v[idx * 2] = w * g[0]; v[idx * 2 + 1] = w * g[1];
     }
     const uint32_t lane = threadIdx.x & 63u;
-    const bool tail = (dbg_skip & 8u) ? valid : merge_cell_rows<D>(valid, pg, v);
+    const bool tail = merge_cell_rows<D>(valid, pg, v);
     auto to_half2 = [](float a, float c) {
         const __half2 h = __halves2half2(__float2half_rn(a), __float2half_rn(c));
         return *reinterpret_cast<const uint32_t*>(&h);
@@ -761,8 +761,8 @@ __global__ void __launch_bounds__(NT) k_grid_bwd_bin(const _Float16* __restrict_
                 table_add<_Float16, C>(tab, e, vv);
                 continue;
             }
-            bool in_table = (dbg_skip & 1u) != 0;
-            if (MERGE && !in_table) {
+            bool in_table = false;
+            if (MERGE) {
                 const uint32_t h = (k19 * 2654435761u) >> 22;
 #pragma unroll
                 for (uint32_t pr = 0; pr < 4 && !in_table; pr++) {
@@ -782,8 +782,6 @@ __global__ void __launch_bounds__(NT) k_grid_bwd_bin(const _Float16* __restrict_
             }
         }
     }
-    if (dbg_skip & 2u) return;
-    if ((dbg_skip & 4u) && !tail) return;
     uint32_t tk[TPS], tr[TPS], tv[TPS];                   // MERGE: the table slots this thread turns into records
 #pragma unroll
     for (int j = 0; j < TPS; j++) { tk[j] = kMergeEmpty; tr[j] = 0; tv[j] = 0; }
@@ -936,10 +934,6 @@ __global__ void __launch_bounds__(kReduceThreads) k_grid_bwd_bin_reduce(_Float16
 // workspace of the binned scatter: the caller's (ngp_grid_encode_backward_workspace gives the size that lets every level of a
 // group go through the bins in one pass; with less, the levels are processed in smaller groups, with none they use atomics)
 constexpr size_t kBinWorkspaceMax = (size_t)4 << 30;    // levels are processed in groups that fit this
-static bool g4_off() {                                   // diagnostics (NGP_GRID_NO_G4 set): the one-lane-per-(point, level) kernel for every shape
-    static const bool off = getenv("NGP_GRID_NO_G4") != nullptr;
-    return off;
-}
 #ifndef NGP_BIN_NT
 #define NGP_BIN_NT 1024
 #endif
@@ -949,29 +943,15 @@ constexpr uint32_t kMergeMaxRes = 1024;                   // levels up to this r
 // where nothing is shared across rays: 268 k points 912 -> 1022 steps/s without it, 1 M points 477 -> 493, 4 M 156 -> 161, 10 M 48.1 ->
 // 48.4 (scripts/bench_train_typical.py, NGP_TRAIN_RAYS).  The library cannot see the pixel order; batches this large are frames.
 constexpr uint32_t kMergeMinPoints = 1u << 24;
-static uint32_t merge_min_points() {                     // (NGP_GRID_MERGE_MIN overrides it, read per call: the tests run both variants)
-    const char* e = getenv("NGP_GRID_MERGE_MIN");
-    return e ? (uint32_t)atoll(e) : kMergeMinPoints;
-}
-static uint32_t merge_max_res() {                        // (NGP_GRID_MERGE_RES overrides the threshold: diagnostics)
-    static const uint32_t v = getenv("NGP_GRID_MERGE_RES") ? (uint32_t)atoi(getenv("NGP_GRID_MERGE_RES")) : kMergeMaxRes;
-    return v;
-}
-static bool merge_off() {                                // diagnostics (NGP_GRID_NO_MERGE set): the plain first pass for every level
-    static const bool off = getenv("NGP_GRID_NO_MERGE") != nullptr;
-    return off;
-}
-static bool bin_off() {                                  // diagnostics (NGP_GRID_NO_BINS set): atomics for every level
-    static const bool off = getenv("NGP_GRID_NO_BINS") != nullptr;
-    return off;
-}
+// (NGP_GRID_MERGE_MIN overrides it, read per call: the tests run both variants)
+static uint32_t merge_min_points() { return env_u32("NGP_GRID_MERGE_MIN", kMergeMinPoints); }
 
 // records one level's regions hold: 1.5 x the 2^D updates per point of a batch without mergeable neighbours, + slack for tiny batches
 // (diagnostics: NGP_GRID_BIN_FILL_PCT=<percent of the updates the regions hold> shrinks them so that ordinary inputs overflow)
 static size_t bin_level_records(uint32_t B, uint32_t corners) {
     constexpr size_t parts = 2 * kBinMax * kBinShards;
-    const char* env = getenv("NGP_GRID_BIN_FILL_PCT");
-    const size_t pct = env && atoi(env) > 0 ? (size_t)atoi(env) : 150;
+    const int32_t env = (int32_t)env_u32("NGP_GRID_BIN_FILL_PCT", 150);
+    const size_t pct = env > 0 ? (size_t)env : 150;
     return (((size_t)B * corners * pct / 100 + kBinMax * kBinShards * 128) / parts) * parts;
 }
 static size_t bin_level_bytes(uint32_t B, uint32_t corners) {
@@ -1073,10 +1053,10 @@ static void launch_backward(const void* grad, const float* inputs, void* grad_em
         uint32_t n_bin = 0;
         // the levels whose cells the neighbouring rays of a workgroup share come first: they take the merging variant of the first pass
         uint32_t n_merge = 0;
-        if (!bin_off() && B >= 128u * 1024u)
+        if (B >= 128u * 1024u)
             for (int pass = 0; pass < 2; pass++) {
                 for (uint32_t l = 0; l < L; l++) {
-                    const bool merge = lv.resolution[l] <= merge_max_res() && !merge_off() && B >= merge_min_points();
+                    const bool merge = lv.resolution[l] <= kMergeMaxRes && B >= merge_min_points();
                     if (merge == (pass == 0) && !((small_mask >> l) & 1u) && lv.offset[l + 1] - lv.offset[l] <= kBinMax * kBinEntries) bl.level[n_bin++] = l;
                 }
                 if (pass == 0) n_merge = n_bin;
@@ -1088,7 +1068,6 @@ static void launch_backward(const void* grad, const float* inputs, void* grad_em
         group = group < n_bin ? group : n_bin;
         char* ws = group ? (char*)workspace : nullptr;
         if (ws) {
-            static const uint32_t dbg_skip = getenv("NGP_GRID_BWD_SKIP") ? (uint32_t)atoi(getenv("NGP_GRID_BWD_SKIP")) : 0u;
             constexpr uint32_t NT = NGP_BIN_NT;
             const uint32_t n_pb = div_up(B, NT);
             const size_t lds_bin = (size_t)NT * (1u << D) * sizeof(uint2);
@@ -1108,22 +1087,21 @@ static void launch_backward(const void* grad, const float* inputs, void* grad_em
                 (void)hipMemsetAsync(plan.fill, 0, (size_t)n * kBinMax * kBinShards * kFillStride * sizeof(uint32_t), s);
                 if (merge)
                     k_grid_bwd_bin<D, NT, true><<<dim3(n_pb, n), NT, lds_merge, s>>>((const _Float16*)grad, inputs, (_Float16*)grad_emb, B, lv, gridtype,
-                                                                                     ac, bl, first, plan, io, dbg_skip);
+                                                                                     ac, bl, first, plan, io);
                 else
                     k_grid_bwd_bin<D, NT, false><<<dim3(n_pb, n), NT, lds_bin, s>>>((const _Float16*)grad, inputs, (_Float16*)grad_emb, B, lv, gridtype,
-                                                                                    ac, bl, first, plan, io, dbg_skip);
+                                                                                    ac, bl, first, plan, io);
                 // a bin holds at most 32 regions of `cap` records: no more reducing workgroups than that can keep busy
                 uint32_t max_split = 1;
                 while (max_split < kBinSplit && (size_t)level_records / kBinMax >= (size_t)2 * max_split * kBinSplitMin) max_split *= 2;
                 k_grid_bwd_bin_reduce<<<dim3(kBinMax * max_split, n), kReduceThreads, lds_red, s>>>((_Float16*)grad_emb, lv, bl, first, plan);
-                if (getenv("NGP_GRID_BWD_STATS")) {      // diagnostics: how evenly the regions filled
+                if (env_set("NGP_GRID_BWD_STATS")) {      // diagnostics: how evenly the regions filled
                     std::vector<uint32_t> h((size_t)n * kBinMax * kBinShards * kFillStride);
                     (void)hipStreamSynchronize(s);
                     (void)hipMemcpy(h.data(), plan.fill, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
                     for (uint32_t i = 0; i < n; i++) {
                         const uint32_t level = bl.level[first + i];
-                        const uint32_t hs = lv.offset[level + 1] - lv.offset[level];
-                        const uint32_t nb = kBinMax; (void)hs;
+                        const uint32_t nb = kBinMax;
                         const uint32_t cap = region_cap(level_records, nb);
                         uint64_t tot = 0, over = 0; uint32_t mx = 0;
                         for (uint32_t r = 0; r < nb * kBinShards; r++) {
@@ -1186,7 +1164,7 @@ static int grid_encode_forward(const float* inputs, const void* embeddings, cons
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("grid_encode_forward", s, B);
     const bool g = calc_grad_inputs != 0, ac = align_corners != 0;
-    if (dtype == NGP_F16 && D == 3 && C == 2 && !g4_off()) {
+    if (dtype == NGP_F16 && D == 3 && C == 2) {
         // the common shape: four levels per lane, optionally through the per-cell corner records (same values, same arithmetic)
         GridLevels cell_off = {};
         const uint4* cells = nullptr;
@@ -1288,7 +1266,7 @@ int ngp_grid_encode_backward_strided(const void* grad, const float* inputs, cons
 
 size_t ngp_grid_encode_backward_workspace(uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype) {
     // only the binned scatter of an fp16, two-feature table on a large batch uses it (launch_backward)
-    if (dtype != NGP_F16 || C != 2 || B < 128u * 1024u || bin_off()) return 0;
+    if (dtype != NGP_F16 || C != 2 || B < 128u * 1024u) return 0;
     const size_t per_level = bin_level_bytes(B, 1u << D);
     const size_t all = per_level * L;
     if (all <= kBinWorkspaceMax) return all;

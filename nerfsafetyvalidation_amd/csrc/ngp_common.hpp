@@ -25,6 +25,10 @@ int check_launch(const char* what);
         }                                      \
     } while (0)
 
+// ---- diagnostics switches read from the environment (capi.hip; read on every call, never cached) ----
+bool env_set(const char* name);                        // the variable exists
+uint32_t env_u32(const char* name, uint32_t dflt);     // its integer value, `dflt` when it does not
+
 // ---- optional per-kernel timing (ngp_prof_*) -----------------------------------
 struct ProfScope {
     ProfScope(const char* name, hipStream_t s, double units);

@@ -780,9 +780,8 @@ int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t
     char* extra = (char*)workspace + train_counts_bytes(N);      // the two copies, then the trace
     float2* trace = nullptr;
     if (lin && train_trace_bytes(N) && max_steps <= kTraceMaxSteps) trace = (float2*)(extra + kTrainLinBytes + kCoarseMaxBytes);
-    // both passes: a wave per ray on the step lattice (NGP_MARCH_TRAIN_NO_WAVE: never), a lane per ray with the trace replayed, or marching twice
-    static const bool wave_off = getenv("NGP_MARCH_TRAIN_NO_WAVE") != nullptr;
-    enum { kWave, kTraced, kLin, kPlain } const form = !lin ? kPlain : (!trace ? kLin : ((dt_gamma == 0.0f && !wave_off) ? kWave : kTraced));
+    // both passes: a wave per ray on the step lattice (dt_gamma == 0 only), a lane per ray with the trace replayed, or marching twice
+    enum { kWave, kTraced, kLin, kPlain } const form = !lin ? kPlain : (!trace ? kLin : (dt_gamma == 0.0f ? kWave : kTraced));
     if (lin) tl = build_occupancy_lin(grid, C, H, extra, extra + kTrainLinBytes, s);
 #define NGP_COUNT(LIN_, TRACE_)                                                                                                                   \
     k_march_train_count<LIN_, TRACE_><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb, rng, \

@@ -76,7 +76,8 @@ constexpr uint32_t kSpecK = 8;            // most reference iterations per launc
 constexpr uint32_t kSpecMarginDiv = 16;   // first launch: entered only if n_alive - N/2 > N / kSpecMarginDiv
 // largest q for which a launch covers several iterations (K * q <= 8 samples per ray and launch, K >= 2)
 constexpr uint32_t kSpecMaxQ = 8;
-constexpr uint32_t kSpecMaxSamples = 32;  // samples per ray and launch in the n_step >= 5 regimes
+constexpr uint32_t kSpecMaxSamples = 32;  // samples per ray and launch in the n_step >= 5 regimes (k_render_compact's cap_hi)
+constexpr uint32_t kSpecMidSamples = 8;   // ... and in the n_step 2..4 regimes (its cap_mid_max)
 constexpr uint32_t kSpecSafetyX2 = 1;     // later launches: sized for kSpecSafetyX2 / 2 x the recent death rate (+ 4 sigma + 16 rays).  1.5 x until
                                           // a failed launch came to be replayed as its verified prefix: a wrong guess now costs the discarded
                                           // launch only, and the larger launches win (bound-2 frame: 49.5 -> 41.8 launches, 4.80 -> 4.48 ms)
@@ -869,8 +870,7 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
             uint32_t sq = 0;
             while ((unsigned long long)(sq + 1) * (sq + 1) <= recent) sq++;
             const unsigned long long rate = (unsigned long long)recent + 4ull * sq + 16ull;
-            const uint32_t safety_x2 = (spec_allowed >> 8) ? (spec_allowed >> 8) : kSpecSafetyX2;   // (diagnostics may override the factor)
-            uint32_t K = (uint32_t)((unsigned long long)headroom * 2u / (safety_x2 * rate));
+            uint32_t K = (uint32_t)((unsigned long long)headroom * 2u / (kSpecSafetyX2 * rate));
             // at most 8 samples per ray and launch while n_step is small; in the n_step >= 5 regimes (few rays, every launch
             // latency-bound) up to kSpecMaxSamples.  With n_step = 8 the guess cannot fail: N // n_alive only grows as rays die.
             const uint32_t cap_mid = 8u * q < cap_mid_max ? 8u * q : cap_mid_max;      // (n_alive <= N / q: at most 8 N samples per launch)
@@ -1007,20 +1007,21 @@ struct ngp_render_ctx {
     hipEvent_t ev[kRing];
     int num_cu = 256;
     bool has_debug = false;      // ngp_render_ctx_set_debug: this context's own diagnostics state (else the process default)
-    int debug_flags = 0;
-    unsigned long long* debug_stamps = nullptr;
-    uint32_t* debug_sample_hash = nullptr;
+    DebugState debug;
+    void* owned[20] = {};        // every hipMalloc'ed buffer above (ctx_alloc), for ngp_render_ctx_destroy
+    uint32_t n_owned = 0;
 };
 
-// this context's own diagnostics state (ngp_render_ctx_set_debug), else the process default
-static DebugState debug_snapshot(const ngp_render_ctx* ctx) {
-    if (ctx && ctx->has_debug) {
-        DebugState d;
-        d.flags = ctx->debug_flags; d.stamps = ctx->debug_stamps; d.sample_hash = ctx->debug_sample_hash;
-        return d;
-    }
-    return ngp::debug_snapshot();
+// hipMalloc into one of the context's pointers; the context owns the buffer from then on
+template <typename T>
+static bool ctx_alloc(ngp_render_ctx* c, T** p, size_t bytes) {
+    if (c->n_owned == sizeof(c->owned) / sizeof(c->owned[0]) || hipMalloc(p, bytes) != hipSuccess) return false;
+    c->owned[c->n_owned++] = *p;
+    return true;
 }
+
+// this context's own diagnostics state (ngp_render_ctx_set_debug), else the process default
+static DebugState debug_snapshot(const ngp_render_ctx* ctx) { return ctx->has_debug ? ctx->debug : ngp::debug_snapshot(); }
 
 extern "C" {
 
@@ -1035,21 +1036,21 @@ int ngp_render_ctx_create(uint32_t max_rays, ngp_render_ctx** out) {
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) c->num_cu = prop.multiProcessorCount;
     const size_t max_items = items_bound(max_rays, (uint32_t)c->num_cu * 16u) + 8;
-    ok &= hipMalloc(&c->alive[0], (size_t)max_rays * 4) == hipSuccess;
-    ok &= hipMalloc(&c->alive[1], (size_t)max_rays * 4) == hipSuccess;
-    ok &= hipMalloc(&c->staging, chunks * 64 * 4) == hipSuccess;
-    ok &= hipMalloc(&c->chunk_count, (max_items > (size_t)div_up(max_rays, 256) ? max_items : (size_t)div_up(max_rays, 256)) * 4) == hipSuccess;
-    ok &= hipMalloc(&c->rays_t, (size_t)max_rays * 4) == hipSuccess;
-    ok &= hipMalloc(&c->coarse, kCoarseMaxBytes) == hipSuccess;
-    ok &= hipMalloc(&c->ctl, 2 * sizeof(Ctl)) == hipSuccess;
-    ok &= hipMalloc(&c->stat_shards, kStatShards * sizeof(unsigned long long)) == hipSuccess;
-    ok &= hipMalloc(&c->death_shards, 2 * (size_t)kDeathWords * sizeof(uint32_t)) == hipSuccess;   // two buffers, by launch parity
-    ok &= hipMalloc(&c->backup, (size_t)max_rays * 2 * sizeof(float4)) == hipSuccess;
+    ok &= ctx_alloc(c, &c->alive[0], (size_t)max_rays * 4);
+    ok &= ctx_alloc(c, &c->alive[1], (size_t)max_rays * 4);
+    ok &= ctx_alloc(c, &c->staging, chunks * 64 * 4);
+    ok &= ctx_alloc(c, &c->chunk_count, (max_items > (size_t)div_up(max_rays, 256) ? max_items : (size_t)div_up(max_rays, 256)) * 4);
+    ok &= ctx_alloc(c, &c->rays_t, (size_t)max_rays * 4);
+    ok &= ctx_alloc(c, &c->coarse, kCoarseMaxBytes);
+    ok &= ctx_alloc(c, &c->ctl, 2 * sizeof(Ctl));
+    ok &= ctx_alloc(c, &c->stat_shards, kStatShards * sizeof(unsigned long long));
+    ok &= ctx_alloc(c, &c->death_shards, 2 * (size_t)kDeathWords * sizeof(uint32_t));   // two buffers, by launch parity
+    ok &= ctx_alloc(c, &c->backup, (size_t)max_rays * 2 * sizeof(float4));
     // (n_alive * n_step <= 8 N in every regime of the schedule: n_step <= 8 while more than N / 5 rays live, <= 32 below that)
-    ok &= hipMalloc(&c->march_samples, ((size_t)max_rays + 512) * 8 * sizeof(float2)) == hipSuccess;   // (n_alive / q + 64) * 8 q samples, q <= 4
-    ok &= hipMalloc(&c->march_counts, (size_t)max_rays) == hipSuccess;
-    ok &= hipMalloc(&c->heads, 2 * sizeof(QueueHeads)) == hipSuccess;
-    ok &= hipMalloc(&c->packed, (size_t)(sig_halfs(2) + sig_halfs(3)) * 2) == hipSuccess;
+    ok &= ctx_alloc(c, &c->march_samples, ((size_t)max_rays + 512) * 8 * sizeof(float2));   // (n_alive / q + 64) * 8 q samples, q <= 4
+    ok &= ctx_alloc(c, &c->march_counts, (size_t)max_rays);
+    ok &= ctx_alloc(c, &c->heads, 2 * sizeof(QueueHeads));
+    ok &= ctx_alloc(c, &c->packed, (size_t)(sig_halfs(2) + sig_halfs(3)) * 2);
     ok &= hipHostMalloc(&c->status, kRing * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
     if (ok) {
         memset(c->status, 0, kRing * sizeof(unsigned long long));
@@ -1079,8 +1080,7 @@ int ngp_render_ctx_set_frame_width(ngp_render_ctx* ctx, uint32_t width) {
 int ngp_render_ctx_destroy(ngp_render_ctx* c) {
     if (!c) return NGP_OK;
     (void)hipDeviceSynchronize();      // a render call no longer ends with a synchronize: its run-ahead launches may still use the scratch
-    (void)hipFree(c->alive[0]); (void)hipFree(c->alive[1]); (void)hipFree(c->staging); (void)hipFree(c->chunk_count);
-    (void)hipFree(c->rays_t); (void)hipFree(c->coarse); (void)hipFree(c->grid_lin); (void)hipFree(c->death_shards); (void)hipFree(c->backup); (void)hipFree(c->march_samples); (void)hipFree(c->march_counts); (void)hipFree(c->dump_rec); (void)hipFree(c->dump_iter); (void)hipFree(c->ctl); (void)hipFree(c->stat_shards); (void)hipFree(c->heads); (void)hipFree(c->packed);
+    for (uint32_t i = 0; i < c->n_owned; i++) (void)hipFree(c->owned[i]);
     if (c->status) (void)hipHostFree(c->status);
     if (c->fin) (void)hipHostFree(c->fin);
     for (int i = 0; i < kRing; i++) (void)hipEventDestroy(c->ev[i]);
@@ -1088,7 +1088,7 @@ int ngp_render_ctx_destroy(ngp_render_ctx* c) {
     return NGP_OK;
 }
 
-// Render calls in progress in this process (a scheduling hint only: see the persistent workgroup count in ngp_render_rays)
+// Render calls in progress in this process (a scheduling hint only: see the persistent workgroup count in enqueue_launch)
 static std::atomic<int> g_active_renders{0};
 struct ActiveRender {
     ActiveRender() { g_active_renders.fetch_add(1, std::memory_order_relaxed); }
@@ -1101,11 +1101,11 @@ struct ActiveRender {
 static bool choose_occupancy(ngp_render_ctx* ctx, const ngp_model* model, const DebugState& dbg, hipStream_t s, RenderArgs& ra) {
     const uint32_t C = model->cascade, H = model->grid_size;
     const size_t cells = (size_t)C * H * H * H;
-    // bit 3 of the debug flags turns the linear re-layout off; without the coarse filter there is none either
+    // (NGP_DBG_NO_LIN turns the linear re-layout off; without the coarse filter there is none either)
     bool lin = !dbg.coarse_off() && !dbg.lin_off() && occupancy_lin_fits(C, H, model->density_bitfield, kLinMaxBytes, kCoarseMaxBytes);
     // (the Morton-order filter asks less of the grid: any H whose block bits fit)
     const bool use_coarse = !dbg.coarse_off() && cells % 4096 == 0 && cells / 64 / 8 <= kCoarseMaxBytes && ((uintptr_t)model->density_bitfield & 7) == 0;
-    if (lin && !ctx->grid_lin && hipMalloc(&ctx->grid_lin, kLinMaxBytes) != hipSuccess) lin = false;
+    if (lin && !ctx->grid_lin && !ctx_alloc(ctx, &ctx->grid_lin, kLinMaxBytes)) lin = false;
     if (lin) {
         ra.occ = build_occupancy_lin(model->density_bitfield, C, H, ctx->grid_lin, ctx->coarse, s);
         ra.block_jump = dbg.jump_off() ? 0u : 1u;
@@ -1118,6 +1118,163 @@ static bool choose_occupancy(ngp_render_ctx* ctx, const ngp_model* model, const 
         ra.sort_slow = 0;
     }
     return lin;
+}
+
+// What a call's launches share: the loop's scratch (context), the grid (model), the schedule (arguments) and the diagnostics state.
+// The caller's own pointers (rays, outputs, padding) are filled in by ngp_render_rays.
+static void fill_render_args(const ngp_render_ctx* ctx, const ngp_model* model, const DebugState& dbg, uint32_t N, float dt_gamma,
+                             uint32_t max_steps, uint32_t perturb, RenderArgs& ra) {
+    ra.rays_t = ctx->rays_t;
+    ra.staging = ctx->staging; ra.chunk_count = ctx->chunk_count; ra.stat_shards = ctx->stat_shards;
+    ra.wave_slots = dbg.narrow_items_off() ? 0u : (uint32_t)ctx->num_cu * 16u;
+    ra.pre_verdict = dbg.pre_verdict_off() ? 0u : 1u;
+    ra.cell_runs = dbg.cell_runs_off() ? 0u : 1u;
+    ra.wave_march_max = (dbg.wave_march_off() || dt_gamma != 0.0f) ? 0u : (uint32_t)ctx->num_cu * 64u;
+    ra.backup = ctx->backup;
+    ra.march_samples = ctx->march_samples; ra.march_counts = ctx->march_counts;
+    ra.bitfield = model->density_bitfield; ra.cascade = model->cascade; ra.grid_size = model->grid_size;
+    ra.max_steps = max_steps; ra.perturb = perturb; ra.dt_gamma = dt_gamma;
+    ra.n_rays = N;
+    ra.rng.seed((uint64_t)perturb);  // raymarching.cu:819
+    ra.stamps = dbg.stamps;
+    ra.sort_slow = (perturb == 0 && !dbg.sort_off()) ? 1u : 0u;   // needs the coarse filter: choose_occupancy clears it without
+    ra.sample_hash = dbg.sample_hash;
+}
+
+// the kernel instantiation of a call: (index recipe) x (corner rounding)
+typedef void (*IterKernel)(NetArgs, GridLevels, RenderArgs);
+static IterKernel choose_iter_kernel(const NetArgs& na, const GridLevels& lv) {
+    static const IterKernel kIter[2][3] = {{k_render_iter<0, false>, k_render_iter<1, false>, k_render_iter<2, false>},
+                                           {k_render_iter<0, true>, k_render_iter<1, true>, k_render_iter<2, true>}};
+    return kIter[na.hacc() ? 1 : 0][needs_generic(lv) ? 1 : (na.cells ? 2 : 0)];
+}
+
+// Enqueues launch number `launched` of a call: the march, the network over its samples, the compaction that publishes its status word.
+// `ub`: the host's upper bound of the launch's n_alive.
+static void enqueue_launch(ngp_render_ctx* ctx, const NetArgs& na, const GridLevels& lv, RenderArgs& ra, IterKernel iter_kernel, size_t lds,
+                           bool lin, uint32_t ub, uint32_t launched, uint32_t spec_allowed, uint32_t call_tag, hipStream_t s) {
+    const uint32_t cur = launched & 1;
+    const uint32_t chunks = items_bound(ub, ra.wave_slots);     // work items of the launch, at most
+    // persistent: resident workgroups pull chunks from a queue.  k_render_iter at two workgroups per CU holds every vector register and
+    // 144 KB of the LDS of the CUs it runs on, so nothing of another frame's launches runs beside it; at five eighths of that it
+    // is 5 % slower on its own (its bound is the gather, not the waves in flight) and leaves room for another call's march and
+    // compaction kernels: +2-3 % frames/s with three calls in flight.  Taken when another render call of this process is in progress
+    // (results do not depend on the workgroup count).
+    const uint32_t blocks_per_cu = lds <= 80 * 1024 ? 2 : 1;
+    const uint32_t blocks_pct = g_active_renders.load(std::memory_order_relaxed) > 1 ? 62u : 100u;
+    const uint32_t max_blocks = (uint32_t)ctx->num_cu * blocks_per_cu * blocks_pct / 100u;
+    const uint32_t want_blocks = div_up(chunks, kWaves);
+    const uint32_t blocks = want_blocks < max_blocks ? want_blocks : max_blocks;
+    ra.alive_in = ctx->alive[cur];
+    ra.ctl = ctx->ctl + cur;
+    ra.heads = ctx->heads + cur;
+    ra.death_shards = ctx->death_shards + (size_t)cur * kDeathWords;
+    {
+        ProfScope pm("k_march_ahead", s, 0);  // per-launch events only when ngp_prof_enable(1)
+        // (one wave per ray when the launch turns out to have at most wave_march_max rays: four rays per block)
+        const uint32_t by_wave = div_up(ub < ra.wave_march_max ? ub : ra.wave_march_max, 4);
+        const uint32_t by_lane = div_up(ub ? ub : 1, 256);
+        if (lin) k_march_ahead<true><<<by_lane > by_wave ? by_lane : by_wave, 256, 0, s>>>(ra, na.bound);
+        else k_march_ahead<false><<<div_up(ub ? ub : 1, 256), 256, 0, s>>>(ra, na.bound);
+    }
+    {
+        ProfScope pk("k_render_iter", s, 0);
+        iter_kernel<<<blocks, kThreads, lds, s>>>(na, lv, ra);
+    }
+    k_render_compact<<<div_up(chunks, 8), 256, 0, s>>>(ctx->ctl + cur, ctx->ctl + (cur ^ 1), ctx->staging, ctx->chunk_count,
+                                                       ctx->alive[cur ^ 1], ra.n_rays, ra.max_steps, ctx->stat_shards, ctx->heads + (cur ^ 1),
+                                                       ctx->status_dev + launched % kRing, ctx->seq_base + launched + 1,
+                                                       ctx->death_shards + (size_t)cur * kDeathWords, spec_allowed, ctx->alive[cur],
+                                                       ctx->backup, ctx->rays_t, ra.weights_sum, ra.depth, ra.image, ra.sample_hash, ctx->stat_shards,
+                                                       ctx->death_shards + (size_t)(cur ^ 1) * kDeathWords, ra.wave_slots, kSpecMidSamples,
+                                                       kSpecMaxSamples, ctx->fin_dev, call_tag);
+}
+
+// Consumes every status word that has already landed (known -> launched); blocks only when the host is kLookahead launches ahead.
+// Each word gives the next launch's bound `ub`, the last one sets `done`.
+static int consume_status(const ngp_render_ctx* ctx, hipStream_t s, uint32_t launched, uint32_t call_tag, bool trace, uint32_t& known,
+                          uint32_t& ub, bool& done) {
+    while (known < launched) {
+        const bool must_wait = launched - known >= (uint32_t)kLookahead;
+        volatile unsigned long long* slot = ctx->status + known % kRing;
+        const uint32_t want_seq = ctx->seq_base + known + 1;
+        unsigned long long w = *slot;
+        if ((uint32_t)(w >> 32) != want_seq) {
+            if (!must_wait) break;
+            uint32_t spins = 0;
+            while ((uint32_t)((w = *slot) >> 32) != want_seq) {
+                // every 2^20 polls (tens of milliseconds: far longer than any launch) make sure the stream is still alive.  Rarely,
+                // because the query is not free on the device side: the runtime answers it with a marker packet in the queue, and the
+                // kernels behind it start ~6 us late -- at every 4096 polls that was one gap per launch (kernel timeline, round 3)
+                if ((++spins & 0xFFFFFu) == 0) {
+                    const hipError_t q = hipStreamQuery(s);
+                    if (q != hipSuccess && q != hipErrorNotReady) {
+                        set_error("render_rays: %s", hipGetErrorString(q));
+                        return NGP_ELAUNCH;
+                    }
+                    if (q == hipSuccess && (uint32_t)(*slot >> 32) != want_seq) {   // everything ran, nothing was published: cannot happen
+                        set_error("render_rays: the device finished without publishing iteration %u", known);
+                        return NGP_ELAUNCH;
+                    }
+                }
+                __builtin_ia32_pause();
+            }
+        }
+        known++;
+        ub = (uint32_t)w & 0x7FFFFFFFu;
+        if (trace) fprintf(stderr, "[ngp] call %u launch %u: n_alive %u%s\n", call_tag, known, ub, ((w >> 31) & 1ull) ? " done" : "");
+        if ((w >> 31) & 1ull) { done = true; break; }
+    }
+    return NGP_OK;
+}
+
+// The finished loop's counters -> *stats_host (and, with `sync`, the wait for the stream).  `last`: the Ctl after the last launch.
+static int read_counters(const ngp_render_ctx* ctx, hipStream_t s, const Ctl* last, uint32_t call_tag, uint32_t N, uint32_t launches, int sync,
+                         ngp_render_stats* stats_host) {
+    bool have_fin = false;
+    Ctl fin = {};   // state after the last enqueued iteration (done is sticky)
+    if (stats_host && !sync) {
+        // the finished loop's counters arrive in pinned memory next to the status word the loop has already seen: a short,
+        // bounded wait for the four tags (they are stored just before that word), then no synchronize and no copy
+        volatile unsigned long long* f = ctx->fin;
+        unsigned long long w[4] = {0, 0, 0, 0};
+        for (uint32_t spin = 0; spin < 200000u && !have_fin; spin++) {
+            bool all = true;
+            for (int i = 0; i < 4; i++) {
+                w[i] = f[i];
+                all = all && (w[i] >> 48) == (0x8000u | call_tag);
+            }
+            have_fin = all;
+            if (!have_fin) __builtin_ia32_pause();
+        }
+        if (have_fin) {
+            fin.samples_marched = w[0] & 0xFFFFFFFFFFFFull;
+            fin.samples_slots = w[1] & 0xFFFFFFFFFFFFull;
+            fin.iters = (uint32_t)((w[2] >> 24) & 0xFFFFFFu);
+            fin.rollbacks = (uint32_t)(w[2] & 0xFFFFFFu);
+            fin.last_n_alive = (uint32_t)((w[3] >> 8) & 0xFFFFFFFFu);
+            fin.last_n_step = (uint32_t)(w[3] & 0xFFu);
+        }
+    }
+    if ((stats_host && !have_fin) || sync) {
+        if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&fin, last, sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("render_rays: %s", hipGetErrorString(hipGetLastError()));
+            return NGP_ELAUNCH;
+        }
+        have_fin = true;
+    }
+    if (have_fin && stats_host) {
+        stats_host->samples_marched = fin.samples_marched;
+        stats_host->samples_slots = fin.samples_slots;
+        stats_host->iterations = fin.iters;
+        stats_host->rays = N;
+        stats_host->last_n_alive = fin.last_n_alive;
+        stats_host->last_n_step = fin.last_n_step;
+        stats_host->launches = launches;
+        stats_host->replayed = fin.rollbacks;
+        prof_add_units("k_render_iter", (double)fin.samples_marched);
+    }
+    return NGP_OK;
 }
 
 int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* rays_o, const float* rays_d, const float* nears,
@@ -1141,7 +1298,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     // fragment-major weights: the model's own (ngp_pack_weights, packed once per parameter version) or, without them, packed into
     // this context's buffer now
     const _Float16* packed = model && model->packed_weights ? (const _Float16*)model->packed_weights : ctx->packed;
-    int rc = fill_net(model, dbg, packed, na, lv);
+    int rc = fill_net(model, packed, na, lv);
     if (rc) return rc;
     NGP_REQUIRE(!na.f32(), "render_rays: the occupancy-grid loop is built for the fp16 network (ngp_model::precision == NGP_PREC_F16)");
     if (!model->packed_weights) {
@@ -1149,12 +1306,10 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
         k_pack_weights<<<div_up(n_packed, 256), 256, 0, s>>>((const _Float16*)model->sigma_weights, na.sig_mm,
                                                              (const _Float16*)model->color_weights, na.col_mm, ctx->packed);
     }
-    // several reference iterations per launch (see Ctl): not with jitter
-    // bit 0: launches may cover several reference iterations; bit 1: but never the last one (its tensors are wanted); bits 8..: diagnostics
-    // bit 0: launches may cover several iterations; bit 1: the last iteration runs on its own; bit 2 (diagnostics): a failed launch is
-    // replayed as ONE iteration instead of its verified prefix; bits 8-11: safety factor override
-    const uint32_t spec_allowed = (!dbg.spec_off() && perturb == 0)
-                                      ? (1u | (last_sigmas ? 2u : 0u) | (dbg.prefix_replay_off() ? 4u : 0u) | (dbg.spec_safety_x2() << 8)) : 0u;
+    // several reference iterations per launch (see Ctl), not with jitter.  bit 0: launches may cover several iterations; bit 1: the last
+    // iteration runs on its own (its tensors are wanted); bit 2 (diagnostics): a failed launch is replayed as ONE iteration instead of
+    // its verified prefix
+    const uint32_t spec_allowed = (!dbg.spec_off() && perturb == 0) ? (1u | (last_sigmas ? 2u : 0u) | (dbg.prefix_replay_off() ? 4u : 0u)) : 0u;
     // scheduling hint (ngp_render_ctx_set_frame_width): whole rows of 4x4-pixel tiles only; not with jitter (seeded with the list index)
     const uint32_t fw = ctx->frame_width;
     const uint32_t tile_w = (perturb == 0 && !dbg.tile_off() && fw >= 4 && fw % 4 == 0 && N % (4 * fw) == 0) ? fw : 0u;
@@ -1164,37 +1319,17 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
                                                  dbg.sample_hash, ctx->stat_shards, ctx->heads, ctx->death_shards, spec_allowed, tile_w);
 
     RenderArgs ra = {};
-    ra.rays_o = rays_o; ra.rays_d = rays_d; ra.fars = fars; ra.rays_t = ctx->rays_t;
+    ra.rays_o = rays_o; ra.rays_d = rays_d; ra.fars = fars;
     ra.weights_sum = weights_sum; ra.depth = depth; ra.image = image;
     ra.last_sigmas = last_sigmas; ra.last_rgbs = last_rgbs;
     if (pad_value_host) { ra.pad_sigma = pad_value_host[0]; ra.pad_r = pad_value_host[1]; ra.pad_g = pad_value_host[2]; ra.pad_b = pad_value_host[3]; }
-    ra.staging = ctx->staging; ra.chunk_count = ctx->chunk_count; ra.stat_shards = ctx->stat_shards;
-    {
-        static const char* env = getenv("NGP_ITEM_SLOTS");       // diagnostics (A/B timing): 0 = 64-entry items always
-        ra.wave_slots = dbg.narrow_items_off() ? 0u : (env ? (uint32_t)atoi(env) : (uint32_t)ctx->num_cu * 16u);
-        static const bool no_pre = getenv("NGP_NO_PRE_VERDICT") != nullptr;   // diagnostics: every multi-iteration launch runs as planned
-        ra.pre_verdict = (no_pre || dbg.pre_verdict_off()) ? 0u : 1u;
-        static const bool no_runs = getenv("NGP_NO_CELL_RUNS") != nullptr;   // diagnostics (A/B timing): a probe per sample
-        ra.cell_runs = (no_runs || dbg.cell_runs_off()) ? 0u : 1u;
-        static const char* wm = getenv("NGP_WAVE_MARCH_MAX");    // diagnostics (A/B timing): 0 = a lane per ray always
-        ra.wave_march_max = (dbg.wave_march_off() || dt_gamma != 0.0f) ? 0u : (wm ? (uint32_t)atoi(wm) : (uint32_t)ctx->num_cu * 64u);
-    }
-    ra.backup = ctx->backup;
-    ra.march_samples = ctx->march_samples; ra.march_counts = ctx->march_counts;
-    ra.bitfield = model->density_bitfield; ra.cascade = model->cascade; ra.grid_size = model->grid_size;
-    ra.max_steps = max_steps; ra.perturb = perturb; ra.dt_gamma = dt_gamma;
-    ra.n_rays = N;
-    ra.rng.seed((uint64_t)perturb);  // raymarching.cu:819
-    ra.stamps = dbg.stamps;
-    ra.sort_slow = (perturb == 0 && !dbg.sort_off()) ? 1u : 0u;   // needs the coarse filter; checked below
-    ra.sample_hash = dbg.sample_hash;
-
+    fill_render_args(ctx, model, dbg, N, dt_gamma, max_steps, perturb, ra);
     const bool lin = choose_occupancy(ctx, model, dbg, s, ra);
     if ((ra.sort_slow || tile_w) && last_sigmas) {
         // regrouped alive list + last-iteration tensors requested: collect per-ray records, restore the row order afterwards
         if (!ctx->dump_rec) {
-            if (hipMalloc(&ctx->dump_rec, (size_t)ctx->max_rays * 8 * sizeof(float4)) != hipSuccess ||
-                hipMalloc(&ctx->dump_iter, (size_t)ctx->max_rays * 4) != hipSuccess) {
+            if (!ctx_alloc(ctx, &ctx->dump_rec, (size_t)ctx->max_rays * 8 * sizeof(float4)) ||
+                !ctx_alloc(ctx, &ctx->dump_iter, (size_t)ctx->max_rays * 4)) {
                 set_error("render_rays: cannot allocate the per-ray record buffer");
                 return NGP_ENODEVICE;
             }
@@ -1204,173 +1339,45 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
         ra.dump_iter = ctx->dump_iter;
     }
     const size_t lds = weights_bytes(na) + sizeof(LevelTab) + (size_t)kWaves * sizeof(WaveSlab);
-    const uint32_t blocks_per_cu = lds <= 80 * 1024 ? 2 : 1;
-    const bool generic = needs_generic(lv);
-    const bool use_cells = na.cells != nullptr;
-    // the kernel instantiation of this call: (index recipe) x (corner rounding)
-    typedef void (*IterKernel)(NetArgs, GridLevels, RenderArgs);
-    const int mode = generic ? 1 : (use_cells ? 2 : 0);
-    static const IterKernel kIter[2][3] = {{k_render_iter<0, false>, k_render_iter<1, false>, k_render_iter<2, false>},
-                                           {k_render_iter<0, true>, k_render_iter<1, true>, k_render_iter<2, true>}};
-    const IterKernel iter_kernel = kIter[na.hacc() ? 1 : 0][mode];
+    const IterKernel iter_kernel = choose_iter_kernel(na, lv);
     ensure_dynamic_lds(reinterpret_cast<const void*>(iter_kernel), 160 * 1024);
     NGP_REQUIRE(lds <= 160 * 1024, "render_rays: LDS budget exceeded (%zu bytes)", lds);
 
-    static const uint32_t cap_mid_env = getenv("NGP_SPEC_CAP_MID") ? (uint32_t)atoi(getenv("NGP_SPEC_CAP_MID")) : 8u;
-    const uint32_t cap_mid_max = cap_mid_env < 8u ? 8u : (cap_mid_env > kSpecMaxSamples ? kSpecMaxSamples : cap_mid_env);
-    static const uint32_t cap_hi_env = getenv("NGP_SPEC_CAP_HI") ? (uint32_t)atoi(getenv("NGP_SPEC_CAP_HI")) : kSpecMaxSamples;
-    const uint32_t cap_hi = cap_hi_env < 8u ? 8u : (cap_hi_env > kSpecMaxSamples ? kSpecMaxSamples : cap_hi_env);
+    const bool trace = env_set("NGP_TRACE_SCHEDULE");   // diagnostics: prints the alive count after every launch
     const uint32_t call_tag = ++ctx->calls & 0x7FFFu;
     uint32_t ub = N;          // host-side upper bound of n_alive
     uint32_t launched = 0;    // iterations enqueued
     uint32_t known = 0;       // iterations whose resulting status the host has read
-    uint32_t launches = 2;
     bool done = false;
     while (!done) {
-        const uint32_t cur = launched & 1;
-        const uint32_t chunks = items_bound(ub, ra.wave_slots);     // work items of the launch, at most
-        // persistent: resident workgroups pull chunks from a queue.  k_render_iter at two workgroups per CU holds every vector register and
-        // 144 KB of the LDS of the CUs it runs on, so nothing of another frame's launches runs beside it; at five eighths of that it
-        // is 5 % slower on its own (its bound is the gather, not the waves in flight) and leaves room for another call's march and
-        // compaction kernels: +2-3 % frames/s with three calls in flight.  Taken when another render call of this process is in progress
-        // (results do not depend on the workgroup count; NGP_ITER_BLOCKS_PCT fixes the percentage for an A/B).
-        static const uint32_t pct_env = getenv("NGP_ITER_BLOCKS_PCT") ? (uint32_t)atoi(getenv("NGP_ITER_BLOCKS_PCT")) : 0u;
-        const uint32_t blocks_pct = pct_env ? pct_env : (g_active_renders.load(std::memory_order_relaxed) > 1 ? 62u : 100u);
-        const uint32_t max_blocks = (uint32_t)ctx->num_cu * blocks_per_cu * blocks_pct / 100u;
-        const uint32_t want_blocks = div_up(chunks, kWaves);
-        const uint32_t blocks = want_blocks < max_blocks ? want_blocks : max_blocks;
-        ra.alive_in = ctx->alive[cur];
-        ra.ctl = ctx->ctl + cur;
-        ra.heads = ctx->heads + cur;
-        ra.death_shards = ctx->death_shards + (size_t)cur * kDeathWords;
-        {
-            ProfScope pm("k_march_ahead", s, 0);  // per-launch events only when ngp_prof_enable(1)
-            // (one wave per ray when the launch turns out to have at most wave_march_max rays: four rays per block)
-            const uint32_t by_wave = div_up(ub < ra.wave_march_max ? ub : ra.wave_march_max, 4);
-            const uint32_t by_lane = div_up(ub ? ub : 1, 256);
-            if (lin) k_march_ahead<true><<<by_lane > by_wave ? by_lane : by_wave, 256, 0, s>>>(ra, na.bound);
-            else k_march_ahead<false><<<div_up(ub ? ub : 1, 256), 256, 0, s>>>(ra, na.bound);
-        }
-        {
-            ProfScope pk("k_render_iter", s, 0);
-            iter_kernel<<<blocks, kThreads, lds, s>>>(na, lv, ra);
-        }
-        k_render_compact<<<div_up(chunks, 8), 256, 0, s>>>(ctx->ctl + cur, ctx->ctl + (cur ^ 1), ctx->staging, ctx->chunk_count,
-                                                           ctx->alive[cur ^ 1], N, max_steps, ctx->stat_shards, ctx->heads + (cur ^ 1),
-                                                           ctx->status_dev + launched % kRing, ctx->seq_base + launched + 1,
-                                                           ctx->death_shards + (size_t)cur * kDeathWords, spec_allowed, ctx->alive[cur],
-                                                           ctx->backup, ctx->rays_t, weights_sum, depth, image, dbg.sample_hash, ctx->stat_shards,
-                                                           ctx->death_shards + (size_t)(cur ^ 1) * kDeathWords, ra.wave_slots, cap_mid_max, cap_hi, ctx->fin_dev, call_tag);
+        enqueue_launch(ctx, na, lv, ra, iter_kernel, lds, lin, ub, launched, spec_allowed, call_tag, s);
         launched++;
-        launches += 3;
-        // consume every status that has already landed; block only when too far ahead
-        while (known < launched) {
-            static const uint32_t lookahead = getenv("NGP_LOOKAHEAD") ? (uint32_t)atoi(getenv("NGP_LOOKAHEAD")) : (uint32_t)kLookahead;   // (A/B timing)
-            const bool must_wait = launched - known >= lookahead;
-            volatile unsigned long long* slot = ctx->status + known % kRing;
-            const uint32_t want_seq = ctx->seq_base + known + 1;
-            unsigned long long w = *slot;
-            if ((uint32_t)(w >> 32) != want_seq) {
-                if (!must_wait) break;
-                uint32_t spins = 0;
-                while ((uint32_t)((w = *slot) >> 32) != want_seq) {
-                    // every 2^20 polls (tens of milliseconds: far longer than any launch) make sure the stream is still alive.  Rarely,
-                    // because the query is not free on the device side: the runtime answers it with a marker packet in the queue, and the
-                    // kernels behind it start ~6 us late -- at every 4096 polls that was one gap per launch (kernel timeline, round 3)
-                    if ((++spins & 0xFFFFFu) == 0) {
-                        const hipError_t q = hipStreamQuery(s);
-                        if (q != hipSuccess && q != hipErrorNotReady) {
-                            set_error("render_rays: %s", hipGetErrorString(q));
-                            return NGP_ELAUNCH;
-                        }
-                        if (q == hipSuccess && (uint32_t)(*slot >> 32) != want_seq) {   // everything ran, nothing was published: cannot happen
-                            set_error("render_rays: the device finished without publishing iteration %u", known);
-                            return NGP_ELAUNCH;
-                        }
-                    }
-                    __builtin_ia32_pause();
-                }
-            }
-            known++;
-            ub = (uint32_t)w & 0x7FFFFFFFu;
-            static const bool trace_sched = getenv("NGP_TRACE_SCHEDULE") != nullptr;   // diagnostics: the alive count after every launch
-            if (trace_sched) fprintf(stderr, "[ngp] call %u launch %u: n_alive %u%s\n", call_tag, known, ub, ((w >> 31) & 1ull) ? " done" : "");
-            if ((w >> 31) & 1ull) { done = true; break; }
-        }
+        rc = consume_status(ctx, s, launched, call_tag, trace, known, ub, done);
+        if (rc) return rc;
         if (launched > 2u * max_steps + 16u) {  // cannot happen: every launch advances step by >= 1 or is the rollback of one that did
             set_error("render_rays: iteration bound exceeded");
             return NGP_ELAUNCH;
         }
     }
     ctx->seq_base += launched;
+    const Ctl* last = ctx->ctl + (launched & 1);   // the state after the last launch (done is sticky)
     if (ra.dump_rec) {
         const uint32_t nb = div_up(N, 256);
-        const Ctl* fin_state = ctx->ctl + (launched & 1);   // the state after the last launch (done is sticky)
-        k_dump_count<<<nb, 256, 0, s>>>(ctx->dump_iter, N, fin_state, ctx->chunk_count);
+        k_dump_count<<<nb, 256, 0, s>>>(ctx->dump_iter, N, last, ctx->chunk_count);
         k_dump_scan<<<1, 1024, 0, s>>>(ctx->chunk_count, nb);
-        k_dump_gather<<<nb, 256, 0, s>>>(ctx->dump_iter, ctx->dump_rec, N, fin_state, ctx->chunk_count,
+        k_dump_gather<<<nb, 256, 0, s>>>(ctx->dump_iter, ctx->dump_rec, N, last, ctx->chunk_count,
                                          last_sigmas, last_rgbs, ra.pad_sigma, ra.pad_r, ra.pad_g, ra.pad_b);
     }
     rc = check_launch("render_rays");
     if (rc) return rc;
-    bool have_fin = false;
-    Ctl fin = {};   // state after the last enqueued iteration (done is sticky)
-    if (stats_host && !sync) {
-        // the finished loop's counters arrive in pinned memory next to the status word the loop above has already seen: a short,
-        // bounded wait for the four tags (they are stored just before that word), then no synchronize and no copy
-        volatile unsigned long long* f = ctx->fin;
-        unsigned long long w[4] = {0, 0, 0, 0};
-        for (uint32_t spin = 0; spin < 200000u && !have_fin; spin++) {
-            bool all = true;
-            for (int i = 0; i < 4; i++) {
-                w[i] = f[i];
-                all = all && (w[i] >> 48) == (0x8000u | call_tag);
-            }
-            have_fin = all;
-            if (!have_fin) __builtin_ia32_pause();
-        }
-        if (have_fin) {
-            fin.samples_marched = w[0] & 0xFFFFFFFFFFFFull;
-            fin.samples_slots = w[1] & 0xFFFFFFFFFFFFull;
-            fin.iters = (uint32_t)((w[2] >> 24) & 0xFFFFFFu);
-            fin.rollbacks = (uint32_t)(w[2] & 0xFFFFFFu);
-            fin.last_n_alive = (uint32_t)((w[3] >> 8) & 0xFFFFFFFFu);
-            fin.last_n_step = (uint32_t)(w[3] & 0xFFu);
-        }
-    }
-    if ((stats_host && !have_fin) || sync) {
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            set_error("render_rays: %s", hipGetErrorString(hipGetLastError()));
-            return NGP_ELAUNCH;
-        }
-        if (hipMemcpy(&fin, ctx->ctl + (launched & 1), sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("render_rays: %s", hipGetErrorString(hipGetLastError()));
-            return NGP_ELAUNCH;
-        }
-        have_fin = true;
-    }
-    if (have_fin) {
-        if (stats_host) {
-            stats_host->samples_marched = fin.samples_marched;
-            stats_host->samples_slots = fin.samples_slots;
-            stats_host->iterations = fin.iters;
-            stats_host->rays = N;
-            stats_host->last_n_alive = fin.last_n_alive;
-            stats_host->last_n_step = fin.last_n_step;
-            stats_host->launches = launches;
-            stats_host->replayed = fin.rollbacks;
-            prof_add_units("k_render_iter", (double)fin.samples_marched);
-        }
-    }
-    return NGP_OK;
+    return read_counters(ctx, s, last, call_tag, N, 2 + 3 * launched, sync, stats_host);
 }
 
 int ngp_render_ctx_set_debug(ngp_render_ctx* ctx, int enable, int flags, unsigned long long* stamps, uint32_t* sample_hash) {
     NGP_REQUIRE(ctx, "render_ctx_set_debug: null context");
+    if (!debug_flags_valid(flags, "render_ctx_set_debug")) return NGP_EINVAL;
     ctx->has_debug = enable != 0;
-    ctx->debug_flags = flags;
-    ctx->debug_stamps = stamps;
-    ctx->debug_sample_hash = sample_hash;
+    ctx->debug.flags = flags; ctx->debug.stamps = stamps; ctx->debug.sample_hash = sample_hash;
     return NGP_OK;
 }
 

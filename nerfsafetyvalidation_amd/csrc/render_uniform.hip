@@ -742,7 +742,7 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
     NetArgs na;
     GridLevels lv;
     const DebugState dbg = debug_snapshot();
-    int rc = fill_net(model, dbg, (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     NGP_REQUIRE(lds <= 96 * 1024, "render_uniform: the packed weights need %zu bytes of LDS", lds);
@@ -752,9 +752,8 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
     ProfScope prof("render_uniform", s, (double)N * T);
     // tiles across sixteen neighbouring rays (twice the per-sample rate) once there are enough groups of sixteen to occupy the chip;
     // a pose-estimator batch (1024 scattered pixels, every ray dumped) keeps one ray per wave
-    const bool per_ray = getenv("NGP_UNIFORM_PER_RAY") != nullptr;            // diagnostics (read per call: tests switch it): tiles along one ray for every size
-    const uint32_t x16_min = getenv("NGP_UNIFORM_X16_MIN") ? (uint32_t)atoi(getenv("NGP_UNIFORM_X16_MIN")) : kUniformX16MinRays;
-    if (!per_ray && N >= x16_min) {
+    const bool per_ray = env_set("NGP_UNIFORM_PER_RAY");    // diagnostics (read per call: tests switch it): tiles along one ray for every size
+    if (!per_ray && N >= kUniformX16MinRays) {
         // frame_width (scheduling hint, results do not depend on it): the rays are the pixels of row-major frames this wide -> a
         // group is a 4x4-pixel block instead of a 1x16 strip (its sixteen rays are closer together and end at more similar depths)
         uint32_t fw = frame_width;
@@ -762,9 +761,8 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
         uint32_t gb = div_up(div_up(N, 16), 4);
         // as many workgroups as are RESIDENT at once (each strides over the groups): four per CU, or what the LDS holds -- the fp32
         // weights take 40 KB per workgroup, three fit, and with 1024 workgroups the fourth of every CU ran as a second round at a third
-        // of the occupancy (800x800 x 512 samples, fp32: 8.01 -> 7.56 ms; NGP_UNIFORM_BLOCKS fixes the count for an A/B)
-        static const uint32_t gb_env = getenv("NGP_UNIFORM_BLOCKS") ? (uint32_t)atoi(getenv("NGP_UNIFORM_BLOCKS")) : 0u;
-        const uint32_t gb_cap = gb_env ? gb_env : resident_blocks(lds);
+        // of the occupancy (800x800 x 512 samples, fp32: 8.01 -> 7.56 ms)
+        const uint32_t gb_cap = resident_blocks(lds);
         if (gb > gb_cap) gb = gb_cap;
         NGP_WITH_NET(variant, {
             ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NET>), 96 * 1024);
@@ -802,7 +800,7 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     NGP_REQUIRE(model && model->packed_weights, "render_upsample: model->packed_weights is NULL (ngp_pack_weights fills it)");
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     NGP_REQUIRE(!na.f32(), "render_upsample: built for the fp16 network (ngp_model::precision == NGP_PREC_F16)");
     const size_t fixed = weights_bytes(na) + sizeof(LevelTab), per_wave = ((size_t)5 * T + (size_t)4 * U) * sizeof(float);
@@ -833,7 +831,7 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
                                                                  aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
     };
     const size_t need = upsample_workspace_bytes(N, T, U);
-    if (!(workspace && workspace_bytes >= need && N >= kUniformX16MinRays && getenv("NGP_UPSAMPLE_PER_RAY") == nullptr)) {
+    if (!(workspace && workspace_bytes >= need && N >= kUniformX16MinRays && !env_set("NGP_UPSAMPLE_PER_RAY"))) {
         per_ray(nullptr, nullptr);      // everything along the ray in one launch
         return check_launch("render_upsample");
     }
@@ -883,7 +881,7 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
 size_t ngp_render_uniform_backward_lds(const ngp_model* model, uint32_t T) {
     if (!model) return 0;
     NetArgs na = {};
-    na.sig_mm = model->sigma_hidden_mm; na.col_mm = model->color_hidden_mm; na.dbg_shrink = model->precision == NGP_PREC_F32 ? 256u : 0u;
+    na.sig_mm = model->sigma_hidden_mm; na.col_mm = model->color_hidden_mm; na.prec_bits = model->precision == NGP_PREC_F32 ? 256u : 0u;
     if (!bwd_shape_ok(na)) return (size_t)-1;
     const size_t wb = na.f32() ? NetF32<0>::wb_bytes(na) : NetF16<0>::wb_bytes(na);
     return net_w_bytes(na) + wb + sizeof(LevelTab) + (size_t)(na.f32() ? 4 : kGradWaves) * 3 * T * 4;
@@ -900,7 +898,7 @@ int ngp_render_uniform_backward(const ngp_model* model, const void* packed_weigh
     hipStream_t s = (hipStream_t)stream;
     NetArgs na;
     GridLevels lv;
-    int rc = fill_net(model, debug_snapshot(), (const _Float16*)model->packed_weights, na, lv);
+    int rc = fill_net(model, (const _Float16*)model->packed_weights, na, lv);
     if (rc) return rc;
     NGP_REQUIRE(bwd_shape_ok(na), "render_uniform_backward: the fp32 form supports at most 1 / 2 hidden matmuls (got %u / %u)", na.sig_mm, na.col_mm);
     GradArgs ga = {rays_o, rays_d, nears, fars, lin, grad_image, grad_depth, grad_weights_sum, grad_aggregated_density, grad_rays_o, grad_rays_d,
@@ -909,8 +907,7 @@ int ngp_render_uniform_backward(const ngp_model* model, const void* packed_weigh
     NGP_REQUIRE(lds <= 160 * 1024, "render_uniform_backward: LDS budget exceeded (%zu bytes: at most %u samples per ray with this network)", lds, T);
     ProfScope prof("render_uniform_backward", s, (double)N * T);
     // four rays per workgroup: always in fp32; in fp16 while that still gives every CU at most two rounds of work
-    static const int force_gw = getenv("NGP_GRAD_WAVES") ? atoi(getenv("NGP_GRAD_WAVES")) : 0;     // diagnostics
-    const bool four = na.f32() || (force_gw ? force_gw == 4 : N <= 2048);
+    const bool four = na.f32() || N <= 2048;
     uint32_t blocks = div_up(N, four ? 4 : kGradWaves);
     if (blocks > 512) blocks = 512;
     NGP_WITH_NET(net_variant(na, lv), {

@@ -60,7 +60,7 @@ flops_b = (Bf + 128) * 2 * 2 * (32 * 64 + 64 * 64 + 64 * 16)    # dX chain + dW,
 print(json.dumps({"op": "ffmlp_backward 32-64-64-16 (activation chain + split-K weight gradients)", "B": Bf, "ms": round(ms_b, 4),
                   "rows_per_s": round(Bf / ms_b * 1e3), "tflops": round(flops_b / ms_b / 1e9, 1)}))
 if os.environ.get("NGP_DBG_FLAGS"):
-    lib.ngp_debug_disable_march_queue(int(os.environ["NGP_DBG_FLAGS"]))   # A/B diagnostics (bits 4-7: fold the hashed levels)
+    lib.ngp_debug_disable_march_queue(int(os.environ["NGP_DBG_FLAGS"]))   # A/B diagnostics (the NGP_DBG_* flag word)
 sc = StonehengeScene(H=64, W=64, bound=2); model = sc.build_model(dev)
 with torch.autocast("cuda", dtype=torch.float16):
     fm = model.fused_model()          # (the fp16 snapshot: what the model hands out under autocast)

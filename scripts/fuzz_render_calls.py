@@ -36,7 +36,13 @@ for i in range(n_calls):
         a = model.render(ro, rd, **kw); sa = dict(model.last_render_stats)
         a2 = model.render(ro, rd, **kw)
         # the same call with one of the renderer's shortcuts switched off (or without the last-iteration tensors): identical bits
-        flags = int(rng.choice([1, 2, 4, 6, 8, 10, 256, 8192, 16384, 32768, 65536, 16384 | 32768 | 65536, 131072, 131072 | 1, 131072 | 262144, 262144, 0]))   # (bits 14-16: round 3's launch cut, narrow items, prefix replay; 17: a lane per ray in the march)
+        D = _lib
+        flags = int(rng.choice([D.NGP_DBG_NO_BLOCK_JUMP, D.NGP_DBG_NO_COARSE, D.NGP_DBG_NO_SLOW_SORT, D.NGP_DBG_NO_COARSE | D.NGP_DBG_NO_SLOW_SORT,
+                                D.NGP_DBG_NO_LIN, D.NGP_DBG_NO_COARSE | D.NGP_DBG_NO_LIN, D.NGP_DBG_ONE_ITER_PER_LAUNCH, D.NGP_DBG_NO_TILES,
+                                D.NGP_DBG_NO_PRE_VERDICT, D.NGP_DBG_WIDE_ITEMS, D.NGP_DBG_REPLAY_ONE_ITER,
+                                D.NGP_DBG_NO_PRE_VERDICT | D.NGP_DBG_WIDE_ITEMS | D.NGP_DBG_REPLAY_ONE_ITER, D.NGP_DBG_LANE_MARCH,
+                                D.NGP_DBG_LANE_MARCH | D.NGP_DBG_NO_BLOCK_JUMP, D.NGP_DBG_LANE_MARCH | D.NGP_DBG_PROBE_PER_SAMPLE,
+                                D.NGP_DBG_PROBE_PER_SAMPLE, 0]))
         lib.ngp_debug_disable_march_queue(flags)
         model.return_last_tensors = bool(rng.random() < 0.7)
         try:

@@ -91,3 +91,32 @@ def test_cell_table_size_is_host_arithmetic():
         assert lib.ngp_cell_tables_bytes(ctypes.byref(m), n) == 32 * sum(int(r) ** 3 for r in res[:n])
     assert lib.ngp_cell_tables_bytes(ctypes.byref(m), 16) == 0          # 4068^3 cells do not fit 32-bit record indices
     assert 38e9 < lib.ngp_cell_tables_bytes(ctypes.byref(m), 12) < 39e9
+
+
+def test_library_reads_exactly_the_documented_switches():
+    """The whole NUL-terminated strings of libngp_hip.so that look like a switch (NGP_[A-Z0-9_]+: the names it hands to getenv) are the
+    rows of INTEGRATION.md's "Environment switches" table that the library reads -- no undocumented switch, no stale row."""
+    from nerfsafetyvalidation_amd import _lib
+    blob = open(_lib.SO_PATH, "rb").read()
+    in_library = {s.decode() for s in blob.split(b"\0") if re.fullmatch(rb"NGP_[A-Z0-9_]+", s)}
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = text[text.index("## Environment switches"):]
+    table = table[:table.index("\n### ")]
+    documented = set(re.findall(r"^\| `(NGP_[A-Z0-9_]+)` \| library \|", table, flags=re.M))
+    assert len(documented) == 6
+    assert in_library == documented
+
+
+def test_debug_flag_names_and_validation():
+    """_lib's NGP_DBG_* constants are the header's enum, and the process-default setter refuses a word with any other bit (host only)."""
+    from nerfsafetyvalidation_amd import _lib
+    enum = {n: 1 << int(b) for n, b in re.findall(r"(NGP_DBG_[A-Z_]+) = 1 << (\d+),", open(HEADER).read())}
+    assert len(enum) == 11 and all(getattr(_lib, n) == v for n, v in enum.items())
+    lib, every = _lib.lib(), sum(enum.values())
+    try:
+        assert lib.ngp_debug_disable_march_queue(every) == 0
+        for bad in (1 << 4, 1 << 7, 1 << 9, 1 << 12, 1 << 19, every + (1 << 5), -1):
+            assert lib.ngp_debug_disable_march_queue(bad) == -1, bad      # NGP_EINVAL
+            assert b"unknown debug flag bits" in lib.ngp_last_error()
+    finally:
+        assert lib.ngp_debug_disable_march_queue(0) == 0

@@ -243,11 +243,14 @@ def test_block_jump_and_linear_layout_keep_the_sample_sequence(setup, device):
     try:
         # all shortcuts / no block jump / Morton-order probes / one reference iteration per launch / the frame-width hint (live
         # rays listed in 4x4-pixel tiles) on top of everything
-        # ... / 4: no slow-ray grouping and 6: no coarse filter either -- the alive list stays in reference order and the last-iteration
+        # ... / NO_SLOW_SORT: no slow-ray grouping and NO_COARSE | NO_SLOW_SORT: no coarse filter either -- the alive list stays in reference order and the last-iteration
         # tensors are written slot-major WHILE launches cover several iterations (the combination of the bound >= 4 scenes)
-        # 131072: one lane per ray in every launch (frames this small otherwise march one WAVE per ray, lattice windows of 64 points)
-        # 131072 | 262144: ... and a probe for every sample (no runs of samples inside one occupied cell)
-        for flags in (0, 1, 8, 256, 4, 6, 131072, 131072 | 1, 131072 | 262144, "tiles"):
+        # LANE_MARCH: one lane per ray in every launch (frames this small otherwise march one WAVE per ray, lattice windows of 64 points)
+        # LANE_MARCH | PROBE_PER_SAMPLE: ... and a probe for every sample (no runs of samples inside one occupied cell)
+        variants = (_lib.NGP_DBG_NO_BLOCK_JUMP, _lib.NGP_DBG_NO_LIN, _lib.NGP_DBG_ONE_ITER_PER_LAUNCH, _lib.NGP_DBG_NO_SLOW_SORT,
+                    _lib.NGP_DBG_NO_COARSE | _lib.NGP_DBG_NO_SLOW_SORT, _lib.NGP_DBG_LANE_MARCH, _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_NO_BLOCK_JUMP,
+                    _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_PROBE_PER_SAMPLE, "tiles")
+        for flags in (0,) + variants:
             lib.ngp_debug_disable_march_queue(0 if flags == "tiles" else flags)
             h = torch.zeros(N, dtype=torch.int32, device=device)
             lib.ngp_debug_set_sample_hash(h.data_ptr())
@@ -260,13 +263,13 @@ def test_block_jump_and_linear_layout_keep_the_sample_sequence(setup, device):
         lib.ngp_debug_set_sample_hash(None)
         lib.ngp_debug_disable_march_queue(0)
     assert sc.W % 4 == 0 and N % (4 * sc.W) == 0      # (the hint is only taken for whole rows of tiles)
-    for flags in (1, 8, 256, 4, 6, 131072, 131072 | 1, 131072 | 262144, "tiles"):
+    for flags in variants:
         assert torch.equal(outs[0][0], outs[flags][0]), flags
         assert torch.equal(outs[0][1], outs[flags][1]), flags
         assert torch.equal(outs[0][3], outs[flags][3]) and torch.equal(outs[0][4], outs[flags][4]), flags   # last-iteration tensors
         for key in ("samples_marched", "samples_slots", "iterations"):
             assert outs[0][2][key] == outs[flags][2][key], (flags, key)
-    assert outs[0][2]["launches"] < outs[256][2]["launches"]      # several reference iterations per launch were used
+    assert outs[0][2]["launches"] < outs[_lib.NGP_DBG_ONE_ITER_PER_LAUNCH][2]["launches"]      # several reference iterations per launch were used
     assert outs[0][2]["samples_marched"] > 10000
 
 
@@ -319,7 +322,7 @@ def test_multi_iteration_launch_is_verified_and_replayed(setup, device):
     outs = {}
     try:
         model.density_scale = 4.0e4
-        for flags in (0, 65536, 256):      # verified prefix replayed as one launch (default) / one iteration replayed / one iteration per launch
+        for flags in (0, _lib.NGP_DBG_REPLAY_ONE_ITER, _lib.NGP_DBG_ONE_ITER_PER_LAUNCH):      # verified prefix replayed as one launch (default) / one iteration replayed / one iteration per launch
             lib.ngp_debug_disable_march_queue(flags)
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
                 img = model.render(_t(ro, device)[None], _t(rd, device)[None], bg_color=1, perturb=False)["image"].float()
@@ -327,12 +330,12 @@ def test_multi_iteration_launch_is_verified_and_replayed(setup, device):
     finally:
         model.density_scale = old_scale
         lib.ngp_debug_disable_march_queue(0)
-    assert outs[0][1]["replayed"] >= 1 and outs[65536][1]["replayed"] >= 1 and outs[256][1]["replayed"] == 0   # rolled-back launches
-    assert outs[0][1]["launches"] <= outs[65536][1]["launches"]
-    for flags in (0, 65536):
-        assert torch.equal(outs[flags][0], outs[256][0])
+    assert outs[0][1]["replayed"] >= 1 and outs[_lib.NGP_DBG_REPLAY_ONE_ITER][1]["replayed"] >= 1 and outs[_lib.NGP_DBG_ONE_ITER_PER_LAUNCH][1]["replayed"] == 0   # rolled-back launches
+    assert outs[0][1]["launches"] <= outs[_lib.NGP_DBG_REPLAY_ONE_ITER][1]["launches"]
+    for flags in (0, _lib.NGP_DBG_REPLAY_ONE_ITER):
+        assert torch.equal(outs[flags][0], outs[_lib.NGP_DBG_ONE_ITER_PER_LAUNCH][0])
         for key in ("samples_marched", "samples_slots", "iterations"):
-            assert outs[flags][1][key] == outs[256][1][key], (flags, key)
+            assert outs[flags][1][key] == outs[_lib.NGP_DBG_ONE_ITER_PER_LAUNCH][1][key], (flags, key)
 
 
 def test_rays_almost_parallel_to_an_axis_leave_empty_blocks_in_one_step(setup, device):
@@ -366,7 +369,8 @@ def test_rays_almost_parallel_to_an_axis_leave_empty_blocks_in_one_step(setup, d
     outs, probes = {}, {}
     stamps = torch.zeros(16, dtype=torch.int64, device=device)
     try:
-        for flags in (0, 1, 131072, 131072 | 1, 131072 | 262144):
+        for flags in (0, _lib.NGP_DBG_NO_BLOCK_JUMP, _lib.NGP_DBG_LANE_MARCH, _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_NO_BLOCK_JUMP,
+                      _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_PROBE_PER_SAMPLE):
             lib.ngp_debug_disable_march_queue(flags)
             h = torch.zeros(N, dtype=torch.int32, device=device)
             lib.ngp_debug_set_sample_hash(h.data_ptr())
@@ -382,12 +386,12 @@ def test_rays_almost_parallel_to_an_axis_leave_empty_blocks_in_one_step(setup, d
         lib.ngp_debug_set_stamps(None)
         lib.ngp_debug_set_sample_hash(None)
         lib.ngp_debug_disable_march_queue(0)
-    for flags in (0, 131072, 131072 | 1, 131072 | 262144):
-        assert torch.equal(outs[1][0], outs[flags][0]) and torch.equal(outs[1][1], outs[flags][1]), flags
+    for flags in (0, _lib.NGP_DBG_LANE_MARCH, _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_NO_BLOCK_JUMP, _lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_PROBE_PER_SAMPLE):
+        assert torch.equal(outs[_lib.NGP_DBG_NO_BLOCK_JUMP][0], outs[flags][0]) and torch.equal(outs[_lib.NGP_DBG_NO_BLOCK_JUMP][1], outs[flags][1]), flags
         for key in ("samples_marched", "samples_slots", "iterations"):
-            assert outs[1][2][key] == outs[flags][2][key], (flags, key)
+            assert outs[_lib.NGP_DBG_NO_BLOCK_JUMP][2][key] == outs[flags][2][key], (flags, key)
     assert outs[0][2]["samples_marched"] > 5 * N, outs[0][2]                 # the rays cross the scene
-    assert probes[131072] < 0.6 * probes[131072 | 1], probes          # and leave its empty blocks in single steps
+    assert probes[_lib.NGP_DBG_LANE_MARCH] < 0.6 * probes[_lib.NGP_DBG_LANE_MARCH | _lib.NGP_DBG_NO_BLOCK_JUMP], probes          # and leave its empty blocks in single steps
     # against the oracle's march of the same rays (rays whose termination fp16 noise moved excepted, as in the test below)
     want = Hh.oracle_run_cuda(setup[2], ro, rd, sc.bitfield(), sc.bound, sc.cascade, sc.density_scale)
     same = outs[0][0].cpu().numpy().view(np.uint32) == want["sample_hash"]
@@ -408,7 +412,8 @@ def test_launch_cut_short_before_the_network_and_narrow_work_items(device):
     N = ro.shape[0]
     outs = {}
     try:
-        for flags in (0, 16384, 32768, 131072, 262144, 16384 | 32768 | 256):     # (131072: no launch marches one wave per ray -- the last ones of this frame do)
+        for flags in (0, _lib.NGP_DBG_NO_PRE_VERDICT, _lib.NGP_DBG_WIDE_ITEMS, _lib.NGP_DBG_LANE_MARCH, _lib.NGP_DBG_PROBE_PER_SAMPLE, 
+                      _lib.NGP_DBG_NO_PRE_VERDICT | _lib.NGP_DBG_WIDE_ITEMS | _lib.NGP_DBG_ONE_ITER_PER_LAUNCH):     # (LANE_MARCH: no launch marches one wave per ray -- the last ones of this frame do)
             lib.ngp_debug_disable_march_queue(flags)
             hashes = torch.zeros(N, dtype=torch.int32, device=device)
             lib.ngp_debug_set_sample_hash(hashes.data_ptr())
@@ -420,11 +425,11 @@ def test_launch_cut_short_before_the_network_and_narrow_work_items(device):
     finally:
         lib.ngp_debug_set_sample_hash(None)
         lib.ngp_debug_disable_march_queue(0)
-    ref = outs[16384 | 32768 | 256]                                  # one iteration per launch, 64-entry items
+    ref = outs[_lib.NGP_DBG_NO_PRE_VERDICT | _lib.NGP_DBG_WIDE_ITEMS | _lib.NGP_DBG_ONE_ITER_PER_LAUNCH]   # one iteration per launch, 64-entry items
     assert ref[3]["replayed"] == 0
-    assert outs[16384][3]["replayed"] >= 1                           # as planned: the first launch fails its verification
-    assert outs[0][3]["replayed"] < outs[16384][3]["replayed"]      # cut short instead
-    for flags in (0, 16384, 32768, 131072, 262144):
+    assert outs[_lib.NGP_DBG_NO_PRE_VERDICT][3]["replayed"] >= 1                           # as planned: the first launch fails its verification
+    assert outs[0][3]["replayed"] < outs[_lib.NGP_DBG_NO_PRE_VERDICT][3]["replayed"]      # cut short instead
+    for flags in (0, _lib.NGP_DBG_NO_PRE_VERDICT, _lib.NGP_DBG_WIDE_ITEMS, _lib.NGP_DBG_LANE_MARCH, _lib.NGP_DBG_PROBE_PER_SAMPLE):
         got = outs[flags]
         # (depth is 0 / 0 = NaN on the rays that miss the box, renderer.py:381)
         assert torch.equal(got[0], ref[0]) and torch.equal(got[1].nan_to_num(nan=-7.0), ref[1].nan_to_num(nan=-7.0)) and torch.equal(got[2], ref[2]), flags
@@ -721,7 +726,7 @@ def test_fused_sample_sequence_bit_exact(setup, device, view, queue):
     lib = _lib.lib()
     buf = torch.zeros(ro.shape[0], dtype=torch.int32, device=device)
     lib.ngp_debug_set_sample_hash(buf.data_ptr())
-    lib.ngp_debug_disable_march_queue(0 if queue else 2)
+    lib.ngp_debug_disable_march_queue(0 if queue else _lib.NGP_DBG_NO_COARSE)
     try:
         _render(model, sc, view, device, True)
         torch.cuda.synchronize()
@@ -748,7 +753,7 @@ def test_step_budget_ends_inside_a_multi_iteration_launch(setup, device, max_ste
     ro, rd = Hh.pinhole_rays(sc.poses[3], sc.intrinsics, sc.H, sc.W)
     outs = {}
     try:
-        for flags in (0, 256):
+        for flags in (0, _lib.NGP_DBG_ONE_ITER_PER_LAUNCH):
             lib.ngp_debug_disable_march_queue(flags)
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
                 r = model.render(_t(ro, device)[None], _t(rd, device)[None], bg_color=1, perturb=False, max_steps=max_steps)
@@ -756,7 +761,7 @@ def test_step_budget_ends_inside_a_multi_iteration_launch(setup, device, max_ste
             outs[flags] = (r["image"].float().clone(), r["sigmas"].clone(), r["rgbs"].clone(), dict(model.last_render_stats))
     finally:
         lib.ngp_debug_disable_march_queue(0)
-    a, b = outs[0], outs[256]
+    a, b = outs[0], outs[_lib.NGP_DBG_ONE_ITER_PER_LAUNCH]
     assert torch.equal(a[0], b[0])
     assert a[1].shape == b[1].shape and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
     for key in ("samples_marched", "samples_slots", "iterations"):
@@ -769,7 +774,7 @@ def test_full_size_frame_properties(device, bound, radius, view):
     """BASELINE.json's full size -- 800x800 Stonehenge (configs[1], the bench workload: bound 2, cameras inside the box) and the
     Lego setting (configs[3]: bound 1, one cascade, cameras OUTSIDE the box at r = 3.2) -- checked through properties
     that do not need the oracle on 640 k rays: (a) the renderer's shortcuts -- x-fastest bit layout, block jump, several iterations per launch, slow-ray grouping,
-    4x4-pixel tile order -- leave every output BIT-identical to the plain form (no shortcut at all: flags 1|2|4|8|256|8192); (b) rays
+    4x4-pixel tile order -- leave every output BIT-identical to the plain form (no shortcut at all: NO_BLOCK_JUMP | NO_COARSE | NO_SLOW_SORT | NO_LIN | ONE_ITER_PER_LAUNCH | NO_TILES); (b) rays
     are independent: a strip of rows rendered on its own gives the same pixels bit for bit; (c) ranges: 0 <= weights_sum <= 1 + 1e-4,
     colours in [0, 1], normalised depth in [0, 1], rays that miss the box show the background; (d) determinism; (e) every 97th ray
     against the CPU oracle within the fp16 network's tolerance."""
@@ -796,7 +801,7 @@ def test_full_size_frame_properties(device, bound, radius, view):
         return r, h, dict(model.last_render_stats)
 
     full, h_full, st_full = render(0, frame_width=sc.W)
-    plain, h_plain, st_plain = render(1 | 2 | 4 | 8 | 256 | 8192)
+    plain, h_plain, st_plain = render(_lib.NGP_DBG_NO_BLOCK_JUMP | _lib.NGP_DBG_NO_COARSE | _lib.NGP_DBG_NO_SLOW_SORT | _lib.NGP_DBG_NO_LIN | _lib.NGP_DBG_ONE_ITER_PER_LAUNCH | _lib.NGP_DBG_NO_TILES)
     # (a)
     for key in ("image", "depth", "sigmas", "rgbs"):
         assert _same_bits(full[key], plain[key]), key
