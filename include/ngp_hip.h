@@ -567,6 +567,37 @@ NGP_API int ngp_adam_step_dev(float* param, const float* grad, float* exp_avg, f
                       float beta2, float eps, const float* step_dev, const float* grad_scale_dev, const float* found_inf_dev,
                       ngp_stream_t stream);
 
+/* ---------------- data side of Trainer.train_step / eval_step (nerf/utils.py:426-480, nerf/provider.py:311-316) ---------------- */
+
+/* Ground-truth colours of one batch of rays out of the resident image store, one thread per ray:
+ *   gt_rgb[i] = rgb * a + bg * (1 - a)   (C == 4; utils.py:442)      gt_rgb[i] = rgb   (C == 3)
+ * store: [n_img][n_pix][C] of store_dtype 0 = f32, 1 = f16, 2 = uint8 (a code k stands for (float)k / 255, the provider's
+ * `image.astype(np.float32) / 255`); C in {3, 4}.  frame_base: index of the frame's first PIXEL in the store (frame * n_pix); inds
+ * int64 [N] pixel ids inside the frame, or NULL = pixels 0 .. N-1 in order (evaluation: N = n_pix).  An id outside [0, n_pix) reads
+ * nothing and gives NaN.  bg float [N,3], or NULL = white.  table: NULL, or 256 floats that replace k / 255 for the COLOUR channels
+ * of a uint8 store (the linear colour space: srgb_to_linear of the 256 codes, utils.py:430-431; alpha is never converted) -- refused
+ * for the other store types.  round_half != 0, or an f16 store: the reference holds the images in half (provider.py:250-254) and the
+ * blend above is half arithmetic, every operation rounded to half; otherwise every operation is one fp32 operation (no fused
+ * multiply-add).  gt_rgb float [N,3]. */
+NGP_API int ngp_train_targets(const void* store, int store_dtype, uint32_t C, uint64_t frame_base, uint32_t n_pix, const int64_t* inds,
+                      uint32_t N, const float* bg, const float* table, int round_half, float* gt_rgb, ngp_stream_t stream);
+
+/* MSELoss(reduction='none')(pred, gt).mean(-1) and its mean over the rays (utils.py:450,480) in one launch (two above 16384 rays):
+ * pred [N,3] of pred_dtype 0 = f32 / 1 = f16, gt float [N,3] -> per_ray float [N] = ((d0^2 + d1^2) + d2^2) / 3, *mean (device float).
+ * The mean is a fixed-order sum -- 64-ray groups by a butterfly, the groups in double, strided by 64 and by the same butterfly --
+ * that depends on N alone: no float atomics, the same bits on every call and for either launch shape.
+ * error_row (float [map_len], may be NULL) with inds_coarse (int64 [N]): error_row[inds_coarse[i]] = 0.1 * error_row[inds_coarse[i]] +
+ * 0.9 * per_ray[i], the error-map update of utils.py:474-475 (the OLD value weighted by 0.1).  PRECONDITION: the ids are distinct, as
+ * torch.multinomial(..., replacement=False) draws them (two rays on one entry would race); an id outside [0, map_len) is skipped.
+ * workspace: ngp_photo_loss_workspace(N) bytes (0 up to 16384 rays: NULL is fine). */
+NGP_API size_t ngp_photo_loss_workspace(uint32_t N);
+NGP_API int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, uint32_t N, float* per_ray, float* mean, float* error_row,
+                           uint32_t map_len, const int64_t* inds_coarse, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+/* grad_pred [N,3] (pred's dtype) = *g * 2 * (pred - gt) / (3 N); g is a DEVICE float (the GradScaler's scaled seed gradient never
+ * comes back to the host). */
+NGP_API int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred,
+                            ngp_stream_t stream);
+
 /* ---------------- keypoint detection (nav/features.py) ---------------- */
 /* SIFT's detection stage with cv2.SIFT_create()'s defaults (3 layers per octave, contrast 0.04, edge 10, sigma 1.6, first octave -1)
  * on an RGB uint8 frame [H][W][3], and the state estimator's interest mask (nav/estimator_helpers.py:95-107).  Outputs, both uint8

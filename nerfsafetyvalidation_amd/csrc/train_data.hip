@@ -1,0 +1,220 @@
+// The data side of a training / evaluation step (reference: nerf/provider.py:311-316, nerf/utils.py:426-480): ground-truth colours out
+// of the resident image store, the per-ray MSE with its mean and the error-map update, and the loss's gradient.  The reference spends a
+// dozen small torch operators and autograd nodes on this per step; here it is one launch each way.  Wave64, vector loads and stores only.
+#include "ngp_common.hpp"
+
+namespace ngp {
+
+constexpr uint32_t kStoreF32 = 0, kStoreF16 = 1, kStoreU8 = 2;
+constexpr uint32_t kLossOneBlockRays = 16384;      // up to here one 1024-thread workgroup does the whole loss (the training batch: one launch)
+constexpr uint32_t kLossOneBlockThreads = 1024;
+constexpr uint32_t kLossThreads = 256;             // above: 256 rays per workgroup, then k_photo_final
+
+__device__ __forceinline__ float round_half(float x) { return (float)(_Float16)x; }
+
+// One stored channel as the float the provider yields.  uint8: table[k] when a table is given (colour channels, linear space), else k / 255.
+template <uint32_t DT>
+__device__ __forceinline__ float load_channel(const void* store, size_t at, const float* table) {
+    if (DT == kStoreF32) return ((const float*)store)[at];
+    if (DT == kStoreF16) return (float)((const _Float16*)store)[at];
+    const uint32_t code = ((const uint8_t*)store)[at];
+    return table ? table[code] : (float)code / 255.0f;
+}
+
+template <uint32_t DT, uint32_t C, bool HALF>
+__global__ void __launch_bounds__(256) k_train_targets(const void* __restrict__ store, uint64_t frame_base, uint32_t n_pix,
+                                                       const int64_t* __restrict__ inds, uint32_t N, const float* __restrict__ bg,
+                                                       const float* __restrict__ table, float* __restrict__ gt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int64_t pix = inds ? inds[i] : (int64_t)i;
+    float* out = gt + (size_t)i * 3;
+    if (pix < 0 || pix >= (int64_t)n_pix) {      // torch.gather would raise; nothing is read, the target is NaN
+        out[0] = out[1] = out[2] = __builtin_nanf("");
+        return;
+    }
+    const size_t at = ((size_t)frame_base + (size_t)pix) * C;
+    float rgb[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) {
+        rgb[c] = load_channel<DT>(store, at + c, table);
+        if (HALF) rgb[c] = round_half(rgb[c]);
+    }
+    if (C == 4) {
+        float a = load_channel<DT>(store, at + 3, nullptr);
+        if (HALF) a = round_half(a);
+        // images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:])   (utils.py:442): four operators, four roundings
+        float rest = 1.0f - a;
+        if (HALF) rest = round_half(rest);
+#pragma unroll
+        for (uint32_t c = 0; c < 3; c++) {
+            float b = bg ? bg[(size_t)i * 3 + c] : 1.0f;
+            float front = rgb[c] * a, back = b * rest;
+            if (HALF) { front = round_half(front); back = round_half(back); }
+            rgb[c] = front + back;
+            if (HALF) rgb[c] = round_half(rgb[c]);
+        }
+    }
+    out[0] = rgb[0];
+    out[1] = rgb[1];
+    out[2] = rgb[2];
+}
+
+// ---- photometric loss -------------------------------------------------------------------------------------------------------------
+// The order of the sum is a function of N alone: (1) the 64 rays of a group by the xor butterfly below, in float; (2) lane l of ONE
+// wave adds the groups l, l + 64, ... in double, in that order; (3) the same butterfly over the 64 lanes, in double.
+template <typename T>
+__device__ __forceinline__ T butterfly_sum(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__device__ __forceinline__ void final_mean(const float* groups, uint32_t n_groups, uint32_t N, float* mean) {   // one whole wave calls this
+    const uint32_t lane = threadIdx.x & 63;
+    double acc = 0.0;
+    for (uint32_t g = lane; g < n_groups; g += 64) acc += (double)groups[g];
+    acc = butterfly_sum(acc);
+    if (lane == 0) *mean = (float)(acc / (double)N);
+}
+
+template <typename P>
+__device__ __forceinline__ float ray_loss(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t i, uint32_t N, float* __restrict__ per_ray,
+                                          float* __restrict__ error_row, uint32_t map_len, const int64_t* __restrict__ inds_coarse) {
+    if (i >= N) return 0.0f;            // (+0 leaves a sum of non-negative terms unchanged)
+    const size_t at = (size_t)i * 3;
+    const float d0 = (float)pred[at] - gt[at], d1 = (float)pred[at + 1] - gt[at + 1], d2 = (float)pred[at + 2] - gt[at + 2];
+    const float loss = ((d0 * d0 + d1 * d1) + d2 * d2) / 3.0f;
+    per_ray[i] = loss;
+    if (error_row) {
+        const int64_t cell = inds_coarse[i];
+        if (cell >= 0 && cell < (int64_t)map_len) error_row[cell] = 0.1f * error_row[cell] + 0.9f * loss;     // distinct ids (header)
+    }
+    return loss;
+}
+
+template <typename P>
+__global__ void __launch_bounds__(kLossOneBlockThreads) k_photo_loss_one_block(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
+                                                                              float* __restrict__ per_ray, float* __restrict__ mean,
+                                                                              float* __restrict__ error_row, uint32_t map_len,
+                                                                              const int64_t* __restrict__ inds_coarse) {
+    __shared__ float s_groups[kLossOneBlockRays / 64];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t rounds = ((N + kLossOneBlockThreads - 1) / kLossOneBlockThreads);
+    for (uint32_t r = 0; r < rounds; r++) {
+        const float v = butterfly_sum(ray_loss(pred, gt, r * kLossOneBlockThreads + threadIdx.x, N, per_ray, error_row, map_len, inds_coarse));
+        if (lane == 0) s_groups[r * (kLossOneBlockThreads / 64) + wave] = v;
+    }
+    __syncthreads();
+    if (wave == 0) final_mean(s_groups, ((N + 63) / 64), N, mean);
+}
+
+template <typename P>
+__global__ void __launch_bounds__(kLossThreads) k_photo_loss_groups(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
+                                                                    float* __restrict__ per_ray, float* __restrict__ error_row, uint32_t map_len,
+                                                                    const int64_t* __restrict__ inds_coarse, float* __restrict__ groups) {
+    const uint32_t i = blockIdx.x * kLossThreads + threadIdx.x;
+    const float v = butterfly_sum(ray_loss(pred, gt, i, N, per_ray, error_row, map_len, inds_coarse));
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < ((N + 63) / 64)) groups[i >> 6] = v;
+}
+
+__global__ void __launch_bounds__(64) k_photo_final(const float* __restrict__ groups, uint32_t n_groups, uint32_t N, float* __restrict__ mean) {
+    final_mean(groups, n_groups, N, mean);
+}
+
+template <typename P>
+__global__ void __launch_bounds__(256) k_photo_loss_backward(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t n3, float three_n,
+                                                             const float* __restrict__ g, P* __restrict__ grad) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n3) return;
+    grad[k] = (P)(*g * (2.0f * ((float)pred[k] - gt[k])) / three_n);
+}
+
+}  // namespace ngp
+
+using namespace ngp;
+
+template <uint32_t DT, uint32_t C>
+static void launch_targets(bool half, const void* store, uint64_t frame_base, uint32_t n_pix, const int64_t* inds, uint32_t N, const float* bg,
+                           const float* table, float* gt, hipStream_t s) {
+    const uint32_t blocks = div_up(N, 256);
+    if (half)
+        k_train_targets<DT, C, true><<<blocks, 256, 0, s>>>(store, frame_base, n_pix, inds, N, bg, table, gt);
+    else
+        k_train_targets<DT, C, false><<<blocks, 256, 0, s>>>(store, frame_base, n_pix, inds, N, bg, table, gt);
+}
+
+extern "C" {
+
+int ngp_train_targets(const void* store, int store_dtype, uint32_t C, uint64_t frame_base, uint32_t n_pix, const int64_t* inds, uint32_t N,
+                      const float* bg, const float* table, int round_half, float* gt_rgb, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(store && gt_rgb, "train_targets: null pointer");
+    NGP_REQUIRE(C == 3 || C == 4, "train_targets: C must be 3 or 4 (got %u)", C);
+    NGP_REQUIRE(store_dtype >= 0 && store_dtype <= 2, "train_targets: store dtype must be 0 (f32), 1 (f16) or 2 (uint8)");
+    NGP_REQUIRE(!table || store_dtype == (int)kStoreU8, "train_targets: the code table needs a uint8 store");
+    NGP_REQUIRE(inds || N <= n_pix, "train_targets: %u rays in pixel order but the frame has %u pixels", N, n_pix);
+    hipStream_t s = (hipStream_t)stream;
+    const bool half = round_half != 0 || store_dtype == (int)kStoreF16;
+    ProfScope prof("train_targets", s, (double)N);
+#define NGP_TARGETS(DT)                                                                          \
+    if (C == 3) launch_targets<DT, 3>(half, store, frame_base, n_pix, inds, N, bg, table, gt_rgb, s); \
+    else launch_targets<DT, 4>(half, store, frame_base, n_pix, inds, N, bg, table, gt_rgb, s)
+    if (store_dtype == (int)kStoreF32) { NGP_TARGETS(kStoreF32); }
+    else if (store_dtype == (int)kStoreF16) { NGP_TARGETS(kStoreF16); }
+    else { NGP_TARGETS(kStoreU8); }
+#undef NGP_TARGETS
+    return check_launch("train_targets");
+}
+
+size_t ngp_photo_loss_workspace(uint32_t N) { return N <= kLossOneBlockRays ? 0 : (size_t)div_up(N, 64) * sizeof(float); }
+
+int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, uint32_t N, float* per_ray, float* mean, float* error_row,
+                           uint32_t map_len, const int64_t* inds_coarse, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
+    NGP_REQUIRE(N > 0, "photo_loss_forward: no rays");
+    NGP_REQUIRE(N <= 0xFFFFFF00u, "photo_loss_forward: too many rays");
+    NGP_REQUIRE(pred && gt && per_ray && mean, "photo_loss_forward: null pointer");
+    NGP_REQUIRE(pred_dtype == 0 || pred_dtype == 1, "photo_loss_forward: pred dtype must be 0 (f32) or 1 (f16)");
+    NGP_REQUIRE(!error_row || inds_coarse, "photo_loss_forward: an error-map row needs inds_coarse");
+    const size_t need = ngp_photo_loss_workspace(N);
+    if (need && (!workspace || workspace_bytes < need)) {
+        set_error("photo_loss_forward: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
+        return NGP_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("photo_loss", s, (double)N);
+    if (!need) {
+        if (pred_dtype == 0)
+            k_photo_loss_one_block<float><<<1, kLossOneBlockThreads, 0, s>>>((const float*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
+        else
+            k_photo_loss_one_block<_Float16><<<1, kLossOneBlockThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
+        return check_launch("photo_loss_forward");
+    }
+    const uint32_t blocks = div_up(N, kLossThreads);
+    if (pred_dtype == 0)
+        k_photo_loss_groups<float><<<blocks, kLossThreads, 0, s>>>((const float*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
+    else
+        k_photo_loss_groups<_Float16><<<blocks, kLossThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
+    int rc = check_launch("photo_loss_forward");
+    if (rc) return rc;
+    k_photo_final<<<1, 64, 0, s>>>((const float*)workspace, div_up(N, 64), N, mean);
+    return check_launch("photo_loss_forward (final)");
+}
+
+int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(pred && gt && g && grad_pred, "photo_loss_backward: null pointer");
+    NGP_REQUIRE(pred_dtype == 0 || pred_dtype == 1, "photo_loss_backward: pred dtype must be 0 (f32) or 1 (f16)");
+    NGP_REQUIRE(N <= 0xFFFFFFFFu / 3, "photo_loss_backward: too many rays");
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n3 = N * 3;
+    const float three_n = (float)(3.0 * (double)N);
+    ProfScope prof("photo_loss_backward", s, (double)N);
+    if (pred_dtype == 0)
+        k_photo_loss_backward<float><<<div_up(n3, 256), 256, 0, s>>>((const float*)pred, gt, n3, three_n, g, (float*)grad_pred);
+    else
+        k_photo_loss_backward<_Float16><<<div_up(n3, 256), 256, 0, s>>>((const _Float16*)pred, gt, n3, three_n, g, (_Float16*)grad_pred);
+    return check_launch("photo_loss_backward");
+}
+
+}  // extern "C"

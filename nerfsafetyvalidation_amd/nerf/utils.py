@@ -17,6 +17,16 @@ def custom_meshgrid(*args):
     return torch.meshgrid(*args, indexing="ij")
 
 
+def linear_to_srgb(x):
+    """nerf/utils.py:42-44"""
+    return torch.where(x < 0.0031308, 12.92 * x, 1.055 * x ** 0.41666 - 0.055)
+
+
+def srgb_to_linear(x):
+    """nerf/utils.py:47-49"""
+    return torch.where(x < 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4)
+
+
 class _RaysKernel(torch.autograd.Function):
     """ngp_get_rays with its vector-Jacobian product: the reference builds rays with differentiable torch ops
     (utils.py:103-111) and the Estimator / Planner differentiate through them with respect to the pose."""
@@ -48,8 +58,24 @@ class _RaysKernel(torch.autograd.Function):
         return grad_poses, None, None, None, None
 
 
+def _rays_torch(poses, intrinsics, H, W, inds):
+    """the reference's own formulas (utils.py:69-71, 95-111), for poses on the HOST: a dataset served on a CPU device (NeRFDataset /
+    Trainer bookkeeping without a GPU).  Nothing on a HIP device comes here."""
+    fx, fy, cx, cy = intrinsics
+    pix = torch.arange(H * W, device=poses.device) if inds is None else inds.long()
+    i = (pix % W).float() + 0.5
+    j = torch.div(pix, W, rounding_mode="floor").float() + 0.5
+    zs = torch.ones_like(i)
+    directions = torch.stack(((i - cx) / fx * zs, (j - cy) / fy * zs, zs), dim=-1)
+    directions = directions / torch.norm(directions, dim=-1, keepdim=True)
+    rays_d = directions.expand(poses.shape[0], -1, 3) @ poses[:, :3, :3].transpose(-1, -2)
+    return poses[..., None, :3, 3].expand_as(rays_d), rays_d
+
+
 def _rays_kernel(poses, intrinsics, H, W, inds):
     """poses [B,4,4] -> rays_o, rays_d [B, n_pix, 3] for pixel ids `inds` (int32 [n_pix], shared by all cameras) or all pixels."""
+    if not poses.is_cuda:
+        return _rays_torch(poses, intrinsics, H, W, inds)
     return _RaysKernel.apply(poses, intrinsics, H, W, inds)
 
 

@@ -28,6 +28,24 @@ def intrinsics(H, W, camera_angle_x=CAMERA_ANGLE_X):
     return np.array([fl, fl, W / 2, H / 2], dtype=np.float64)
 
 
+def look_at_poses(centers):
+    """[n,4,4] cam2world looking at the origin from `centers` [n,3]: the look-at construction of rand_poses (nerf/provider.py:81-89),
+    shared by orbit_poses below and nerf/provider.py's rand_poses."""
+    centers = np.asarray(centers)
+
+    def normalize(v):
+        return v / (np.linalg.norm(v, axis=-1, keepdims=True) + 1e-10)
+
+    forward = -normalize(centers)
+    up = np.tile(np.array([0.0, -1.0, 0.0]), (len(centers), 1))
+    right = normalize(np.cross(forward, up))
+    up = normalize(np.cross(right, forward))
+    poses = np.tile(np.eye(4), (len(centers), 1, 1))
+    poses[:, :3, :3] = np.stack([right, up, forward], -1)
+    poses[:, :3, 3] = centers
+    return poses
+
+
 def orbit_poses(n_theta=5, n_phi=40, radius=1.5, theta_range=(np.pi / 3, 2 * np.pi / 3)):
     """[n_theta*n_phi, 4, 4] float32 cam2world on a fixed grid (200 views by default)."""
     thetas = np.linspace(theta_range[0], theta_range[1], n_theta)
@@ -36,17 +54,7 @@ def orbit_poses(n_theta=5, n_phi=40, radius=1.5, theta_range=(np.pi / 3, 2 * np.
     tt, pp = tt.reshape(-1), pp.reshape(-1)
     centers = np.stack([radius * np.sin(tt) * np.sin(pp), radius * np.cos(tt), radius * np.sin(tt) * np.cos(pp)], -1)
 
-    def normalize(v):
-        return v / (np.linalg.norm(v, axis=-1, keepdims=True) + 1e-10)
-
-    forward = -normalize(centers)
-    up = np.tile(np.array([0.0, -1.0, 0.0]), (len(tt), 1))
-    right = normalize(np.cross(forward, up))
-    up = normalize(np.cross(right, forward))
-    poses = np.tile(np.eye(4), (len(tt), 1, 1))
-    poses[:, :3, :3] = np.stack([right, up, forward], -1)
-    poses[:, :3, 3] = centers
-    return poses.astype(np.float32)
+    return look_at_poses(centers).astype(np.float32)
 
 
 def _expand_bits(v):
