@@ -598,6 +598,28 @@ NGP_API int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float
 NGP_API int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred,
                             ngp_stream_t stream);
 
+/* ---------------- image quality (uncertainty/evaluation/image_metrics.py:79-135; nerf/utils.py PSNRMeter) ---------------- */
+
+/* The sums behind PSNR and SSIM of B three-channel frames in one pass.  pred and target are float images addressed by ELEMENT strides
+ * (the same for both): element (b, c, y, x) is at b * stride_b + c * stride_c + y * stride_y + x * stride_x, so the Trainer's
+ * [B,H,W,3] and the reference modules' [B,3,H,W] are read in place (strides >= 0).  mask: float [B,H,W] of weights, or NULL = all one.
+ * The SSIM map is torchmetrics' structural_similarity_index_measure(data_range, return_full_image=True): window g (x) g with
+ * g[i] = exp(-(i / 1.5)^2 / 2) / sum, i = -5..5; both images reflect-padded by 5 (index -k -> k, H-1+k -> H-1-k); the windowed sums of
+ * p, t, p^2, t^2, p t give mu_p, mu_t, var_p = max(E[p^2] - mu_p^2, 0) (likewise var_t), cov = E[p t] - mu_p mu_t (not clamped);
+ * c1 = (0.01 range)^2, c2 = (0.03 range)^2;  ssim = ((2 mu_p mu_t + c1)(2 cov + c2)) / ((mu_p^2 + mu_t^2 + c1)(var_p + var_t + c2)).
+ * The window sums and the formula are evaluated in double.  ssim_map (float [B,H,W], may be NULL) receives the mean over the channels.
+ * stats (device, [B,8] doubles), per image:
+ *   [0] sum mask * ssim (channel mean)   [1] sum mask   [2..4] sum mask * (pred - target)^2 per channel   [5] H * W   [6] [7] 0
+ * Partial sums per workgroup go to the CALLER's workspace (ngp_image_quality_workspace(B, H, W) bytes, 8-byte aligned; NGP_EWORKSPACE
+ * when smaller) and are added in double in a fixed order by a second small launch: no atomics, no state between calls -- the same bits
+ * on every call, per image independent of the rest of the batch, and calls on different streams with their own workspaces do not
+ * interact.  H, W in [6, 32768] (torch's reflect pad needs more than 5), 1 <= B <= 65535, data_range > 0: NGP_EINVAL otherwise,
+ * nothing launched (the workspace size of a refused shape is 0). */
+NGP_API size_t ngp_image_quality_workspace(uint32_t B, uint32_t H, uint32_t W);
+NGP_API int ngp_image_quality(const float* pred, const float* target, const float* mask, uint32_t B, uint32_t H, uint32_t W,
+                      int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x, float data_range, float* ssim_map,
+                      double* stats, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+
 /* ---------------- keypoint detection (nav/features.py) ---------------- */
 /* SIFT's detection stage with cv2.SIFT_create()'s defaults (3 layers per octave, contrast 0.04, edge 10, sigma 1.6, first octave -1)
  * on an RGB uint8 frame [H][W][3], and the state estimator's interest mask (nav/estimator_helpers.py:95-107).  Outputs, both uint8

@@ -11,7 +11,7 @@ import torch
 
 from .nerf.provider import NeRFDataset
 from .nerf.trainer import Trainer
-from .nerf.utils import PSNRMeter, seed_everything
+from .nerf.utils import PSNRMeter, SSIMMeter, seed_everything
 from .optim import Adam
 
 
@@ -54,6 +54,9 @@ def parse_args(argv=None):
     ### experimental
     parser.add_argument('--error_map', action='store_true', help="use error map to sample rays")
 
+    ### evaluation (not in the reference)
+    parser.add_argument('--ssim', action='store_true', help="also report SSIM at evaluation (after PSNR, which still picks the best checkpoint)")
+
     opt = parser.parse_args(argv)
     opt.rand_pose = -1      # (CLIP-guided training on random poses is not ported; the dataset and the Trainer read the field)
 
@@ -92,7 +95,7 @@ def main(argv=None):
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 
     if opt.test:
-        metrics = [PSNRMeter(), ]
+        metrics = [PSNRMeter(), ] + ([SSIMMeter()] if opt.ssim else [])
         trainer = Trainer('ngp', opt, model, device=device, workspace=opt.workspace, criterion=criterion, fp16=opt.fp16, metrics=metrics,
                           use_checkpoint=opt.ckpt)
         test_loader = NeRFDataset(opt, device=device, type='test').dataloader()
@@ -108,7 +111,7 @@ def main(argv=None):
     # decay to 0.1 * init_lr at last iter step
     scheduler = lambda optimizer: torch.optim.lr_scheduler.LambdaLR(optimizer, lambda iter: 0.1 ** min(iter / opt.iters, 1))
 
-    metrics = [PSNRMeter(), ]
+    metrics = [PSNRMeter(), ] + ([SSIMMeter()] if opt.ssim else [])
     trainer = Trainer('ngp', opt, model, device=device, workspace=opt.workspace, optimizer=optimizer, criterion=criterion, ema_decay=0.95,
                       fp16=opt.fp16, lr_scheduler=scheduler, scheduler_update_every_step=True, metrics=metrics, use_checkpoint=opt.ckpt,
                       eval_interval=50)

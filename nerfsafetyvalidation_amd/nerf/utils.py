@@ -168,3 +168,42 @@ class PSNRMeter:
 
     def report(self):
         return f"PSNR = {self.measure():.6f}"
+
+
+class SSIMMeter:
+    """Mean SSIM over the evaluated frames, next to PSNRMeter in a Trainer's metric list.  Every update is one pass over the two frames
+    (uncertainty/evaluation/image_metrics.py::image_quality_stats: one ngp_image_quality launch on a HIP device) whose sums stay on the
+    device; measure() is the one read-back.  The same pass yields the squared error, so measure_psnr() gives PSNRMeter's number
+    (-10 log10 of the mean over all channels of an update, averaged over the updates) without the per-frame copy to the host."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.V = 0          # sum of the per-frame SSIM (a 0-dim float64 tensor after the first update)
+        self.N = 0          # frames
+        self.P = 0          # sum of the per-update PSNR
+        self.U = 0          # updates
+
+    def update(self, preds, truths):
+        """preds, truths: [B,H,W,3] in [0, 1] (tensors or numpy arrays).  Whole frames only: SSIM has no meaning for the [B,N,3] ray
+        batches of a training step, which raise."""
+        from ..uncertainty.evaluation.image_metrics import image_quality_stats
+        preds, truths = torch.as_tensor(preds), torch.as_tensor(truths)
+        stats, _ = image_quality_stats(preds, truths.to(preds.device), channels_last=True)
+        self.V = self.V + (stats[:, 0] / stats[:, 1]).sum()
+        self.N += stats.shape[0]
+        self.P = self.P - 10 * torch.log10(stats[:, 2:5].sum() / (3 * stats[:, 5].sum()))
+        self.U += 1
+
+    def measure(self):
+        return float(self.V) / self.N
+
+    def measure_psnr(self):
+        return float(self.P) / self.U
+
+    def write(self, writer, global_step, prefix=""):
+        writer.add_scalar(os.path.join(prefix, "SSIM"), self.measure(), global_step)
+
+    def report(self):
+        return f"SSIM = {self.measure():.6f}"
