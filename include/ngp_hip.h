@@ -598,6 +598,46 @@ NGP_API int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float
 NGP_API int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred,
                             ngp_stream_t stream);
 
+/* ---------------- distortion regulariser (loss.py:29-76 eff_distloss; mip-NeRF 360 eq. 15 in its O(n) form) ---------------- */
+
+/* Per ray of a table rays int32 [N,3] = (index, offset, count), with per-sample weight w_i, position m_i (non-decreasing) and width
+ * delta_i at the packed rows offset .. offset + count - 1:
+ *   L_ray = 2 sum_i w_i (m_i Wpre_i - WMpre_i) + (1/3) sum_i w_i^2 delta_i,   Wpre_i = sum_{j<i} w_j,  WMpre_i = sum_{j<i} w_j m_j
+ *         ( = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i for sorted m; for unsorted m it is still the expression above,
+ *           which is what the reference evaluates)
+ *   g_i   = dL_ray / dw_i = 2 (m_i (Wpre_i - Wsuf_i) + (WMsuf_i - WMpre_i)) + (2/3) delta_i w_i
+ * loss_rays float [N]: L_ray at slot `index`;  *loss (device float) = (sum of loss_rays) / N, N counting every row of the table;
+ * totals float [N,2]: (sum w, sum w m) of the ray at slot `index`, which the backward call reads.  The index column must hold every
+ * slot 0 .. N-1 once (as march_rays_train writes it; a row with index >= N is ignored, its slot is not written).  One wave per ray,
+ * prefix sums by wave scans; the mean is the fixed-order sum of ngp_photo_loss_forward over the SLOTS.  No atomics: the same bits on
+ * every call and for every order of the table's rows.  workspace: ngp_distortion_workspace(N) bytes (0 up to 16384 rays).
+ *
+ * ngp_distortion_train_*: the packed layout of march_rays_train, sigmas float [M], deltas float [M,2] = (dt, gap), 8-byte aligned:
+ *   alpha_i = 1 - exp(-sigma_i dt_i),  T_0 = 1,  T_{i+1} = T_i (1 - alpha_i),  w_i = alpha_i T_i,
+ *   m_i = scale * sum_{k<=i} gap_k  (the t that composite_rays_train integrates into depth),  delta_i = scale * dt_i,
+ * scale float [N] read at `index` (NULL = 1; the renderer passes 1 / (far - near)).  The ray ends behind the first sample with
+ * T_{i+1} < 1e-4, that sample included (the forward rule of composite_rays_train); a ray with count == 0 or offset + count >= M is
+ * dropped as composite_rays_train drops it: loss 0, no gradient.  T is the running product of the (1 - alpha).
+ *   grad_sigmas[offset + k] = (*grad_loss / N) dt_k (g_k T_{k+1} - sum_{i>k} g_i w_i)     for every live sample k
+ * -- the exact derivative, the sample that stops the ray included (composite_rays_train_backward writes none for that one).  Rows of
+ * dead samples, of dropped rays and of no ray are NOT written: hand in zeros.  grad_loss is a device float.
+ *
+ * ngp_distortion_forward / _backward: the same scans on given w, m float [M] and interval (float [M], or NULL: interval_scalar for
+ * every sample); every sample of a ray is live, and a ray is dropped only when count == 0 or offset + count > M (a dense [B,T] input
+ * is the table (i, i T, T) with M = B T).  grad_w[offset + k] = (*grad_loss / N) g_k; other rows are not written. */
+NGP_API size_t ngp_distortion_workspace(uint32_t N);
+NGP_API int ngp_distortion_train_forward(const float* sigmas, const float* deltas, const int32_t* rays, const float* scale, uint32_t M,
+                                 uint32_t N, float* loss_rays, float* totals, float* loss, void* workspace, size_t workspace_bytes,
+                                 ngp_stream_t stream);
+NGP_API int ngp_distortion_train_backward(const float* grad_loss, const float* sigmas, const float* deltas, const int32_t* rays,
+                                  const float* scale, const float* totals, uint32_t M, uint32_t N, float* grad_sigmas,
+                                  ngp_stream_t stream);
+NGP_API int ngp_distortion_forward(const float* w, const float* m, const float* interval, float interval_scalar, const int32_t* rays,
+                           uint32_t M, uint32_t N, float* loss_rays, float* totals, float* loss, void* workspace,
+                           size_t workspace_bytes, ngp_stream_t stream);
+NGP_API int ngp_distortion_backward(const float* grad_loss, const float* w, const float* m, const float* interval, float interval_scalar,
+                            const int32_t* rays, const float* totals, uint32_t M, uint32_t N, float* grad_w, ngp_stream_t stream);
+
 /* ---------------- image quality (uncertainty/evaluation/image_metrics.py:79-135; nerf/utils.py PSNRMeter) ---------------- */
 
 /* The sums behind PSNR and SSIM of B three-channel frames in one pass.  pred and target are float images addressed by ELEMENT strides

@@ -54,6 +54,9 @@ def parse_args(argv=None):
     ### experimental
     parser.add_argument('--error_map', action='store_true', help="use error map to sample rays")
 
+    ### regularisation (not in the reference's entry point; its loss.py has the term)
+    parser.add_argument('--lambda_distort', type=float, default=0, help="weight of the distortion loss on the ray weights (0 = off)")
+
     ### evaluation (not in the reference)
     parser.add_argument('--ssim', action='store_true', help="also report SSIM at evaluation (after PSNR, which still picks the best checkpoint)")
 

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, raymarching
+from ..loss import eff_distloss
 from . import sampling
 from .sampling import sample_pdf  # noqa: F401  (renderer.py:12-46: importable from here as in the reference)
 
@@ -182,7 +183,13 @@ class NeRFRenderer(nn.Module):
         depth = (weights * relative).sum(dim=-1)
         image = (weights.unsqueeze(-1) * rgbs).sum(dim=-2)
         image = image + (1 - weights_sum).unsqueeze(-1) * self._backdrop(origins, directions, bg_color)
+        extra = {}
+        if self.training and torch.is_grad_enabled() and kwargs.get("lambda_distort", 0) > 0:
+            # the distortion regulariser on the normalised depths, each sample with the interval its weight was formed with
+            intervals = torch.cat([depths[:, 1:] - depths[:, :-1], last_interval.unsqueeze(-1)], dim=-1)
+            extra["loss_distort"] = eff_distloss(weights, relative, intervals / span.unsqueeze(-1))
         return {
+            **extra,
             "depth": depth.view(*prefix),
             "image": image.view(*prefix, 3),
             "weights_sum": weights_sum,
@@ -214,8 +221,9 @@ class NeRFRenderer(nn.Module):
             return None
         return (C.c_float * 3)(*vals)
 
-    def _march_train(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays):
-        """training branch (renderer.py:286-327): one march over all rays, one network call, one differentiable compositing"""
+    def _march_train(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays, distort=False):
+        """training branch (renderer.py:286-327): one march over all rays, one network call, one differentiable compositing;
+        `distort`: also the distortion regulariser of the same samples, on depths normalised by the ray's span (else None)"""
         counter = self.step_counter[self.local_step % 16]      # ring of the last 16 steps' sample counts (-> mean_count)
         counter.zero_()
         self.local_step += 1
@@ -227,7 +235,8 @@ class NeRFRenderer(nn.Module):
             sigmas = self.density_scale * sigmas
         if sigmas.dim() != 1:
             raise RuntimeError("run_cuda: the network must return one density per sample (residual stacks are not part of this path)")
-        return (*raymarching.composite_rays_train(sigmas, rgbs, deltas, rays), sigmas, rgbs)
+        loss_distort = raymarching.distortion_rays_train(sigmas, deltas, rays, 1 / (fars - nears)) if distort else None
+        return (*raymarching.composite_rays_train(sigmas, rgbs, deltas, rays), sigmas, rgbs, loss_distort)
 
     def _march_eval_operators(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb):
         """eval branch, operator by operator (renderer.py:337-373) -- what the fused renderer (ngp_render_rays) replaces and is
@@ -266,8 +275,11 @@ class NeRFRenderer(nn.Module):
         backdrop = self._backdrop(origins, directions, bg_color)
         out = {}
         if self.training:
-            acc, depth, image, sigmas, rgbs = self._march_train(origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays)
+            acc, depth, image, sigmas, rgbs, loss_distort = self._march_train(origins, directions, nears, fars, dt_gamma, max_steps, perturb,
+                                                                              force_all_rays, distort=torch.is_grad_enabled() and kwargs.get("lambda_distort", 0) > 0)
             out["weights_sum"] = acc
+            if loss_distort is not None:
+                out["loss_distort"] = loss_distort
         else:
             fm = self.fused_model() if self.fused and not torch.is_grad_enabled() else None
             if fm is not None and not fm.f32:      # (the fused occupancy-grid loop exists for the fp16 network; fp32 takes the operators)

@@ -276,6 +276,13 @@ class Trainer(object):
         else:
             loss = targets.reference_loss(self.criterion, pred_rgb, gt_rgb, self.error_map, data.get('index'), data.get('inds_coarse'))
 
+        # the distortion regulariser (opt-in): the renderer computed it because `lambda_distort` reached it through vars(opt)
+        self.last_loss_distort = None
+        lam = getattr(self.opt, "lambda_distort", 0)
+        if lam > 0:
+            self.last_loss_distort = outputs["loss_distort"]
+            loss = loss + lam * self.last_loss_distort
+
         return pred_rgb, gt_rgb, loss
 
     def eval_step(self, data):
@@ -459,6 +466,8 @@ class Trainer(object):
                     metric.update(preds, truths)
             if writer is not None:
                 writer.add_scalar("train/loss", loss_val, self.global_step)
+                if getattr(self, "last_loss_distort", None) is not None:
+                    writer.add_scalar("train/loss_distort", self.last_loss_distort.item(), self.global_step)
                 writer.add_scalar("train/lr", self.optimizer.param_groups[0]['lr'], self.global_step)
 
         if self.ema is not None:

@@ -23,7 +23,7 @@ from torch.amp import custom_bwd, custom_fwd
 from .. import _lib
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
-           "composite_rays_train", "march_rays", "composite_rays"]
+           "composite_rays_train", "distortion_rays_train", "march_rays", "composite_rays"]
 
 USE_OCCUPANCY_LIN = True        # march_rays keeps derived copies of the occupancy bits per bitfield version (False: the plain kernel, for A/B)
 
@@ -204,6 +204,64 @@ class _composite_rays_train(Function):
 
 
 composite_rays_train = _composite_rays_train.apply
+
+
+def _distortion_workspace(L, N, device):
+    nbytes = L.ngp_distortion_workspace(N)
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), nbytes
+
+
+class _distortion_rays_train(Function):
+    @staticmethod
+    @_fwd32
+    def forward(ctx, sigmas, deltas, rays, scale):
+        sigmas, deltas, rays = sigmas.float().contiguous(), deltas.float().contiguous(), rays.contiguous()
+        scale = None if scale is None else scale.float().contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        loss_rays = torch.zeros(N, dtype=sigmas.dtype, device=sigmas.device)
+        totals = torch.zeros(N, 2, dtype=sigmas.dtype, device=sigmas.device)
+        loss = torch.zeros((), dtype=sigmas.dtype, device=sigmas.device)
+        L = _lib.lib()
+        ws, ws_bytes = _distortion_workspace(L, N, sigmas.device)
+        _lib.check(L.ngp_distortion_train_forward(_lib.ptr(sigmas), _lib.ptr(deltas), _lib.ptr(rays), _lib.ptr(scale), M, N, _lib.ptr(loss_rays),
+                                                  _lib.ptr(totals), _lib.ptr(loss), _lib.ptr(ws), ws_bytes, _lib.stream()),
+                   "distortion_train_forward")
+        ctx.save_for_backward(sigmas, deltas, rays, scale, totals)
+        ctx.dims = [M, N]
+        ctx.mark_non_differentiable(loss_rays)
+        return loss, loss_rays
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_loss, _grad_loss_rays):
+        sigmas, deltas, rays, scale, totals = ctx.saved_tensors
+        M, N = ctx.dims
+        grad_sigmas = torch.zeros_like(sigmas)      # rows of dead samples, of dropped rays and of no ray read 0
+        _lib.check(_lib.lib().ngp_distortion_train_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(sigmas), _lib.ptr(deltas),
+                                                            _lib.ptr(rays), _lib.ptr(scale), _lib.ptr(totals), M, N, _lib.ptr(grad_sigmas),
+                                                            _lib.stream()), "distortion_train_backward")
+        return grad_sigmas, None, None, None
+
+
+def distortion_rays_train(sigmas, deltas, rays, scale=None, return_rays=False):
+    """The distortion regulariser (mip-NeRF 360) on march_rays_train's packed samples -> scalar, differentiable in sigmas.
+
+    sigmas [M], deltas [M,2] = (dt, gap), rays int32 [N,3] = (index, offset, count), scale [N] per ray slot (None = 1; the renderer
+    passes 1 / (far - near)).  Per ray, with alpha_i = 1 - exp(-sigma_i dt_i), T_{i+1} = T_i (1 - alpha_i), w_i = alpha_i T_i,
+    m_i = scale * (gap_0 + ... + gap_i), delta_i = scale * dt_i:
+        L_ray = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+    over the samples up to and including the first with T_{i+1} < 1e-4 (composite_rays_train's forward rule); rays with no samples or
+    with offset + count >= M are dropped as composite_rays_train drops them.  The result is sum(L_ray) / N over ALL N rows of the table.
+
+    The gradient is the exact derivative for every live sample, the one that stops the ray INCLUDED -- unlike
+    composite_rays_train's backward, which writes no gradient for that sample.  Dead samples and dropped rays get 0.
+    One HIP launch per direction plus the fixed-order mean: no atomics, the same bits on every call (csrc/distortion.hip).
+    return_rays: also return L_ray per slot [N] (not differentiable)."""
+    if rays.shape[0] == 0:
+        loss, loss_rays = sigmas.float().sum() * 0, sigmas.new_zeros(0, dtype=torch.float32)
+    else:
+        loss, loss_rays = _distortion_rays_train.apply(sigmas, deltas, rays, scale)
+    return (loss, loss_rays) if return_rays else loss
 
 
 # ---------------------------------------------------------------- inference
