@@ -12,6 +12,7 @@
  *   _gridencoder   gridencoder/src/gridencoder.h:12-13,   gridencoder/src/bindings.cpp:5-8
  *   _shencoder     shencoder/src/shencoder.h:10-13,       shencoder/src/bindings.cpp:5-8
  *   _ffmlp         ffmlp/src/ffmlp.h:8-15,                ffmlp/src/bindings.cpp:5-11
+ *   _freqencoder   freqencoder/src/freqencoder.h:6-10,    freqencoder/src/bindings.cpp:5-8
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless its name ends in _host;
@@ -168,6 +169,20 @@ NGP_API int ngp_sh_encode_forward(const float* inputs, float* outputs, uint32_t 
 /* shencoder.cu:422-441.  grad_inputs f32 [B,3] is ACCUMULATED into (caller zero-fills). */
 NGP_API int ngp_sh_encode_backward(const float* grad, const float* inputs, uint32_t B, uint32_t D, uint32_t C,
                            const float* dy_dx, float* grad_inputs, ngp_stream_t stream);
+
+/* ---------------- _freqencoder (freqencoder/src/bindings.cpp:5-8) ---------------- */
+
+/* freqencoder.cu:97-110.  inputs f32 [B,D]; outputs f32 [B,C], C = D + 2 D deg, columns
+ *   [ x (D) | sin(2^0 x) (D) | cos(2^0 x) (D) | sin(2^1 x) (D) | cos(2^1 x) (D) | ... ]        (the reference's order, :28-58)
+ * The first D columns are bit copies of the input; the others are full-precision sin / cos of the EXACT float 2^f x (within 4 ulp of
+ * 1.0 of the real value; not the reference's __sinf(2^f x + pi/2)).  D >= 1, 0 <= deg <= 16 (0: the copy alone); B * C may pass 2^32
+ * (64-bit indexing).  B = 0 succeeds without a launch. */
+NGP_API int ngp_freq_encode_forward(const float* inputs, float* outputs, uint32_t B, uint32_t D, uint32_t deg, ngp_stream_t stream);
+/* freqencoder.cu:113-129, but sin / cos are recomputed from `inputs` (the outputs are not read):
+ *   grad_inputs[b,d] = grad[b,d] + sum_f 2^f (grad_sin[f,b,d] cos(2^f x) - grad_cos[f,b,d] sin(2^f x)),   f ascending, one thread
+ * grad f32 [B,C]; grad_inputs f32 [B,D] is WRITTEN (no zero fill needed).  No atomics: the same bits on every call. */
+NGP_API int ngp_freq_encode_backward(const float* grad, const float* inputs, uint32_t B, uint32_t D, uint32_t deg, float* grad_inputs,
+                             ngp_stream_t stream);
 
 /* ---------------- the elementwise steps between the two FFMLPs (nerf/network_ff.py:55-70) ----------------
  * What the reference's NeRFNetwork.forward does in torch between sigma_net and color_net, and after color_net, as one kernel each way

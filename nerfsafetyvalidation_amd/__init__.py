@@ -5,6 +5,7 @@ Sub-packages mirror the reference's operator packages one to one:
     nerfsafetyvalidation_amd.raymarching   <->  raymarching/
     nerfsafetyvalidation_amd.gridencoder   <->  gridencoder/
     nerfsafetyvalidation_amd.shencoder     <->  shencoder/
+    nerfsafetyvalidation_amd.freqencoder   <->  freqencoder/
     nerfsafetyvalidation_amd.ffmlp         <->  ffmlp/
     nerfsafetyvalidation_amd.nerf          <->  nerf/ (renderer, network, network_ff, utils.get_rays)
     nerfsafetyvalidation_amd.encoding / .activation
@@ -22,7 +23,7 @@ __version__ = "0.1.0"
 from . import mesh  # noqa: E402,F401  (save_mesh, extract_geometry, isosurface)
 from . import cem  # noqa: E402,F401  (run_cem, refit, failure_probability, SeedableMultivariateNormal; rollout.run_validation dispatches to it)
 
-_DROPIN = ["raymarching", "gridencoder", "shencoder", "ffmlp", "encoding", "activation"]
+_DROPIN = ["raymarching", "gridencoder", "shencoder", "freqencoder", "ffmlp", "encoding", "activation"]
 
 
 def install_dropin(include_nerf=False):

@@ -78,6 +78,8 @@ SIGNATURES = {
     "ngp_grid_encode_backward_workspace": [_u32, _u32, _u32, _u32, _int],
     "ngp_sh_encode_forward": [_vp, _vp, _u32, _u32, _u32, _int, _vp, _vp],
     "ngp_sh_encode_backward": [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp],
+    "ngp_freq_encode_forward": [_vp, _vp, _u32, _u32, _u32, _vp],
+    "ngp_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _vp, _vp],
     "ngp_ff_sigma_color_input": [_vp, _vp, _u32, _u32, _vp, _vp, _vp],
     "ngp_ff_sigma_color_input_backward": [_vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "ngp_ff_rgb": [_vp, _u32, _vp, _vp],

@@ -38,6 +38,8 @@ def parse_args(argv=None):
     ### network backbone options
     parser.add_argument('--fp16', action='store_true', help="use amp mixed precision training")
     parser.add_argument('--ff', action='store_true', help="use fully-fused MLP")
+    parser.add_argument('--encoding_dir', type=str, default='sphere_harmonics', choices=['sphere_harmonics', 'frequency'],
+                        help="view-direction encoding (frequency = positional encoding, degree 6; not with --ff)")
 
     ### dataset options
     parser.add_argument('--color_space', type=str, default='srgb', help="Color space, supports (linear, srgb)")
@@ -70,6 +72,7 @@ def parse_args(argv=None):
     if opt.ff:
         opt.fp16 = True
         assert opt.bg_radius <= 0, "background model is not implemented for --ff"
+        assert opt.encoding_dir == 'sphere_harmonics', "--encoding_dir frequency is not implemented for --ff (its colour input is SH-only)"
     return opt
 
 
@@ -85,6 +88,7 @@ def main(argv=None):
 
     model = NeRFNetwork(
         encoding="hashgrid",
+        encoding_dir=opt.encoding_dir,
         bound=opt.bound,
         cuda_ray=opt.cuda_ray,
         density_scale=1,

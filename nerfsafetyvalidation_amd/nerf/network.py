@@ -116,7 +116,12 @@ class NeRFNetwork(NeRFRenderer):
         (table cast by gridencoder/grid.py:36-39, nn.Linear autocast to half), fp32 outside it (validate.py's rollout);
         None when the configuration is not the fused shape."""
         from .. import _fused
+        from ..gridencoder import GridEncoder
+        from ..shencoder import SHEncoder
         if self.bg_radius > 0:
+            return None
+        # the fused kernels hard-code a hash-grid table and SH degree 4: any other encoder (frequency, ...) evaluates through the operators
+        if not (isinstance(self.encoder, GridEncoder) and isinstance(self.encoder_dir, SHEncoder) and self.encoder_dir.degree == 4):
             return None
         f32 = not torch.is_autocast_enabled("cuda")
         if f32 and (self.encoder.embeddings.dtype != torch.float32 or len(self.sigma_net) > 3 or len(self.color_net) > 4):

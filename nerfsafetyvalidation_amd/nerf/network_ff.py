@@ -169,6 +169,10 @@ class NeRFNetwork(NeRFRenderer):
                                num_layers=self.num_layers)
         self.num_layers_color = num_layers_color
         self.hidden_dim_color = hidden_dim_color
+        if encoding_dir != "sphere_harmonics":
+            # the glue between the two FFMLPs (ngp_ff_sigma_color_input) and the 32-wide colour input are built around SH degree 4
+            raise NotImplementedError(f"encoding_dir '{encoding_dir}' is not available with the fully fused MLP: its colour input is "
+                                      "[SH(16) | geo_feat(15) | 0]; use nerf.network.NeRFNetwork for other direction encodings")
         self.encoder_dir, self.in_dim_color = get_encoder(encoding_dir)
         self.in_dim_color += self.geo_feat_dim + 1
         self.color_net = FFMLP(input_dim=self.in_dim_color, output_dim=3, hidden_dim=self.hidden_dim_color,
