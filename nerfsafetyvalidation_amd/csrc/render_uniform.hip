@@ -8,6 +8,118 @@
 namespace ngp {
 
 // ------------------------------------------------------------------------------------------
+// The steps of NeRFRenderer.run's sampling and compositing (nerf/renderer.py:150-244) that the kernels below share, each stated once.
+// ------------------------------------------------------------------------------------------
+struct RaySetup {
+    float ox, oy, oz, dx, dy, dz, near, span, sample_dist;
+    __device__ __forceinline__ float z_at(const float* lin, uint32_t i) const { return near + span * lin[i]; }   // :150 (mul, then add: eager torch does not fuse)
+    __device__ __forceinline__ float depth_ratio(float zv) const { return (zv - near) / span; }   // :227; 0/0 = NaN for rays that miss the box
+};
+// ORIGIN = false: a kernel that evaluates no position (rays_o is not read)
+template <bool ORIGIN = true>
+__device__ __forceinline__ RaySetup load_ray(const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t ray, uint32_t T) {
+    float ox = 0, oy = 0, oz = 0;
+    if constexpr (ORIGIN) { ox = rays_o[(size_t)ray * 3]; oy = rays_o[(size_t)ray * 3 + 1]; oz = rays_o[(size_t)ray * 3 + 2]; }
+    const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
+    const float near = nears[ray], far = fars[ray], span = far - near;
+    return {ox, oy, oz, dx, dy, dz, near, span, span * (1.0f / (float)T)};      // :153 (tensor / Python scalar on the GPU = multiplication with the fp32 reciprocal)
+}
+__device__ __forceinline__ void sample_point(const RaySetup& r, float zv, float lo, float hi, float& x, float& y, float& z) {   // :159-160, :181-182
+    x = clampf(r.ox + r.dx * zv, lo, hi);
+    y = clampf(r.oy + r.dy * zv, lo, hi);
+    z = clampf(r.oz + r.dz * zv, lo, hi);
+}
+__device__ __forceinline__ float sample_alpha(float delta, float density_scale, float sigma) { return 1.0f - expf(((-delta) * density_scale) * sigma); }   // :208
+__device__ __forceinline__ float alpha_survival(float alpha) { return (1.0f - alpha) + 1e-15f; }                                                       // :209
+__device__ __forceinline__ bool weight_masked(float w) { return w > 1e-4f; }      // :216, the samples whose colour the reference evaluates
+// a ray stops where its transmittance falls below this: everything further down is weighted by less, below fp32 resolution of the
+// O(1) sums
+constexpr float kSpentTransmittance = 1e-10f;
+
+// inclusive scan (product or sum) over groups of W lanes; l = lane within the group
+template <int W, bool MUL>
+__device__ __forceinline__ float scan_inclusive(float v, uint32_t l) {
+#pragma unroll
+    for (int off = 1; off < W; off <<= 1) {
+        const float o = __shfl_up(v, off, W);
+        if (l >= (uint32_t)off) v = MUL ? v * o : v + o;
+    }
+    return v;
+}
+// cumprod(1 - alpha + 1e-15) of :209-210 over a tile of W samples, lane = sample: the transmittance in front of the lane's sample, given
+// `carry` = the product over the earlier tiles; tile_product is what the tile multiplies into carry
+template <int W>
+__device__ __forceinline__ float tile_transmittance(float p, float carry, uint32_t l, float& tile_product) {
+    const float incl = scan_inclusive<W, true>(p, l);
+    const float excl = __shfl_up(incl, 1, W);
+    tile_product = __shfl(incl, W - 1, W);
+    return carry * (l == 0 ? 1.0f : excl);
+}
+
+// colour of a tile's samples from the sigma net's outputs s16, evaluated (by the whole wave) only when `any` holds for some lane -- the
+// reference's masked colour query (:216-218); lanes that are not `masked` read zero
+template <class NET>
+__device__ __forceinline__ void masked_color(const NetArgs& na, const char* Wlds, uint32_t lane, const RaySetup& r, const typename NET::geo_t (&s16)[4],
+                                             bool any, bool masked, float& cr, float& cg, float& cb) {
+    cr = 0; cg = 0; cb = 0;
+    if (__ballot(any) != 0ull) {
+        NET::color(na, Wlds, lane, r.dx, r.dy, r.dz, s16, cr, cg, cb);
+        if (!masked) { cr = 0; cg = 0; cb = 0; }
+    }
+}
+
+// one of the per-sample rows the reference returns for the last ray chunk
+__device__ __forceinline__ void dump_sample(float* sigmas, float* rgbs, size_t row, float sigma, float cr, float cg, float cb) {
+    sigmas[row] = sigma;
+    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
+}
+
+// a lane's partial sums of the four per-ray outputs
+struct RaySums {
+    float ws, dep, r, g, b, agg;
+    __device__ __forceinline__ void add(const RaySetup& ray, float zv, float w, float sigma, float cr, float cg, float cb) {
+        ws += w;
+        const float qz = ray.depth_ratio(zv);
+        dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));                   // torch.clamp keeps the NaN, as the reference does
+        r += w * cr; g += w * cg; b += w * cb;                                       // :231
+        agg += w * sigma;                                                            // :244
+    }
+    __device__ __forceinline__ void reduce16() {
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) {
+            ws += __shfl_xor(ws, off, 16); dep += __shfl_xor(dep, off, 16); agg += __shfl_xor(agg, off, 16);
+            r += __shfl_xor(r, off, 16); g += __shfl_xor(g, off, 16); b += __shfl_xor(b, off, 16);
+        }
+    }
+    __device__ __forceinline__ void store(uint32_t ray, float* weights_sum, float* depth, float* image, float* aggregated_density) const {
+        weights_sum[ray] = ws; depth[ray] = dep; aggregated_density[ray] = agg;
+        image[(size_t)ray * 3] = r; image[(size_t)ray * 3 + 1] = g; image[(size_t)ray * 3 + 2] = b;
+    }
+};
+
+// ray -> (group of sixteen, slot in the group) as the across-ray kernels form their groups: 1x16 strips, or 4x4-pixel blocks of row-major
+// frames `frame_w` wide (frame_w % 4 == 0, N % (4 * frame_w) == 0: checked on the host)
+__device__ __forceinline__ void ray_slot(uint32_t ray, uint32_t frame_w, uint32_t& grp, uint32_t& c) {
+    if (frame_w) {
+        const uint32_t row = ray / frame_w, col = ray - row * frame_w;
+        grp = (row >> 2) * (frame_w >> 2) + (col >> 2);
+        c = (row & 3u) * 4u + (col & 3u);
+    } else {
+        grp = ray >> 4;
+        c = ray & 15u;
+    }
+}
+// (group, slot) -> ray, the inverse of ray_slot; the slots past the last ray of a ragged last group give a ray >= N
+__device__ __forceinline__ uint32_t group_ray(uint32_t grp, uint32_t c, uint32_t frame_w) {
+    uint32_t ray = grp * 16 + c;
+    if (frame_w) {
+        const uint32_t bpr = frame_w >> 2, by = grp / bpr, bx = grp - by * bpr;
+        ray = (by * 4 + (c >> 2)) * frame_w + bx * 4 + (c & 3);
+    }
+    return ray;
+}
+
+// ------------------------------------------------------------------------------------------
 // NeRFRenderer.run, uniform sampling without upsampling (nerf/renderer.py:125-258): the path validate.py -O executes
 // (cuda_ray = False, num_steps = 512).  One wave walks one ray 16 samples at a time: positions from the linspace table,
 // fused hash-grid + sigma net, in-wave transmittance scan (alphas * cumprod(1 - alphas + 1e-15), :206-210), colour net only
@@ -30,73 +142,42 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform(NetAr
     const uint32_t lane = threadIdx.x & 63, c = lane & 15;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t ray = wave; ray < N; ray += n_waves) {
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153 (tensor / Python scalar on the GPU = multiplication with the fp32 reciprocal)
+        const RaySetup r = load_ray(rays_o, rays_d, nears, fars, ray, T);
         const bool dump = sigmas != nullptr && ray >= dump_begin;
         float carry = 1.0f;                                                          // cumprod of (1 - alpha + 1e-15) over earlier tiles
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;             // per-lane partial sums (lanes 0..15)
+        RaySums sums = {};                                                           // per-lane partial sums (lanes 0..15)
         for (uint32_t i0 = 0; i0 < T; i0 += 16) {
             const uint32_t idx = i0 + c;
             const bool valid = idx < T;
             const uint32_t ii = valid ? idx : T - 1;
-            const float zv = near + span * lin[ii];                                  // :150 (mul, then add: eager torch does not fuse)
-            const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);                  // :159-160
-            const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-            const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
+            const float zv = r.z_at(lin, ii);
+            float x, y, z;
+            sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
             float sigma;
             typename NET::geo_t s16[4];
             NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
             // ---- lanes 0..15 hold sigma of samples i0..i0+15 (the other quarters compute along with them; only lane < 16 results are used)
-            const float z_next = (ii + 1 < T) ? near + span * lin[ii + 1] : 0.0f;
-            const float delta = (ii + 1 < T) ? z_next - zv : sample_dist;           // :206-207
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;   // :208
-            const float p = (1.0f - alpha) + 1e-15f;                                 // :209
-            float incl = p;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl_in_tile = __shfl_up(incl, 1, 16);
-            const float Tr = carry * (c == 0 ? 1.0f : excl_in_tile);
+            const float z_next = (ii + 1 < T) ? r.z_at(lin, ii + 1) : 0.0f;
+            const float delta = (ii + 1 < T) ? z_next - zv : r.sample_dist;         // :206-207
+            const float alpha = valid ? sample_alpha(delta, na.density_scale, sigma) : 0.0f;
+            float tile_product;
+            const float Tr = tile_transmittance<16>(alpha_survival(alpha), carry, c, tile_product);
             const float w = alpha * Tr;                                              // :210
-            const bool masked = valid && w > 1e-4f;                                  // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked && lane < 16) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
+            const bool masked = valid && weight_masked(w);
+            float cr, cg, cb;
+            masked_color<NET>(na, Wlds, lane, r, s16, masked && lane < 16, masked, cr, cg, cb);
             if (lane < 16 && valid) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227; 0/0 = NaN for rays that miss the box and
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));         // torch.clamp keeps the NaN, as the reference does
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;                         // :231
-                a_agg += w * sigma;                                                  // :244
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * T + idx;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
+                sums.add(r, zv, w, sigma, cr, cg, cb);
+                if (dump) dump_sample(sigmas, rgbs, (size_t)(ray - dump_begin) * T + idx, sigma, cr, cg, cb);
             }
             // (lanes 16..63 evaluate other rows of the sigma net in `sigma`: only quarter 0's transmittance is the ray's.  The exit
             //  below must be taken by the WHOLE wave at once -- a quarter that left early would stop gathering its levels -- hence
             //  the broadcast of lane 0's value)
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));
-            // everything further down the ray is weighted by <= carry: below fp32 resolution of the O(1) sums
-            if (!dump && carry < 1e-10f) break;
+            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * tile_product)));
+            if (!dump && carry < kSpentTransmittance) break;
         }
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            a_ws += __shfl_xor(a_ws, off, 16); a_dep += __shfl_xor(a_dep, off, 16); a_agg += __shfl_xor(a_agg, off, 16);
-            a_r += __shfl_xor(a_r, off, 16); a_g += __shfl_xor(a_g, off, 16); a_b += __shfl_xor(a_b, off, 16);
-        }
-        if (lane == 0) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
+        sums.reduce16();
+        if (lane == 0) sums.store(ray, weights_sum, depth, image, aggregated_density);
     }
 }
 
@@ -107,9 +188,7 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform(NetAr
 // walks ray 16 g + c; a ray whose transmittance is spent idles until the last ray of its group is (neighbouring pixels end at
 // similar depths).  Per-sample granularity of the stop: a ray ends after the first sample that leaves carry < 1e-10.
 constexpr uint32_t kUniformX16MinRays = 65536;      // (measured: section 4 of DESIGN.md)
-// DENS: the density pass alone -- sigma of every uniform sample of every ray into sigmas [N, T], no colour, no sums, no early stop
-// (the coarse pass of the importance resampling, ngp_density_uniform).
-template <class NET, bool DENS = false>
+template <class NET>
 __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(NetArgs na, GridLevels lv, const float* __restrict__ rays_o,
                                                                const float* __restrict__ rays_d, const float* __restrict__ nears,
                                                                const float* __restrict__ fars, uint32_t N, uint32_t T,
@@ -117,8 +196,7 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(N
                                                                float* __restrict__ depth, float* __restrict__ image,
                                                                float* __restrict__ aggregated_density, uint32_t dump_begin,
                                                                float* __restrict__ sigmas, float* __restrict__ rgbs, float aabb_lo, float aabb_hi,
-                                                               uint32_t frame_w, unsigned long long* __restrict__ stamps,
-                                                               const float* __restrict__ z_in, _Float16* __restrict__ geo_out) {
+                                                               uint32_t frame_w, unsigned long long* __restrict__ stamps) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const char* Wlds = smem;
     LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
@@ -127,86 +205,44 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(N
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     const uint32_t n_groups = (N + 15) / 16;
     for (uint32_t grp = wave; grp < n_groups; grp += n_waves) {
-        uint32_t ray_raw = grp * 16 + c;
-        if (frame_w) {      // 4x4-pixel blocks of row-major frames `frame_w` wide (frame_w % 4 == 0, N % (4 * frame_w) == 0: checked on the host)
-            const uint32_t bpr = frame_w >> 2, by = grp / bpr, bx = grp - by * bpr;
-            ray_raw = (by * 4 + (c >> 2)) * frame_w + bx * 4 + (c & 3);
-        }
+        const uint32_t ray_raw = group_ray(grp, c, frame_w);
         const bool live = ray_raw < N;
-        const uint32_t ray = live ? ray_raw : N - 1;
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
+        const uint32_t ray = live ? ray_raw : N - 1;      // (slots past the last ray read the last ray)
+        const RaySetup r = load_ray(rays_o, rays_d, nears, fars, ray, T);
         const bool dump = live && sigmas != nullptr && ray >= dump_begin;
         float carry = 1.0f;
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
+        RaySums sums = {};
         bool running = live;
         uint32_t n_iter = 0, n_counted = 0;
-        if constexpr (DENS && !NET::kF32) {      // z_in: the depths come from the resampling instead of the uniform table.  Scratch arrays are GROUP-major,
-            // [group][sample][ray of the group]: the sixteen rays' values of one sample are 64 (sigma, depth) or 512 (geo) contiguous bytes
-            for (uint32_t i = 0; i < T; i++) {
-                const size_t at = ((size_t)grp * T + i) * 16 + c;
-                const float zs = z_in ? (live ? z_in[at] : 0.0f) : near + span * lin[i];    // (slots past the last ray were never written)
-                const float x = clampf(ox + dx * zs, aabb_lo, aabb_hi), y = clampf(oy + dy * zs, aabb_lo, aabb_hi), z = clampf(oz + dz * zs, aabb_lo, aabb_hi);
-                float sigma;
-                _Float16 s16[4];
-                NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-                if (lane < 16) sigmas[at] = sigma;
-                // the sigma net's sixteen outputs (sigma's pre-activation + the 15 geometry features), 4 per quarter: what the colour
-                // net of the compositing launch needs of this sample
-                if (geo_out) {
-                    half4 h4 = {s16[0], s16[1], s16[2], s16[3]};
-                    *reinterpret_cast<half4*>(geo_out + at * 16 + (lane >> 4) * 4) = h4;
-                }
-            }
-            continue;
-        }
-        float zv = near + span * lin[0];                                             // :150
+        float zv = r.z_at(lin, 0);
         for (uint32_t i = 0; i < T; i++) {
             n_iter++;
-            const float z_next = (i + 1 < T) ? near + span * lin[i + 1] : 0.0f;
-            const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);                  // :159-160
-            const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-            const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
+            const float z_next = (i + 1 < T) ? r.z_at(lin, i + 1) : 0.0f;
+            float x, y, z;
+            sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
             float sigma;
             typename NET::geo_t s16[4];
             NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
             // (quarter 0 holds sigma; the other quarters evaluate other rows of the sigma net in `sigma` and follow quarter 0's
             //  decisions through the ballots below)
-            const float delta = (i + 1 < T) ? z_next - zv : sample_dist;             // :206-207
-            const float alpha = 1.0f - expf(((-delta) * na.density_scale) * sigma);  // :208
+            const float delta = (i + 1 < T) ? z_next - zv : r.sample_dist;           // :206-207
+            const float alpha = sample_alpha(delta, na.density_scale, sigma);
             const float w = alpha * carry;                                           // :210
             const bool counted = running && lane < 16;
-            const bool masked = counted && w > 1e-4f;                                // :216
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
+            const bool masked = counted && weight_masked(w);
+            float cr, cg, cb;
+            masked_color<NET>(na, Wlds, lane, r, s16, masked, masked, cr, cg, cb);
             if (counted) {
                 n_counted++;
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;                         // :231
-                a_agg += w * sigma;                                                  // :244
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * T + i;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-                carry *= (1.0f - alpha) + 1e-15f;                                    // :209
-                if (!dump && carry < 1e-10f) running = false;                        // what follows is weighted by <= carry
+                sums.add(r, zv, w, sigma, cr, cg, cb);
+                if (dump) dump_sample(sigmas, rgbs, (size_t)(ray - dump_begin) * T + i, sigma, cr, cg, cb);
+                carry *= alpha_survival(alpha);
+                if (!dump && carry < kSpentTransmittance) running = false;
             }
             if (__ballot(running && lane < 16) == 0ull) break;
             zv = z_next;
         }
-        if (lane < 16 && live) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
+        if (lane < 16 && live) sums.store(ray, weights_sum, depth, image, aggregated_density);
         if (stamps) {    // diagnostics (ngp_debug_set_stamps): depth indices walked by the group x 16 lanes, and those that carried a running ray
             uint32_t mine = lane < 16 ? n_counted : 0u;
 #pragma unroll
@@ -216,16 +252,43 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(N
     }
 }
 
-// ray -> (group of sixteen, slot in the group) as k_render_uniform_x16 forms its groups: 1x16 strips, or 4x4-pixel blocks of frames
-// `frame_w` wide
-__device__ __forceinline__ void ray_slot(uint32_t ray, uint32_t frame_w, uint32_t& grp, uint32_t& c) {
-    if (frame_w) {
-        const uint32_t row = ray / frame_w, col = ray - row * frame_w;
-        grp = (row >> 2) * (frame_w >> 2) + (col >> 2);
-        c = (row & 3u) * 4u + (col & 3u);
-    } else {
-        grp = ray >> 4;
-        c = ray & 15u;
+// The density pass alone, tiles across sixteen rays as in k_render_uniform_x16 (fp16 network): sigma of T samples of every ray, no
+// colour, no sums, no early stop -- the two density launches of the large-batch importance resampling.  z_in = NULL: the uniform depths;
+// else the resampled ones.  z_in, sigmas and geo_out are GROUP-major, [group][sample][ray of the group]: the sixteen rays' values of
+// one sample are 64 (sigma, depth) or 512 (geo) contiguous bytes.
+template <class NET>
+__global__ void __launch_bounds__(256, 4) k_density_x16(NetArgs na, GridLevels lv, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                        const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N, uint32_t T,
+                                                        const float* __restrict__ lin, const float* __restrict__ z_in, float* __restrict__ sigmas,
+                                                        _Float16* __restrict__ geo_out, float aabb_lo, float aabb_hi, uint32_t frame_w) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const char* Wlds = smem;
+    LevelTab* lt = reinterpret_cast<LevelTab*>(smem + NET::w_bytes(na));
+    stage_block(na, lv, smem, lt, NET::w_bytes(na));
+    const uint32_t lane = threadIdx.x & 63, c = lane & 15;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t n_groups = (N + 15) / 16;
+    for (uint32_t grp = wave; grp < n_groups; grp += n_waves) {
+        const uint32_t ray_raw = group_ray(grp, c, frame_w);
+        const bool live = ray_raw < N;
+        const uint32_t ray = live ? ray_raw : N - 1;      // (slots past the last ray read the last ray)
+        const RaySetup r = load_ray(rays_o, rays_d, nears, fars, ray, T);
+        for (uint32_t i = 0; i < T; i++) {
+            const size_t at = ((size_t)grp * T + i) * 16 + c;
+            const float zs = z_in ? (live ? z_in[at] : 0.0f) : r.z_at(lin, i);    // (slots past the last ray were never written)
+            float x, y, z;
+            sample_point(r, zs, aabb_lo, aabb_hi, x, y, z);
+            float sigma;
+            _Float16 s16[4];
+            NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
+            if (lane < 16) sigmas[at] = sigma;
+            // the sigma net's sixteen outputs (sigma's pre-activation + the 15 geometry features), 4 per quarter: what the colour
+            // net of the compositing launch needs of this sample
+            if (geo_out) {
+                half4 h4 = {s16[0], s16[1], s16[2], s16[3]};
+                *reinterpret_cast<half4*>(geo_out + at * 16 + (lane >> 4) * 4) = h4;
+            }
+        }
     }
 }
 
@@ -253,22 +316,16 @@ __global__ void __launch_bounds__(256, 4) k_composite_merged_x16(NetArgs na, Gri
     const uint32_t n_groups = (N + 15) / 16, Tm = T + U;
     const float inf = __builtin_huge_valf();
     for (uint32_t grp = wave; grp < n_groups; grp += n_waves) {
-        uint32_t ray_raw = grp * 16 + c;
-        if (frame_w) {
-            const uint32_t bpr = frame_w >> 2, by = grp / bpr, bx = grp - by * bpr;
-            ray_raw = (by * 4 + (c >> 2)) * frame_w + bx * 4 + (c & 3);
-        }
+        const uint32_t ray_raw = group_ray(grp, c, frame_w);
         const bool live = ray_raw < N;
-        const uint32_t ray = live ? ray_raw : N - 1;
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
+        const uint32_t ray = live ? ray_raw : N - 1;      // (slots past the last ray read the last ray)
+        const RaySetup r = load_ray<false>(nullptr, rays_d, nears, fars, ray, T);
         const bool dump = live && sigmas != nullptr && ray >= dump_begin;
         const size_t cbase = (size_t)grp * T * 16 + c, fbase = (size_t)grp * U * 16 + c;
         uint32_t i = 0, j = 0;                                                       // next coarse / fine sample of this lane's ray
-        float zci = near + span * lin[0], zfj = live ? zf[fbase] : 0.0f;                 // (slots past the last ray were never written)
-        float carry = 1.0f, a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
+        float zci = r.z_at(lin, 0), zfj = live ? zf[fbase] : 0.0f;                   // (slots past the last ray were never written)
+        float carry = 1.0f;
+        RaySums sums = {};
         bool running = live;
         for (uint32_t m = 0; m < Tm; m++) {
             const bool from_c = zci <= zfj;                                          // (an exhausted run holds +inf; both cannot be)
@@ -276,41 +333,30 @@ __global__ void __launch_bounds__(256, 4) k_composite_merged_x16(NetArgs na, Gri
             const size_t at = from_c ? cbase + (size_t)i * 16 : fbase + (size_t)j * 16;
             const float sigma = (from_c ? sc : sf)[at];
             const _Float16* gp = (from_c ? geo_c : geo_f) + at * 16 + q * 4;
-            if (from_c) { i++; zci = i < T ? near + span * lin[i] : inf; }
+            if (from_c) { i++; zci = i < T ? r.z_at(lin, i) : inf; }
             else { j++; zfj = j < U ? (live ? zf[fbase + (size_t)j * 16] : 0.0f) : inf; }
             const float z_next = zci <= zfj ? zci : zfj;
-            const float delta = (m + 1 < Tm) ? z_next - zv : sample_dist;            // :206-207
-            const float alpha = 1.0f - expf(((-delta) * na.density_scale) * sigma);  // :208
+            const float delta = (m + 1 < Tm) ? z_next - zv : r.sample_dist;          // :206-207
+            const float alpha = sample_alpha(delta, na.density_scale, sigma);
             const float w = alpha * carry;                                           // :210
             const bool counted = running && lane < 16;
-            const bool masked = counted && w > 1e-4f;                                // :216
+            const bool masked = counted && weight_masked(w);
             float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
+            if (__ballot(masked) != 0ull) {      // (as masked_color does, on the sigma net's outputs that the density launches kept)
                 const half4 h4 = *reinterpret_cast<const half4*>(gp);
                 const _Float16 s16[4] = {h4[0], h4[1], h4[2], h4[3]};
-                net_color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
+                net_color(na, Wlds, lane, r.dx, r.dy, r.dz, s16, cr, cg, cb);
                 if (!masked) { cr = 0; cg = 0; cb = 0; }
             }
             if (counted) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;
-                a_agg += w * sigma;
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * Tm + m;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
-                carry *= (1.0f - alpha) + 1e-15f;                                    // :209
-                if (!dump && carry < 1e-10f) running = false;
+                sums.add(r, zv, w, sigma, cr, cg, cb);
+                if (dump) dump_sample(sigmas, rgbs, (size_t)(ray - dump_begin) * Tm + m, sigma, cr, cg, cb);
+                carry *= alpha_survival(alpha);
+                if (!dump && carry < kSpentTransmittance) running = false;
             }
             if (__ballot(running && lane < 16) == 0ull) break;
         }
-        if (lane < 16 && live) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
+        if (lane < 16 && live) sums.store(ray, weights_sum, depth, image, aggregated_density);
     }
 }
 
@@ -335,7 +381,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
                                                          float* __restrict__ aggregated_density, uint32_t dump_begin, float* __restrict__ sigmas,
                                                          float* __restrict__ rgbs, float aabb_lo, float aabb_hi,
                                                          const float* __restrict__ sc_in, float* __restrict__ zf_out, uint32_t frame_w) {
-    // sc_in: sigma of the uniform samples, evaluated by k_render_uniform_x16<DENS> (tiles across rays);  zf_out: stop after the resampling
+    // sc_in: sigma of the uniform samples, evaluated by k_density_x16 (tiles across rays);  zf_out: stop after the resampling
     // and hand the new depths over.  Both group-major (frame_w as in that launch): the middle launch of the large-batch form.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const size_t w_bytes = net_w_bytes_f16(na);
@@ -353,11 +399,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
     float* sm = zm + Tm;
 #define NGP_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
     for (uint32_t ray = blockIdx.x * wpb + wid; ray < N; ray += gridDim.x * wpb) {
-        const float ox = rays_o[(size_t)ray * 3], oy = rays_o[(size_t)ray * 3 + 1], oz = rays_o[(size_t)ray * 3 + 2];
-        const float dx = rays_d[(size_t)ray * 3], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-        const float near = nears[ray], far = fars[ray];
-        const float span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);                          // :153
+        const RaySetup r = load_ray(rays_o, rays_d, nears, fars, ray, T);
         const bool dump = sigmas != nullptr && ray >= dump_begin;
         uint32_t g_grp, g_c;
         ray_slot(ray, frame_w, g_grp, g_c);
@@ -368,7 +410,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
             float* sdst = phase ? sf : sc;
             if (!phase && sc_in) {  // the coarse pass was evaluated across rays: take its sigma
                 for (uint32_t i = lane; i < n; i += 64) {
-                    zdst[i] = near + span * lin[i];
+                    zdst[i] = r.z_at(lin, i);
                     sdst[i] = sc_in[((size_t)g_grp * T + i) * 16 + g_c];
                 }
             } else
@@ -376,10 +418,9 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
                 const uint32_t idx = i0 + c;
                 const bool valid = idx < n;
                 const uint32_t ii = valid ? idx : n - 1;
-                const float zv = phase ? zf[ii] : near + span * lin[ii];             // :150
-                const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);              // :159-160, :181-182
-                const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-                const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
+                const float zv = phase ? zf[ii] : r.z_at(lin, ii);
+                float x, y, z;
+                sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
                 float sigma;
                 _Float16 s16[4];
                 net_density<MODE>(na, Wlds, *lt, lane, x, y, z, sigma, s16);
@@ -393,17 +434,12 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
                 const uint32_t t = t0 + lane;
                 const bool on = t < T;
                 const uint32_t tt = on ? t : T - 1;
-                const float delta = tt + 1 < T ? zc[tt + 1] - zc[tt] : sample_dist;
-                const float alpha = on ? 1.0f - expf(((-delta) * na.density_scale) * sc[tt]) : 0.0f;
-                float incl = on ? (1.0f - alpha) + 1e-15f : 1.0f;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const float o = __shfl_up(incl, off, 64);
-                    if (lane >= (uint32_t)off) incl *= o;
-                }
-                const float excl = __shfl_up(incl, 1, 64);
-                if (on) cdf[t] = alpha * (carry * (lane == 0 ? 1.0f : excl));
-                carry *= __shfl(incl, 63, 64);
+                const float delta = tt + 1 < T ? zc[tt + 1] - zc[tt] : r.sample_dist;
+                const float alpha = on ? sample_alpha(delta, na.density_scale, sc[tt]) : 0.0f;
+                float tile_product;
+                const float Tr = tile_transmittance<64>(on ? alpha_survival(alpha) : 1.0f, carry, lane, tile_product);
+                if (on) cdf[t] = alpha * Tr;
+                carry *= tile_product;
             }
             NGP_WAVE_SYNC();
             // sample_pdf(bins = mid points [T - 1], weights[1:-1] [T - 2]) (:12-46): cdf[k], k = 0 .. T - 2, in place of weights[k]
@@ -416,12 +452,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
             for (uint32_t t0 = 0; t0 < Tw; t0 += 64) {
                 const uint32_t t = t0 + lane;
                 const float pdf = t < Tw ? (cdf[t + 1] + 1e-5f) / sum : 0.0f;
-                float incl = pdf;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const float o = __shfl_up(incl, off, 64);
-                    if (lane >= (uint32_t)off) incl += o;
-                }
+                const float incl = scan_inclusive<64, false>(pdf, lane);
                 if (t < Tw) cdf[t + 1] = run + incl;                                 // :21
                 run += __shfl(incl, 63, 64);
             }
@@ -467,58 +498,35 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
         NGP_WAVE_SYNC();
         // ---- 5. compositing over the merged samples (:206-244)
         float carry = 1.0f;
-        float a_ws = 0, a_dep = 0, a_r = 0, a_g = 0, a_b = 0, a_agg = 0;
+        RaySums sums = {};
         for (uint32_t i0 = 0; i0 < Tm; i0 += 16) {
             const uint32_t idx = i0 + c;
             const bool valid = idx < Tm;
             const uint32_t ii = valid ? idx : Tm - 1;
             const float zv = zm[ii], sigma = sm[ii];
-            const float delta = (ii + 1 < Tm) ? zm[ii + 1] - zv : sample_dist;       // :206-207
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;
-            float incl = (1.0f - alpha) + 1e-15f;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl_in_tile = __shfl_up(incl, 1, 16);
-            const float w = alpha * (carry * (c == 0 ? 1.0f : excl_in_tile));        // :210
-            const bool masked = valid && w > 1e-4f;                                  // :216
+            const float delta = (ii + 1 < Tm) ? zm[ii + 1] - zv : r.sample_dist;     // :206-207
+            const float alpha = valid ? sample_alpha(delta, na.density_scale, sigma) : 0.0f;
+            float tile_product;
+            const float w = alpha * tile_transmittance<16>(alpha_survival(alpha), carry, c, tile_product);   // :210
+            const bool masked = valid && weight_masked(w);
             float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked) != 0ull) {
-                const float x = clampf(ox + dx * zv, aabb_lo, aabb_hi);
-                const float y = clampf(oy + dy * zv, aabb_lo, aabb_hi);
-                const float z = clampf(oz + dz * zv, aabb_lo, aabb_hi);
-                float s_again;
+            if (__ballot(masked) != 0ull) {      // (as masked_color does, with the sigma net evaluated again for the geometry features it did not keep)
+                float x, y, z, s_again;
+                sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
                 _Float16 s16[4];
                 net_density<MODE>(na, Wlds, *lt, lane, x, y, z, s_again, s16);
-                net_color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
+                net_color(na, Wlds, lane, r.dx, r.dy, r.dz, s16, cr, cg, cb);
                 if (!masked) { cr = 0; cg = 0; cb = 0; }
             }
             if (lane < 16 && valid) {
-                a_ws += w;
-                const float qz = (zv - near) / span;                                 // :227
-                a_dep += w * (qz != qz ? qz : fminf(1.0f, fmaxf(0.0f, qz)));
-                a_r += w * cr; a_g += w * cg; a_b += w * cb;
-                a_agg += w * sigma;
-                if (dump) {
-                    const size_t row = (size_t)(ray - dump_begin) * Tm + idx;
-                    sigmas[row] = sigma;
-                    rgbs[row * 3] = cr; rgbs[row * 3 + 1] = cg; rgbs[row * 3 + 2] = cb;
-                }
+                sums.add(r, zv, w, sigma, cr, cg, cb);
+                if (dump) dump_sample(sigmas, rgbs, (size_t)(ray - dump_begin) * Tm + idx, sigma, cr, cg, cb);
             }
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));
-            if (!dump && carry < 1e-10f) break;
+            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * tile_product)));
+            if (!dump && carry < kSpentTransmittance) break;
         }
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            a_ws += __shfl_xor(a_ws, off, 16); a_dep += __shfl_xor(a_dep, off, 16); a_agg += __shfl_xor(a_agg, off, 16);
-            a_r += __shfl_xor(a_r, off, 16); a_g += __shfl_xor(a_g, off, 16); a_b += __shfl_xor(a_b, off, 16);
-        }
-        if (lane == 0) {
-            weights_sum[ray] = a_ws; depth[ray] = a_dep; aggregated_density[ray] = a_agg;
-            image[(size_t)ray * 3] = a_r; image[(size_t)ray * 3 + 1] = a_g; image[(size_t)ray * 3 + 2] = a_b;
-        }
+        sums.reduce16();
+        if (lane == 0) sums.store(ray, weights_sum, depth, image, aggregated_density);
         NGP_WAVE_SYNC();      // the next ray overwrites the arrays
     }
 #undef NGP_WAVE_SYNC
@@ -580,53 +588,40 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
     float* s_T = s_g + T;                            // transmittance before the sample
 
     for (uint32_t ray = blockIdx.x * GW + wid; ray < ga.N; ray += gridDim.x * GW) {
-        const float ox = ga.rays_o[(size_t)ray * 3], oy = ga.rays_o[(size_t)ray * 3 + 1], oz = ga.rays_o[(size_t)ray * 3 + 2];
-        const float dx = ga.rays_d[(size_t)ray * 3], dy = ga.rays_d[(size_t)ray * 3 + 1], dz = ga.rays_d[(size_t)ray * 3 + 2];
-        const float near = ga.nears[ray], far = ga.fars[ray], span = far - near;
-        const float sample_dist = span * (1.0f / (float)T);
+        const RaySetup r = load_ray(ga.rays_o, ga.rays_d, ga.nears, ga.fars, ray, T);
         const float Gi0 = ga.g_image[(size_t)ray * 3], Gi1 = ga.g_image[(size_t)ray * 3 + 1], Gi2 = ga.g_image[(size_t)ray * 3 + 2];
         const float Gd = ga.g_depth ? ga.g_depth[ray] : 0.0f, Gw = ga.g_ws ? ga.g_ws[ray] : 0.0f, Ga = ga.g_agg ? ga.g_agg[ray] : 0.0f;
-        // ---------------- pass 1: forward, exactly k_render_uniform's arithmetic ----------------
+        // ---------------- pass 1: forward, k_render_uniform's tile loop from the same helpers ----------------
         float carry = 1.0f;
         uint32_t t_end = T;                                           // samples >= t_end carry no weight (transmittance below 1e-10)
         for (uint32_t i0 = 0; i0 < T; i0 += 16) {
             const uint32_t idx = i0 + c;
             const bool valid = idx < T;
             const uint32_t ii = valid ? idx : T - 1;
-            const float zv = near + span * ga.lin[ii];
-            const float x = clampf(ox + dx * zv, ga.aabb_lo, ga.aabb_hi), y = clampf(oy + dy * zv, ga.aabb_lo, ga.aabb_hi),
-                        z = clampf(oz + dz * zv, ga.aabb_lo, ga.aabb_hi);
+            const float zv = r.z_at(ga.lin, ii);
+            float x, y, z;
+            sample_point(r, zv, ga.aabb_lo, ga.aabb_hi, x, y, z);
             float sigma;
             typename NET::geo_t s16[4];
             NET::density(na, Wlds, *lt, lane, x, y, z, sigma, s16);
-            const float z_next = (ii + 1 < T) ? near + span * ga.lin[ii + 1] : 0.0f;
-            const float delta = (ii + 1 < T) ? z_next - zv : sample_dist;
-            const float alpha = valid ? 1.0f - expf(((-delta) * na.density_scale) * sigma) : 0.0f;
-            const float p = (1.0f - alpha) + 1e-15f;
-            float incl = p;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const float o = __shfl_up(incl, off, 16);
-                if (c >= (uint32_t)off) incl *= o;
-            }
-            const float excl = __shfl_up(incl, 1, 16);
-            const float Tr = carry * (c == 0 ? 1.0f : excl);
+            const float z_next = (ii + 1 < T) ? r.z_at(ga.lin, ii + 1) : 0.0f;
+            const float delta = (ii + 1 < T) ? z_next - zv : r.sample_dist;
+            const float alpha = valid ? sample_alpha(delta, na.density_scale, sigma) : 0.0f;
+            float tile_product;
+            const float Tr = tile_transmittance<16>(alpha_survival(alpha), carry, c, tile_product);
             const float w = alpha * Tr;
-            const bool masked = valid && w > 1e-4f;
-            float cr = 0, cg = 0, cb = 0;
-            if (__ballot(masked && lane < 16) != 0ull) {
-                NET::color(na, Wlds, lane, dx, dy, dz, s16, cr, cg, cb);
-                if (!masked) { cr = 0; cg = 0; cb = 0; }
-            }
-            if (lane < 16 && valid) {
-                const float qz = (zv - near) / span;
+            const bool masked = valid && weight_masked(w);
+            float cr, cg, cb;
+            masked_color<NET>(na, Wlds, lane, r, s16, masked && lane < 16, masked, cr, cg, cb);
+            if (lane < 16 && valid) {     // (instead of the forward's sums: the sample's state for the reverse scan; a NaN depth ratio has no gradient)
+                const float qz = r.depth_ratio(zv);
                 const float rel = qz != qz ? 0.0f : fminf(1.0f, fmaxf(0.0f, qz));
                 s_sig[idx] = sigma;
                 s_T[idx] = Tr;
                 s_g[idx] = fmaf(Gi0, cr, fmaf(Gi1, cg, Gi2 * cb)) + Gd * rel + Gw + Ga * sigma;
             }
-            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * __shfl(incl, 15, 16))));   // quarter 0's value, for the whole wave
-            if (carry < 1e-10f) { t_end = (i0 + 16 < T) ? i0 + 16 : T; break; }
+            carry = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(carry * tile_product)));              // quarter 0's value, for the whole wave
+            if (carry < kSpentTransmittance) { t_end = (i0 + 16 < T) ? i0 + 16 : T; break; }
         }
         __builtin_amdgcn_wave_barrier();
         // ---------------- reverse scan: dL/dsigma_j and the colour scale w_j [w_j > 1e-4] ----------------
@@ -635,11 +630,11 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
             const uint32_t t = c0 - 64 + lane;
             const bool on = t < t_end;
             const uint32_t tt = on ? t : t_end - 1;
-            const float zv = near + span * ga.lin[tt];
-            const float delta = (tt + 1 < T) ? (near + span * ga.lin[tt + 1]) - zv : sample_dist;
+            const float zv = r.z_at(ga.lin, tt);
+            const float delta = (tt + 1 < T) ? r.z_at(ga.lin, tt + 1) - zv : r.sample_dist;
             const float sg = s_sig[tt], Tr = s_T[tt];
-            const float e = expf(((-delta) * na.density_scale) * sg);
-            const float alpha = 1.0f - e, p = (1.0f - alpha) + 1e-15f, w = alpha * Tr;
+            const float e = expf(((-delta) * na.density_scale) * sg);               // (sample_alpha's exponential, kept for its derivative)
+            const float alpha = 1.0f - e, p = alpha_survival(alpha), w = alpha * Tr;
             const float g = on ? s_g[tt] : 0.0f;
             const float gw = on ? g * w : 0.0f;
             float inc = gw;
@@ -658,7 +653,7 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
                     o4[0] = sg; o4[1] = Tr; o4[2] = g; o4[3] = dsg;
                 }
                 s_sig[t] = dsg;
-                s_g[t] = w > 1e-4f ? w : 0.0f;
+                s_g[t] = weight_masked(w) ? w : 0.0f;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -669,8 +664,8 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
             const uint32_t idx = i0 + c;
             const bool valid = idx < t_end;
             const uint32_t ii = valid ? idx : t_end - 1;
-            const float zv = near + span * ga.lin[ii];
-            const float ux = ox + dx * zv, uy = oy + dy * zv, uz = oz + dz * zv;          // before the clip (for its derivative)
+            const float zv = r.z_at(ga.lin, ii);
+            const float ux = r.ox + r.dx * zv, uy = r.oy + r.dy * zv, uz = r.oz + r.dz * zv;   // before the clip (for its derivative)
             const float x = clampf(ux, ga.aabb_lo, ga.aabb_hi), y = clampf(uy, ga.aabb_lo, ga.aabb_hi), z = clampf(uz, ga.aabb_lo, ga.aabb_hi);
             // ---- forward recompute, keeping corners and activations
             typename NET::Tape tape;
@@ -682,7 +677,7 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
             float gdir[3] = {0, 0, 0};
             if (__ballot(wscale != 0.0f && lane < 16) != 0ull) {
                 const float wsc = __shfl(wscale, c, 64);             // lanes 0..15 hold the per-sample values: broadcast to the sample's 4 lanes
-                NET::color_vjp(na, Wlds, Wb, lane, dx, dy, dz, s16, wsc, G, gdir, gso);
+                NET::color_vjp(na, Wlds, Wb, lane, r.dx, r.dy, r.dz, s16, wsc, G, gdir, gso);
             }
             // ---- sigma: trunc_exp backward (activation.py:12-17) on output 0
             {
@@ -726,6 +721,21 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
 
 using namespace ngp;
 
+// frame_width (scheduling hint, results do not depend on it): the rays are the pixels of row-major frames this wide -> a group of the
+// across-ray kernels is a 4x4-pixel block instead of a 1x16 strip (its sixteen rays are closer together and end at more similar
+// depths).  0 where the rays are not whole rows of 4x4 blocks.
+static uint32_t usable_frame_width(uint32_t frame_width, uint32_t N) {
+    return frame_width && (frame_width % 4 != 0 || N % (4 * frame_width) != 0) ? 0 : frame_width;
+}
+
+// runs STMT with MODE bound to the grid variant `mode` of the fp16 network (net_density<MODE>), as NGP_WITH_NET does with NET
+#define NGP_WITH_MODE(mode, ...)                                   \
+    switch (mode) {                                                \
+        case 1: { constexpr int MODE = 1; __VA_ARGS__; } break;    \
+        case 2: { constexpr int MODE = 2; __VA_ARGS__; } break;    \
+        default: { constexpr int MODE = 0; __VA_ARGS__; } break;   \
+    }
+
 extern "C" {
 
 int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t N,
@@ -754,10 +764,7 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
     // a pose-estimator batch (1024 scattered pixels, every ray dumped) keeps one ray per wave
     const bool per_ray = env_set("NGP_UNIFORM_PER_RAY");    // diagnostics (read per call: tests switch it): tiles along one ray for every size
     if (!per_ray && N >= kUniformX16MinRays) {
-        // frame_width (scheduling hint, results do not depend on it): the rays are the pixels of row-major frames this wide -> a
-        // group is a 4x4-pixel block instead of a 1x16 strip (its sixteen rays are closer together and end at more similar depths)
-        uint32_t fw = frame_width;
-        if (fw && (fw % 4 != 0 || N % (4 * fw) != 0)) fw = 0;
+        const uint32_t fw = usable_frame_width(frame_width, N);
         uint32_t gb = div_up(div_up(N, 16), 4);
         // as many workgroups as are RESIDENT at once (each strides over the groups): four per CU, or what the LDS holds -- the fp32
         // weights take 40 KB per workgroup, three fit, and with 1024 workgroups the fourth of every CU ran as a second round at a third
@@ -767,7 +774,7 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
         NGP_WITH_NET(variant, {
             ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NET>), 96 * 1024);
             k_render_uniform_x16<NET><<<gb, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density,
-                                                           dump_begin, sigmas, rgbs, -model->bound, model->bound, fw, dbg.stamps, nullptr, nullptr);
+                                                           dump_begin, sigmas, rgbs, -model->bound, model->bound, fw, dbg.stamps);
         });
         return check_launch("render_uniform");
     }
@@ -810,32 +817,24 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     uint32_t waves = (uint32_t)((budget - fixed) / per_wave);
     waves = waves > 4 ? 4 : waves;
     const size_t lds = fixed + waves * per_wave;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<0>), 160 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<1>), 160 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<2>), 160 * 1024);
     uint32_t blocks = div_up(N, waves);
     if (blocks > 1024) blocks = 1024;
     ProfScope prof("render_upsample", s, (double)N * (T + U));
     const int mode = needs_generic(lv) ? 1 : (na.cells ? 2 : 0);
-    uint32_t fw = frame_width;
-    if (fw && (fw % 4 != 0 || N % (4 * fw) != 0)) fw = 0;
+    const uint32_t fw = usable_frame_width(frame_width, N);
     auto per_ray = [&](const float* sc_in, float* zf_out) {
-        if (mode == 1)
-            k_render_upsample<1><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-        else if (mode == 2)
-            k_render_upsample<2><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-        else
-            k_render_upsample<0><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                 aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
+        NGP_WITH_MODE(mode, {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<MODE>), 160 * 1024);
+            k_render_upsample<MODE><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
+                                                                    aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
+        });
     };
     const size_t need = upsample_workspace_bytes(N, T, U);
     if (!(workspace && workspace_bytes >= need && N >= kUniformX16MinRays && !env_set("NGP_UPSAMPLE_PER_RAY"))) {
         per_ray(nullptr, nullptr);      // everything along the ray in one launch
         return check_launch("render_upsample");
     }
-    // Large batches: four launches through the caller's scratch (group-major arrays, see k_render_uniform_x16<DENS>).  The two density
+    // Large batches: four launches through the caller's scratch (group-major arrays, see k_density_x16).  The two density
     // passes take their tiles ACROSS sixteen neighbouring rays (twice the per-sample rate of tiles along a ray) and keep the sigma
     // net's outputs; the per-ray kernel resamples between them; merge + compositing run across the rays as well, colour net only.
     const size_t Np = ((size_t)N + 15) / 16 * 16;
@@ -844,37 +843,22 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     float* sf = zf + Np * U;
     _Float16* gc = reinterpret_cast<_Float16*>(sf + Np * U);
     _Float16* gf = gc + Np * T * 16;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<0>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<1>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NetF16<2>, true>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<0>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<1>), 96 * 1024);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<2>), 96 * 1024);
     uint32_t gb = div_up(div_up(N, 16), 4);
     if (gb > 1024) gb = 1024;
     auto density = [&](uint32_t n, const float* z_in, float* out, _Float16* geo) {
-        if (mode == 1)
-            k_render_uniform_x16<NetF16<1>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
-        else if (mode == 2)
-            k_render_uniform_x16<NetF16<2>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
-        else
-            k_render_uniform_x16<NetF16<0>, true><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, nullptr, nullptr, nullptr, nullptr, 0, out,
-                                                                 nullptr, -model->bound, model->bound, fw, nullptr, z_in, geo);
+        NGP_WITH_MODE(mode, {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(k_density_x16<NetF16<MODE>>), 96 * 1024);
+            k_density_x16<NetF16<MODE>><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, z_in, out, geo, -model->bound, model->bound, fw);
+        });
     };
     density(T, nullptr, sc, gc);
     per_ray(sc, zf);
     density(U, zf, sf, gf);
-    if (mode == 1)
-        k_composite_merged_x16<1><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
-    else if (mode == 2)
-        k_composite_merged_x16<2><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
-    else
-        k_composite_merged_x16<0><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
-                                                         aggregated_density, dump_begin, sigmas, rgbs, fw);
+    NGP_WITH_MODE(mode, {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_composite_merged_x16<MODE>), 96 * 1024);
+        k_composite_merged_x16<MODE><<<gb, 256, fixed, s>>>(na, lv, rays_d, nears, fars, N, T, U, lin, sc, zf, sf, gc, gf, weights_sum, depth, image,
+                                                            aggregated_density, dump_begin, sigmas, rgbs, fw);
+    });
     return check_launch("render_upsample");
 }
 

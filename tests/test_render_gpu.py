@@ -528,7 +528,7 @@ def test_run_full_size_frame_properties(setup, device, monkeypatch):
                          ids=["strips", "blocks_4x4", "ragged_ray_count"])
 def test_resampling_with_density_passes_across_rays(setup, device, backbone, T, U, fw, H, W, monkeypatch):
     """ngp_render_upsample from 65 536 rays on: the coarse and the fine density pass take their tiles across sixteen neighbouring rays
-    (k_render_uniform_x16<DENS>), the per-ray kernel resamples between them, merge + compositing run across the rays too
+    (k_density_x16), the per-ray kernel resamples between them, merge + compositing run across the rays too
     (k_composite_merged_x16: two-pointer merge per lane, colour net on the kept sigma-net outputs) -- four launches through a caller
     workspace.  Same samples as the one-launch form (NGP_UPSAMPLE_PER_RAY), with or without the frame-width hint; rays that miss the
     box and a dumped last chunk included."""
@@ -580,11 +580,13 @@ def test_run_path_several_cameras_per_call(setup, device, U):
     assert torch.equal(both["rgbs"], singles[2]["rgbs"]) and torch.equal(both["sigmas"], singles[2]["sigmas"])
 
 
+@pytest.mark.parametrize("T", [96, 17, 1])
 @pytest.mark.parametrize("backbone", ["ff", "linear"])
-def test_run_kernel_forms_agree(setup, device, backbone):
+def test_run_kernel_forms_agree(setup, device, backbone, T):
     """ngp_render_uniform takes its tiles across sixteen neighbouring rays from 65 536 rays on (k_render_uniform_x16) and along one ray
     below: the same 256x256 frame as one call and as two half calls -- per-sample tensors bit for bit, per-ray sums to fp32 summation
-    order, rays that miss the box included; a ragged ray count (not a multiple of 16) and rays that may not stop early (dump)."""
+    order, rays that miss the box included; a ragged ray count (not a multiple of 16) and rays that may not stop early (dump).
+    T = 96 is six whole tiles along the ray, 17 leaves a ragged last tile, 1 is less than one tile."""
     from nerfsafetyvalidation_amd import raymarching
     sc = _scene(H=255, W=259)
     model = sc.build_model(device, backbone=backbone, cuda_ray=False)
@@ -593,7 +595,6 @@ def test_run_kernel_forms_agree(setup, device, backbone):
     o, d = _t(ro, device), _t(rd, device)
     N = o.shape[0]
     assert N >= 65536 + 16 and N % 16 != 0
-    T = 96
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
         fm = model.fused_model()
         nears, fars = raymarching.near_far_from_aabb(o, d, model.aabb_infer, model.min_near)
