@@ -434,6 +434,40 @@ NGP_API int ngp_isosurface_count(const float* u, uint32_t X, uint32_t Y, uint32_
 NGP_API int ngp_isosurface_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, const void* workspace,
                                 size_t workspace_bytes, uint64_t V, uint64_t F, float* vertices, int32_t* faces, ngp_stream_t stream);
 
+/* Rays against a triangle mesh through a uniform grid (DESIGN.md "The ground-truth world"; world.py).  tri_data float [F,12],
+ * 16-byte aligned: per triangle the rows (v0, 0), (e1 = v1 - v0, 0), (e2 = v2 - v0, 0).  The grid is host arithmetic of the caller:
+ * cell (a, b, c) covers lo + (a, b, c) * cell .. lo + (a + 1, b + 1, c + 1) * cell, 1..256 cells per axis, inv_cell = 1 / cell;
+ * `grow` is added to every side of a triangle's bounding box before it is binned; a ray whose origin has a component beyond `reach`
+ * in magnitude is tested against all F triangles instead of walking the grid.
+ *   ngp_raycast_bin_count  counts int32 [F]: the number of cells triangle f's grown box overlaps.
+ *   ngp_raycast_bin_emit   offsets int64 [F] = the exclusive scan of counts, P = their sum: pair_cell / pair_tri int32 [P], triangle
+ *                          f's pairs at offsets[f].., its cells in C order.  The caller sorts the pairs by cell (stable: every
+ *                          cell's triangles ascending) and builds cell_start int32 [nx ny nz + 1].
+ *   ngp_raycast            rays_o / rays_d float [N,3] -> t float [N] (+inf on a miss), prim int32 [N] (-1 on a miss), u, v float [N]
+ *                          (0 on a miss), by the hit rule of csrc/raycast.hip: Moeller-Trumbore, two-sided, one IEEE operation per
+ *                          step, accepted iff u >= 0, v >= 0, u + v <= 1, t_min < t < t_max; the smallest t wins, equal t goes to the
+ *                          lowest triangle index; a ray with a non-finite component or a zero direction misses.  The result does not
+ *                          depend on the grid or on frame_width.  frame_width: 0, or the width W of the row-major frame(s) the rays
+ *                          are (W divides N): a wave then takes an 8 x 8 pixel tile.  N == 0 launches nothing.
+ *   ngp_raycast_shade      image float [N,3] and image_u8 uint8 [N,3] ((uint8)(x * 255)): the barycentric blend of the vertex colours
+ *                          (colors float [V,3] with faces int32 [F,3]; both null: mid-grey) times ambient + (1 - ambient) |n . d| /
+ *                          (|n| |d|), n = e1 x e2, clamped to [0, 1]; bg_color3_host (host memory) where prim < 0.
+ * F, P, N < 2^31 (NGP_EINVAL otherwise, nothing launched).  No atomics, no workspace, no global state. */
+typedef struct ngp_raycast_grid {
+    float lo[3], cell[3], inv_cell[3], grow[3];
+    float reach;
+    uint32_t n[3];
+} ngp_raycast_grid;
+NGP_API int ngp_raycast_bin_count(const float* tri_data, uint32_t F, const ngp_raycast_grid* grid, int32_t* counts, ngp_stream_t stream);
+NGP_API int ngp_raycast_bin_emit(const float* tri_data, uint32_t F, const ngp_raycast_grid* grid, const int64_t* offsets, uint64_t P,
+                                 int32_t* pair_cell, int32_t* pair_tri, ngp_stream_t stream);
+NGP_API int ngp_raycast(const float* rays_o, const float* rays_d, uint64_t N, const ngp_raycast_grid* grid, const int32_t* cell_start,
+                        const int32_t* pair_tri, uint64_t P, const float* tri_data, uint32_t F, float t_min, float t_max,
+                        uint32_t frame_width, float* t, int32_t* prim, float* u, float* v, ngp_stream_t stream);
+NGP_API int ngp_raycast_shade(const float* rays_d, const int32_t* prim, const float* u, const float* v, uint64_t N, const float* tri_data,
+                              const int32_t* faces, uint32_t F, const float* colors, uint32_t V, float ambient,
+                              const float* bg_color3_host, float* image, uint8_t* image_u8, ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

@@ -44,6 +44,11 @@ class RenderStats(C.Structure):
                 ("last_n_alive", _u32), ("last_n_step", _u32), ("launches", _u32), ("replayed", _u32)]
 
 
+class RaycastGrid(C.Structure):
+    """struct ngp_raycast_grid"""
+    _fields_ = [("lo", _f32 * 3), ("cell", _f32 * 3), ("inv_cell", _f32 * 3), ("grow", _f32 * 3), ("reach", _f32), ("n", _u32 * 3)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES).  Mirrors include/ngp_hip.h one to one;
 # tests/test_abi.py checks that every declaration in the header has an entry here and is exported.
 SIGNATURES = {
@@ -135,6 +140,10 @@ SIGNATURES = {
     "ngp_isosurface_workspace": [_u32, _u32, _u32],
     "ngp_isosurface_count": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, _vp, _vp],
     "ngp_isosurface_emit": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _vp],
+    "ngp_raycast_bin_count": [_vp, _u32, C.POINTER(RaycastGrid), _vp, _vp],
+    "ngp_raycast_bin_emit": [_vp, _u32, C.POINTER(RaycastGrid), _vp, C.c_uint64, _vp, _vp, _vp],
+    "ngp_raycast": [_vp, _vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp],
+    "ngp_raycast_shade": [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u32, _vp, _u32, _f32, C.POINTER(C.c_float), _vp, _vp, _vp],
     "ngp_sift_workspace": [_u32, _u32],
     "ngp_sift_layer_offset": [_u32, _u32, _int, _int],
     "ngp_sift_octaves": [_u32, _u32],

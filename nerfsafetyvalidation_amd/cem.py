@@ -196,11 +196,11 @@ def best_solution(q, simulator, sim):
 
 def run_cem(model, intrinsics, H, W, steps, m=10, m_elite=5, kmax=5, seed=0, q=None, start_k=0, sdf=None, best_solution=False, rank=0,
             world_size=1, group=None, in_flight=3, render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None,
-            estimator_cfg=None, uq_method=RO.UQ_GAUSSIAN, uq_kwargs=None):
+            estimator_cfg=None, uq_method=RO.UQ_GAUSSIAN, uq_kwargs=None, world=None):
     """CrossEntropyMethod.optimize() with every population run like run_rollout's simulations.  m, m_elite, kmax: validate.py:39's
     10, 5, 5.  q: the proposal to start from (default: the target p); with start_k it is the reference's `--k` resume.  sdf: a
     collision.SignedDistanceField, REQUIRED (the analytic 0 / 9999 stand-in gives CEM nothing to rank).  The other keywords are
-    run_rollout's; the refit needs every rank's rows, so gather=False is only accepted on one rank.
+    run_rollout's (world: the world.MeshWorld every simulation's sensor looks at, or None); the refit needs every rank's rows, so gather=False is only accepted on one rank.
     Returns (rows [total, CEM_ROW_WIDTH] float64 in (population, simulation, step) order, result, this rank's counters).  result:
     means / covs / q (the final proposal), population_scores / elite_scores (the two series the reference plots, :209,220),
     elite_indices, refit_info and the refitted population_means / population_covs per population, stopped_early (None, or the population whose refit gave no valid q -- the
@@ -225,7 +225,7 @@ def run_cem(model, intrinsics, H, W, steps, m=10, m_elite=5, kmax=5, seed=0, q=N
     def make(population, q_k):
         return CEMSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
                             planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg, uq_method=uq_method,
-                            uq_kwargs=uq_kwargs, p=p, q=q_k, population=population)
+                            uq_kwargs=uq_kwargs, world=world, p=p, q=q_k, population=population)
 
     result = {"population_scores": [], "elite_scores": [], "elite_indices": [], "refit_info": [], "population_means": [],
               "population_covs": [], "stopped_early": None}

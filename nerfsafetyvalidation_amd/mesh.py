@@ -7,6 +7,7 @@
                          CPU tensor / numpy array: the same rule and order in numpy (the package's CPU path)
     extract_geometry   extract_fields + isosurface + the reference's scaling to the bounds
     save_mesh          extract_geometry of model.density over model.aabb_infer, written as a binary PLY
+    write_ply/read_ply the binary PLY (optionally with uchar vertex colours) and its reader
     mesh_to_world      NeRF axes -> the world frame of collision.py's boxes (the inverse of collision.to_nerf)
 
 The rule (DESIGN.md "Mesh export"): marching tetrahedra on the Kuhn split.  A lattice point is inside iff u > threshold (strict;
@@ -263,20 +264,76 @@ def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
     return vertices, f.cpu().numpy()
 
 
-def write_ply(path, vertices, triangles):
-    """binary little-endian PLY: `float x y z` per vertex, `list uchar int vertex_indices` per face"""
+def _ply_colors(colors, n):
+    """vertex colours [V,3] as uint8: uint8 as it is, floats in [0, 1] as round(c * 255)"""
+    c = np.asarray(colors)
+    if c.shape != (n, 3):
+        raise ValueError(f"write_ply: colors [V,3] (got {c.shape} for {n} vertices)")
+    if c.dtype == np.uint8:
+        return c
+    return np.rint(np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def write_ply(path, vertices, triangles, colors=None):
+    """binary little-endian PLY: `float x y z` per vertex (and `uchar red green blue` with colors: uint8, or floats in [0, 1] stored as
+    round(c * 255)), `list uchar int vertex_indices` per face.  Without colors the file is what it has always been."""
     v = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
     t = np.ascontiguousarray(triangles, dtype="<i4").reshape(-1, 3)
+    rgb = "" if colors is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n{rgb}"
               f"element face {t.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    if colors is None:
+        vertex_bytes = v.tobytes()
+    else:
+        vrec = np.empty(v.shape[0], dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+        vrec["p"], vrec["c"] = v, _ply_colors(colors, v.shape[0])
+        vertex_bytes = vrec.tobytes()
     rec = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     rec["n"] = 3
     rec["i"] = t
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
-        fh.write(v.tobytes())
+        fh.write(vertex_bytes)
         fh.write(rec.tobytes())
+
+
+def read_ply(path):
+    """what write_ply writes -> (vertices float32 [V,3], triangles int32 [F,3], colors uint8 [V,3] or None).  Binary little-endian,
+    vertex properties `float x y z` and optionally `uchar red green blue`, triangles as `list uchar int vertex_indices`; anything
+    else is a ValueError."""
+    with open(path, "rb") as fh:
+        blob = fh.read()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"read_ply: {path} is not a PLY file")
+    lines = [ln.split() for ln in blob[:end].decode("ascii").split("\n")[1:] if ln.strip() and not ln.startswith("comment")]
+    if not lines or lines[0] != ["format", "binary_little_endian", "1.0"]:
+        raise ValueError("read_ply: only binary_little_endian 1.0")
+    elements = []
+    for ln in lines[1:]:
+        if ln[0] == "element":
+            elements.append((ln[1], int(ln[2]), []))
+        elif ln[0] == "property" and elements:
+            elements[-1][2].append(tuple(ln[1:]))
+        else:
+            raise ValueError(f"read_ply: unexpected header line {' '.join(ln)}")
+    xyz = [("float", "x"), ("float", "y"), ("float", "z")]
+    rgb = [("uchar", "red"), ("uchar", "green"), ("uchar", "blue")]
+    if [e[0] for e in elements] != ["vertex", "face"] or elements[0][2] not in (xyz, xyz + rgb) or \
+            elements[1][2] != [("list", "uchar", "int", "vertex_indices")]:
+        raise ValueError("read_ply: expected `float x y z [uchar red green blue]` vertices and `list uchar int vertex_indices` faces")
+    n_v, n_f, colored = elements[0][1], elements[1][1], elements[0][2] == xyz + rgb
+    vtype = np.dtype([("p", "<f4", (3,))] + ([("c", "u1", (3,))] if colored else []))
+    ftype = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    body = blob[end + len(b"end_header\n"):]
+    if len(body) != n_v * vtype.itemsize + n_f * ftype.itemsize:
+        raise ValueError("read_ply: the body's size does not match the header (only triangles are read)")
+    vrec = np.frombuffer(body, dtype=vtype, count=n_v)
+    frec = np.frombuffer(body, dtype=ftype, count=n_f, offset=n_v * vtype.itemsize)
+    if n_f and (frec["n"] != 3).any():
+        raise ValueError("read_ply: a face is not a triangle")
+    return vrec["p"].astype(np.float32), frec["i"].astype(np.int32), (vrec["c"].copy() if colored else None)
 
 
 def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False):

@@ -12,9 +12,12 @@ validation/simulators/NerfSimulator.py:66-157), reduced to the part that is this
     reward    = clip(loglik(noise) - 36 * sigma_d, -72, 36) NerfSimulator.py:159-181
     one CSV row                                             MonteCarlo.py:58-116
 
-Not here (out of scope): the Blender subprocess that renders the ground-truth image and the SIFT / iNeRF state
-estimator.  Their places are taken by fixed, documented stand-ins so that the rollout still produces every column of the
-reference's CSV.  The signed distance field is opt-in (`sdf`, a collision.SignedDistanceField: built on the GPU from the NeRF's
+Not here (out of scope): the SIFT / iNeRF state estimator unless it is asked for (below).  Its place is taken by a
+fixed, documented stand-in so that the rollout still produces every column of the reference's CSV.  The ground-truth image of the
+reference's second simulator (BlenderSimulator.py:82,102: Agent.get_img, a Blender subprocess) is opt-in without Blender (`world`, a
+world.MeshWorld: a HIP ray caster looking at a triangle mesh): every step the world's frame of the true pose, quantised to uint8, is
+kept as `world_image` and, with the estimator, is the sensor image in the place of render #1 -- so the NeRF's model error enters the
+rollout.  The NeRF renders and the step's uncertainty run as without it.  The signed distance field is opt-in (`sdf`, a collision.SignedDistanceField: built on the GPU from the NeRF's
 density, or the reference's own `sdf.npy` through from_array): each interpolated state is looked up as NerfSimulator.py:131-147
 does -- the value starts at 9999, a point outside the field keeps the previous value, the first collision ends the check.
 Without it (`sdf=None`, the default) the stand-in looks the four interpolated states up in the analytic occupancy of the
@@ -232,7 +235,7 @@ class RolloutSimulator:
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
-                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None):
+                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
         sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up.
@@ -241,7 +244,11 @@ class RolloutSimulator:
         uq_method: envConfig.json's key.  The default, 'Gaussian Approximation', is the path described above.  'Bayesian Laplace
         Approximation': uncertain.uncertainty on render #2 and its rays (NerfSimulator.py:110), the row's uncertainty column holds the
         root mean variance and the reward is reward_fn_laplace.  uq_kwargs: its keywords (lr -- the reference passes filter.lrate,
-        1e-3 -- and BayesianLaplace.fit's, e.g. n_steps, likelihood_gradient, lm_solver)."""
+        1e-3 -- and BayesianLaplace.fit's, e.g. n_steps, likelihood_gradient, lm_solver).
+        world: None (the NeRF is its own world: render #1 is the sensor image), or a world.MeshWorld: the true world
+        (BlenderSimulator.py:82,102).  Every step its frame of the true pose is kept as self.world_image (uint8 [H,W,3] numpy) and,
+        with estimator_cfg, is the estimator's sensor image; shared and read-only between simulations."""
+        self.world, self.world_image = world, None
         if uq_method not in (UQ_GAUSSIAN, UQ_LAPLACE):
             raise ValueError(f"Unrecognized uncertainty quantification method {uq_method}")
         self.uq_method, self.uq_kwargs, self.last_trace = uq_method, dict(uq_kwargs or {}), None
@@ -362,12 +369,17 @@ class RolloutSimulator:
 
     def observe(self, pose):
         """NerfSimulator.py:100-110: the NeRF render of the true pose, the same frame again for the UQ -> sigma_d_opt.  With the
-        estimator, render #1's image quantised as :102-106 (* 255, astype(uint8)) becomes self.sensor_image."""
+        estimator, render #1's image quantised as :102-106 (* 255, astype(uint8)) becomes self.sensor_image -- or, with a world, the
+        world's frame of the pose (BlenderSimulator.py:82,102)."""
         with torch.no_grad():
+            if self.world is not None:
+                self.world_image = self.world.render(pose, self.intrinsics, self.H, self.W)["image_u8"].cpu().numpy()
+                if self.estimator is not None:
+                    self.sensor_image = self.world_image
             out = None
             for i in range(self.renders_per_step):
                 out = self.render(pose)
-                if i == 0 and self.estimator is not None:
+                if i == 0 and self.estimator is not None and self.world is None:
                     img = torch.squeeze(out["image"]).float().cpu().numpy().reshape((self.H, self.W, -1))
                     img *= 255
                     self.sensor_image = img.astype(np.uint8)
@@ -486,13 +498,14 @@ def gather_rows(results, n_simulations, steps, width, world_size=1, group=None, 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
                 render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None,
-                uq_method=UQ_GAUSSIAN, uq_kwargs=None):
+                uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
     a collision.SignedDistanceField every simulation's collision check looks up.  estimator_cfg: None, or nav.estimator_config()'s
     dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps).
-    uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged)."""
+    uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged).  world: None, or the
+    world.MeshWorld every simulation's sensor looks at (RolloutSimulator's `world`; shared, read-only)."""
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -502,7 +515,7 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
                                    planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg,
-                                   uq_method=uq_method, uq_kwargs=uq_kwargs)
+                                   uq_method=uq_method, uq_kwargs=uq_kwargs, world=world)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
@@ -517,9 +530,18 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
 STRESS_MONTE_CARLO, STRESS_CEM = "Monte Carlo", "Cross Entropy Method"     # envConfig.json's stress_test
 
 
-def run_validation(stress_test, *args, **kwargs):
+SIM_NERF, SIM_BLENDER = "NerfSimulator", "BlenderSimulator"               # envConfig.json's simulator
+
+
+def run_validation(stress_test, *args, simulator=SIM_NERF, **kwargs):
     """validate.py:23-49: envConfig.json's `stress_test` picks the loop -- 'Monte Carlo' -> run_rollout(*args, **kwargs),
-    'Cross Entropy Method' -> cem.run_cem(*args, **kwargs); anything else is an error (the reference prints and exits)"""
+    'Cross Entropy Method' -> cem.run_cem(*args, **kwargs); anything else is an error (the reference prints and exits).  `simulator`
+    is envConfig.json's key of that name: 'NerfSimulator' (the default: the NeRF is its own world) or 'BlenderSimulator' (the sensor
+    looks at the true world: needs world=, a world.MeshWorld); anything else is an error."""
+    if simulator not in (SIM_NERF, SIM_BLENDER):
+        raise ValueError(f"Unrecognized simulator {simulator}")
+    if simulator == SIM_BLENDER and kwargs.get("world") is None:
+        raise ValueError("run_validation: simulator 'BlenderSimulator' needs world= (a world.MeshWorld: the true world its camera looks at)")
     if stress_test == STRESS_MONTE_CARLO:
         return run_rollout(*args, **kwargs)
     if stress_test == STRESS_CEM:

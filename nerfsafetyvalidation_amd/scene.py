@@ -95,6 +95,31 @@ def henge_occupancy(x, y, z):
     return occ
 
 
+def henge_colors(x, y, z):
+    """deterministic vertex colours [n,3] float32 in [0, 1], a fixed function of position: ground, outer stones, the lintel ring, the
+    inner uprights and their tops each get a base colour, modulated by a smooth pattern so that a frame has texture"""
+    x, y, z = [np.asarray(a, np.float64) for a in (x, y, z)]
+    r = np.sqrt(x * x + z * z)
+    ground, outer = y < -0.295, r > 0.45
+    base = np.where(ground[:, None], [0.36, 0.46, 0.26],
+                    np.where(outer[:, None], np.where((y >= 0.045)[:, None], [0.78, 0.72, 0.60], [0.55, 0.55, 0.62]),
+                             np.where((y >= 0.145)[:, None], [0.82, 0.64, 0.48], [0.62, 0.50, 0.44])))
+    pattern = 0.82 + 0.18 * np.sin(37.0 * x + 11.0 * y) * np.sin(29.0 * z - 17.0 * y)
+    return np.clip(base * pattern[:, None], 0.0, 1.0).astype(np.float32)
+
+
+def henge_mesh(resolution=64):
+    """The synthetic scene as a triangle mesh in the NeRF's axes -> (vertices float32 [V,3], faces int32 [F,3], colors float32 [V,3]):
+    mesh.isosurface (numpy path) of henge_occupancy sampled on a resolution^3 lattice over [-1, 1]^3 at threshold 0.5, coloured by
+    henge_colors.  The world world.MeshWorld looks at; with mesh.mesh_to_world its vertices feed collision.occupancy_from_points."""
+    from .mesh import isosurface
+    axis = np.linspace(-1.0, 1.0, resolution)
+    occ = henge_occupancy(axis[:, None, None], axis[None, :, None], axis[None, None, :]).astype(np.float32)
+    v, f = isosurface(occ, 0.5)
+    vertices = (v / np.float32(resolution - 1) * np.float32(2.0) - np.float32(1.0)).astype(np.float32)
+    return vertices, f, henge_colors(vertices[:, 0], vertices[:, 1], vertices[:, 2])
+
+
 def density_grid(bound=2, grid_size=128, occupied_value=1.0):
     """[cascade, grid_size^3] float32 density grid in Morton order (nerf/renderer.py:453-544 layout)."""
     cascade = 1 + math.ceil(math.log2(bound))

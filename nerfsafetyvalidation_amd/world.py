@@ -1,0 +1,368 @@
+"""The ground-truth world: a camera that looks at a triangle mesh, not at the NeRF (DESIGN.md "The ground-truth world").
+
+The reference's second simulator (validation/simulators/BlenderSimulator.py:82,102) hands the estimator an image of the TRUE world
+(Agent.get_img, a Blender subprocess); the NeRF is only the drone's model of it.  MeshWorld is that camera without Blender: rays from
+nerf.utils.get_rays (so a world frame and a NeRF frame of one pose are pixel-aligned) cast against a mesh, shaded by a headlight.
+
+    MeshWorld(vertices, faces, colors=None, resolution=None, frame="nerf")
+        .cast(rays_o, rays_d, t_min=0.0, t_max=inf, frame_width=None)  -> {"t", "prim", "u", "v"}
+        .shade(rays_d, hit, bg_color=1.0, ambient=0.3)                 -> (image float32 [...,3], image_u8 uint8 [...,3])
+        .render(pose, intrinsics, H, W, bg_color=1.0)                  -> {"image", "image_u8", "depth", "prim"}
+
+A mesh on a HIP device goes through csrc/raycast.hip (a uniform grid, one lane per ray) on the current stream; a CPU tensor or a numpy
+array through numpy: brute force over all triangles, chunked -- the package's CPU implementation, as mesh.isosurface has one.
+
+The hit rule is the specification; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
+    per triangle v0, e1 = v1 - v0, e2 = v2 - v0;  p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det, s = o - v0,
+    u = (s . p) * inv, q = s x e1, v = (d . q) * inv, t = (e2 . q) * inv;  a . b = (ax bx + ay by) + az bz,
+    (a x b).x = ay bz - az by (and cyclic);  accept iff u >= 0 and v >= 0 and u + v <= 1 and t_min < t < t_max (NaN fails);
+    the closest hit is the smallest t, equal t goes to the lowest triangle index; a ray with a non-finite component or a zero
+    direction misses.  A miss is t = +inf, prim = -1, u = v = 0.
+The grid only chooses which triangles a ray is tested against: no result depends on it, nor on frame_width.
+
+The grid rule (grid_params): the vertices' bounding box padded by ext / 128 + S / 1024 on every side (ext its largest extent, S the
+largest of ext and the largest coordinate magnitude); `resolution=None` picks n_a = round(size_a * cbrt(4 F / volume)) cells on axis
+a, clamped to 1..256 -- about four cells per triangle, cells near cubic; a triangle's bounding box is grown by
+max(cell / 32, S / 4096) on every side before it is binned, and rays whose origin lies beyond 64 S walk no grid (all triangles).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .collision import PLANNER_ROT, to_nerf
+
+MAX_CELLS_PER_AXIS = 256
+PAD_EXTENT, PAD_SCALE = 2.0 ** -7, 2.0 ** -10       # padding of the grid box: ext * PAD_EXTENT + S * PAD_SCALE
+GROW_CELL, GROW_SCALE = 2.0 ** -5, 2.0 ** -12       # growth of a triangle's box at binning: max(cell * GROW_CELL, S * GROW_SCALE)
+REACH = 64.0                                        # rays starting beyond REACH * S are tested against every triangle
+CELLS_PER_TRIANGLE = 4.0                            # the automatic resolution's target
+DEFAULT_AMBIENT = 0.3
+GREY = 0.5
+_CHUNK_PAIRS = 1 << 20                              # (ray, triangle) pairs per chunk of the numpy path
+
+_f32 = np.float32
+
+
+# ------------------------------------------------------------------------------------------------------------- the grid (host)
+def grid_params(vmin, vmax, n_faces, resolution=None):
+    """the grid of a mesh with bounding box vmin..vmax (float32 [3]) and n_faces triangles -> dict of float32 arrays lo, cell,
+    inv_cell, grow [3], float32 reach, int n [3].  All of it float32 host arithmetic, shared by the kernels and the numpy binning."""
+    vmin, vmax = np.asarray(vmin, _f32), np.asarray(vmax, _f32)
+    ext = _f32((vmax - vmin).max())
+    S = _f32(max(ext, np.abs(vmin).max(), np.abs(vmax).max()))
+    if not S > 0:
+        S = _f32(1.0)
+    pad = _f32(ext * _f32(PAD_EXTENT) + S * _f32(PAD_SCALE))
+    lo = (vmin - pad).astype(_f32)
+    size = ((vmax + pad) - lo).astype(_f32)
+    if resolution is None:
+        k = np.cbrt(CELLS_PER_TRIANGLE * max(1, int(n_faces)) / float(np.prod(size.astype(np.float64))))
+        n = np.clip(np.rint(size.astype(np.float64) * k), 1, MAX_CELLS_PER_AXIS).astype(np.int64)
+    else:
+        n = np.asarray(resolution, dtype=np.int64).reshape(-1)
+        if n.size == 1:
+            n = np.repeat(n, 3)
+        if n.shape != (3,) or (n < 1).any():
+            raise ValueError(f"MeshWorld: resolution is one or three positive cell counts (got {resolution})")
+        if (n > MAX_CELLS_PER_AXIS).any():
+            raise ValueError(f"MeshWorld: at most {MAX_CELLS_PER_AXIS} cells per axis (got {tuple(int(v) for v in n)})")
+    cell = (size / n.astype(_f32)).astype(_f32)
+    inv_cell = (_f32(1.0) / cell).astype(_f32)
+    grow = np.maximum(cell * _f32(GROW_CELL), S * _f32(GROW_SCALE)).astype(_f32)
+    return {"lo": lo, "cell": cell, "inv_cell": inv_cell, "grow": grow, "reach": _f32(_f32(REACH) * S), "n": n}
+
+
+def _grid_struct(g):
+    s = _lib.RaycastGrid()
+    for a in range(3):
+        s.lo[a], s.cell[a], s.inv_cell[a], s.grow[a], s.n[a] = float(g["lo"][a]), float(g["cell"][a]), float(g["inv_cell"][a]), float(g["grow"][a]), int(g["n"][a])
+    s.reach = float(g["reach"])
+    return s
+
+
+def pack_triangles(vertices, faces):
+    """vertices float32 [V,3], faces integer [F,3] (numpy or tensors of one device) -> tri_data float32 [F,12]: the rows (v0, 0),
+    (e1 = v1 - v0, 0), (e2 = v2 - v0, 0), each difference one float32 subtraction"""
+    xp = torch if isinstance(vertices, torch.Tensor) else np
+    idx = faces.long() if xp is torch else faces.astype(np.int64)
+    v0, v1, v2 = vertices[idx[:, 0]], vertices[idx[:, 1]], vertices[idx[:, 2]]
+    if xp is torch:
+        out = torch.zeros(idx.shape[0], 12, dtype=torch.float32, device=vertices.device)
+    else:
+        out = np.zeros((idx.shape[0], 12), dtype=_f32)
+    out[:, 0:3], out[:, 4:7], out[:, 8:11] = v0, v1 - v0, v2 - v0
+    return out
+
+
+def triangle_cells(tri_data, g):
+    """numpy: the inclusive cell range of every triangle's grown bounding box -> (c0, c1) int64 [F,3]; k_bin_count's arithmetic"""
+    t = np.asarray(tri_data, _f32)
+    v0, a, b = t[:, 0:3], t[:, 0:3] + t[:, 4:7], t[:, 0:3] + t[:, 8:11]
+    lo, hi = np.minimum(v0, np.minimum(a, b)), np.maximum(v0, np.maximum(a, b))
+    top = (g["n"] - 1).astype(_f32)
+    with np.errstate(all="ignore"):
+        c0 = np.floor(((lo - g["grow"]) - g["lo"]) * g["inv_cell"])
+        c1 = np.floor(((hi + g["grow"]) - g["lo"]) * g["inv_cell"])
+    c0 = np.minimum(np.fmax(c0, _f32(0)), top).astype(np.int64)
+    c1 = np.maximum(np.minimum(np.fmax(c1, _f32(0)), top).astype(np.int64), c0)
+    return c0, c1
+
+
+def bin_triangles_numpy(tri_data, g):
+    """the kernels' binning in numpy -> (cell_start int32 [cells + 1], pair_tri int32 [P]): cell c's triangles are
+    pair_tri[cell_start[c]:cell_start[c + 1]], ascending; cells in C order"""
+    c0, c1 = triangle_cells(tri_data, g)
+    span = c1 - c0 + 1
+    counts = span.prod(1)
+    P = int(counts.sum())
+    if P >= 2 ** 31:
+        raise ValueError(f"MeshWorld: {P} (cell, triangle) pairs do not fit int32 indices; use a coarser grid")
+    tri = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    j = np.arange(P, dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts)
+    sy, sz = span[tri, 1], span[tri, 2]
+    x, y, z = c0[tri, 0] + j // (sy * sz), c0[tri, 1] + (j // sz) % sy, c0[tri, 2] + j % sz
+    cell = (x * g["n"][1] + y) * g["n"][2] + z
+    order = np.argsort(cell, kind="stable")
+    n_cells = int(np.prod(g["n"]))
+    cell_start = np.searchsorted(cell[order], np.arange(n_cells + 1)).astype(np.int32)
+    return cell_start, tri[order].astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------------------- the numpy path
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def hit_terms(o, d, tri_data, dtype=_f32):
+    """the hit rule's det, u, v, t for every (ray, triangle): o, d [R,3], tri_data [F,12] -> four [R,F] arrays of `dtype` (float32:
+    the rule itself; float64: the same formulas, for error measurements)"""
+    o, d, T = np.asarray(o, dtype), np.asarray(d, dtype), np.asarray(tri_data, dtype)
+    oc, dc = [o[:, None, k] for k in range(3)], [d[:, None, k] for k in range(3)]
+    v0, e1, e2 = [T[None, :, k] for k in range(0, 3)], [T[None, :, k] for k in range(4, 7)], [T[None, :, k] for k in range(8, 11)]
+    with np.errstate(all="ignore"):
+        p = _cross(dc, e2)
+        det = _dot(e1, p)
+        inv = dtype(1.0) / det
+        s = [oc[k] - v0[k] for k in range(3)]
+        u = _dot(s, p) * inv
+        q = _cross(s, e1)
+        v = _dot(dc, q) * inv
+        t = _dot(e2, q) * inv
+    return det, u, v, t
+
+
+def cast_numpy(o, d, tri_data, t_min=0.0, t_max=np.inf):
+    """brute force by the hit rule, float32: o, d [N,3] -> {"t" float32 (+inf on a miss), "prim" int32 (-1), "u", "v" float32 (0)}"""
+    o, d, tri_data = np.ascontiguousarray(o, _f32).reshape(-1, 3), np.ascontiguousarray(d, _f32).reshape(-1, 3), np.asarray(tri_data, _f32)
+    N, F = o.shape[0], tri_data.shape[0]
+    t_min, t_max = _f32(t_min), _f32(t_max)
+    out = {"t": np.full(N, np.inf, _f32), "prim": np.full(N, -1, np.int32), "u": np.zeros(N, _f32), "v": np.zeros(N, _f32)}
+    valid = np.isfinite(o).all(1) & np.isfinite(d).all(1) & (d != 0).any(1)
+    chunk = max(1, _CHUNK_PAIRS // max(1, F))
+    for i0 in range(0, N, chunk):
+        sl = slice(i0, min(N, i0 + chunk))
+        det, u, v, t = hit_terms(o[sl], d[sl], tri_data)
+        with np.errstate(all="ignore"):
+            ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= _f32(1.0)) & (t > t_min) & (t < t_max) & valid[sl, None]
+        tm = np.where(ok, t, _f32(np.inf))
+        best = tm.min(1)
+        hit = ok.any(1)
+        prim = np.argmax(ok & (tm == best[:, None]), 1)            # the lowest index among the closest
+        rows = np.arange(prim.shape[0])
+        out["t"][sl] = np.where(hit, best, _f32(np.inf))
+        out["prim"][sl] = np.where(hit, prim, -1)
+        out["u"][sl] = np.where(hit, u[rows, prim], _f32(0))
+        out["v"][sl] = np.where(hit, v[rows, prim], _f32(0))
+    return out
+
+
+def shade_numpy(d, prim, u, v, tri_data, faces, colors, bg, ambient):
+    """k_raycast_shade in numpy float32 -> (image float32 [N,3], image_u8 uint8 [N,3])"""
+    d, T = np.asarray(d, _f32).reshape(-1, 3), np.asarray(tri_data, _f32)
+    prim = np.asarray(prim).reshape(-1)
+    hit = prim >= 0
+    f = np.where(hit, prim, 0)
+    u, v = np.asarray(u, _f32).reshape(-1), np.asarray(v, _f32).reshape(-1)
+    w = (_f32(1.0) - u) - v
+    if colors is None:
+        col = np.full((d.shape[0], 3), GREY, _f32)
+    else:
+        c = np.asarray(colors, _f32)[np.asarray(faces)[f].astype(np.int64)]           # [N, 3 corners, 3]
+        col = (w[:, None] * c[:, 0] + u[:, None] * c[:, 1]) + v[:, None] * c[:, 2]
+    e1, e2 = [T[f, k] for k in range(4, 7)], [T[f, k] for k in range(8, 11)]
+    n, dc = _cross(e1, e2), [d[:, k] for k in range(3)]
+    with np.errstate(all="ignore"):
+        length = np.sqrt(_dot(n, n)) * np.sqrt(_dot(dc, dc))
+        cosine = np.where(length > 0, np.minimum(np.abs(_dot(n, dc)) / length, _f32(1.0)), _f32(0)).astype(_f32)
+        shade = _f32(ambient) + (_f32(1.0) - _f32(ambient)) * cosine
+        rgb = np.minimum(np.maximum(col * shade[:, None], _f32(0)), _f32(1.0))
+    image = np.where(hit[:, None], rgb, np.asarray(bg, _f32)[None, :]).astype(_f32)
+    return image, (np.clip(image, 0, 1) * _f32(255.0)).astype(np.uint8)
+
+
+def _bg3(bg_color):
+    bg = np.asarray(bg_color.detach().cpu().numpy() if isinstance(bg_color, torch.Tensor) else bg_color, _f32).reshape(-1)
+    if bg.size == 1:
+        bg = np.repeat(bg, 3)
+    if bg.shape != (3,):
+        raise ValueError("bg_color is a scalar or three values")
+    return bg
+
+
+# ------------------------------------------------------------------------------------------------------------- the world
+class MeshWorld:
+    """A triangle mesh as the world a camera looks at.  vertices [V,3], faces integer [F,3], colors [V,3] (float in [0, 1], or uint8)
+    or None (mid-grey): tensors (the mesh lives on their device) or numpy arrays (the CPU path).  frame="world": the vertices are in
+    the planner's world frame and are turned into the NeRF's axes first (collision.to_nerf with PLANNER_ROT).
+    Attributes: device, n_vertices, n_faces, grid (grid_params' dict), dims (nx, ny, nz), pairs, mean_pairs_per_cell, and the
+    read-only tables tri_data, cell_start, pair_tri.  Shared freely between threads and streams: nothing is written after __init__."""
+
+    def __init__(self, vertices, faces, colors=None, resolution=None, frame="nerf"):
+        if frame not in ("nerf", "world"):
+            raise ValueError(f"MeshWorld: frame is 'nerf' or 'world' (got {frame!r})")
+        v = torch.as_tensor(np.asarray(vertices) if not isinstance(vertices, torch.Tensor) else vertices.detach())
+        f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces.detach()).to(v.device)
+        if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError(f"MeshWorld: vertices [V,3] and faces [F,3] (got {tuple(v.shape)} and {tuple(f.shape)})")
+        if v.shape[0] == 0 or f.shape[0] == 0:
+            raise ValueError("MeshWorld: the mesh is empty")
+        if f.shape[0] >= 2 ** 31 or v.shape[0] >= 2 ** 31:
+            raise ValueError("MeshWorld: V and F must be < 2^31")
+        if f.dtype.is_floating_point or f.dtype == torch.bool:
+            raise ValueError("MeshWorld: faces are integer vertex indices")
+        v = v.to(torch.float32)
+        if frame == "world":
+            v = to_nerf(v, PLANNER_ROT)
+        v = v.contiguous()
+        self.device = v.device
+        f_lo, f_hi = int(f.min()), int(f.max())
+        if f_lo < 0 or f_hi >= v.shape[0]:
+            raise ValueError(f"MeshWorld: faces index outside the {v.shape[0]} vertices ({f_lo} .. {f_hi})")
+        lo_hi = torch.stack([v.min(0).values, v.max(0).values]).cpu().numpy()
+        if not np.isfinite(lo_hi).all():
+            raise ValueError("MeshWorld: a vertex is not finite")
+        self.vertices, self.faces = v, f.to(torch.int32).contiguous()
+        self.n_vertices, self.n_faces = int(v.shape[0]), int(f.shape[0])
+        if colors is not None:
+            c = torch.as_tensor(np.asarray(colors) if not isinstance(colors, torch.Tensor) else colors.detach()).to(v.device)
+            if tuple(c.shape) != (self.n_vertices, 3):
+                raise ValueError(f"MeshWorld: colors [V,3] (got {tuple(c.shape)})")
+            colors = (c.to(torch.float32) / 255.0 if c.dtype == torch.uint8 else c.to(torch.float32)).contiguous()
+        self.colors = colors
+        self.grid = grid_params(lo_hi[0], lo_hi[1], self.n_faces, resolution)
+        self.dims = tuple(int(n) for n in self.grid["n"])
+        self.tri_data = pack_triangles(self.vertices, self.faces)
+        if self.device.type == "cuda":
+            self._build_hip()
+        else:
+            cs, pt = bin_triangles_numpy(self.tri_data.numpy(), self.grid)
+            self.cell_start, self.pair_tri = torch.from_numpy(cs), torch.from_numpy(pt)
+        self.pairs = int(self.pair_tri.shape[0])
+        self.mean_pairs_per_cell = self.pairs / float(np.prod(self.dims))
+
+    def _build_hip(self):
+        lib, F = _lib.lib(), self.n_faces
+        self._grid_c = _grid_struct(self.grid)
+        n_cells = int(np.prod(self.dims))
+        with torch.cuda.device(self.device):
+            counts = torch.empty(F, dtype=torch.int32, device=self.device)
+            _lib.check(lib.ngp_raycast_bin_count(_lib.ptr(self.tri_data), F, ctypes.byref(self._grid_c), _lib.ptr(counts), _lib.stream()),
+                       "raycast_bin_count")
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            P = int(ends[-1])
+            if P >= 2 ** 31:
+                raise ValueError(f"MeshWorld: {P} (cell, triangle) pairs do not fit int32 indices; use a coarser grid")
+            offsets = (ends - counts).contiguous()
+            pair_cell = torch.empty(P, dtype=torch.int32, device=self.device)
+            pair_tri = torch.empty(P, dtype=torch.int32, device=self.device)
+            _lib.check(lib.ngp_raycast_bin_emit(_lib.ptr(self.tri_data), F, ctypes.byref(self._grid_c), _lib.ptr(offsets), P, _lib.ptr(pair_cell),
+                                                _lib.ptr(pair_tri), _lib.stream()), "raycast_bin_emit")
+            cells, order = torch.sort(pair_cell, stable=True)
+            self.pair_tri = pair_tri[order].contiguous()
+            self.cell_start = torch.searchsorted(cells, torch.arange(n_cells + 1, dtype=torch.int32, device=self.device)).to(torch.int32).contiguous()
+
+    # ---- casting
+    def _rays(self, rays_o, rays_d):
+        tensors = isinstance(rays_o, torch.Tensor)
+        o = torch.as_tensor(rays_o).detach().to(self.device, torch.float32)
+        d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
+        if o.shape != d.shape or o.dim() < 1 or o.shape[-1] != 3:
+            raise ValueError(f"MeshWorld.cast: rays_o and rays_d [..., 3] of one shape (got {tuple(o.shape)} and {tuple(d.shape)})")
+        if o.numel() // 3 >= 2 ** 31:
+            raise ValueError("MeshWorld.cast: N must be < 2^31")
+        return o.reshape(-1, 3).contiguous(), d.reshape(-1, 3).contiguous(), tuple(o.shape[:-1]), tensors
+
+    def cast(self, rays_o, rays_d, t_min=0.0, t_max=float("inf"), frame_width=None):
+        """rays [..., 3] -> {"t" float32 (+inf on a miss), "prim" int32 (-1), "u", "v" float32} of shape [...], on the world's device
+        (numpy arrays for numpy rays on a CPU world).  frame_width: the rays are whole row-major frames of that width -- a
+        scheduling hint of the HIP path (a wave takes an 8 x 8 pixel tile); the result does not depend on it."""
+        t_min, t_max = float(t_min), float(t_max)
+        if t_min != t_min or t_max != t_max:
+            raise ValueError("MeshWorld.cast: t_min / t_max is NaN")
+        o, d, shape, tensors = self._rays(rays_o, rays_d)
+        N = o.shape[0]
+        if frame_width is not None and (int(frame_width) < 1 or N % int(frame_width)):
+            raise ValueError(f"MeshWorld.cast: frame_width {frame_width} does not divide the {N} rays")
+        if self.device.type != "cuda":
+            out = cast_numpy(o.numpy(), d.numpy(), self.tri_data.numpy(), t_min, t_max)
+            out = {k: a.reshape(shape) for k, a in out.items()}
+            return {k: torch.from_numpy(a) for k, a in out.items()} if tensors else out
+        out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+               "u": torch.empty(N, dtype=torch.float32, device=self.device), "v": torch.empty(N, dtype=torch.float32, device=self.device)}
+        if N:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().ngp_raycast(_lib.ptr(o), _lib.ptr(d), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
+                                                  _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_data), self.n_faces, t_min, t_max,
+                                                  int(frame_width or 0), _lib.ptr(out["t"]), _lib.ptr(out["prim"]), _lib.ptr(out["u"]),
+                                                  _lib.ptr(out["v"]), _lib.stream()), "raycast")
+        return {k: a.reshape(shape) for k, a in out.items()}
+
+    def shade(self, rays_d, hit, bg_color=1.0, ambient=DEFAULT_AMBIENT):
+        """a cast's result -> (image float32 [..., 3] in [0, 1], image_u8 uint8 [..., 3] = (uint8)(image * 255), Agent.get_img's
+        quantisation): the barycentric blend of the vertex colours (mid-grey without) times ambient + (1 - ambient) |n . d| / (|n| |d|),
+        a two-sided headlight; bg_color (a scalar or three values; white, the reference's white_bg) on a miss"""
+        if not 0.0 <= float(ambient) <= 1.0:
+            raise ValueError("MeshWorld.shade: ambient must be in [0, 1]")
+        bg = _bg3(bg_color)
+        tensors = isinstance(rays_d, torch.Tensor)
+        d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
+        shape = tuple(d.shape[:-1])
+        d = d.reshape(-1, 3).contiguous()
+        N = d.shape[0]
+        prim, u, v = [torch.as_tensor(hit[k]).to(self.device).reshape(-1).contiguous() for k in ("prim", "u", "v")]
+        if prim.shape[0] != N:
+            raise ValueError("MeshWorld.shade: the hit record is not of these rays")
+        if self.device.type != "cuda":
+            image, u8 = shade_numpy(d.numpy(), prim.numpy(), u.numpy(), v.numpy(), self.tri_data.numpy(), self.faces.numpy(),
+                                    None if self.colors is None else self.colors.numpy(), bg, ambient)
+            image, u8 = image.reshape(shape + (3,)), u8.reshape(shape + (3,))
+            return (torch.from_numpy(image), torch.from_numpy(u8)) if tensors else (image, u8)
+        image = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+        u8 = torch.empty(N, 3, dtype=torch.uint8, device=self.device)
+        if N:
+            bg_c = (ctypes.c_float * 3)(*[float(b) for b in bg])
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().ngp_raycast_shade(_lib.ptr(d), _lib.ptr(prim.to(torch.int32)), _lib.ptr(u.to(torch.float32)),
+                                                        _lib.ptr(v.to(torch.float32)), N, _lib.ptr(self.tri_data), _lib.ptr(self.faces), self.n_faces,
+                                                        _lib.ptr(self.colors), self.n_vertices, float(ambient), bg_c, _lib.ptr(image), _lib.ptr(u8),
+                                                        _lib.stream()), "raycast_shade")
+        return image.reshape(shape + (3,)), u8.reshape(shape + (3,))
+
+    def render(self, pose, intrinsics, H, W, bg_color=1.0, ambient=DEFAULT_AMBIENT):
+        """pose [4,4] cam2world (this package's camera convention) -> {"image" float32 [H,W,3], "image_u8" uint8 [H,W,3], "depth"
+        float32 [H,W] = t * |d| (+inf on a miss), "prim" int32 [H,W]} as tensors on the world's device.  The rays are
+        nerf.utils.get_rays' of the pose: pixel-aligned with the NeRF's frame of the same pose."""
+        from .nerf.utils import get_rays
+        pose = torch.as_tensor(pose).detach().to(self.device, torch.float32).reshape(1, 4, 4)
+        rays = get_rays(pose, intrinsics, H, W)
+        o, d = rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3)
+        hit = self.cast(o, d, frame_width=W)
+        image, u8 = self.shade(d, hit, bg_color, ambient)
+        depth = hit["t"] * torch.linalg.vector_norm(d, dim=-1)
+        return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": hit["prim"].reshape(H, W)}

@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Render frames of a triangle mesh (world.MeshWorld) into a blender-format folder that NeRFDataset / main_nerf read, so that one mesh
+can be the world a NeRF is trained on, validated against (rollout's `world`) and collision-checked against:
+
+    python scripts/make_mesh_dataset.py OUT [--size 200] [--train 100] [--val 2] [--test 4] [--ply PATH] [--device cuda:0]
+
+The mesh is scene.henge_mesh() (the synthetic scene, in the NeRF's axes) or, with --ply, any mesh mesh.write_ply wrote (vertex colours
+when it has them).  The cameras are scene.orbit_poses.  The frames are RGBA: the headlight-shaded colour, alpha 1 on a hit and 0 on a
+miss.  Read it back with `--scale 1 --offset 0 0 0 --bound 2`.  --device cpu renders through the package's numpy path."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from nerfsafetyvalidation_amd.mesh import read_ply
+from nerfsafetyvalidation_amd.nerf.provider import write_blender_dataset
+from nerfsafetyvalidation_amd.scene import CAMERA_ANGLE_X, henge_mesh, intrinsics, orbit_poses
+from nerfsafetyvalidation_amd.world import MeshWorld
+
+
+def render_frames(world, poses, size):
+    """-> uint8 [n, size, size, 4]"""
+    K = intrinsics(size, size)
+    frames = []
+    for pose in poses:
+        out = world.render(torch.from_numpy(pose), K, size, size, bg_color=0.0)
+        alpha = (out["prim"] >= 0).to(torch.uint8) * 255
+        frames.append(torch.cat([out["image_u8"], alpha[..., None]], -1).cpu().numpy())
+    return np.stack(frames)
+
+
+def make(out, size=200, n_train=100, n_val=2, n_test=4, ply=None, device="cuda:0", resolution=64):
+    dev = torch.device(device)
+    vertices, faces, colors = read_ply(ply) if ply else henge_mesh(resolution)
+    world = MeshWorld(torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), None if colors is None else torch.from_numpy(colors).to(dev))
+    poses = orbit_poses()
+    n_all = len(poses)
+    train = [int(v) for v in np.linspace(0, n_all, n_train, endpoint=False)]
+    rest = [v for v in range(n_all) if v not in set(train)] or list(range(n_all))
+    pick = lambda n, shift: [rest[(shift + i * max(1, len(rest) // max(1, n))) % len(rest)] for i in range(n)]
+    for split, views in (("train", train), ("val", pick(n_val, 0)), ("test", pick(n_test, 1))):
+        write_blender_dataset(out, poses[views], render_frames(world, poses[views], size), CAMERA_ANGLE_X, split)
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--size", type=int, default=200)
+    ap.add_argument("--train", type=int, default=100)
+    ap.add_argument("--val", type=int, default=2)
+    ap.add_argument("--test", type=int, default=4)
+    ap.add_argument("--ply", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    make(a.out, a.size, a.train, a.val, a.test, a.ply, a.device)
+    print(f"wrote {a.train} train / {a.val} val / {a.test} test views of {a.size}x{a.size} to {a.out}")
