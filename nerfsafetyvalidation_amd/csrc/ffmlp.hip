@@ -330,15 +330,23 @@ static void launch_ffmlp(const uint16_t* in, const uint16_t* w, uint32_t B, uint
                                                (_Float16*)fwd, (_Float16*)out);
 }
 
+// the checks of the shape that the forward and the backward calls share (`hint`: what the forward calls add about a ragged batch)
+static int check_ffmlp_shape(const char* what, const char* hint, uint32_t B, uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers) {
+    NGP_REQUIRE(B % 16 == 0, "%s: batch size must be a multiple of 16 (got %u)%s", what, B, hint);
+    NGP_REQUIRE(input_dim > 0 && input_dim % 16 == 0, "FFMLP input_dim should be 16 * m (m > 0), but got %u", input_dim);
+    NGP_REQUIRE(output_dim == 16, "FFMLP current only supports (padded) output dim == 16, but got %u", output_dim);
+    NGP_REQUIRE(num_layers >= 2, "FFMLP num_layers should be larger than 2 (3 matmuls), but got %u", num_layers);
+    NGP_REQUIRE(hidden_dim == 16 || hidden_dim == 32 || hidden_dim == 64 || hidden_dim == 128 || hidden_dim == 256,
+                "FFMLP only support hidden_dim in [16, 32, 64, 128, 256], but got %u", hidden_dim);  // ffmlp.cu:658
+    return NGP_OK;
+}
+
 static int ffmlp_run(const uint16_t* inputs, const uint16_t* weights, uint32_t B, uint32_t input_dim, uint32_t output_dim,
                      uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, uint32_t output_activation, uint16_t* fwd,
                      uint16_t* outputs, hipStream_t s, const char* what, bool planes = false) {
     if (B == 0) return NGP_OK;
     NGP_REQUIRE(inputs && weights && outputs, "%s: null pointer", what);
-    NGP_REQUIRE(B % 16 == 0, "%s: batch size must be a multiple of 16 (got %u); the FFMLP wrapper pads a ragged tail to 16", what, B);
-    NGP_REQUIRE(input_dim > 0 && input_dim % 16 == 0, "FFMLP input_dim should be 16 * m (m > 0), but got %u", input_dim);
-    NGP_REQUIRE(output_dim == 16, "FFMLP current only supports (padded) output dim == 16, but got %u", output_dim);
-    NGP_REQUIRE(num_layers >= 2, "FFMLP num_layers should be larger than 2 (3 matmuls), but got %u", num_layers);
+    if (int rc = check_ffmlp_shape(what, "; the FFMLP wrapper pads a ragged tail to 16", B, input_dim, output_dim, hidden_dim, num_layers)) return rc;
     ProfScope prof("ffmlp_forward", s, B);
     if (planes) {
         NGP_REQUIRE(hidden_dim == 64 && input_dim % 32 == 0 && ffmlp_lds_halves(input_dim, 64, num_layers) * sizeof(_Float16) <= kFfmlpLdsMax,
@@ -361,10 +369,7 @@ static int ffmlp_run(const uint16_t* inputs, const uint16_t* weights, uint32_t B
         case 32: launch_ffmlp<2>(inputs, weights, B, input_dim, num_layers, activation, output_activation, fwd, outputs, s); break;
         case 64: launch_ffmlp<4>(inputs, weights, B, input_dim, num_layers, activation, output_activation, fwd, outputs, s); break;
         case 128: launch_ffmlp<8>(inputs, weights, B, input_dim, num_layers, activation, output_activation, fwd, outputs, s); break;
-        case 256: launch_ffmlp<16>(inputs, weights, B, input_dim, num_layers, activation, output_activation, fwd, outputs, s); break;
-        default:
-            set_error("FFMLP only support hidden_dim in [16, 32, 64, 128, 256], but got %u", hidden_dim);  // ffmlp.cu:658
-            return NGP_EINVAL;
+        default: launch_ffmlp<16>(inputs, weights, B, input_dim, num_layers, activation, output_activation, fwd, outputs, s); break;
     }
     return check_launch(what);
 }
@@ -839,18 +844,25 @@ static uint32_t fused_bwd_blocks(uint32_t B, uint32_t in_dim, uint32_t NL) {
 static bool fused_bwd_applies(uint32_t in_dim, uint32_t hidden_dim, uint32_t num_layers) {
     return hidden_dim == 64 && num_layers >= 2 && num_layers <= 4 && in_dim <= 64;
 }
-template <int NL, bool PLANES = false>
-static void launch_bwd_fused(const uint16_t* grad, const uint16_t* inputs, const uint16_t* w, const uint16_t* fwd, uint32_t B, uint32_t in_dim,
-                             uint32_t act, uint16_t* bwd, uint16_t* gi, float* ws, uint32_t P, hipStream_t s) {
-    const size_t lds = fused_bwd_lds_bytes(in_dim, NL);
-    const uint32_t n_groups = div_up(B / 16, 4 * kFusedTPW);
-    typedef void (*Kern)(const _Float16*, const _Float16*, const _Float16*, const _Float16*, uint32_t, uint32_t, uint32_t, _Float16*, _Float16*, uint32_t,
-                         float*, uint32_t);
-    const Kern kern = fwd ? (act == 0 ? k_ffmlp_bwd_fused<NL, PLANES, true, false> : k_ffmlp_bwd_fused<NL, PLANES, false, false>)
-                          : (act == 0 ? k_ffmlp_bwd_fused<NL, PLANES, true, true> : k_ffmlp_bwd_fused<NL, PLANES, false, true>);
+// ... and its RECOMP variant (whole K = 32 blocks of inputs): such a shape's backward takes forward_buffer == NULL
+static bool fused_bwd_recomputes(uint32_t in_dim, uint32_t hidden_dim, uint32_t num_layers) { return fused_bwd_applies(in_dim, hidden_dim, num_layers) && in_dim % 32 == 0; }
+typedef void (*FusedBwdKern)(const _Float16*, const _Float16*, const _Float16*, const _Float16*, uint32_t, uint32_t, uint32_t, _Float16*, _Float16*, uint32_t,
+                             float*, uint32_t);
+template <int NL, bool PLANES>
+static FusedBwdKern fused_bwd_kern(bool relu, bool recomp) {
+    return recomp ? (relu ? k_ffmlp_bwd_fused<NL, PLANES, true, true> : k_ffmlp_bwd_fused<NL, PLANES, false, true>)
+                  : (relu ? k_ffmlp_bwd_fused<NL, PLANES, true, false> : k_ffmlp_bwd_fused<NL, PLANES, false, false>);
+}
+// NL = 1 to 3 hidden matrices (fused_bwd_applies); fwd == NULL: the RECOMP variant; blocks = fused_bwd_blocks(B, in_dim, NL)
+static void launch_bwd_fused(uint32_t NL, bool planes, const uint16_t* grad, const uint16_t* inputs, const uint16_t* w, const uint16_t* fwd, uint32_t B,
+                             uint32_t in_dim, uint32_t act, uint16_t* bwd, uint16_t* gi, float* ws, uint32_t P, uint32_t blocks, hipStream_t s) {
+    const bool relu = act == 0, rc = fwd == nullptr;
+    const FusedBwdKern kern = NL == 1 ? (planes ? fused_bwd_kern<1, true>(relu, rc) : fused_bwd_kern<1, false>(relu, rc))
+                            : NL == 2 ? (planes ? fused_bwd_kern<2, true>(relu, rc) : fused_bwd_kern<2, false>(relu, rc))
+                                      : (planes ? fused_bwd_kern<3, true>(relu, rc) : fused_bwd_kern<3, false>(relu, rc));
     ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-    kern<<<fused_bwd_blocks(B, in_dim, NL), 256, lds, s>>>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)w, (const _Float16*)fwd, B, in_dim,
-                                                           act, (_Float16*)bwd, (_Float16*)gi, n_groups, ws, P);
+    kern<<<blocks, 256, fused_bwd_lds_bytes(in_dim, NL), s>>>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)w, (const _Float16*)fwd, B, in_dim, act,
+                                                              (_Float16*)bwd, (_Float16*)gi, div_up(B / 16, 4 * kFusedTPW), ws, P);
 }
 
 // One wave per workgroup.  blockIdx.x = batch chunk, blockIdx.y = unit: up to 4x4 output fragments of one matrix.
@@ -969,14 +981,38 @@ __global__ void __launch_bounds__(64 * kReduceWaves) k_ffmlp_bwd_reduce(const fl
 static uint32_t splitk_plan(uint32_t B, uint32_t P, size_t workspace_bytes, uint32_t& S) {
     S = B / 256 ? B / 256 : 1;
     if (S > 1024) S = 1024;
-    const size_t cap = workspace_bytes / ((size_t)P * 4);
+    const size_t cap = P ? workspace_bytes / ((size_t)P * 4) : 0;      // (P == 0: a shape no call accepts, which a query may still ask about)
     if (S > cap) S = cap ? (uint32_t)cap : 1;
     const uint32_t chunk = div_up(div_up(B, S), 16) * 16;
     S = div_up(B, chunk);
     return chunk;
 }
+constexpr size_t kSplitkMaxBytes = (size_t)256 << 20;
 static uint32_t ffmlp_params(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
     return hidden_dim * (input_dim + (num_layers - 1) * hidden_dim + 16);
+}
+
+// Which form a backward call takes and what it needs for it, decided here for ffmlp_backward and for the three entry points a caller
+// sizes its buffers with.  The fused form runs where the shape has one AND the workspace holds a partial per workgroup of it; anything
+// else -- a fused shape with a smaller workspace included -- takes the two-kernel form, which reads and writes both activation buffers.
+// The size and query entry points have no workspace to plan with: they plan with kSplitkMaxBytes, which ngp_ffmlp_backward_workspace's
+// answer never exceeds and which, like that answer, is enough for the fused form of every shape that has one.
+struct FfmlpBwdPlan {
+    uint32_t P;                 // parameters: a partial is P x 4 bytes
+    uint32_t S;                 // partials k_ffmlp_bwd_reduce sums: workgroups of the fused kernel, or batch chunks of the weight-gradient kernel
+    uint32_t split_S, chunk;    // the batch split this workspace allows the two-kernel form: chunks, rows per chunk
+    bool fused, needs_forward_buffer, needs_backward_buffer;
+};
+static FfmlpBwdPlan plan_ffmlp_backward(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers, size_t workspace_bytes = kSplitkMaxBytes) {
+    FfmlpBwdPlan p = {};
+    p.P = ffmlp_params(input_dim, hidden_dim, num_layers);
+    p.chunk = splitk_plan(B, p.P, workspace_bytes, p.split_S);
+    const uint32_t blocks = fused_bwd_applies(input_dim, hidden_dim, num_layers) ? fused_bwd_blocks(B, input_dim, num_layers - 1) : 0;
+    p.fused = blocks && workspace_bytes >= (size_t)blocks * p.P * 4;
+    p.S = p.fused ? blocks : p.split_S;
+    p.needs_forward_buffer = !(p.fused && fused_bwd_recomputes(input_dim, hidden_dim, num_layers));
+    p.needs_backward_buffer = !p.fused;
+    return p;
 }
 
 template <int HB, int TPW>
@@ -1037,48 +1073,29 @@ static int ffmlp_backward(const uint16_t* grad, const uint16_t* inputs, const ui
         return NGP_OK;
     }
     NGP_REQUIRE(grad && inputs && weights && grad_weights, "ffmlp_backward: null pointer");
-    NGP_REQUIRE(forward_buffer || ngp_ffmlp_backward_recomputes(input_dim, hidden_dim, num_layers),
+    NGP_REQUIRE(forward_buffer || fused_bwd_recomputes(input_dim, hidden_dim, num_layers),
                 "ffmlp_backward: forward_buffer is NULL and this shape does not recompute the activations (ngp_ffmlp_backward_recomputes)");
     NGP_REQUIRE(!calc_grad_inputs || grad_inputs, "ffmlp_backward: calc_grad_inputs without a grad_inputs buffer");
-    NGP_REQUIRE(B % 16 == 0, "ffmlp_backward: batch size must be a multiple of 16 (got %u)", B);
-    NGP_REQUIRE(input_dim > 0 && input_dim % 16 == 0, "FFMLP input_dim should be 16 * m (m > 0), but got %u", input_dim);
-    NGP_REQUIRE(output_dim == 16, "FFMLP current only supports (padded) output dim == 16, but got %u", output_dim);
-    NGP_REQUIRE(num_layers >= 2, "FFMLP num_layers should be larger than 2 (3 matmuls), but got %u", num_layers);
-    NGP_REQUIRE(hidden_dim == 16 || hidden_dim == 32 || hidden_dim == 64 || hidden_dim == 128 || hidden_dim == 256,
-                "FFMLP only support hidden_dim in [16, 32, 64, 128, 256], but got %u", hidden_dim);
+    if (int rc = check_ffmlp_shape("ffmlp_backward", "", B, input_dim, output_dim, hidden_dim, num_layers)) return rc;
     uint16_t* gi = calc_grad_inputs ? grad_inputs : nullptr;
-    const uint32_t P = ffmlp_params(input_dim, hidden_dim, num_layers);
+    const FfmlpBwdPlan p = plan_ffmlp_backward(B, input_dim, hidden_dim, num_layers, workspace_bytes);
+    const uint32_t P = p.P, S = p.S;
     NGP_REQUIRE(workspace && workspace_bytes >= (size_t)P * 4 && ((uintptr_t)workspace & 15) == 0,
                 "ffmlp_backward: split-K workspace missing, misaligned or smaller than one set of partials (%zu < %zu bytes); "
                 "ngp_ffmlp_backward_workspace() gives the size", workspace_bytes, (size_t)P * 4);
     float* ws = reinterpret_cast<float*>(workspace);
     ProfScope prof("ffmlp_backward", s, B);
-    if (fused_bwd_applies(input_dim, hidden_dim, num_layers) &&
-        workspace_bytes >= (size_t)fused_bwd_blocks(B, input_dim, num_layers - 1) * P * 4) {
-        const uint32_t S = fused_bwd_blocks(B, input_dim, num_layers - 1);
-        if (planes) {
-            NGP_REQUIRE(input_dim % 4 == 0, "ffmlp_backward: the level-major input layout needs input_dim %% 4 == 0");
-            switch (num_layers) {
-                case 2: launch_bwd_fused<1, true>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-                case 3: launch_bwd_fused<2, true>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-                default: launch_bwd_fused<3, true>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-            }
-        } else
-        switch (num_layers) {
-            case 2: launch_bwd_fused<1>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-            case 3: launch_bwd_fused<2>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-            default: launch_bwd_fused<3>(grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, s); break;
-        }
-        int rc = check_launch("ffmlp_backward (activation and weight gradients)");
-        if (rc) return rc;
+    NGP_REQUIRE(p.fused || !planes, "ffmlp_backward: the level-major input layout is built for the 64-wide networks (2-4 layers, input_dim <= 64) with the "
+                                    "workspace ngp_ffmlp_backward_workspace() asks for");
+    NGP_REQUIRE((forward_buffer || !p.needs_forward_buffer) && (backward_buffer || !p.needs_backward_buffer),
+                "ffmlp_backward: this shape (or workspace) takes the two-kernel form, which needs forward_buffer and backward_buffer "
+                "(the fused form of the 64-wide networks needs the workspace ngp_ffmlp_backward_workspace() asks for)");
+    if (p.fused) {      // (the level planes' pairs of columns: input_dim is a multiple of 16)
+        launch_bwd_fused(num_layers - 1, planes, grad, inputs, weights, forward_buffer, B, input_dim, activation, backward_buffer, gi, ws, P, S, s);
+        if (int rc = check_launch("ffmlp_backward (activation and weight gradients)")) return rc;
         k_ffmlp_bwd_reduce<<<div_up(P, 64), 64 * kReduceWaves, 0, s>>>(ws, S, P, (_Float16*)grad_weights);
         return check_launch("ffmlp_backward (split-K reduction)");
     }
-    NGP_REQUIRE(!planes, "ffmlp_backward: the level-major input layout is built for the 64-wide networks (2-4 layers, input_dim <= 64) with the "
-                         "workspace ngp_ffmlp_backward_workspace() asks for");
-    NGP_REQUIRE(backward_buffer && forward_buffer, "ffmlp_backward: this shape (or workspace) takes the two-kernel form, which needs forward_buffer and backward_buffer");
-    uint32_t S;
-    const uint32_t chunk = splitk_plan(B, P, workspace_bytes, S);
     switch (hidden_dim) {
         case 16: launch_bwd_chain<1, 4>(grad, weights, forward_buffer, B, input_dim, num_layers, activation, backward_buffer, gi, s); break;
         case 32: launch_bwd_chain<2, 4>(grad, weights, forward_buffer, B, input_dim, num_layers, activation, backward_buffer, gi, s); break;
@@ -1086,14 +1103,12 @@ static int ffmlp_backward(const uint16_t* grad, const uint16_t* inputs, const ui
         case 128: launch_bwd_chain<8, 2>(grad, weights, forward_buffer, B, input_dim, num_layers, activation, backward_buffer, gi, s); break;
         default: launch_bwd_chain<16, 1>(grad, weights, forward_buffer, B, input_dim, num_layers, activation, backward_buffer, gi, s); break;
     }
-    int rc = check_launch("ffmlp_backward (activation gradients)");
-    if (rc) return rc;
+    if (int rc = check_launch("ffmlp_backward (activation gradients)")) return rc;
     const uint32_t HG = div_up(hidden_dim / 16, 4), IG = div_up(input_dim / 16, 4);
     const uint32_t units = HG * IG + (num_layers - 1) * HG * HG + HG;
     k_ffmlp_bwd_wgrad<<<dim3(S, units), 64, 0, s>>>((const _Float16*)grad, (const _Float16*)inputs, (const _Float16*)forward_buffer,
-                                                    (const _Float16*)backward_buffer, B, input_dim, hidden_dim, num_layers, chunk, ws, P);
-    rc = check_launch("ffmlp_backward (weight gradients)");
-    if (rc) return rc;
+                                                    (const _Float16*)backward_buffer, B, input_dim, hidden_dim, num_layers, p.chunk, ws, P);
+    if (int rc = check_launch("ffmlp_backward (weight gradients)")) return rc;
     k_ffmlp_bwd_reduce<<<div_up(P, 64), 64 * kReduceWaves, 0, s>>>(ws, S, P, (_Float16*)grad_weights);
     return check_launch("ffmlp_backward (split-K reduction)");
 }
@@ -1122,22 +1137,17 @@ int ngp_ffmlp_backward_planes(const uint16_t* grad, const uint16_t* inputs, cons
 }
 
 size_t ngp_ffmlp_backward_workspace(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    const uint32_t P = ffmlp_params(input_dim, hidden_dim, num_layers);
-    uint32_t S;
-    (void)splitk_plan(B ? B : 16, P, (size_t)256 << 20, S);
-    if (fused_bwd_applies(input_dim, hidden_dim, num_layers)) {
-        const uint32_t blocks = fused_bwd_blocks(B ? B : 16, input_dim, num_layers - 1);
-        S = S > blocks ? S : blocks;
-    }
-    return (size_t)S * P * 4;
+    // room for the fused form's partials and for the two-kernel form's full batch split, whichever is more
+    const FfmlpBwdPlan p = plan_ffmlp_backward(B ? B : 16, input_dim, hidden_dim, num_layers);
+    return (size_t)(p.S > p.split_S ? p.S : p.split_S) * p.P * 4;
 }
 
 int ngp_ffmlp_backward_recomputes(uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    return fused_bwd_applies(input_dim, hidden_dim, num_layers) && input_dim % 32 == 0 ? 1 : 0;
+    return plan_ffmlp_backward(16, input_dim, hidden_dim, num_layers).needs_forward_buffer ? 0 : 1;
 }
 
 size_t ngp_ffmlp_backward_buffer_bytes(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    return fused_bwd_applies(input_dim, hidden_dim, num_layers) ? 0 : (size_t)num_layers * B * hidden_dim * sizeof(_Float16);
+    return plan_ffmlp_backward(B ? B : 16, input_dim, hidden_dim, num_layers).needs_backward_buffer ? (size_t)num_layers * B * hidden_dim * sizeof(_Float16) : 0;
 }
 
 // The reference creates its CUTLASS split-K side streams and events here (ffmlp.cu:721-741).  This library keeps no state

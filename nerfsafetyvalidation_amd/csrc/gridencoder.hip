@@ -18,6 +18,7 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 #include <stdio.h>
@@ -43,23 +44,7 @@ __device__ __forceinline__ uint32_t fast_hash(const uint32_t (&p)[D]) {
     return r;
 }
 
-// :54-72 (entry index, i.e. without the `* C + ch`)
-template <int D>
-__device__ __forceinline__ uint32_t grid_entry(uint32_t gridtype, bool align_corners, uint32_t hashmap_size, uint32_t resolution,
-                                               const uint32_t (&p)[D]) {
-    uint32_t stride = 1, index = 0;
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-        if (stride <= hashmap_size) {
-            index += p[d] * stride;
-            stride *= align_corners ? resolution : (resolution + 1);
-        }
-    }
-    if (gridtype == 0 && stride > hashmap_size) index = fast_hash<D>(p);
-    return index % hashmap_size;
-}
-
-// The same index from what fill_levels worked out once per level on the host (GridLevels: the strides of the dimensions the :58-62
+// :54-72 (entry index, i.e. without the `* C + ch`) from what fill_levels worked out once per level on the host (GridLevels: the strides of the dimensions the :58-62
 // loop consumes -- 0 for the others --, whether the level is hashed, and how the final `% hashmap_size` acts: not at all on a dense
 // level, as a mask on a power-of-two size, as a real modulo otherwise).  `level` is wave-uniform: the recipe is scalar, and the common
 // cases carry no integer division (a 32-bit modulo is ~35 vector instructions on gfx950 -- eight per point and level in every kernel
@@ -954,9 +939,13 @@ static size_t bin_level_records(uint32_t B, uint32_t corners) {
     const size_t pct = env > 0 ? (size_t)env : 150;
     return (((size_t)B * corners * pct / 100 + kBinMax * kBinShards * 128) / parts) * parts;
 }
-static size_t bin_level_bytes(uint32_t B, uint32_t corners) {
-    return bin_level_records(B, corners) * sizeof(uint2) + (size_t)kBinMax * kBinShards * kFillStride * sizeof(uint32_t);
+static size_t bin_level_bytes(size_t level_records) {      // ... and the level's fill counters
+    return level_records * sizeof(uint2) + (size_t)kBinMax * kBinShards * kFillStride * sizeof(uint32_t);
 }
+// only an fp16, two-feature table on a batch of kBinMinPoints or more goes through the bins (the plan below and
+// ngp_grid_encode_backward_workspace)
+constexpr uint32_t kBinMinPoints = 128u * 1024u;
+static bool bins_apply(size_t elem_bytes, uint32_t C, uint32_t B) { return elem_bytes == 2 && C == 2 && B >= kBinMinPoints; }
 
 // :317-343
 template <typename T, int D, int C>
@@ -1019,55 +1008,92 @@ static void launch_forward(const float* inputs, const void* emb, void* out, uint
         k_grid_forward<T, D, C, false><<<nblocks, kGridBlock, 0, s>>>(inputs, (const T*)emb, (T*)out, B, L, lv, nullptr, gridtype, ac, io);
 }
 
+// Which route each level's updates take, worked out on the host before anything is launched (no HIP calls; each of the two switches
+// above is read once): the levels accumulated in LDS, the levels of an fp16, two-feature table on a large batch that go through the
+// bins -- as many per launch as the caller's workspace holds --, and the rest, which take the run-combining atomics.
+struct GridBwdPlan {
+    uint32_t small_mask, n_small;       // LDS levels (k_grid_backward_small) ...
+    size_t small_lds;                   // ... and the bytes of the largest slice among them
+    BinLevels bin;                      // binned levels in launch order: the n_merge levels of the merging first pass come first
+    uint32_t n_bin, n_merge;
+    size_t level_records, per_level;    // records and workspace bytes of one binned level
+    uint32_t group;                     // binned levels per launch; 0: no level is binned (not this kind of call, or no workspace for one)
+    BinLevels rest;                     // the levels left to k_grid_backward
+    uint32_t n_rest;
+};
+
+static GridBwdPlan plan_grid_backward(const GridLevels& lv, uint32_t L, uint32_t B, uint32_t D, uint32_t C, size_t elem_bytes,
+                                      bool have_workspace, size_t workspace_bytes) {
+    GridBwdPlan p = {};
+    // levels accumulated in LDS: worth it from a few thousand points per entry-kilobyte on; the slice must fit kSmallMaxFloats
+    for (uint32_t l = 0; l < L; l++) {
+        const uint32_t floats = (lv.offset[l + 1] - lv.offset[l]) * C;
+        if (floats <= kSmallMaxFloats && (size_t)B * 8 >= (size_t)floats * 16) {
+            p.small_mask |= 1u << l;
+            p.n_small++;
+            p.small_lds = std::max(p.small_lds, floats * sizeof(unsigned long long));
+        }
+    }
+    uint32_t done_mask = p.small_mask;
+    if (bins_apply(elem_bytes, C, B)) {
+        // the levels whose cells the neighbouring rays of a workgroup share come first: they take the merging variant of the first pass
+        const uint32_t merge_min = merge_min_points();
+        for (int pass = 0; pass < 2; pass++) {
+            for (uint32_t l = 0; l < L; l++) {
+                const bool merge = lv.resolution[l] <= kMergeMaxRes && B >= merge_min;
+                if (merge == (pass == 0) && !((p.small_mask >> l) & 1u) && lv.offset[l + 1] - lv.offset[l] <= kBinMax * kBinEntries) p.bin.level[p.n_bin++] = l;
+            }
+            if (pass == 0) p.n_merge = p.n_bin;
+        }
+        p.level_records = bin_level_records(B, 1u << D);
+        p.per_level = bin_level_bytes(p.level_records);
+        const size_t usable = have_workspace ? std::min(workspace_bytes, kBinWorkspaceMax) : 0;
+        p.group = (uint32_t)std::min<size_t>(usable / p.per_level, p.n_bin);
+        for (uint32_t i = 0; i < (p.group ? p.n_bin : 0u); i++) done_mask |= 1u << p.bin.level[i];
+    }
+    for (uint32_t l = 0; l < L; l++)
+        if (!((done_mask >> l) & 1u)) p.rest.level[p.n_rest++] = l;
+    return p;
+}
+
+// diagnostics (NGP_GRID_BWD_STATS): how evenly the regions of the n levels of a launch group filled
+static void dump_bin_fill(const GridLevels& lv, const BinLevels& bl, uint32_t first, uint32_t n, uint32_t B, const BinPlan& bins, hipStream_t s) {
+    std::vector<uint32_t> h((size_t)n * kBinMax * kBinShards * kFillStride);
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpy(h.data(), bins.fill, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    const uint32_t cap = region_cap(bins.level_records, kBinMax);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t level = bl.level[first + i];
+        uint64_t tot = 0, over = 0; uint32_t mx = 0;
+        for (uint32_t r = 0; r < kBinMax * kBinShards; r++) {
+            const uint32_t f = h[((size_t)i * kBinMax * kBinShards + r) * kFillStride];
+            tot += f; mx = f > mx ? f : mx; over += f > cap ? f - cap : 0;
+        }
+        fprintf(stderr, "[grid bwd] level %u res %u hashed %d: records %llu (%.2f per point) max region %u cap %u mean %.0f overflow %llu\n", level,
+                lv.resolution[level], (int)lv.hashed[level], (unsigned long long)tot, (double)tot / B, mx, cap, (double)tot / (kBinMax * kBinShards),
+                (unsigned long long)over);
+    }
+}
+
 template <typename T, int D, int C>
 static void launch_backward(const void* grad, const float* inputs, void* grad_emb, uint32_t B, uint32_t L, const GridLevels& lv, bool gi,
                             const void* dy_dx, void* grad_inputs, uint32_t gridtype, bool ac, void* workspace, size_t workspace_bytes,
                             GridIo io, hipStream_t s) {
-    const uint32_t nb = div_up(B, kGridBlock);
     if (!grad_emb) {   // frozen table (the rollout's pose gradients): only the input gradient
         if (gi) k_grid_input_backward<T, D, C><<<div_up(B * D, kGridBlock), kGridBlock, 0, s>>>((const T*)grad, (const T*)dy_dx, (T*)grad_inputs, B, L, io);
         return;
     }
-    // levels accumulated in LDS: worth it from a few thousand points per entry-kilobyte on; the slice must fit kSmallMaxFloats
-    uint32_t small_mask = 0, n_small = 0;
-    size_t lds = 0;
-    for (uint32_t l = 0; l < L; l++) {
-        const uint32_t floats = (lv.offset[l + 1] - lv.offset[l]) * (uint32_t)C;
-        if (floats <= kSmallMaxFloats && (size_t)B * 8 >= (size_t)floats * 16) {
-            small_mask |= 1u << l;
-            n_small++;
-            lds = lds > floats * sizeof(unsigned long long) ? lds : floats * sizeof(unsigned long long);
-        }
-    }
-    if (n_small) {
+    const GridBwdPlan p = plan_grid_backward(lv, L, B, D, C, sizeof(T), workspace != nullptr, workspace_bytes);
+    if (p.n_small) {
         auto kern = k_grid_backward_small<T, D, C>;
         ensure_dynamic_lds((const void*)kern, (int)(kSmallMaxFloats * sizeof(unsigned long long)));
         const uint32_t n_pb = div_up(B, (uint32_t)kSmallThreads);
         const uint32_t bx = n_pb < 256u ? n_pb : 256u;
-        kern<<<dim3(bx, n_small), kSmallThreads, lds, s>>>((const T*)grad, inputs, (T*)grad_emb, B, lv, gridtype, ac, small_mask, io);
+        kern<<<dim3(bx, p.n_small), kSmallThreads, p.small_lds, s>>>((const T*)grad, inputs, (T*)grad_emb, B, lv, gridtype, ac, p.small_mask, io);
     }
     // hashed levels of an fp16, two-feature table: binned two-pass scatter instead of one scattered atomic per update
-    uint32_t done_mask = small_mask, n_done = n_small;
     if constexpr (sizeof(T) == 2 && C == 2) {
-        BinLevels bl = {};
-        uint32_t n_bin = 0;
-        // the levels whose cells the neighbouring rays of a workgroup share come first: they take the merging variant of the first pass
-        uint32_t n_merge = 0;
-        if (B >= 128u * 1024u)
-            for (int pass = 0; pass < 2; pass++) {
-                for (uint32_t l = 0; l < L; l++) {
-                    const bool merge = lv.resolution[l] <= kMergeMaxRes && B >= merge_min_points();
-                    if (merge == (pass == 0) && !((small_mask >> l) & 1u) && lv.offset[l + 1] - lv.offset[l] <= kBinMax * kBinEntries) bl.level[n_bin++] = l;
-                }
-                if (pass == 0) n_merge = n_bin;
-            }
-        const size_t level_records = bin_level_records(B, 1u << D);
-        const size_t per_level = bin_level_bytes(B, 1u << D);
-        const size_t usable = workspace ? (workspace_bytes < kBinWorkspaceMax ? workspace_bytes : kBinWorkspaceMax) : 0;
-        uint32_t group = n_bin ? (uint32_t)(usable / per_level) : 0;
-        group = group < n_bin ? group : n_bin;
-        char* ws = group ? (char*)workspace : nullptr;
-        if (ws) {
+        if (p.group) {
             constexpr uint32_t NT = NGP_BIN_NT;
             const uint32_t n_pb = div_up(B, NT);
             const size_t lds_bin = (size_t)NT * (1u << D) * sizeof(uint2);
@@ -1076,70 +1102,51 @@ static void launch_backward(const void* grad, const float* inputs, void* grad_em
             ensure_dynamic_lds((const void*)k_grid_bwd_bin<D, NT, true>, (int)lds_merge);
             const size_t lds_red = (size_t)kBinEntries * 2 * sizeof(unsigned long long);
             ensure_dynamic_lds((const void*)k_grid_bwd_bin_reduce, (int)lds_red);
-            BinPlan plan;
-            plan.records = reinterpret_cast<uint2*>(ws);
-            plan.fill = reinterpret_cast<uint32_t*>(ws + (size_t)group * level_records * sizeof(uint2));
-            plan.level_records = level_records;
-            for (uint32_t first = 0, n = 0; first < n_bin; first += n) {
-                const bool merge = first < n_merge;
-                const uint32_t left = (merge ? n_merge : n_bin) - first;           // (a group does not mix the two variants)
-                n = left < group ? left : group;
-                (void)hipMemsetAsync(plan.fill, 0, (size_t)n * kBinMax * kBinShards * kFillStride * sizeof(uint32_t), s);
+            char* ws = (char*)workspace;
+            const BinPlan bins = {reinterpret_cast<uint2*>(ws), reinterpret_cast<uint32_t*>(ws + (size_t)p.group * p.level_records * sizeof(uint2)),
+                                  p.level_records};
+            // a bin holds at most 32 regions of `cap` records: no more reducing workgroups than that can keep busy
+            uint32_t max_split = 1;
+            while (max_split < kBinSplit && p.level_records / kBinMax >= (size_t)2 * max_split * kBinSplitMin) max_split *= 2;
+            const bool stats = env_set("NGP_GRID_BWD_STATS");
+            for (uint32_t first = 0, n = 0; first < p.n_bin; first += n) {
+                const bool merge = first < p.n_merge;
+                const uint32_t left = (merge ? p.n_merge : p.n_bin) - first;       // (a group does not mix the two variants)
+                n = left < p.group ? left : p.group;
+                (void)hipMemsetAsync(bins.fill, 0, (size_t)n * kBinMax * kBinShards * kFillStride * sizeof(uint32_t), s);
                 if (merge)
                     k_grid_bwd_bin<D, NT, true><<<dim3(n_pb, n), NT, lds_merge, s>>>((const _Float16*)grad, inputs, (_Float16*)grad_emb, B, lv, gridtype,
-                                                                                     ac, bl, first, plan, io);
+                                                                                     ac, p.bin, first, bins, io);
                 else
                     k_grid_bwd_bin<D, NT, false><<<dim3(n_pb, n), NT, lds_bin, s>>>((const _Float16*)grad, inputs, (_Float16*)grad_emb, B, lv, gridtype,
-                                                                                    ac, bl, first, plan, io);
-                // a bin holds at most 32 regions of `cap` records: no more reducing workgroups than that can keep busy
-                uint32_t max_split = 1;
-                while (max_split < kBinSplit && (size_t)level_records / kBinMax >= (size_t)2 * max_split * kBinSplitMin) max_split *= 2;
-                k_grid_bwd_bin_reduce<<<dim3(kBinMax * max_split, n), kReduceThreads, lds_red, s>>>((_Float16*)grad_emb, lv, bl, first, plan);
-                if (env_set("NGP_GRID_BWD_STATS")) {      // diagnostics: how evenly the regions filled
-                    std::vector<uint32_t> h((size_t)n * kBinMax * kBinShards * kFillStride);
-                    (void)hipStreamSynchronize(s);
-                    (void)hipMemcpy(h.data(), plan.fill, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-                    for (uint32_t i = 0; i < n; i++) {
-                        const uint32_t level = bl.level[first + i];
-                        const uint32_t nb = kBinMax;
-                        const uint32_t cap = region_cap(level_records, nb);
-                        uint64_t tot = 0, over = 0; uint32_t mx = 0;
-                        for (uint32_t r = 0; r < nb * kBinShards; r++) {
-                            const uint32_t f = h[((size_t)i * kBinMax * kBinShards + r) * kFillStride];
-                            tot += f; mx = f > mx ? f : mx; over += f > cap ? f - cap : 0;
-                        }
-                        fprintf(stderr, "[grid bwd] level %u res %u hashed %d: records %llu (%.2f per point) max region %u cap %u mean %.0f overflow %llu\n", level,
-                                lv.resolution[level], (int)lv.hashed[level], (unsigned long long)tot, (double)tot / B, mx, cap, (double)tot / (nb * kBinShards),
-                                (unsigned long long)over);
-                    }
-                }
+                                                                                    ac, p.bin, first, bins, io);
+                k_grid_bwd_bin_reduce<<<dim3(kBinMax * max_split, n), kReduceThreads, lds_red, s>>>((_Float16*)grad_emb, lv, p.bin, first, bins);
+                if (stats) dump_bin_fill(lv, p.bin, first, n, B, bins, s);
             }
-            for (uint32_t i = 0; i < n_bin; i++) done_mask |= 1u << bl.level[i];
-            n_done += n_bin;
         }
     }
-    if (n_done < L) {
-        BinLevels rest = {};
-        uint32_t n_rest = 0;
-        for (uint32_t l = 0; l < L; l++)
-            if (!((done_mask >> l) & 1u)) rest.level[n_rest++] = l;
-        k_grid_backward<T, D, C><<<nb * n_rest, kGridBlock, 0, s>>>((const T*)grad, inputs, (T*)grad_emb, B, L, lv, gridtype, ac, rest, n_rest, io);
-    }
+    if (p.n_rest)
+        k_grid_backward<T, D, C><<<div_up(B, kGridBlock) * p.n_rest, kGridBlock, 0, s>>>((const T*)grad, inputs, (T*)grad_emb, B, L, lv, gridtype, ac, p.rest,
+                                                                                         p.n_rest, io);
     if (gi) k_grid_input_backward<T, D, C><<<div_up(B * D, kGridBlock), kGridBlock, 0, s>>>((const T*)grad, (const T*)dy_dx, (T*)grad_inputs, B, L, io);
 }
 
-#define NGP_DISPATCH_DC(FN, T, ...)                                              \
+// FN<T, D, C> for the run-time D and C.  _EVEN: without C == 1, for the fp16 backward -- its table atomics add pairs of halves, and
+// grid_encode_backward refuses the shape before it gets here.
+#define NGP_DISPATCH_DC_EVEN(FN, T, ...)                                         \
     switch (D * 16 + C) {                                                       \
-        case 2 * 16 + 1: FN<T, 2, 1>(__VA_ARGS__); break;                        \
         case 2 * 16 + 2: FN<T, 2, 2>(__VA_ARGS__); break;                        \
         case 2 * 16 + 4: FN<T, 2, 4>(__VA_ARGS__); break;                        \
         case 2 * 16 + 8: FN<T, 2, 8>(__VA_ARGS__); break;                        \
-        case 3 * 16 + 1: FN<T, 3, 1>(__VA_ARGS__); break;                        \
         case 3 * 16 + 2: FN<T, 3, 2>(__VA_ARGS__); break;                        \
         case 3 * 16 + 4: FN<T, 3, 4>(__VA_ARGS__); break;                        \
         case 3 * 16 + 8: FN<T, 3, 8>(__VA_ARGS__); break;                        \
         default: break;                                                         \
     }
+#define NGP_DISPATCH_DC(FN, T, ...)                                              \
+    if (C == 1 && D == 2) FN<T, 2, 1>(__VA_ARGS__);                              \
+    else if (C == 1 && D == 3) FN<T, 3, 1>(__VA_ARGS__);                         \
+    else NGP_DISPATCH_DC_EVEN(FN, T, __VA_ARGS__)
 
 }  // namespace ngp
 
@@ -1147,17 +1154,23 @@ using namespace ngp;
 
 extern "C" {
 
+// the checks of the shape that the forward and the backward call share (`what`: the caller's name in the messages that carry one)
+static int check_grid_shape(const char* what, uint32_t D, uint32_t C, uint32_t L, int dtype, GridIo io) {
+    NGP_REQUIRE(D == 2 || D == 3, "GridEncoding: D must be 2 or 3 on this build (got %u)", D);
+    NGP_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8, "GridEncoding: C must be 1, 2, 4, or 8.");
+    NGP_REQUIRE(io.ls % C == 0 && io.bs % C == 0 && io.ls >= C && io.bs >= C, "%s: strides must be non-zero multiples of C", what);   // (C != 0 by now)
+    NGP_REQUIRE(L >= 1 && L <= (uint32_t)kMaxLevels, "GridEncoding: L must be in [1, %d]", kMaxLevels);
+    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, "%s: dtype must be NGP_F32 or NGP_F16", what);
+    return NGP_OK;
+}
+
 static int grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets_host, void* outputs, uint32_t B,
                                uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs, void* dy_dx,
                                uint32_t gridtype, int align_corners, int dtype, const void* cell_tables, uint32_t cell_levels,
                                GridIo io, ngp_stream_t stream) {
     if (B == 0) return NGP_OK;
-    NGP_REQUIRE(io.ls % C == 0 && io.bs % C == 0 && io.ls >= C && io.bs >= C, "grid_encode_forward: strides must be non-zero multiples of C");
     NGP_REQUIRE(inputs && embeddings && offsets_host && outputs, "grid_encode_forward: null pointer");
-    NGP_REQUIRE(D == 2 || D == 3, "GridEncoding: D must be 2 or 3 on this build (got %u)", D);
-    NGP_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8, "GridEncoding: C must be 1, 2, 4, or 8.");
-    NGP_REQUIRE(L >= 1 && L <= (uint32_t)kMaxLevels, "GridEncoding: L must be in [1, %d]", kMaxLevels);
-    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, "grid_encode_forward: dtype must be NGP_F32 or NGP_F16");
+    if (int rc = check_grid_shape("grid_encode_forward", D, C, L, dtype, io)) return rc;
     NGP_REQUIRE(!calc_grad_inputs || dy_dx, "grid_encode_forward: dy_dx is NULL but calc_grad_inputs is set");
     GridLevels lv;
     fill_levels(lv, offsets_host, L, S, H, D, gridtype, align_corners != 0);
@@ -1203,11 +1216,7 @@ static int grid_encode_backward(const void* grad, const float* inputs, const voi
     if (B == 0) return NGP_OK;
     NGP_REQUIRE(grad && inputs && offsets_host, "grid_encode_backward: null pointer");
     NGP_REQUIRE(grad_embeddings || calc_grad_inputs, "grid_encode_backward: neither the table gradient nor the input gradient is requested");
-    NGP_REQUIRE(io.ls % C == 0 && io.bs % C == 0 && io.ls >= C && io.bs >= C, "grid_encode_backward: strides must be non-zero multiples of C");
-    NGP_REQUIRE(D == 2 || D == 3, "GridEncoding: D must be 2 or 3 on this build (got %u)", D);
-    NGP_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8, "GridEncoding: C must be 1, 2, 4, or 8.");
-    NGP_REQUIRE(L >= 1 && L <= (uint32_t)kMaxLevels, "GridEncoding: L must be in [1, %d]", kMaxLevels);
-    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, "grid_encode_backward: dtype must be NGP_F32 or NGP_F16");
+    if (int rc = check_grid_shape("grid_encode_backward", D, C, L, dtype, io)) return rc;
     NGP_REQUIRE(!(dtype == NGP_F16 && C == 1), "grid_encode_backward: fp16 with C == 1 is unsupported (grid.py:38 forces fp32 for odd C)");
     NGP_REQUIRE(!calc_grad_inputs || (dy_dx && grad_inputs), "grid_encode_backward: dy_dx/grad_inputs NULL but calc_grad_inputs set");
     GridLevels lv;
@@ -1219,15 +1228,8 @@ static int grid_encode_backward(const void* grad, const float* inputs, const voi
         NGP_DISPATCH_DC(launch_backward, float, grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace,
                         workspace_bytes, io, s)
     } else {
-        switch (D * 16 + C) {
-            case 2 * 16 + 2: launch_backward<_Float16, 2, 2>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            case 2 * 16 + 4: launch_backward<_Float16, 2, 4>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            case 2 * 16 + 8: launch_backward<_Float16, 2, 8>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            case 3 * 16 + 2: launch_backward<_Float16, 3, 2>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            case 3 * 16 + 4: launch_backward<_Float16, 3, 4>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            case 3 * 16 + 8: launch_backward<_Float16, 3, 8>(grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace, workspace_bytes, io, s); break;
-            default: break;
-        }
+        NGP_DISPATCH_DC_EVEN(launch_backward, _Float16, grad, inputs, grad_embeddings, B, L, lv, gi, dy_dx, grad_inputs, gridtype, ac, workspace,
+                             workspace_bytes, io, s)
     }
     return check_launch("grid_encode_backward");
 }
@@ -1265,9 +1267,9 @@ int ngp_grid_encode_backward_strided(const void* grad, const float* inputs, cons
 }
 
 size_t ngp_grid_encode_backward_workspace(uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype) {
-    // only the binned scatter of an fp16, two-feature table on a large batch uses it (launch_backward)
-    if (dtype != NGP_F16 || C != 2 || B < 128u * 1024u) return 0;
-    const size_t per_level = bin_level_bytes(B, 1u << D);
+    // only the binned scatter uses it (plan_grid_backward)
+    if (!bins_apply(dtype == NGP_F16 ? 2 : 4, C, B)) return 0;
+    const size_t per_level = bin_level_bytes(bin_level_records(B, 1u << D));
     const size_t all = per_level * L;
     if (all <= kBinWorkspaceMax) return all;
     const size_t group = kBinWorkspaceMax / per_level;

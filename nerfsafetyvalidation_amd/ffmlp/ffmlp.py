@@ -16,6 +16,38 @@ from .. import _lib
 RECOMPUTE_ACTIVATIONS = True     # (this build; False: keep forward_buffer as the reference does -- tests compare the two)
 
 
+def launch_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, forward_buffer, outputs, planes=False):
+    """planes: inputs are level planes (ngp_ffmlp_forward_planes); forward_buffer None: no activations kept (row inputs: the inference call)"""
+    lib = _lib.lib()
+    if planes:
+        fn, what = lib.ngp_ffmlp_forward_planes, "ffmlp_forward_planes"
+    elif forward_buffer is not None:
+        fn, what = lib.ngp_ffmlp_forward, "ffmlp_forward"
+    else:
+        fn, what = lib.ngp_ffmlp_inference, "ffmlp_inference"
+    _lib.check(fn(_lib.ptr(inputs), _lib.ptr(weights), B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
+                  _lib.ptr(forward_buffer), _lib.ptr(outputs), _lib.stream()), what)
+
+
+def launch_backward(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, calc_grad_inputs, planes=False):
+    """-> (grad_inputs or None, grad_weights).  planes: inputs and grad_inputs are level planes (ngp_ffmlp_backward_planes)."""
+    lib = _lib.lib()
+    # every row / parameter is written by the call; the activation gradients only go to memory for shapes that need them there
+    grad_inputs = torch.empty_like(inputs) if calc_grad_inputs else None
+    grad_weights = torch.empty_like(weights)
+    bbytes = lib.ngp_ffmlp_backward_buffer_bytes(B, input_dim, hidden_dim, num_layers)
+    backward_buffer = torch.empty(num_layers, B, hidden_dim, device=grad.device, dtype=grad.dtype) if bbytes else None
+    # split-K partials of the weight gradients: this call's own scratch from torch's (stream-aware) caching allocator, so
+    # backward passes running concurrently on other streams never share it
+    wbytes = lib.ngp_ffmlp_backward_workspace(B, input_dim, hidden_dim, num_layers)
+    work = torch.empty((wbytes + 3) // 4, dtype=torch.float32, device=grad.device)
+    fn = lib.ngp_ffmlp_backward_planes if planes else lib.ngp_ffmlp_backward
+    _lib.check(fn(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(weights), _lib.ptr(forward_buffer), B, input_dim, output_dim, hidden_dim, num_layers, activation,
+                  output_activation, int(calc_grad_inputs), _lib.ptr(backward_buffer), _lib.ptr(grad_inputs), _lib.ptr(grad_weights), _lib.ptr(work), wbytes,
+                  _lib.stream()), "ffmlp_backward")
+    return grad_inputs, grad_weights
+
+
 class _ffmlp_forward(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.half)
@@ -30,25 +62,13 @@ class _ffmlp_forward(Function):
             # ffmlp.cu:636-642 CHECK_IS_HALF; outside autocast the caller must hand in half tensors
             raise RuntimeError("FFMLP: inputs and weights must be half tensors (call under autocast or cast explicitly)")
         outputs = torch.empty(B, output_dim, device=inputs.device, dtype=inputs.dtype)
-        lib = _lib.lib()
         ctx.planes = planes
         # The reference keeps every hidden layer's activations for the backward pass (forward_buffer, ffmlp.py:37-45: 128 B per row and
         # layer written here, read there).  For the shapes whose backward kernel can compute them again from the inputs it reads anyway
         # (ngp_ffmlp_backward_recomputes: bit-identical values) the training forward stores none -- it is the inference call.
-        keep = not inference and not (RECOMPUTE_ACTIVATIONS and lib.ngp_ffmlp_backward_recomputes(input_dim, hidden_dim, num_layers))
+        keep = not inference and not (RECOMPUTE_ACTIVATIONS and _lib.lib().ngp_ffmlp_backward_recomputes(input_dim, hidden_dim, num_layers))
         forward_buffer = torch.empty(num_layers, B, hidden_dim, device=inputs.device, dtype=inputs.dtype) if keep else None
-        if planes:
-            _lib.check(lib.ngp_ffmlp_forward_planes(_lib.ptr(inputs), _lib.ptr(weights), B, input_dim, output_dim, hidden_dim, num_layers,
-                                                    activation, output_activation, _lib.ptr(forward_buffer), _lib.ptr(outputs),
-                                                    _lib.stream()), "ffmlp_forward_planes")
-        elif keep:
-            _lib.check(lib.ngp_ffmlp_forward(_lib.ptr(inputs), _lib.ptr(weights), B, input_dim, output_dim, hidden_dim, num_layers,
-                                             activation, output_activation, _lib.ptr(forward_buffer), _lib.ptr(outputs),
-                                             _lib.stream()), "ffmlp_forward")
-        else:
-            _lib.check(lib.ngp_ffmlp_inference(_lib.ptr(inputs), _lib.ptr(weights), B, input_dim, output_dim, hidden_dim,
-                                               num_layers, activation, output_activation, None, _lib.ptr(outputs),
-                                               _lib.stream()), "ffmlp_inference")
+        launch_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, forward_buffer, outputs, planes)
         if not inference:
             ctx.save_for_backward(inputs, weights, outputs, forward_buffer)
             ctx.dims = (input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, calc_grad_inputs)
@@ -61,24 +81,8 @@ class _ffmlp_forward(Function):
         grad = grad.contiguous()
         inputs, weights, outputs, forward_buffer = ctx.saved_tensors
         input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, calc_grad_inputs = ctx.dims
-        lib = _lib.lib()
-        # every row / parameter is written by the call; the activation gradients only go to memory for shapes that need them there
-        grad_inputs = torch.empty_like(inputs) if calc_grad_inputs else None
-        grad_weights = torch.empty_like(weights)
-        bbytes = lib.ngp_ffmlp_backward_buffer_bytes(B, input_dim, hidden_dim, num_layers)
-        backward_buffer = torch.empty(num_layers, B, hidden_dim, device=grad.device, dtype=grad.dtype) if bbytes else None
-        # split-K partials of the weight gradients: this call's own scratch from torch's (stream-aware) caching allocator, so
-        # backward passes running concurrently on other streams never share it
-        wbytes = lib.ngp_ffmlp_backward_workspace(B, input_dim, hidden_dim, num_layers)
-        work = torch.empty((wbytes + 3) // 4, dtype=torch.float32, device=grad.device)
-        fn = lib.ngp_ffmlp_backward_planes if ctx.planes else lib.ngp_ffmlp_backward
-        _lib.check(fn(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(weights), _lib.ptr(forward_buffer), B,
-                      input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
-                      int(calc_grad_inputs), _lib.ptr(backward_buffer), _lib.ptr(grad_inputs),
-                      _lib.ptr(grad_weights), _lib.ptr(work), wbytes, _lib.stream()), "ffmlp_backward")
-        if calc_grad_inputs:
-            return grad_inputs, grad_weights, None, None, None, None, None, None, None, None, None
-        return None, grad_weights, None, None, None, None, None, None, None, None, None
+        return launch_backward(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
+                               calc_grad_inputs, ctx.planes) + (None,) * 9
 
 
 ffmlp_forward = _ffmlp_forward.apply

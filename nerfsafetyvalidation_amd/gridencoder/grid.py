@@ -141,6 +141,35 @@ def _table_for_call(embeddings, offsets, B, D, C, L, S, H, gridtype, align_corne
     return embeddings, cells, cell_levels
 
 
+def launch_forward(inputs, embeddings, offsets_host, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners, cells, cell_levels, strides=None):
+    """The native forward call.  outputs: the operator's level-major [L, B, C], or, with strides = (level_stride, point_stride) in
+    elements, wherever those put a (level, point) pair (ngp_grid_encode_forward_strided).  dy_dx None: no input gradient is prepared."""
+    lib, calc, code = _lib.lib(), int(dy_dx is not None), _lib.dtype_code(embeddings)
+    if strides is None:
+        rc = lib.ngp_grid_encode_forward(_lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(outputs), B, D, C, L, S, H, calc, _lib.ptr(dy_dx),
+                                         gridtype, int(align_corners), code, _lib.ptr(cells), cell_levels, _lib.stream())
+    else:
+        rc = lib.ngp_grid_encode_forward_strided(_lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(outputs), B, D, C, L, S, H, calc, _lib.ptr(dy_dx),
+                                                 gridtype, int(align_corners), code, _lib.ptr(cells), cell_levels, strides[0], strides[1], _lib.stream())
+    _lib.check(rc, "grid_encode_forward")
+
+
+def launch_backward(grad, inputs, embeddings, offsets_host, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners, strides=None):
+    """The native backward call, `grad` laid out as launch_forward's outputs.  grad_embeddings None: frozen table; dy_dx and grad_inputs None: no
+    input gradient.  The scratch of the binned table-gradient scatter (large fp16 batches only) is this call's own, from torch's stream-aware allocator."""
+    lib, calc, code = _lib.lib(), int(grad_inputs is not None), _lib.dtype_code(embeddings)
+    wbytes = lib.ngp_grid_encode_backward_workspace(B, D, C, L, code) if grad_embeddings is not None else 0
+    work = torch.empty(wbytes, dtype=torch.uint8, device=grad.device) if wbytes else None
+    if strides is None:
+        rc = lib.ngp_grid_encode_backward(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(grad_embeddings), B, D, C, L, S, H, calc,
+                                          _lib.ptr(dy_dx), _lib.ptr(grad_inputs), gridtype, int(align_corners), code, _lib.ptr(work), wbytes, _lib.stream())
+    else:
+        rc = lib.ngp_grid_encode_backward_strided(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(grad_embeddings), B, D, C, L, S, H,
+                                                  calc, _lib.ptr(dy_dx), _lib.ptr(grad_inputs), gridtype, int(align_corners), code, _lib.ptr(work), wbytes,
+                                                  strides[0], strides[1], _lib.stream())
+    _lib.check(rc, "grid_encode_backward")
+
+
 class _grid_encode(Function):
     @staticmethod
     @custom_fwd(device_type="cuda")
@@ -162,11 +191,7 @@ class _grid_encode(Function):
         outputs = torch.empty(L, B, C, device=inputs.device, dtype=embeddings.dtype)
         dy_dx = torch.empty(B, L * D * C, device=inputs.device, dtype=embeddings.dtype) if calc_grad_inputs else None
 
-        lib = _lib.lib()
-        _lib.check(lib.ngp_grid_encode_forward(_lib.ptr(inputs), _lib.ptr(embeddings), _lib.host_i32(offsets), _lib.ptr(outputs),
-                                               B, D, C, L, S, H, int(calc_grad_inputs), _lib.ptr(dy_dx), gridtype,
-                                               int(align_corners), _lib.dtype_code(embeddings), _lib.ptr(cells), cell_levels, _lib.stream()),
-                   "grid_encode_forward")
+        launch_forward(inputs, embeddings, _lib.host_i32(offsets), outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners, cells, cell_levels)
 
         # [L,B,C] -> [B, L*C] (grid.py:52).  (The scattered 4-byte writes of producing [B, L*C] in the kernel cost more than this copy:
         # 8.9 vs 5.3 + 1.8 ms on 29.5 M points.  Where the consumer is an FFMLP, _grid_encode_planes hands it the planes as they are.)
@@ -194,15 +219,8 @@ class _grid_encode(Function):
             return None, None, None, None, None, None, None, None
         grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if calc_grad_inputs else None
 
-        lib = _lib.lib()
-        # scratch of the binned table-gradient scatter (large fp16 batches only): this call's own, from torch's stream-aware allocator
-        wbytes = lib.ngp_grid_encode_backward_workspace(B, D, C, L, _lib.dtype_code(embeddings)) if grad_embeddings is not None else 0
-        work = torch.empty(wbytes, dtype=torch.uint8, device=grad.device) if wbytes else None
-        _lib.check(lib.ngp_grid_encode_backward(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), _lib.host_i32(offsets),
-                                                _lib.ptr(grad_embeddings), B, D, C, L, S, H, int(calc_grad_inputs),
-                                                _lib.ptr(dy_dx) if calc_grad_inputs else None, _lib.ptr(grad_inputs), gridtype,
-                                                int(ctx.align_corners), _lib.dtype_code(embeddings), _lib.ptr(work), wbytes,
-                                                _lib.stream()), "grid_encode_backward")
+        launch_backward(grad, inputs, embeddings, _lib.host_i32(offsets), grad_embeddings, B, D, C, L, S, H, dy_dx if calc_grad_inputs else None,
+                        grad_inputs, gridtype, ctx.align_corners)
         if calc_grad_inputs:
             return grad_inputs.to(inputs.dtype), grad_embeddings, None, None, None, None, None, None
         return None, grad_embeddings, None, None, None, None, None, None
@@ -233,10 +251,7 @@ class _grid_encode_planes(Function):
         outputs = torch.empty(L, Bp, C, device=inputs.device, dtype=embeddings.dtype)
         if Bp != B:
             outputs[:, B:].zero_()
-        _lib.check(_lib.lib().ngp_grid_encode_forward_strided(_lib.ptr(inputs), _lib.ptr(embeddings), _lib.host_i32(offsets), _lib.ptr(outputs),
-                                                              B, D, C, L, S, H, 0, None, gridtype, int(align_corners),
-                                                              _lib.dtype_code(embeddings), _lib.ptr(cells), cell_levels, Bp * C, C, _lib.stream()),
-                   "grid_encode_forward")
+        launch_forward(inputs, embeddings, _lib.host_i32(offsets), outputs, B, D, C, L, S, H, None, gridtype, align_corners, cells, cell_levels, (Bp * C, C))
         ctx.save_for_backward(inputs, embeddings, offsets)
         ctx.dims = [B, D, C, L, S, H, gridtype, Bp]
         ctx.align_corners = align_corners
@@ -251,13 +266,7 @@ class _grid_encode_planes(Function):
             return None, None, None, None, None, None, None, None
         grad = grad.contiguous().to(embeddings.dtype)          # [L, Bp, C], read in place
         grad_embeddings = torch.zeros_like(embeddings)
-        lib = _lib.lib()
-        wbytes = lib.ngp_grid_encode_backward_workspace(B, D, C, L, _lib.dtype_code(embeddings))
-        work = torch.empty(wbytes, dtype=torch.uint8, device=grad.device) if wbytes else None
-        _lib.check(lib.ngp_grid_encode_backward_strided(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), _lib.host_i32(offsets),
-                                                        _lib.ptr(grad_embeddings), B, D, C, L, S, H, 0, None, None, gridtype,
-                                                        int(ctx.align_corners), _lib.dtype_code(embeddings), _lib.ptr(work), wbytes, Bp * C, C,
-                                                        _lib.stream()), "grid_encode_backward")
+        launch_backward(grad, inputs, embeddings, _lib.host_i32(offsets), grad_embeddings, B, D, C, L, S, H, None, None, gridtype, ctx.align_corners, (Bp * C, C))
         return None, grad_embeddings, None, None, None, None, None, None
 
 

@@ -8,10 +8,41 @@ from torch.autograd import Function
 from .. import _lib
 from ..activation import trunc_exp
 from ..encoding import get_encoder
-from ..ffmlp import FFMLP
-from ..gridencoder import GridEncoder
+from ..ffmlp import FFMLP, ffmlp as _ffmlp
+from ..gridencoder import GridEncoder, grid as _grid
 from ..shencoder import SHEncoder
 from .renderer import NeRFRenderer
+
+
+# The launches of the two elementwise steps between the FFMLPs (B of the h.shape[0] padded rows are samples).  The separate nodes below and the
+# one-node form (_ff_network) both go through these and through the launchers of gridencoder.grid and ffmlp.ffmlp: same calls, same operands.
+def _launch_sigma_color_input(h, dirs, B):
+    sigma = torch.empty(B, dtype=torch.float32, device=h.device)
+    cin = torch.empty(h.shape[0], 32, dtype=torch.float16, device=h.device)
+    _lib.check(_lib.lib().ngp_ff_sigma_color_input(_lib.ptr(h), _lib.ptr(dirs), B, h.shape[0], _lib.ptr(sigma), _lib.ptr(cin), _lib.stream()),
+               "ff_sigma_color_input")
+    return sigma, cin
+
+
+def _launch_sigma_color_input_backward(h, g_sigma, g_cin, B):
+    g_sigma = g_sigma.contiguous().float() if g_sigma is not None else None
+    g_cin = g_cin.contiguous().half() if g_cin is not None else None
+    g_h = torch.empty_like(h)
+    _lib.check(_lib.lib().ngp_ff_sigma_color_input_backward(_lib.ptr(h), _lib.ptr(g_sigma), _lib.ptr(g_cin), B, h.shape[0], _lib.ptr(g_h),
+                                                            _lib.stream()), "ff_sigma_color_input_backward")
+    return g_h
+
+
+def _launch_rgb(o16, B):
+    rgb = torch.empty(B, 3, dtype=torch.float16, device=o16.device)
+    _lib.check(_lib.lib().ngp_ff_rgb(_lib.ptr(o16), B, _lib.ptr(rgb), _lib.stream()), "ff_rgb")
+    return rgb
+
+
+def _launch_rgb_backward(g, rgb, B_pad):
+    g_o = torch.empty(B_pad, 16, dtype=torch.float16, device=rgb.device)
+    _lib.check(_lib.lib().ngp_ff_rgb_backward(_lib.ptr(g.contiguous().half()), _lib.ptr(rgb), rgb.shape[0], B_pad, _lib.ptr(g_o), _lib.stream()), "ff_rgb_backward")
+    return g_o
 
 
 class _sigma_color_input(Function):
@@ -20,27 +51,17 @@ class _sigma_color_input(Function):
 
     @staticmethod
     def forward(ctx, h, dirs, B):
-        B_pad = h.shape[0]
-        sigma = torch.empty(B, dtype=torch.float32, device=h.device)
-        cin = torch.empty(B_pad, 32, dtype=torch.float16, device=h.device)
-        _lib.check(_lib.lib().ngp_ff_sigma_color_input(_lib.ptr(h), _lib.ptr(dirs), B, B_pad, _lib.ptr(sigma), _lib.ptr(cin), _lib.stream()),
-                   "ff_sigma_color_input")
         ctx.save_for_backward(h)
         ctx.B = B
         ctx.set_materialize_grads(False)
-        return sigma, cin
+        return _launch_sigma_color_input(h, dirs, B)
 
     @staticmethod
     def backward(ctx, g_sigma, g_cin):
         (h,) = ctx.saved_tensors
         if g_sigma is None and g_cin is None:
             return None, None, None
-        g_sigma = g_sigma.contiguous().float() if g_sigma is not None else None
-        g_cin = g_cin.contiguous().half() if g_cin is not None else None
-        g_h = torch.empty_like(h)
-        _lib.check(_lib.lib().ngp_ff_sigma_color_input_backward(_lib.ptr(h), _lib.ptr(g_sigma), _lib.ptr(g_cin), ctx.B, h.shape[0], _lib.ptr(g_h),
-                                                                _lib.stream()), "ff_sigma_color_input_backward")
-        return g_h, None, None
+        return _launch_sigma_color_input_backward(h, g_sigma, g_cin, ctx.B), None, None
 
 
 class _rgb(Function):
@@ -48,8 +69,7 @@ class _rgb(Function):
 
     @staticmethod
     def forward(ctx, o16, B):
-        rgb = torch.empty(B, 3, dtype=torch.float16, device=o16.device)
-        _lib.check(_lib.lib().ngp_ff_rgb(_lib.ptr(o16), B, _lib.ptr(rgb), _lib.stream()), "ff_rgb")
+        rgb = _launch_rgb(o16, B)
         ctx.save_for_backward(rgb)
         ctx.B_pad = o16.shape[0]
         return rgb
@@ -57,10 +77,7 @@ class _rgb(Function):
     @staticmethod
     def backward(ctx, g):
         (rgb,) = ctx.saved_tensors
-        g_o = torch.empty(ctx.B_pad, 16, dtype=torch.float16, device=rgb.device)
-        _lib.check(_lib.lib().ngp_ff_rgb_backward(_lib.ptr(g.contiguous().half()), _lib.ptr(rgb), rgb.shape[0], ctx.B_pad, _lib.ptr(g_o),
-                                                  _lib.stream()), "ff_rgb_backward")
-        return g_o, None
+        return _launch_rgb_backward(g, rgb, ctx.B_pad), None
 
 
 class _ff_network(Function):
@@ -73,10 +90,7 @@ class _ff_network(Function):
     @staticmethod
     def forward(ctx, x, d, embeddings, sigma_w, color_w, net):
         import numpy as np
-        from ..gridencoder.grid import _table_for_call
-        lib = _lib.lib()
         enc, sn, cn = net.encoder, net.sigma_net, net.color_net
-        st = _lib.stream()
         B = x.shape[0]
         Bp = B + (-B) % 16
         L, C, D = enc.num_levels, enc.level_dim, enc.input_dim
@@ -84,33 +98,26 @@ class _ff_network(Function):
         x01 = ((x + net.bound) / (2 * net.bound)).float().contiguous()
         d = d.float().contiguous()
         inference = not any(ctx.needs_input_grad[2:5])        # (grad mode is off inside a Function's forward: ask the node itself)
-        emb16, cells, cell_levels = _table_for_call(embeddings, enc.offsets, B, D, C, L, S, H, enc.gridtype_id, enc.align_corners)
+        emb16, cells, cell_levels = _grid._table_for_call(embeddings, enc.offsets, B, D, C, L, S, H, enc.gridtype_id, enc.align_corners)
         emb16 = emb16.contiguous()
         offs = _lib.host_i32(enc.offsets)
         dev = x.device
         planes = torch.empty(L, Bp, C, device=dev, dtype=torch.float16)
         if Bp != B:
             planes[:, B:].zero_()
-        _lib.check(lib.ngp_grid_encode_forward_strided(_lib.ptr(x01), _lib.ptr(emb16), offs, _lib.ptr(planes), B, D, C, L, S, H, 0, None,
-                                                       enc.gridtype_id, int(enc.align_corners), _lib.dtype_code(emb16), _lib.ptr(cells), cell_levels,
-                                                       Bp * C, C, st), "grid_encode_forward")
+        _grid.launch_forward(x01, emb16, offs, planes, B, D, C, L, S, H, None, enc.gridtype_id, enc.align_corners, cells, cell_levels, (Bp * C, C))
         sw16, cw16 = sigma_w.detach().to(torch.float16).contiguous(), color_w.detach().to(torch.float16).contiguous()
         h = torch.empty(Bp, 16, device=dev, dtype=torch.float16)
-        _lib.check(lib.ngp_ffmlp_forward_planes(_lib.ptr(planes), _lib.ptr(sw16), Bp, sn.input_dim, 16, sn.hidden_dim, sn.num_layers, sn.activation,
-                                                sn.output_activation, None, _lib.ptr(h), st), "ffmlp_forward_planes")
-        sigma = torch.empty(B, dtype=torch.float32, device=dev)
-        cin = torch.empty(Bp, 32, dtype=torch.float16, device=dev)
-        _lib.check(lib.ngp_ff_sigma_color_input(_lib.ptr(h), _lib.ptr(d), B, Bp, _lib.ptr(sigma), _lib.ptr(cin), st), "ff_sigma_color_input")
+        _ffmlp.launch_forward(planes, sw16, Bp, sn.input_dim, 16, sn.hidden_dim, sn.num_layers, sn.activation, sn.output_activation, None, h, True)
+        sigma, cin = _launch_sigma_color_input(h, d, B)
         o = torch.empty(Bp, 16, device=dev, dtype=torch.float16)
-        _lib.check(lib.ngp_ffmlp_inference(_lib.ptr(cin), _lib.ptr(cw16), Bp, cn.input_dim, 16, cn.hidden_dim, cn.num_layers, cn.activation,
-                                           cn.output_activation, None, _lib.ptr(o), st), "ffmlp_inference")
-        rgb = torch.empty(B, 3, dtype=torch.float16, device=dev)
-        _lib.check(lib.ngp_ff_rgb(_lib.ptr(o), B, _lib.ptr(rgb), st), "ff_rgb")
+        _ffmlp.launch_forward(cin, cw16, Bp, cn.input_dim, 16, cn.hidden_dim, cn.num_layers, cn.activation, cn.output_activation, None, o)
+        rgb = _launch_rgb(o, B)
         if not inference:
             ctx.save_for_backward(x01, emb16, planes, sw16, h, cin, cw16, rgb)
             ctx.cfg = (B, Bp, L, C, D, S, H, enc.gridtype_id, int(enc.align_corners), offs,
-                       (sn.input_dim, sn.hidden_dim, sn.num_layers, sn.activation, sn.output_activation),
-                       (cn.input_dim, cn.hidden_dim, cn.num_layers, cn.activation, cn.output_activation))
+                       (sn.input_dim, 16, sn.hidden_dim, sn.num_layers, sn.activation, sn.output_activation),
+                       (cn.input_dim, 16, cn.hidden_dim, cn.num_layers, cn.activation, cn.output_activation))
         ctx.set_materialize_grads(False)
         return sigma, rgb
 
@@ -118,42 +125,20 @@ class _ff_network(Function):
     def backward(ctx, g_sigma, g_rgb):
         x01, emb16, planes, sw16, h, cin, cw16, rgb = ctx.saved_tensors
         B, Bp, L, C, D, S, H, gridtype, align, offs, scfg, ccfg = ctx.cfg
-        lib = _lib.lib()
-        st = _lib.stream()
-        dev = h.device
         want_emb, want_sw, want_cw = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-
-        def ffmlp_bwd(fn, grad, inputs, w16, cfg, want_inputs):
-            in_dim, hid, layers, act, oact = cfg
-            g_in = torch.empty_like(inputs) if want_inputs else None
-            g_w = torch.empty_like(w16)
-            wbytes = lib.ngp_ffmlp_backward_workspace(Bp, in_dim, hid, layers)
-            work = torch.empty((wbytes + 3) // 4, dtype=torch.float32, device=dev)
-            _lib.check(fn(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(w16), None, Bp, in_dim, 16, hid, layers, act, oact, int(want_inputs), None,
-                          _lib.ptr(g_in), _lib.ptr(g_w), _lib.ptr(work), wbytes, st), "ffmlp_backward")
-            return g_in, g_w
-
         g_cin = g_cw = None
         if g_rgb is not None:
-            g_o = torch.empty(Bp, 16, dtype=torch.float16, device=dev)
-            _lib.check(lib.ngp_ff_rgb_backward(_lib.ptr(g_rgb.contiguous().half()), _lib.ptr(rgb), B, Bp, _lib.ptr(g_o), st), "ff_rgb_backward")
-            g_cin, g_cw = ffmlp_bwd(lib.ngp_ffmlp_backward, g_o, cin, cw16, ccfg, True)
+            g_cin, g_cw = _ffmlp.launch_backward(_launch_rgb_backward(g_rgb, rgb, Bp), cin, cw16, None, Bp, *ccfg, True)
         elif want_cw:
             g_cw = torch.zeros_like(cw16)
         if g_sigma is None and g_cin is None:
             return None, None, None, None, (g_cw if want_cw else None), None
-        g_h = torch.empty_like(h)
-        _lib.check(lib.ngp_ff_sigma_color_input_backward(_lib.ptr(h), _lib.ptr(g_sigma.contiguous().float() if g_sigma is not None else None),
-                                                         _lib.ptr(g_cin), B, Bp, _lib.ptr(g_h), st), "ff_sigma_color_input_backward")
-        g_planes, g_sw = ffmlp_bwd(lib.ngp_ffmlp_backward_planes, g_h, planes, sw16, scfg, want_emb)
+        g_h = _launch_sigma_color_input_backward(h, g_sigma, g_cin, B)
+        g_planes, g_sw = _ffmlp.launch_backward(g_h, planes, sw16, None, Bp, *scfg, want_emb, True)
         g_emb = None
         if want_emb:
             g_emb = torch.zeros_like(emb16)
-            wbytes = lib.ngp_grid_encode_backward_workspace(B, D, C, L, _lib.dtype_code(emb16))
-            work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
-            _lib.check(lib.ngp_grid_encode_backward_strided(_lib.ptr(g_planes), _lib.ptr(x01), _lib.ptr(emb16), offs, _lib.ptr(g_emb), B, D, C, L, S, H,
-                                                            0, None, None, gridtype, align, _lib.dtype_code(emb16), _lib.ptr(work), wbytes, Bp * C, C, st),
-                       "grid_encode_backward")
+            _grid.launch_backward(g_planes, x01, emb16, offs, g_emb, B, D, C, L, S, H, None, None, gridtype, align, (Bp * C, C))
         return None, None, g_emb, (g_sw if want_sw else None), (g_cw if want_cw else None), None
 
 

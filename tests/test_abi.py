@@ -62,6 +62,35 @@ def test_ctypes_layer_binds_every_symbol():
     assert 0 < lib.ngp_render_uniform_backward_lds(ctypes.byref(m), 512) <= 160 * 1024
 
 
+def test_backward_plans_answer_as_before_the_refactor(monkeypatch):
+    """The workspace, buffer and recompute answers of the grid encoder's and the FFMLP's backward (host arithmetic, no GPU) over the
+    sweep of tests/golden/make_golden_plans.py equal, value by value, those recorded from the build that preceded the shared
+    backward plans (tests/golden/backward_plans.json), and the spot values worked out by hand there."""
+    import importlib.util
+    import json
+    from nerfsafetyvalidation_amd import _lib
+    for name in ("NGP_GRID_MERGE_MIN", "NGP_GRID_BIN_FILL_PCT"):
+        monkeypatch.delenv(name, raising=False)
+    spec = importlib.util.spec_from_file_location("make_golden_plans", os.path.join(ROOT, "tests", "golden", "make_golden_plans.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = json.load(open(gen.OUT))
+    assert want["grid_axes"] == gen.GRID and want["ffmlp_axes"] == gen.FFMLP
+    lib = _lib.lib()
+    got = gen.answers(lib, _lib)
+    assert len(got["grid_workspace"]) == 8 * 2 * 4 * 4 * 2 and len(got["ffmlp_workspace_buffer_recomputes"]) == 7 * 5 * 5 * 4
+    for key, axes in (("grid_workspace", gen.GRID), ("ffmlp_workspace_buffer_recomputes", gen.FFMLP)):
+        assert len(got[key]) == len(want[key])
+        wrong = [(shape, g, w) for shape, g, w in zip(gen.sweep(axes), got[key], want[key]) if g != w]
+        assert not wrong, f"{key}: {len(wrong)} shapes answer differently, first (shape, got, recorded): {wrong[:5]}"
+    P = 64 * (32 + 64 + 16)
+    assert P == 7168
+    for B, partials in ((16, 1), (64, 1), (128, 2), (4096, 64), (1 << 20, 1024)):
+        assert lib.ngp_ffmlp_backward_workspace(B, 32, 64, 2) == partials * P * 4
+    for B, nbytes in ((131071, 0), (131072, 276824064), (1 << 25, 3225944064)):
+        assert lib.ngp_grid_encode_backward_workspace(B, 3, 2, 16, _lib.NGP_F16) == nbytes
+
+
 def test_product_never_imports_the_oracle():
     """only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/"""
     pkg = os.path.join(ROOT, "nerfsafetyvalidation_amd")

@@ -50,7 +50,7 @@ def _ro(*arrays):
 
 
 def _routes(offsets, res, B, C, dtype, binned, merging):
-    """the route of each level as launch_backward chooses it (for the printed table only)"""
+    """the route of each level as plan_grid_backward chooses it (for the printed table only)"""
     out = []
     for l in range(len(offsets) - 1):
         size = int(offsets[l + 1] - offsets[l])

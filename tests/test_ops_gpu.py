@@ -758,6 +758,41 @@ def test_ffmlp_backward_buffers_direct(device):
                                           _lib.ptr(got[0]), None, _lib.ptr(got[2]), _lib.ptr(work), wbytes, _lib.stream()), "ffmlp_backward")
 
 
+def test_ffmlp_backward_short_workspace_refusals(device):
+    """A workspace of ONE set of partials where the fused backward wants two (B = 128) sends a 64-wide network to the two-kernel form,
+    which needs both buffers and has no level-plane variant: without them the call is refused before anything is launched --
+    NGP_EINVAL, the outputs untouched, ngp_last_error() naming the size query -- and with them it runs.
+    (The library from before FfmlpBwdPlan answers all three calls the same way; only its message for the first refusal did not
+    name ngp_ffmlp_backward_workspace yet.)"""
+    from nerfsafetyvalidation_amd import _lib
+    lib = _lib.lib()
+    B, nin, hid, nl = 128, 32, 64, 2
+    P = hid * (nin + hid * (nl - 1) + 16)
+    assert lib.ngp_ffmlp_backward_workspace(B, nin, hid, nl) == 2 * P * 4 and lib.ngp_ffmlp_backward_workspace(64, nin, hid, nl) == P * 4
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    g, x, w, fwd = [(torch.rand(s, generator=gen) - 0.5).half().to(device) for s in ((B, 16), (B, nin), (P,), (nl, B, hid))]
+    x_planes = x.view(B, nin // 2, 2).permute(1, 0, 2).contiguous()            # [16, 128, 2]
+    bwd = torch.zeros(nl, B, hid, dtype=torch.float16, device=device)
+    gw, gi = torch.full((P,), 7.0, dtype=torch.float16, device=device), torch.full((B, nin), 7.0, dtype=torch.float16, device=device)
+    work = torch.empty(P, dtype=torch.float32, device=device)
+
+    def call(fn, inputs, fwd_buf, bwd_buf):
+        return fn(_lib.ptr(g), _lib.ptr(inputs), _lib.ptr(w), _lib.ptr(fwd_buf), B, nin, 16, hid, nl, 0, 6, 1, _lib.ptr(bwd_buf), _lib.ptr(gi),
+                  _lib.ptr(gw), _lib.ptr(work), P * 4, _lib.stream())
+
+    def refused(rc):
+        torch.cuda.synchronize()
+        assert rc == -1                                                        # NGP_EINVAL
+        assert bool((gw == 7.0).all()) and bool((gi == 7.0).all())
+        assert b"ngp_ffmlp_backward_workspace" in lib.ngp_last_error(), lib.ngp_last_error()
+
+    refused(call(lib.ngp_ffmlp_backward, x, None, bwd))
+    refused(call(lib.ngp_ffmlp_backward_planes, x_planes, None, None))
+    assert call(lib.ngp_ffmlp_backward, x, fwd, bwd) == 0                      # the two-kernel form
+    torch.cuda.synchronize()
+    assert bool((gw != 7.0).any()) and bool((gi != 7.0).any())
+
+
 def test_ffmlp_rejects_bad_shapes(device):
     from nerfsafetyvalidation_amd.ffmlp import FFMLP
     with pytest.raises(AssertionError):
