@@ -49,6 +49,11 @@ class RaycastGrid(C.Structure):
     _fields_ = [("lo", _f32 * 3), ("cell", _f32 * 3), ("inv_cell", _f32 * 3), ("grow", _f32 * 3), ("reach", _f32), ("n", _u32 * 3)]
 
 
+class VoxelBox(C.Structure):
+    """struct ngp_voxel_box"""
+    _fields_ = [("start", C.c_double * 3), ("granularity", C.c_double), ("shape", _u32 * 3), ("axis", C.c_int32 * 3), ("sign", C.c_int32 * 3)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES).  Mirrors include/ngp_hip.h one to one;
 # tests/test_abi.py checks that every declaration in the header has an entry here and is exported.
 SIGNATURES = {
@@ -144,6 +149,8 @@ SIGNATURES = {
     "ngp_raycast_bin_emit": [_vp, _u32, C.POINTER(RaycastGrid), _vp, C.c_uint64, _vp, _vp, _vp],
     "ngp_raycast": [_vp, _vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _vp],
     "ngp_raycast_shade": [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u32, _vp, _u32, _f32, C.POINTER(C.c_float), _vp, _vp, _vp],
+    "ngp_voxelize_count": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, _vp, _vp],
+    "ngp_voxelize_mark": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, C.c_uint64, C.c_uint64, _vp, _vp],
     "ngp_sift_workspace": [_u32, _u32],
     "ngp_sift_layer_offset": [_u32, _u32, _int, _int],
     "ngp_sift_octaves": [_u32, _u32],

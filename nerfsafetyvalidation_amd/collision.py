@@ -8,7 +8,12 @@ this project has a trained NeRF, not a Blender scene, so the map comes from the 
     occupancy_from_density   max sigma over s^3 points of every cell > thresh    ngp_cell_max_density (HIP)
     occupancy_from_points    createCollisionMap.py:43-53 for any point cloud      numpy
     occupancy_from_fn        a host-side analytic scene (the synthetic henge)     numpy
+    occupancy_from_mesh      every cell a triangle of the world's mesh touches    ngp_voxelize_* (HIP); numpy for a CPU world
     SignedDistanceField.from_occupancy   exact squared EDT in integers            ngp_edt_sq (HIP), then sqrt in float64 / granularity
+
+`occupancy_from_mesh` (world.MeshWorld.occupancy, a conservative surface voxelisation) is the ground truth: the reference's map comes
+from the scene's mesh too, and a model must not mark its own homework.  `SignedDistanceField.from_mesh` is the field of that map, what
+`sdf="world"` resolves to in rollout.run_rollout / cem.run_cem; `map_agreement` scores a NeRF-density map against it.
 
 `from_occupancy` reproduces createSDF.py bit for bit: scipy also takes the float64 square root of an exact integer sum of squares.
 `lookup` is NerfSimulator's host check of one point; `query` the same index rule as a batched device gather.
@@ -144,6 +149,27 @@ def occupancy_from_fn(fn, box, samples_per_axis=2):
     return torch.from_numpy(occ)
 
 
+def occupancy_from_mesh(world, box, rot=PLANNER_ROT):
+    """the true world's map: every cell of `box` that a triangle of `world` (a world.MeshWorld) touches, by world.py's voxelisation
+    rule -> bool [X, Y, Z] on the world's device (HIP for a mesh on the GPU, numpy for a CPU world; the same map).  A superset of
+    occupancy_from_points on the mesh's vertices: no holes where a triangle is larger than a cell.  rot: a signed permutation."""
+    return world.occupancy(box, rot)
+
+
+def map_agreement(pred, truth):
+    """how well a predicted map (a NeRF-density map) matches the truth map (occupancy_from_mesh): two bool maps of one shape (tensors
+    or arrays) -> {"tp", "fp", "fn", "tn"} (ints: occupied in both, in pred only, in truth only, in neither) and "iou" = tp / (tp + fp
+    + fn), "precision" = tp / (tp + fp), "recall" = tp / (tp + fn) (floats; 1.0 where the denominator is 0: nothing to get wrong)"""
+    p, t = torch.as_tensor(pred).bool(), torch.as_tensor(truth).bool()
+    if p.shape != t.shape:
+        raise ValueError(f"map_agreement: maps of one shape (got {tuple(p.shape)} and {tuple(t.shape)})")
+    t = t.to(p.device)
+    tp, fp, fn = [int(v) for v in torch.stack([(p & t).sum(), (p & ~t).sum(), (~p & t).sum()]).cpu()]
+    ratio = lambda a, b: a / b if b else 1.0                          # noqa: E731
+    return {"tp": tp, "fp": fp, "fn": fn, "tn": int(p.numel()) - tp - fp - fn, "iou": ratio(tp, tp + fp + fn),
+            "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn)}
+
+
 def henge_fn(x, y, z):
     """the synthetic scene in the world (drone) frame: scene.henge_occupancy in the NeRF's axes, mapped as rollout.scene_collision
     does (_FLIP_YZ: NeRF = (y, z, x))"""
@@ -191,6 +217,17 @@ class SignedDistanceField:
         return cls(vals, box)
 
     @classmethod
+    def from_mesh(cls, world, box=None, rot=PLANNER_ROT):
+        """the ground-truth field: from_occupancy of occupancy_from_mesh(world, box, rot) (box: default reference_box(), the box
+        NerfSimulator looks values up in).  A HIP world's map goes to ngp_edt_sq on its device without a host round trip; a CPU
+        world's (numpy) map is moved to the current HIP device, as from_occupancy does with any host map -- without one this raises."""
+        box = reference_box() if box is None else box
+        if world.device.type != "cuda" and not torch.cuda.is_available():
+            raise RuntimeError("SignedDistanceField.from_mesh: the distance transform (ngp_edt_sq) is a HIP kernel and no HIP device is "
+                               "available; world.occupancy(box) alone runs on the CPU")
+        return cls.from_occupancy(occupancy_from_mesh(world, box, rot), box)
+
+    @classmethod
     def from_array(cls, sdf, box=None):
         """a field as the reference stores it (`sdf.npy`), as-is; looked up with `box`'s start and granularity (default: NerfSimulator's
         constants, reference_box())"""
@@ -227,3 +264,18 @@ class SignedDistanceField:
         idx = torch.where(ok[..., None], torch.where(idx < 0, idx + n, idx), torch.zeros_like(idx))
         vals = self._device_values(p.device)[idx[..., 0], idx[..., 1], idx[..., 2]]
         return torch.where(ok, vals, torch.full_like(vals, float("nan"))), ok
+
+
+SDF_WORLD = "world"
+
+
+def resolve_sdf(sdf, world, who):
+    """the `sdf` keyword of the rollout entry points: None and a SignedDistanceField pass through; "world" is the ground-truth field
+    of `world` (a world.MeshWorld) over reference_box(), SignedDistanceField.from_mesh -- built here, once per run"""
+    if not isinstance(sdf, str):
+        return sdf
+    if sdf != SDF_WORLD:
+        raise ValueError(f"{who}: sdf is None, a collision.SignedDistanceField or {SDF_WORLD!r} (got {sdf!r})")
+    if world is None:
+        raise ValueError(f"{who}: sdf={SDF_WORLD!r} needs world= (a world.MeshWorld: the mesh the ground-truth field is built from)")
+    return SignedDistanceField.from_mesh(world, reference_box())

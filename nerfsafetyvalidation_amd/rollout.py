@@ -238,7 +238,8 @@ class RolloutSimulator:
                  planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
-        sdf: None (the analytic stand-in, scene_collision) or a collision.SignedDistanceField the collision check looks up.
+        sdf: None (the analytic stand-in, scene_collision), a collision.SignedDistanceField the collision check looks up, or "world":
+        the ground-truth field of `world`'s mesh over reference_box() (SignedDistanceField.from_mesh; needs world=).
         estimator_cfg: None (the planner replans from the true state) or nav.estimator_config()'s dict: the reference's estimator
         turns render #1 of every step into the state the planner replans from (needs planner_cfg).
         uq_method: envConfig.json's key.  The default, 'Gaussian Approximation', is the path described above.  'Bayesian Laplace
@@ -249,6 +250,8 @@ class RolloutSimulator:
         (BlenderSimulator.py:82,102).  Every step its frame of the true pose is kept as self.world_image (uint8 [H,W,3] numpy) and,
         with estimator_cfg, is the estimator's sensor image; shared and read-only between simulations."""
         self.world, self.world_image = world, None
+        from .collision import resolve_sdf
+        sdf = resolve_sdf(sdf, world, "RolloutSimulator")
         if uq_method not in (UQ_GAUSSIAN, UQ_LAPLACE):
             raise ValueError(f"Unrecognized uncertainty quantification method {uq_method}")
         self.uq_method, self.uq_kwargs, self.last_trace = uq_method, dict(uq_kwargs or {}), None
@@ -502,10 +505,13 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
-    a collision.SignedDistanceField every simulation's collision check looks up.  estimator_cfg: None, or nav.estimator_config()'s
+    a collision.SignedDistanceField every simulation's collision check looks up, or "world": the ground-truth field of `world`'s mesh
+    (SignedDistanceField.from_mesh over reference_box(), built once here; a ValueError without world=).  estimator_cfg: None, or nav.estimator_config()'s
     dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps).
     uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged).  world: None, or the
     world.MeshWorld every simulation's sensor looks at (RolloutSimulator's `world`; shared, read-only)."""
+    from .collision import resolve_sdf
+    sdf = resolve_sdf(sdf, world, "run_rollout")
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -537,7 +543,8 @@ def run_validation(stress_test, *args, simulator=SIM_NERF, **kwargs):
     """validate.py:23-49: envConfig.json's `stress_test` picks the loop -- 'Monte Carlo' -> run_rollout(*args, **kwargs),
     'Cross Entropy Method' -> cem.run_cem(*args, **kwargs); anything else is an error (the reference prints and exits).  `simulator`
     is envConfig.json's key of that name: 'NerfSimulator' (the default: the NeRF is its own world) or 'BlenderSimulator' (the sensor
-    looks at the true world: needs world=, a world.MeshWorld); anything else is an error."""
+    looks at the true world: needs world=, a world.MeshWorld); anything else is an error.  With world=, sdf="world" judges the
+    collisions of either loop against the mesh's own field, not against the NeRF's."""
     if simulator not in (SIM_NERF, SIM_BLENDER):
         raise ValueError(f"Unrecognized simulator {simulator}")
     if simulator == SIM_BLENDER and kwargs.get("world") is None:

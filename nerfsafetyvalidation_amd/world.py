@@ -24,6 +24,38 @@ The grid rule (grid_params): the vertices' bounding box padded by ext / 128 + S 
 largest of ext and the largest coordinate magnitude); `resolution=None` picks n_a = round(size_a * cbrt(4 F / volume)) cells on axis
 a, clamped to 1..256 -- about four cells per triangle, cells near cubic; a triangle's bounding box is grown by
 max(cell / 32, S / 4096) on every side before it is binned, and rays whose origin lies beyond 64 S walk no grid (all triangles).
+
+The world is also the truth a rollout's collisions are judged against (DESIGN.md "The ground-truth collision field"): the reference's
+collision map comes from the scene's mesh (validation/utils/createCollisionMap.py), not from the NeRF.  That script marks the cells that
+hold a mesh vertex, which leaves holes wherever a triangle is larger than a cell; here every cell a triangle touches is marked.
+
+        .occupancy(box, rot=PLANNER_ROT)                               -> bool [X,Y,Z] on the world's device
+    voxelize_numpy(vertices_world, faces, box, all_cells=False)        -> bool [X,Y,Z] numpy
+
+A mesh on a HIP device goes through csrc/voxelize.hip on the current stream, a CPU world through voxelize_numpy; the two maps are equal.
+
+The voxelisation rule is the specification (written here once, implemented in voxelize_numpy and in csrc/voxelize.hip):
+    inputs: the world's vertices (float32, the NeRF's axes; the exact vertices, not tri_data: v0 + e1 is not v1) and faces, a
+    collision.GridBox, and rot -- a signed permutation matrix (entries 0 or +-1, one per row and column; anything else is a ValueError),
+    so that the inverse of collision.to_nerf, w_i = sum_j rot[i][j] x_j, is a copy or a negation: no rounding.
+    Everything after the permutation is float64, one IEEE rounding per operation, no contraction;  a . b = (ax bx + ay by) + az bz,
+    (a x b).x = ay bz - az by (and cyclic).
+    Cell (i, j, k) has the centre c_a = start_a + (i_a + 0.5) / g and the half-width h = 0.5 / g, g the box's granularity.
+    A cell is occupied iff at least one face (v0, v1, v2) satisfies (a) or (b):
+    (a) the closed triangle-box separating-axis test (Akenine-Moeller's 13 axes) finds no separating axis.  With the edges
+        e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2 and the normal n = e0 x e1 (of the world vertices: the same for every cell) and the
+        shifted vertices v_k' = v_k - c:
+            box axis a       separates iff  min_k v'_ka > h  or  max_k v'_ka < -h
+            the normal       separates iff  |n . v_0'| > h ((|nx| + |ny|) + |nz|)
+            a = u_i x e_j    separates iff  min_k p_k > r  or  max_k p_k < -r,  p_k = a . v_k',  r = h ((|ax| + |ay|) + |az|)
+        (u_0 x e = (0, -ez, ey), u_1 x e = (ez, 0, -ex), u_2 x e = (-ey, ex, 0): the zero component drops out of both sums exactly).
+        All inequalities are strict, so touching is overlap; a zero axis separates nothing, so a zero-area face is decided by the
+        remaining axes -- conservative.
+    (b) one of the face's three vertices lies in the cell by GridBox.indices' rule, floor((w_a - start_a) g) in float64, inside the box
+        -- so the map is a superset of collision.occupancy_from_points on the vertices the faces use.
+    Candidates: the result is defined over all cells of the box; an implementation may test any superset of the overlapping cells.
+    Both test, per axis, the cells floor((min_k w_ka - start_a) g) - 1 .. floor((max_k w_ka - start_a) g) + 1, clipped to the box
+    (face_candidates); voxelize_numpy(all_cells=True) tests every cell of the box instead, and gives the same map.
 """
 import ctypes
 
@@ -41,6 +73,8 @@ CELLS_PER_TRIANGLE = 4.0                            # the automatic resolution's
 DEFAULT_AMBIENT = 0.3
 GREY = 0.5
 _CHUNK_PAIRS = 1 << 20                              # (ray, triangle) pairs per chunk of the numpy path
+_VOXEL_CHUNK_PAIRS = 1 << 18                        # (face, candidate cell) pairs per chunk of voxelize_numpy
+MAX_PAIRS_PER_LAUNCH = 2 ** 31 - 1                  # ngp_voxelize_mark: pairs per call; a mesh with more is marked in several calls
 
 _f32 = np.float32
 
@@ -215,6 +249,117 @@ def _bg3(bg_color):
     return bg
 
 
+# ------------------------------------------------------------------------------------------------------------- the collision map
+def signed_permutation(rot):
+    """rot [3,3] -> (axis, sign) int [3] with w_i = sign[i] * x[axis[i]] = sum_j rot[i][j] x_j; ValueError unless rot is a signed
+    permutation matrix (entries 0 or +-1, one non-zero per row and column)"""
+    r = np.asarray(rot.detach().cpu().numpy() if isinstance(rot, torch.Tensor) else rot, dtype=np.float64)
+    if r.shape != (3, 3) or not np.isin(r, (-1.0, 0.0, 1.0)).all() or (np.abs(r).sum(0) != 1).any() or (np.abs(r).sum(1) != 1).any():
+        raise ValueError(f"voxelize: rot must be a signed permutation matrix (entries 0 or +-1, one per row and column), got {np.asarray(r).tolist()}")
+    axis = np.abs(r).argmax(1)
+    return axis.astype(np.int64), r[np.arange(3), axis].astype(np.int64)
+
+
+def vertices_to_world(vertices, rot=PLANNER_ROT):
+    """float32 vertices [V,3] in the NeRF's axes (numpy or tensor) -> the world frame, exactly: a copy or a negation per axis"""
+    axis, sign = signed_permutation(rot)
+    cols = [vertices[:, int(axis[a])] if sign[a] > 0 else -vertices[:, int(axis[a])] for a in range(3)]
+    return torch.stack(cols, 1) if isinstance(vertices, torch.Tensor) else np.stack(cols, 1)
+
+
+def check_voxel_box(box):
+    """the boxes both paths accept: at least one cell per axis, fewer than 2^31 cells, and cells that float64 resolves (a box placed
+    2^40 cells or more from the origin has none of the rule's arithmetic left)"""
+    cells = int(np.prod([int(n) for n in box.shape], dtype=object)) if all(n >= 1 for n in box.shape) else 0
+    if cells < 1 or cells >= 2 ** 31:
+        raise ValueError(f"voxelize: the box needs at least one cell per axis and fewer than 2^31 cells (shape {box.shape})")
+    g = box.granularity
+    if not (g > 0 and np.isfinite(g) and np.isfinite(box.start).all()):
+        raise ValueError(f"voxelize: the box needs a finite start and a positive finite granularity ({box})")
+    reach = max(max(abs(s), abs(s + n / g)) for s, n in zip(box.start, box.shape))
+    if not reach * g < 2.0 ** 40:
+        raise ValueError(f"voxelize: the box lies 2^40 cells or more from the origin ({box})")
+
+
+def face_candidates(vertices_world, faces, box):
+    """the candidate cells of every face: per axis floor((min - start) g) - 1 .. floor((max - start) g) + 1 clipped to the box ->
+    (lo int64 [F,3], n int64 [F,3]): the first cell and the number of cells (0: none); the face's cells in C order are its pairs"""
+    tri = np.asarray(vertices_world, _f32)[np.asarray(faces).astype(np.int64)].astype(np.float64)          # [F, vertex, axis]
+    start, g, top = np.asarray(box.start, np.float64), np.float64(box.granularity), np.asarray(box.shape, np.float64) - 1.0
+    with np.errstate(all="ignore"):
+        lo = np.floor((tri.min(1) - start) * g) - 1.0
+        hi = np.floor((tri.max(1) - start) * g) + 1.0
+    some = (hi >= 0.0) & (lo <= top)
+    first = np.where(some, np.maximum(lo, 0.0), 0.0).astype(np.int64)
+    last = np.where(some, np.minimum(hi, top), -1.0).astype(np.int64)
+    return first, np.where(some, last - first + 1, 0)
+
+
+def tri_box_overlap(tri, centre, h):
+    """rule (a) for N (face, cell) pairs: tri float64 [N, vertex, axis] (world), centre float64 [N,3], h the half-width -> bool [N]"""
+    p = tri - centre[:, None, :]
+    out = np.zeros(tri.shape[0], dtype=bool)
+    idx = np.nonzero(~((p.min(1) > h) | (p.max(1) < -h)).any(1))[0]               # the three box axes
+    tri, p = tri[idx], p[idx]
+    e = np.stack([tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 1], tri[:, 0] - tri[:, 2]], 1)         # [M, edge, axis]
+    n = _cross([e[:, 0, a] for a in range(3)], [e[:, 1, a] for a in range(3)])
+    d = _dot(n, [p[:, 0, a] for a in range(3)])
+    sep = np.abs(d) > h * ((np.abs(n[0]) + np.abs(n[1])) + np.abs(n[2]))
+    for j in range(3):
+        ex, ey, ez = e[:, j, 0], e[:, j, 1], e[:, j, 2]
+        for a1, a2, c1, c2 in ((-ez, ey, 1, 2), (ez, -ex, 0, 2), (-ey, ex, 0, 1)):             # u_0 x e, u_1 x e, u_2 x e
+            q = a1[:, None] * p[:, :, c1] + a2[:, None] * p[:, :, c2]
+            r = h * (np.abs(a1) + np.abs(a2))
+            sep |= (q.min(1) > r) | (q.max(1) < -r)
+    out[idx] = ~sep
+    return out
+
+
+def voxelize_numpy(vertices_world, faces, box, all_cells=False):
+    """the voxelisation rule in numpy, chunked over (face, candidate cell) pairs: vertices_world float32 [V,3] (the world frame:
+    vertices_to_world), faces integer [F,3], box a collision.GridBox -> bool [X,Y,Z].  all_cells: every cell of the box is every
+    face's candidate (brute force, for small boxes: the candidates change no result)"""
+    check_voxel_box(box)
+    vw = np.ascontiguousarray(vertices_world, _f32).reshape(-1, 3)
+    fc = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    shape = np.asarray(box.shape, np.int64)
+    start, g = np.asarray(box.start, np.float64), np.float64(box.granularity)
+    h = np.float64(0.5) / g
+    occ = np.zeros(box.shape, dtype=bool)
+    if fc.shape[0] == 0:
+        return occ
+    tri = vw[fc].astype(np.float64)
+    with np.errstate(all="ignore"):
+        cell = np.floor((tri.reshape(-1, 3) - start) * g)                          # rule (b): GridBox.indices' floor
+    cell = cell[((cell >= 0) & (cell <= (shape - 1).astype(np.float64))).all(1)].astype(np.int64)
+    occ[cell[:, 0], cell[:, 1], cell[:, 2]] = True
+    if all_cells:
+        lo, n = np.zeros((fc.shape[0], 3), np.int64), np.tile(shape, (fc.shape[0], 1))
+    else:
+        lo, n = face_candidates(vw, fc, box)
+    counts = n.prod(1)
+    ends = np.cumsum(counts)
+    for p0 in range(0, int(ends[-1]), _VOXEL_CHUNK_PAIRS):
+        pair = np.arange(p0, min(int(ends[-1]), p0 + _VOXEL_CHUNK_PAIRS), dtype=np.int64)
+        f = np.searchsorted(ends, pair, side="right")                              # the first face with ends[f] > pair
+        j = pair - (ends[f] - counts[f])
+        nyz, nz = n[f, 1] * n[f, 2], n[f, 2]
+        ijk = np.stack([lo[f, 0] + j // nyz, lo[f, 1] + (j % nyz) // nz, lo[f, 2] + j % nz], 1)
+        centre = start + (ijk.astype(np.float64) + 0.5) / g
+        hit = ijk[tri_box_overlap(tri[f], centre, h)]
+        occ[hit[:, 0], hit[:, 1], hit[:, 2]] = True
+    return occ
+
+
+def _voxel_box_struct(box, rot):
+    axis, sign = signed_permutation(rot)
+    b = _lib.VoxelBox()
+    b.granularity = float(box.granularity)
+    for a in range(3):
+        b.start[a], b.shape[a], b.axis[a], b.sign[a] = float(box.start[a]), int(box.shape[a]), int(axis[a]), int(sign[a])
+    return b
+
+
 # ------------------------------------------------------------------------------------------------------------- the world
 class MeshWorld:
     """A triangle mesh as the world a camera looks at.  vertices [V,3], faces integer [F,3], colors [V,3] (float in [0, 1], or uint8)
@@ -286,6 +431,33 @@ class MeshWorld:
             cells, order = torch.sort(pair_cell, stable=True)
             self.pair_tri = pair_tri[order].contiguous()
             self.cell_start = torch.searchsorted(cells, torch.arange(n_cells + 1, dtype=torch.int32, device=self.device)).to(torch.int32).contiguous()
+
+    # ---- the collision map
+    def occupancy(self, box, rot=PLANNER_ROT, pairs_per_launch=MAX_PAIRS_PER_LAUNCH):
+        """the cells of `box` (a collision.GridBox, world frame) that the mesh's surface touches, by the module's voxelisation rule
+        -> bool [X,Y,Z] on the world's device.  rot: the signed permutation that collision.to_nerf applied to the world's vertices
+        (ValueError otherwise).  A HIP world runs on the current stream: a count kernel (one lane per face), torch.cumsum, the pair
+        total read back (the only read), and the mark kernel (one lane per (face, candidate cell) pair) once per pairs_per_launch
+        pairs -- a mesh with 2^31 pairs or more takes several launches; the map does not depend on that split."""
+        check_voxel_box(box)
+        if self.device.type != "cuda":
+            vw = vertices_to_world(self.vertices.numpy(), rot)
+            return torch.from_numpy(voxelize_numpy(vw, self.faces.numpy(), box))
+        if not 1 <= int(pairs_per_launch) <= MAX_PAIRS_PER_LAUNCH:
+            raise ValueError(f"MeshWorld.occupancy: pairs_per_launch is 1 .. {MAX_PAIRS_PER_LAUNCH}")
+        lib, b = _lib.lib(), _voxel_box_struct(box, rot)
+        with torch.cuda.device(self.device):
+            occ = torch.empty(box.shape, dtype=torch.uint8, device=self.device)
+            counts = torch.empty(self.n_faces, dtype=torch.int32, device=self.device)
+            _lib.check(lib.ngp_voxelize_count(_lib.ptr(self.vertices), self.n_vertices, _lib.ptr(self.faces), self.n_faces, ctypes.byref(b),
+                                              _lib.ptr(occ), _lib.ptr(counts), _lib.stream()), "voxelize_count")
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            pairs = int(ends[-1])
+            for base in range(0, pairs, int(pairs_per_launch)):
+                _lib.check(lib.ngp_voxelize_mark(_lib.ptr(self.vertices), self.n_vertices, _lib.ptr(self.faces), self.n_faces, ctypes.byref(b),
+                                                 _lib.ptr(ends), base, min(int(pairs_per_launch), pairs - base), _lib.ptr(occ), _lib.stream()),
+                           "voxelize_mark")
+        return occ.view(torch.bool)
 
     # ---- casting
     def _rays(self, rays_o, rays_d):

@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Timings of the ground-truth collision map (world.MeshWorld.occupancy, csrc/voxelize.hip) on one GPU, one JSON line each, also
+written to profiles/voxelize_bench.jsonl.  The mesh is scene.henge_mesh at `--resolutions` (default 64 and 256), the boxes are
+collision.reference_box() (96 x 92 x 24) and collision.collision_map_box() (72 x 96 x 56), 40 cells per metre.  Per mesh and box:
+
+  voxelize     ms of MeshWorld.occupancy on the GPU (zero, count, scan, the pair total read back, mark) between stream events, warmed up,
+               median and min of the repeats; faces, (face, candidate cell) pairs, occupied cells; ms of the numpy path
+               (world.voxelize_numpy, host clock, once) and whether the two maps are equal; ms of collision.occupancy_from_points on the
+               mesh's vertices (the reference's vertex-only rule, host clock) and `missed_by_vertices`: the share of the triangle map's
+               cells that the vertex-only map leaves empty
+  field        ms of SignedDistanceField.from_mesh (map, distance transform, float64 square root on the host), host clock around a
+               synchronise, best of the repeats
+and once, on the finest mesh and reference_box():
+  agreement    collision.map_agreement of the synthetic scene's density map (scene.StonehengeScene.build_model's fp16 network under
+               autocast, occupancy_from_density with 2^3 samples per cell; its random table has no surface, so the threshold is the
+               quantile that occupies as many cells as the mesh map does) against the mesh map, and of the analytic scene's map
+               (occupancy_from_fn(henge_fn): solid stones, where the mesh map is their surface) against it
+
+    python scripts/bench_voxelize.py [--resolutions 64 256] [--repeats 30] [--out profiles/voxelize_bench.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def event_ms(fn, repeats, warmup=3):
+    """ms of fn() between two events on the current stream, per repeat"""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def host_ms(fn, repeats=1, sync=False):
+    out = []
+    for _ in range(repeats):
+        if sync:
+            torch.cuda.synchronize()
+        t = time.perf_counter()
+        res = fn()
+        if sync:
+            torch.cuda.synchronize()
+        out.append((time.perf_counter() - t) * 1e3)
+    return min(out), res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--resolutions", type=int, nargs="+", default=[64, 256])
+    ap.add_argument("--repeats", type=int, default=30)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "voxelize_bench.jsonl"))
+    args = ap.parse_args()
+    from nerfsafetyvalidation_amd import collision as CO
+    from nerfsafetyvalidation_amd import world as WO
+    from nerfsafetyvalidation_amd.mesh import mesh_to_world
+    from nerfsafetyvalidation_amd.scene import StonehengeScene, henge_mesh
+    device = torch.device("cuda:0")
+    lines = []
+
+    def emit(rec):
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+
+    boxes = {"reference_box": CO.reference_box(), "collision_map_box": CO.collision_map_box()}
+    truth = None
+    for R in args.resolutions:
+        t0 = time.perf_counter()
+        v, f, _ = henge_mesh(R)
+        mesh_s = time.perf_counter() - t0
+        world = WO.MeshWorld(torch.from_numpy(v).to(device), torch.from_numpy(f).to(device))
+        vw = WO.vertices_to_world(v, CO.PLANNER_ROT)
+        used = mesh_to_world(v[np.unique(f)])
+        for name, box in boxes.items():
+            gpu = event_ms(lambda: world.occupancy(box), args.repeats)
+            occ = world.occupancy(box)
+            _, n = WO.face_candidates(vw, f, box)
+            numpy_ms, want = host_ms(lambda: WO.voxelize_numpy(vw, f, box))
+            points_ms, points = host_ms(lambda: CO.occupancy_from_points(used, box).numpy(), 3)
+            got = occ.cpu().numpy()
+            emit({"bench": "voxelize", "mesh_resolution": R, "box": name, "shape": list(box.shape), "faces": int(f.shape[0]),
+                  "vertices": int(v.shape[0]), "pairs": int(n.prod(1).sum()), "occupied_cells": int(got.sum()),
+                  "hip": {"median_ms": round(statistics.median(gpu), 4), "min_ms": round(min(gpu), 4), "repeats": len(gpu)},
+                  "numpy_ms": round(numpy_ms, 1), "equal_to_numpy": bool(np.array_equal(got, want)),
+                  "numpy_over_hip": round(numpy_ms / statistics.median(gpu), 1),
+                  "occupancy_from_points_ms": round(points_ms, 2), "vertex_cells": int(points.sum()),
+                  "vertex_cells_outside_map": int((points & ~got).sum()),
+                  "missed_by_vertices": round(float((got & ~points).sum() / max(1, got.sum())), 4), "henge_mesh_host_s": round(mesh_s, 2)})
+            field_ms, _ = host_ms(lambda: CO.SignedDistanceField.from_mesh(world, box), 3, sync=True)
+            emit({"bench": "field", "mesh_resolution": R, "box": name, "from_mesh_ms": round(field_ms, 3)})
+            if name == "reference_box":
+                truth = occ
+
+    box = boxes["reference_box"]
+    sc = StonehengeScene(H=32, W=32, bound=2)
+    model = sc.build_model(device, cuda_ray=False)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        sigma = CO.cell_max_density(model, box, 2)
+    fraction = float(truth.float().mean())
+    thresh = float(torch.quantile(sigma.flatten().float(), 1.0 - fraction))
+    emit({"bench": "agreement", "pred": "density of the synthetic scene's fp16 network", "mesh_resolution": args.resolutions[-1],
+          "box": "reference_box", "thresh": round(thresh, 5), "truth_occupied_fraction": round(fraction, 5),
+          **CO.map_agreement(sigma > thresh, truth)})
+    emit({"bench": "agreement", "pred": "occupancy_from_fn(henge_fn), 2^3 samples per cell", "mesh_resolution": args.resolutions[-1],
+          "box": "reference_box", **CO.map_agreement(CO.occupancy_from_fn(CO.henge_fn, box, 2), truth.cpu())})
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        for rec in lines:
+            fh.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()
