@@ -494,6 +494,26 @@ NGP_API int ngp_voxelize_count(const float* vertices, uint32_t V, const int32_t*
 NGP_API int ngp_voxelize_mark(const float* vertices, uint32_t V, const int32_t* faces, uint32_t F, const ngp_voxel_box* box,
                               const int64_t* ends, uint64_t pair_base, uint64_t n_pairs, uint8_t* map, ngp_stream_t stream);
 
+/* Rays against a list of analytic primitives, merged by depth with a mesh cast (csrc/overlay.hip): the replay's failure view.
+ * The table: 8 floats per primitive, kind, a.xyz, b.xyz, r -- kind 0 a capsule with the axis a-b and the radius r, kind 1 an
+ * axis-aligned box with the centre a and the half extents b.  prims_host is the table in HOST memory, validated before anything is
+ * launched (any other kind, a non-finite field or r <= 0: NGP_EINVAL); prims is the same table in device memory, 16-byte aligned.
+ *   ngp_overlay_cast   rays_o / rays_d float [N,3], t_max float [N] or null (+inf): the far limit per ray, the mesh cast's t of the
+ *                      same ray -> t float [N] (+inf on a miss), prim int32 [N] (-1), normal float [N,3] (unnormalised; 0 on a
+ *                      miss), by the hit rule of csrc/overlay.hip: the ray re-centred on the primitive, nearer roots only, accepted
+ *                      iff t_min < t < t_max[ray]; the smallest t wins, equal t goes to the lowest index; a ray with a non-finite
+ *                      component or a zero direction misses.  frame_width as ngp_raycast's.  P == 0 writes misses; N == 0
+ *                      launches nothing.  The result does not depend on frame_width or on how the table is staged.
+ *   ngp_overlay_shade  where 0 <= prim < P: image float [N,3] and image_u8 uint8 [N,3] ((uint8)(x * 255)) are overwritten with
+ *                      colors float [P,3] of the primitive times ambient + (1 - ambient) |n . d| / (|n| |d|), clamped to [0, 1];
+ *                      every other pixel keeps its bits.
+ * N, P < 2^31 (NGP_EINVAL otherwise, nothing launched).  No atomics, no workspace, no global state. */
+NGP_API int ngp_overlay_cast(const float* rays_o, const float* rays_d, uint64_t N, const float* prims_host, const float* prims, uint32_t P,
+                             float t_min, const float* t_max, uint32_t frame_width, float* t, int32_t* prim, float* normal,
+                             ngp_stream_t stream);
+NGP_API int ngp_overlay_shade(const float* rays_d, const int32_t* prim, const float* normal, uint64_t N, const float* colors, uint32_t P,
+                              float ambient, float* image, uint8_t* image_u8, ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

@@ -22,6 +22,7 @@ __version__ = "0.1.0"
 
 from . import mesh  # noqa: E402,F401  (save_mesh, extract_geometry, isosurface)
 from . import cem  # noqa: E402,F401  (run_cem, refit, failure_probability, SeedableMultivariateNormal; rollout.run_validation dispatches to it)
+from . import replay  # noqa: E402,F401  (run_replay, ReplaySimulator, failure_view, read_results_csv, write_replay_csv)
 
 _DROPIN = ["raymarching", "gridencoder", "shencoder", "freqencoder", "ffmlp", "encoding", "activation"]
 

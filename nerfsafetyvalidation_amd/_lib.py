@@ -151,6 +151,8 @@ SIGNATURES = {
     "ngp_raycast_shade": [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u32, _vp, _u32, _f32, C.POINTER(C.c_float), _vp, _vp, _vp],
     "ngp_voxelize_count": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, _vp, _vp],
     "ngp_voxelize_mark": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, C.c_uint64, C.c_uint64, _vp, _vp],
+    "ngp_overlay_cast": [_vp, _vp, C.c_uint64, _vp, _vp, _u32, _f32, _vp, _u32, _vp, _vp, _vp, _vp],
+    "ngp_overlay_shade": [_vp, _vp, _vp, C.c_uint64, _vp, _u32, _f32, _vp, _vp, _vp],
     "ngp_sift_workspace": [_u32, _u32],
     "ngp_sift_layer_offset": [_u32, _u32, _int, _int],
     "ngp_sift_octaves": [_u32, _u32],

@@ -56,6 +56,37 @@ The voxelisation rule is the specification (written here once, implemented in vo
     Candidates: the result is defined over all cells of the box; an implementation may test any superset of the overlapping cells.
     Both test, per axis, the cells floor((min_k w_ka - start_a) g) - 1 .. floor((max_k w_ka - start_a) g) + 1, clipped to the box
     (face_candidates); voxelize_numpy(all_cells=True) tests every cell of the box instead, and gives the same map.
+
+The world can also be drawn with analytic primitives in it -- the replay's failure view (replay.failure_view; DESIGN.md "Failure
+replay"), in the place of the Blender scene of validation/utils/viz_failures_blend.py:
+
+        .cast_overlay(rays_o, rays_d, prims, t_max=None, t_min=0.0, frame_width=None)   -> {"t", "prim", "normal"}
+        .render_scene(pose, intrinsics, H, W, tubes=(), boxes=(), ...)                  -> render's dict + "overlay_prim"
+    overlay_prims(tubes, boxes)                                                         -> (prims float32 [P,8], colors float32 [P,3])
+
+A HIP world goes through csrc/overlay.hip, a CPU world through cast_overlay_numpy; the two agree bit for bit.  The primitive table
+holds 8 floats per primitive: kind, a.xyz, b.xyz, r -- kind 0 a capsule with the axis a-b and the radius r (a polyline of n points is
+n - 1 capsules), kind 1 an axis-aligned box with the centre a and the half extents b (r is not used by the rule).  Any other kind, a
+non-finite field or r <= 0 is a ValueError.  The overlay's hit rule per (ray, primitive), float32, one rounding per operation:
+    x . y = (x0 y0 + x1 y1) + x2 y2;  (x X y)_0 = x1 y2 - x2 y1 (and cyclic);  dd = d . d (d is not normalised), inv_dd = 1 / dd
+    re-centring on a point c: t0 = (d . (c - o)) inv_dd, o' = o + t0 d, p = o' - c;  an intersection is solved for o' and reported
+        as t = t0 + t' (the cancellation of the quadratics scales with the primitive's size, not the camera's distance)
+    capsule: ba = b - a, baba = ba . ba, rr = r r; three candidates t in this order, a later one replaces an earlier one only when
+        strictly smaller:
+        body      re-centred on m = (a + b) * 0.5: oa = p + (m - a);  u = ba X d, w = ba X oa, A = u . u, B = u . w,
+                  C = w . w - rr baba, h = B B - A C;  iff A > 0 and h >= 0: t' = (-B - sqrt(h)) / A, y = ba . oa + t' (ba . d);
+                  a candidate iff 0 < y < baba;  normal (oa + t' d) baba - ba y
+        cap at a  re-centred on a itself:  Bs = d . p, Cs = p . p - rr, hs = Bs Bs - dd Cs;  iff hs >= 0:
+                  t' = (-Bs - sqrt(hs)) / dd;  normal p + t' d
+        cap at b  the same, re-centred on b (two capsules of a polyline compute the same bits for their joint: it goes to the lower)
+        (nearer roots only: their smallest is where the line enters the capsule, so a ray that starts inside sees nothing of it;
+        a == b gives A = 0, a sphere)
+    box: re-centred on a; per axis k with d_k != 0: inv = 1 / d_k, t1 = (-b_k - p_k) inv, t2 = (b_k - p_k) inv, near = min, far = max;
+        with d_k == 0 a miss iff |p_k| > b_k, else unconstrained;  t' = the largest near (the first axis that attains it gives the
+        normal: its unit vector against d), a hit iff t' <= the smallest far
+    acceptance: accept iff t > t_min and t < t_max[ray] (NaN fails); the smallest t wins, equal t goes to the lowest primitive index;
+        a ray with a non-finite component or a zero direction is a miss: t = +inf, prim = -1, normal = 0.
+    t_max[ray] is the mesh cast's t of the same ray (+inf on a mesh miss): the depth merge with the world is part of the cast.
 """
 import ctypes
 
@@ -247,6 +278,173 @@ def _bg3(bg_color):
     if bg.shape != (3,):
         raise ValueError("bg_color is a scalar or three values")
     return bg
+
+
+# ------------------------------------------------------------------------------------------------------------- the overlay (numpy)
+PRIM_CAPSULE, PRIM_BOX = 0.0, 1.0
+_OVERLAY_CHUNK_PAIRS = 1 << 18                      # (ray, primitive) pairs per chunk of cast_overlay_numpy
+
+
+def check_prims(prims):
+    """the primitive table as float32 [P,8] numpy; ValueError for another shape, a kind other than 0 / 1, a non-finite field, r <= 0"""
+    q = np.array(prims.detach().cpu().numpy() if isinstance(prims, torch.Tensor) else prims, dtype=_f32, order="C")       # (a copy)
+    if q.size == 0:
+        return q.reshape(0, 8)
+    if q.ndim != 2 or q.shape[1] != 8:
+        raise ValueError(f"overlay: the primitive table is [P,8] (kind, a.xyz, b.xyz, r), got {q.shape}")
+    if q.shape[0] >= 2 ** 31:
+        raise ValueError("overlay: P must be < 2^31")
+    bad = ~np.isin(q[:, 0], (PRIM_CAPSULE, PRIM_BOX))
+    if bad.any():
+        raise ValueError(f"overlay: primitive {int(np.argmax(bad))} has kind {q[np.argmax(bad), 0]} (0: capsule, 1: box)")
+    if not np.isfinite(q).all():
+        raise ValueError(f"overlay: primitive {int(np.argmax(~np.isfinite(q).all(1)))} has a non-finite field")
+    if not (q[:, 7] > 0).all():
+        raise ValueError(f"overlay: primitive {int(np.argmax(~(q[:, 7] > 0)))} has r <= 0")
+    return q
+
+
+def overlay_prims(tubes=(), boxes=()):
+    """tubes: (points [n,3], radius, rgb) each -- a polyline, n - 1 capsules (one point: a sphere);  boxes: (centres [m,3], half [3] or
+    a scalar, rgb) each -- m axis-aligned boxes.  -> (prims float32 [P,8], colors float32 [P,3]), tubes first, in the given order"""
+    rows, cols = [], []
+    for points, radius, rgb in tubes:
+        pts = np.asarray(points, _f32).reshape(-1, 3)
+        if pts.shape[0] == 0:
+            continue
+        a, b = (pts[:-1], pts[1:]) if pts.shape[0] > 1 else (pts, pts)
+        n = a.shape[0]
+        rows.append(np.concatenate([np.full((n, 1), PRIM_CAPSULE, _f32), a, b, np.full((n, 1), radius, _f32)], 1))
+        cols.append(np.tile(np.asarray(rgb, _f32).reshape(1, 3), (n, 1)))
+    for centres, half, rgb in boxes:
+        c = np.asarray(centres, _f32).reshape(-1, 3)
+        n = c.shape[0]
+        h = np.broadcast_to(np.asarray(half, _f32).reshape(-1), (3,)) if np.size(half) in (1, 3) else None
+        if h is None:
+            raise ValueError("overlay_prims: a box's half extents are a scalar or three values")
+        rows.append(np.concatenate([np.full((n, 1), PRIM_BOX, _f32), c, np.tile(h[None], (n, 1)), np.ones((n, 1), _f32)], 1))
+        cols.append(np.tile(np.asarray(rgb, _f32).reshape(1, 3), (n, 1)))
+    if not rows:
+        return np.zeros((0, 8), _f32), np.zeros((0, 3), _f32)
+    return check_prims(np.concatenate(rows, 0)), np.ascontiguousarray(np.concatenate(cols, 0), _f32)
+
+
+def overlay_terms(o, d, prims, recentre=True):
+    """the overlay rule's t and normal for every (ray, primitive) before acceptance: o, d [R,3], prims [P,8] -> (t [R,P] (+inf: no
+    candidate), normal 3 x [R,P]), float32.  recentre=False solves for o itself (t0 = 0): NOT the rule,
+    the measurement DESIGN.md quotes as the reason for the re-centring."""
+    o, d, q = np.asarray(o, _f32), np.asarray(d, _f32), np.asarray(prims, _f32)
+    oc, dc = [o[:, None, k] for k in range(3)], [d[:, None, k] for k in range(3)]
+    kind, a, b, r = q[None, :, 0], [q[None, :, 1 + k] for k in range(3)], [q[None, :, 4 + k] for k in range(3)], q[None, :, 7]
+    capsule = kind == _f32(PRIM_CAPSULE)
+    inf, zero = _f32(np.inf), _f32(0)
+    with np.errstate(all="ignore"):
+        dd = _dot(dc, dc)
+        inv_dd = _f32(1.0) / dd
+
+        def centred(c):
+            t0 = _dot(dc, [c[k] - oc[k] for k in range(3)]) * inv_dd
+            if not recentre:
+                t0 = t0 * zero
+            return t0, [(oc[k] + t0 * dc[k]) - c[k] for k in range(3)]
+
+        # ---- capsule
+        m = [(a[k] + b[k]) * _f32(0.5) for k in range(3)]
+        t0, qm = centred(m)
+        ba = [b[k] - a[k] for k in range(3)]
+        oa = [qm[k] + (m[k] - a[k]) for k in range(3)]
+        baba, rr = _dot(ba, ba), r * r
+        u, w = _cross(ba, dc), _cross(ba, oa)
+        A, B = _dot(u, u), _dot(u, w)
+        C = _dot(w, w) - rr * baba
+        h = B * B - A * C
+        tp = (-B - np.sqrt(h)) / A
+        y = _dot(ba, oa) + tp * _dot(ba, dc)
+        body = (A > 0) & (h >= 0) & (y > 0) & (y < baba)
+        t = np.where(body, t0 + tp, inf)
+        n = [np.where(body, (oa[k] + tp * dc[k]) * baba - ba[k] * y, zero) for k in range(3)]
+        for c in (a, b):
+            t0, p = centred(c)
+            Bs = _dot(dc, p)
+            Cs = _dot(p, p) - rr
+            hs = Bs * Bs - dd * Cs
+            tp = (-Bs - np.sqrt(hs)) / dd
+            tc = t0 + tp
+            take = (hs >= 0) & (tc < t)
+            t = np.where(take, tc, t)
+            n = [np.where(take, p[k] + tp * dc[k], n[k]) for k in range(3)]
+        # ---- box
+        t0, pb = centred(a)
+        t_near, t_far = np.full(t.shape, -np.inf, _f32), np.full(t.shape, np.inf, _f32)
+        axis, miss = np.zeros(t.shape, np.int64), np.zeros(t.shape, bool)
+        for k in range(3):
+            still = dc[k] == 0
+            miss |= still & (np.abs(pb[k]) > b[k])
+            inv = _f32(1.0) / dc[k]
+            t1, t2 = (-b[k] - pb[k]) * inv, (b[k] - pb[k]) * inv
+            lo, hi = np.fmin(t1, t2), np.fmax(t1, t2)
+            first = ~still & (lo > t_near)
+            t_near = np.where(first, lo, t_near)
+            axis = np.where(first, k, axis)
+            t_far = np.where(still, t_far, np.fmin(t_far, hi))
+        box_hit = ~miss & (t_near <= t_far)
+        d_axis = np.where(axis == 0, dc[0], np.where(axis == 1, dc[1], dc[2]))
+        sign = np.where(d_axis > 0, _f32(-1.0), _f32(1.0))
+        nb = [np.where(box_hit & (axis == k), sign, zero) for k in range(3)]
+        t = np.where(capsule, t, np.where(box_hit, t0 + t_near, inf))
+        n = [np.where(capsule, n[k], nb[k]) for k in range(3)]
+        return t.astype(_f32), [c.astype(_f32) for c in n]
+
+
+def cast_overlay_numpy(o, d, prims, t_max=None, t_min=0.0):
+    """the overlay rule, float32, chunked over (ray, primitive) pairs: o, d [N,3], prims [P,8], t_max [N] or None (+inf) ->
+    {"t" float32 [N] (+inf on a miss), "prim" int32 [N] (-1), "normal" float32 [N,3] (0)}"""
+    o, d = np.ascontiguousarray(o, _f32).reshape(-1, 3), np.ascontiguousarray(d, _f32).reshape(-1, 3)
+    q = check_prims(prims)
+    N, P = o.shape[0], q.shape[0]
+    far = np.full(N, np.inf, _f32) if t_max is None else np.ascontiguousarray(t_max, _f32).reshape(-1)
+    if far.shape[0] != N:
+        raise ValueError("cast_overlay: t_max is one value per ray")
+    t_min = _f32(t_min)
+    out = {"t": np.full(N, np.inf, _f32), "prim": np.full(N, -1, np.int32), "normal": np.zeros((N, 3), _f32)}
+    if P == 0 or N == 0:
+        return out
+    valid = np.isfinite(o).all(1) & np.isfinite(d).all(1) & (d != 0).any(1)
+    chunk = max(1, _OVERLAY_CHUNK_PAIRS // P)
+    for i0 in range(0, N, chunk):
+        sl = slice(i0, min(N, i0 + chunk))
+        t, n = overlay_terms(o[sl], d[sl], q)
+        with np.errstate(all="ignore"):
+            ok = (t > t_min) & (t < far[sl, None]) & valid[sl, None]
+        tm = np.where(ok, t, _f32(np.inf))
+        best = tm.min(1)
+        hit = ok.any(1)
+        prim = np.argmax(ok & (tm == best[:, None]), 1)            # the lowest index among the closest
+        rows = np.arange(prim.shape[0])
+        out["t"][sl] = np.where(hit, best, _f32(np.inf))
+        out["prim"][sl] = np.where(hit, prim, -1)
+        for k in range(3):
+            out["normal"][sl, k] = np.where(hit, n[k][rows, prim], _f32(0))
+    return out
+
+
+def shade_overlay_numpy(d, prim, normal, colors, ambient, image, image_u8):
+    """k_overlay_shade in numpy float32: copies of image [N,3] / image_u8 [N,3] with the overlay's pixels written over"""
+    d, n = np.asarray(d, _f32).reshape(-1, 3), np.asarray(normal, _f32).reshape(-1, 3)
+    prim, col = np.asarray(prim).reshape(-1), np.asarray(colors, _f32).reshape(-1, 3)
+    image, image_u8 = np.array(image, _f32).reshape(-1, 3), np.array(image_u8, np.uint8).reshape(-1, 3)
+    hit = (prim >= 0) & (prim < col.shape[0])
+    if not hit.any():
+        return image, image_u8
+    nc, dc = [n[:, k] for k in range(3)], [d[:, k] for k in range(3)]
+    with np.errstate(all="ignore"):
+        length = np.sqrt(_dot(nc, nc)) * np.sqrt(_dot(dc, dc))
+        cosine = np.where(length > 0, np.minimum(np.abs(_dot(nc, dc)) / length, _f32(1.0)), _f32(0)).astype(_f32)
+        shade = _f32(ambient) + (_f32(1.0) - _f32(ambient)) * cosine
+        rgb = np.minimum(np.maximum(col[np.where(hit, prim, 0)] * shade[:, None], _f32(0)), _f32(1.0)).astype(_f32)
+    image[hit] = rgb[hit]
+    image_u8[hit] = (np.clip(rgb[hit], 0, 1) * _f32(255.0)).astype(np.uint8)
+    return image, image_u8
 
 
 # ------------------------------------------------------------------------------------------------------------- the collision map
@@ -538,3 +736,84 @@ class MeshWorld:
         image, u8 = self.shade(d, hit, bg_color, ambient)
         depth = hit["t"] * torch.linalg.vector_norm(d, dim=-1)
         return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": hit["prim"].reshape(H, W)}
+
+    # ---- the overlay: analytic primitives drawn into the world (the replay's failure view)
+    def cast_overlay(self, rays_o, rays_d, prims, t_max=None, t_min=0.0, frame_width=None):
+        """rays [..., 3] against the primitive table prims [P,8] (the module's overlay rule) -> {"t" float32 (+inf on a miss), "prim"
+        int32 (-1), "normal" float32 [..., 3] (unnormalised, 0 on a miss)} on the world's device (numpy arrays for numpy rays on a CPU
+        world).  t_max: None (+inf) or the far limit per ray [...] -- a mesh cast's "t" of the same rays hides what lies behind the
+        mesh.  frame_width: cast's scheduling hint; the result does not depend on it."""
+        t_min = float(t_min)
+        if t_min != t_min:
+            raise ValueError("MeshWorld.cast_overlay: t_min is NaN")
+        q = check_prims(prims)
+        o, d, shape, tensors = self._rays(rays_o, rays_d)
+        N, P = o.shape[0], q.shape[0]
+        if frame_width is not None and (int(frame_width) < 1 or N % int(frame_width)):
+            raise ValueError(f"MeshWorld.cast_overlay: frame_width {frame_width} does not divide the {N} rays")
+        far = None
+        if t_max is not None:
+            far = torch.as_tensor(t_max).detach().to(self.device, torch.float32).reshape(-1).contiguous()
+            if far.shape[0] != N:
+                raise ValueError("MeshWorld.cast_overlay: t_max is one value per ray")
+        if self.device.type != "cuda":
+            out = cast_overlay_numpy(o.numpy(), d.numpy(), q, None if far is None else far.numpy(), t_min)
+            out = {k: a.reshape(shape + a.shape[1:]) for k, a in out.items()}
+            return {k: torch.from_numpy(a) for k, a in out.items()} if tensors else out
+        out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+               "normal": torch.empty(N, 3, dtype=torch.float32, device=self.device)}
+        if N:
+            with torch.cuda.device(self.device):
+                q_dev = torch.from_numpy(q).to(self.device) if P else None
+                _lib.check(_lib.lib().ngp_overlay_cast(_lib.ptr(o), _lib.ptr(d), N, q.ctypes.data if P else None, _lib.ptr(q_dev), P, t_min,
+                                                       _lib.ptr(far), int(frame_width or 0), _lib.ptr(out["t"]), _lib.ptr(out["prim"]),
+                                                       _lib.ptr(out["normal"]), _lib.stream()), "overlay_cast")
+        return {k: a.reshape(shape + tuple(a.shape[1:])) for k, a in out.items()}
+
+    def shade_overlay(self, rays_d, hit, colors, image, image_u8, ambient=DEFAULT_AMBIENT):
+        """a cast_overlay result drawn over a frame: where the overlay hit, the pixel of `image` (float32 [..., 3]) and `image_u8`
+        becomes colors[prim] (float [P,3]) times shade's two-sided headlight on the hit's normal, with the same uint8 quantisation;
+        every other pixel keeps its bits -> new (image, image_u8), the inputs are not written"""
+        if not 0.0 <= float(ambient) <= 1.0:
+            raise ValueError("MeshWorld.shade_overlay: ambient must be in [0, 1]")
+        col = np.ascontiguousarray(colors.detach().cpu().numpy() if isinstance(colors, torch.Tensor) else colors, _f32).reshape(-1, 3)
+        tensors = isinstance(image, torch.Tensor)
+        d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
+        shape = tuple(d.shape[:-1])
+        d = d.reshape(-1, 3).contiguous()
+        N, P = d.shape[0], col.shape[0]
+        prim = torch.as_tensor(hit["prim"]).to(self.device, torch.int32).reshape(-1).contiguous()
+        normal = torch.as_tensor(hit["normal"]).to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        img = torch.as_tensor(image).to(self.device, torch.float32).reshape(-1, 3)
+        u8 = torch.as_tensor(image_u8).to(self.device, torch.uint8).reshape(-1, 3)
+        if prim.shape[0] != N or img.shape[0] != N or u8.shape[0] != N:
+            raise ValueError("MeshWorld.shade_overlay: the hit record and the frame are not of these rays")
+        if self.device.type != "cuda":
+            img, u8 = shade_overlay_numpy(d.numpy(), prim.numpy(), normal.numpy(), col, ambient, img.numpy(), u8.numpy())
+            img, u8 = img.reshape(shape + (3,)), u8.reshape(shape + (3,))
+            return (torch.from_numpy(img), torch.from_numpy(u8)) if tensors else (img, u8)
+        img, u8 = img.clone().contiguous(), u8.clone().contiguous()
+        if N and P:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().ngp_overlay_shade(_lib.ptr(d), _lib.ptr(prim), _lib.ptr(normal), N, _lib.ptr(torch.from_numpy(col).to(self.device)),
+                                                        P, float(ambient), _lib.ptr(img), _lib.ptr(u8), _lib.stream()), "overlay_shade")
+        return img.reshape(shape + (3,)), u8.reshape(shape + (3,))
+
+    def render_scene(self, pose, intrinsics, H, W, tubes=(), boxes=(), bg_color=1.0, ambient=DEFAULT_AMBIENT):
+        """render() with analytic primitives in the scene -- the replay's failure view.  tubes: (points [n,3], radius, rgb) each;
+        boxes: (centres [m,3], half [3], rgb) each, in the mesh's axes (overlay_prims).  -> render's dict (image / image_u8 with the
+        primitives drawn over the world where they are nearer than the mesh, depth the nearer of the two, prim the MESH's triangle) plus
+        "overlay_prim" int32 [H,W]: the primitive's index (tubes first, in the given order), -1 where the mesh or the background
+        shows.  Without primitives every entry equals render()'s bit for bit."""
+        from .nerf.utils import get_rays
+        prims, colors = overlay_prims(tubes, boxes)
+        pose = torch.as_tensor(pose).detach().to(self.device, torch.float32).reshape(1, 4, 4)
+        rays = get_rays(pose, intrinsics, H, W)
+        o, d = rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3)
+        hit = self.cast(o, d, frame_width=W)
+        image, u8 = self.shade(d, hit, bg_color, ambient)
+        over = self.cast_overlay(o, d, prims, t_max=hit["t"], frame_width=W)
+        image, u8 = self.shade_overlay(d, over, colors, image, u8, ambient)
+        depth = torch.minimum(hit["t"], over["t"]) * torch.linalg.vector_norm(d, dim=-1)
+        return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": hit["prim"].reshape(H, W),
+                "overlay_prim": over["prim"].reshape(H, W)}
