@@ -1,0 +1,54 @@
+// What the mesh cast and the overlay cast must compute with the same bits (the rules are nerfsafetyvalidation_amd/world.py's
+// docstring): the dot product's grouping, the thread -> ray mapping, the headlight, a pixel's two stores, and the host's
+// frame_width plan.  Included by raycast.hip and overlay.hip only.
+#pragma once
+#include "ngp_common.hpp"
+
+namespace ngp {
+
+constexpr uint32_t kCastBlock = 256;
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// ray index of this thread: row-major, or the 8 x 8 pixel tile form when the rays are whole rows of width W (a wave's rays then walk
+// the same cells).  false: this thread has no ray -- the caller's business: k_raycast returns, k_overlay_cast must not.
+__device__ __forceinline__ bool ray_of_thread(uint32_t N, uint32_t W, uint32_t& ray) {
+    const uint32_t tid = blockIdx.x * kCastBlock + threadIdx.x;
+    if (W == 0) {
+        ray = tid;
+        return tid < N;
+    }
+    const uint32_t H = N / W, tiles_x = (W + 7) / 8;
+    const uint32_t tile = tid >> 6, lane = tid & 63u;
+    const uint32_t px = (tile % tiles_x) * 8 + (lane & 7u), py = (tile / tiles_x) * 8 + (lane >> 3);
+    ray = py * W + px;
+    return px < W && py < H;
+}
+
+// ambient + (1 - ambient) |n . d| / (|n| |d|), the cosine clamped to 1 and 0 where a length is: two-sided, neither vector normalised
+__device__ __forceinline__ float headlight(float nx, float ny, float nz, float dx, float dy, float dz, float ambient) {
+    const float len = sqrtf(dot3(nx, ny, nz, nx, ny, nz)) * sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+    const float c = len > 0.0f ? fminf(fabsf(dot3(nx, ny, nz, dx, dy, dz)) / len, 1.0f) : 0.0f;
+    return ambient + (1.0f - ambient) * c;
+}
+
+// channel k of pixel r: the float, and its uint8 copy (uint8)(clamp(x, 0, 1) * 255)
+__device__ __forceinline__ void store_rgb(float* __restrict__ image, uint8_t* __restrict__ image_u8, uint32_t r, int k, float x) {
+    image[3 * (size_t)r + k] = x;
+    image_u8[3 * (size_t)r + k] = (uint8_t)(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f);
+}
+
+// host: the threads of a cast over N rays.  frame_width must divide N; a frame too thin for tiles (the hint only schedules) goes
+// row-major: frame_width comes back as 0.
+static inline int cast_plan(const char* what, uint64_t N, uint32_t& frame_width, uint32_t& threads) {
+    threads = (uint32_t)N;
+    if (frame_width) {
+        NGP_REQUIRE(N % frame_width == 0, "%s: frame_width %u does not divide N = %llu", what, frame_width, (unsigned long long)N);
+        const uint64_t tiles = (uint64_t)((frame_width + 7) / 8) * ((N / frame_width + 7) / 8);
+        if (tiles * 64 >= ((uint64_t)1 << 31)) frame_width = 0;
+        else threads = (uint32_t)(tiles * 64);
+    }
+    return NGP_OK;
+}
+
+}  // namespace ngp

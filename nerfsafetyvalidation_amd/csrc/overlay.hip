@@ -3,57 +3,32 @@
 // reference's runBlenderOnFailure -> validation/utils/viz_failures_blend.py builds (plans as tubes of radius 0.02, the drone's
 // positions as cubes of half extent 0.0125).
 //
-// The primitive table: 8 floats per primitive, kind, a.xyz, b.xyz, r.  Kind 0: a capsule with the axis a-b and the radius r (a
-// polyline of n points is n - 1 capsules: the joints are round).  Kind 1: an axis-aligned box with the centre a and the half extents b
-// (r is not used by the rule; it is validated like any field).
+// The primitive table (8 floats per primitive: kind, a.xyz, b.xyz, r), the hit rule per (ray, primitive), the acceptance and the depth
+// merge through t_max[ray] are world.py's docstring ("The overlay's hit rule"); overlay_test is that text in float32 with one rounding
+// per operation, in its order (this unit is compiled with -ffp-contract=off, holds no fused multiply-add, and uses the correctly
+// rounded division and square root).
 //
-// The hit rule per (ray, primitive) (DESIGN.md "Failure replay"; world.py's numpy path is the same rule: float32, one rounding per
-// operation, the same order; this unit is compiled with -ffp-contract=off, holds no fused multiply-add, and uses the correctly rounded
-// division and square root):
-//   x . y = (x0 y0 + x1 y1) + x2 y2;  (x X y)_0 = x1 y2 - x2 y1, and cyclic;  dd = d . d (d is not normalised), inv_dd = 1 / dd
-//   re-centring on a point c: t0 = (d . (c - o)) inv_dd, o' = o + t0 d, p = o' - c.  An intersection is solved for o', the point of
-//     the ray's line closest to c, and reported as t = t0 + t': the quadratics' cancellation scales with the primitive's size, not
-//     with the camera's distance.
-//   capsule: ba = b - a, baba = ba . ba, rr = r r; three candidates t, the smallest wins (in this order, a later one only when
-//     strictly smaller):
-//       body      re-centred on m = (a + b) * 0.5: oa = p + (m - a);  u = ba X d, w = ba X oa, A = u . u, B = u . w,
-//                 C = w . w - rr baba, h = B B - A C;  iff A > 0 and h >= 0: t' = (-B - sqrt(h)) / A, y = ba . oa + t' (ba . d);
-//                 a candidate iff 0 < y < baba;  normal (oa + t' d) baba - ba y
-//       cap at a  re-centred on a itself:  Bs = d . p, Cs = p . p - rr, hs = Bs Bs - dd Cs;  iff hs >= 0:
-//                 t' = (-Bs - sqrt(hs)) / dd;  normal p + t' d
-//       cap at b  the same, re-centred on b (two capsules of a polyline compute the same bits for their joint: it goes to the lower)
-//     Only nearer roots: the smallest of them is where the ray's line enters the (convex) capsule, so a ray that starts inside gets a
-//     t <= 0 and sees nothing of the primitive.  a == b gives A = 0: a sphere, no division by zero.
-//   box: re-centred on a; per axis k with d_k != 0: inv = 1 / d_k, t1 = (-b_k - p_k) inv, t2 = (b_k - p_k) inv, near = min, far = max;
-//     with d_k == 0: a miss iff |p_k| > b_k, else the axis does not constrain.  t' = the largest near (the entry; the first axis that
-//     attains it gives the normal, its unit vector against d), a hit iff t' <= the smallest far.
-//   acceptance: accept iff t > t_min && t < t_max[ray] (NaN fails);  the smallest t wins, equal t goes to the lowest primitive
-//     index;  a ray with a non-finite component or a zero direction is a miss: t = +inf, prim = -1, normal = 0.
-//   t_max[ray] is the mesh cast's t of the same ray (+inf where it missed): the depth merge with the world is part of this cast.
-//
-// k_overlay_cast: one lane per ray, 256-thread workgroups (with frame_width a wave takes an 8 x 8 pixel tile, as k_raycast).  The
+// k_overlay_cast: one lane per ray, 256-thread workgroups (ray_of_thread: with frame_width a wave takes an 8 x 8 pixel tile).  The
 // workgroup stages the table through LDS in chunks of 256 records (8 KB); every lane then walks the chunk reading the same address --
 // an LDS broadcast, no bank conflicts.  NO LANE LEAVES BEFORE THE LAST BARRIER: a thread with no ray, or a ray that can no longer be
 // hit (t_max <= t_min), stays in the loop masked; the barrier count depends on P alone.  No atomics; the result per ray does not
 // depend on the chunking.
-#include "ngp_common.hpp"
+#include "cast_common.hpp"
 
 namespace ngp {
 
-constexpr uint32_t kOverlayBlock = 256;
-constexpr uint32_t kOverlayChunk = 256;      // records per LDS chunk: one per thread of the workgroup
+constexpr uint32_t kOverlayChunk = 256;      // records per LDS chunk
+static_assert(kOverlayChunk == kCastBlock, "the staging loop of k_overlay_cast loads one record per thread of the workgroup");
 
 struct OverlayHit {
     float t, nx, ny, nz;
     int32_t prim;
 };
 
-__device__ __forceinline__ float odot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
 // re-centring on c: t0 = (d . (c - o)) inv_dd, o' = o + t0 d -> p = o' - c (the point of the ray's line closest to c, seen from c)
 __device__ __forceinline__ float overlay_recentre(float cx, float cy, float cz, float ox, float oy, float oz, float dx, float dy, float dz,
                                                   float inv_dd, float& px, float& py, float& pz) {
-    const float t0 = odot(dx, dy, dz, cx - ox, cy - oy, cz - oz) * inv_dd;
+    const float t0 = dot3(dx, dy, dz, cx - ox, cy - oy, cz - oz) * inv_dd;
     px = (ox + t0 * dx) - cx;
     py = (oy + t0 * dy) - cy;
     pz = (oz + t0 * dz) - cz;
@@ -66,8 +41,8 @@ __device__ __forceinline__ void overlay_cap(float cx, float cy, float cz, float 
                                             float inv_dd, float rr, float& t_best, float& nx, float& ny, float& nz) {
     float px, py, pz;
     const float t0 = overlay_recentre(cx, cy, cz, ox, oy, oz, dx, dy, dz, inv_dd, px, py, pz);
-    const float Bs = odot(dx, dy, dz, px, py, pz);
-    const float Cs = odot(px, py, pz, px, py, pz) - rr;
+    const float Bs = dot3(dx, dy, dz, px, py, pz);
+    const float Cs = dot3(px, py, pz, px, py, pz) - rr;
     const float hs = Bs * Bs - dd * Cs;
     if (hs >= 0.0f) {
         const float tp = (-Bs - sqrtf(hs)) / dd;
@@ -94,17 +69,17 @@ __device__ __forceinline__ void overlay_test(const float4 ka, const float4 br, i
         const float t0 = overlay_recentre(mx, my, mz, ox, oy, oz, dx, dy, dz, inv_dd, qx, qy, qz);
         const float bax = bx - ax, bay = by - ay, baz = bz - az;
         const float oax = qx + (mx - ax), oay = qy + (my - ay), oaz = qz + (mz - az);
-        const float baba = odot(bax, bay, baz, bax, bay, baz), rr = r * r;
+        const float baba = dot3(bax, bay, baz, bax, bay, baz), rr = r * r;
         const float ux = bay * dz - baz * dy, uy = baz * dx - bax * dz, uz = bax * dy - bay * dx;
-        const float A = odot(ux, uy, uz, ux, uy, uz);
+        const float A = dot3(ux, uy, uz, ux, uy, uz);
         if (A > 0.0f) {
             const float wx = bay * oaz - baz * oay, wy = baz * oax - bax * oaz, wz = bax * oay - bay * oax;
-            const float B = odot(ux, uy, uz, wx, wy, wz);
-            const float C = odot(wx, wy, wz, wx, wy, wz) - rr * baba;
+            const float B = dot3(ux, uy, uz, wx, wy, wz);
+            const float C = dot3(wx, wy, wz, wx, wy, wz) - rr * baba;
             const float h = B * B - A * C;
             if (h >= 0.0f) {
                 const float tp = (-B - sqrtf(h)) / A;
-                const float y = odot(bax, bay, baz, oax, oay, oaz) + tp * odot(bax, bay, baz, dx, dy, dz);
+                const float y = dot3(bax, bay, baz, oax, oay, oaz) + tp * dot3(bax, bay, baz, dx, dy, dz);
                 if (y > 0.0f && y < baba) {
                     t = t0 + tp;
                     nx = (oax + tp * dx) * baba - bax * y;
@@ -148,29 +123,13 @@ __device__ __forceinline__ void overlay_test(const float4 ka, const float4 br, i
     if (t > t_min && t < t_max && t < best.t) best = OverlayHit{t, nx, ny, nz, index};
 }
 
-// ray index of this thread: row-major, or k_raycast's 8 x 8 pixel tile form when the rays are whole rows of width W.  Never a reason
-// to return: the caller keeps a thread without a ray in the loop, masked.
-__device__ __forceinline__ bool overlay_ray_of_thread(uint32_t N, uint32_t W, uint32_t& ray) {
-    const uint32_t tid = blockIdx.x * kOverlayBlock + threadIdx.x;
-    if (W == 0) {
-        ray = tid;
-        return tid < N;
-    }
-    const uint32_t H = N / W, tiles_x = (W + 7) / 8;
-    const uint32_t tile = tid >> 6, lane = tid & 63u;
-    const uint32_t px = (tile % tiles_x) * 8 + (lane & 7u), py = (tile / tiles_x) * 8 + (lane >> 3);
-    ray = py * W + px;
-    return px < W && py < H;
-}
-
-__global__ void __launch_bounds__(kOverlayBlock) k_overlay_cast(const float* __restrict__ rays_o, const float* __restrict__ rays_d, uint32_t N,
-                                                                const float4* __restrict__ prims, uint32_t P, float t_min,
-                                                                const float* __restrict__ t_max, uint32_t frame_width,
-                                                                float* __restrict__ out_t, int32_t* __restrict__ out_prim,
-                                                                float* __restrict__ out_normal) {
+__global__ void __launch_bounds__(kCastBlock) k_overlay_cast(const float* __restrict__ rays_o, const float* __restrict__ rays_d, uint32_t N,
+                                                             const float4* __restrict__ prims, uint32_t P, float t_min,
+                                                             const float* __restrict__ t_max, uint32_t frame_width, float* __restrict__ out_t,
+                                                             int32_t* __restrict__ out_prim, float* __restrict__ out_normal) {
     __shared__ float4 s_ka[kOverlayChunk], s_br[kOverlayChunk];
     uint32_t r = 0;
-    const bool has_ray = overlay_ray_of_thread(N, frame_width, r);
+    const bool has_ray = ray_of_thread(N, frame_width, r);      // never a reason to return: NO LANE LEAVES BEFORE THE LAST BARRIER
     float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, far = 0.0f;
     if (has_ray) {
 #pragma unroll
@@ -183,7 +142,7 @@ __global__ void __launch_bounds__(kOverlayBlock) k_overlay_cast(const float* __r
     const bool finite = isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
     const bool moving = d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f;
     const bool active = has_ray && finite && moving && far > t_min;      // (masked, not gone: the barriers below need every lane)
-    const float dd = odot(d[0], d[1], d[2], d[0], d[1], d[2]), inv_dd = 1.0f / dd;
+    const float dd = dot3(d[0], d[1], d[2], d[0], d[1], d[2]), inv_dd = 1.0f / dd;
     OverlayHit best{INFINITY, 0.0f, 0.0f, 0.0f, -1};
 
     for (uint32_t base = 0; base < P; base += kOverlayChunk) {           // (uniform: P is the same for every thread)
@@ -208,27 +167,20 @@ __global__ void __launch_bounds__(kOverlayBlock) k_overlay_cast(const float* __r
     }
 }
 
-// where the overlay hit: the primitive's colour times ambient + (1 - ambient) |n . d| / (|n| |d|) (k_raycast_shade's two-sided
-// headlight and quantisation) over the world's pixel; every other pixel keeps its bits
-__global__ void __launch_bounds__(kOverlayBlock) k_overlay_shade(const float* __restrict__ rays_d, const int32_t* __restrict__ prim,
-                                                                 const float* __restrict__ normal, uint32_t N, const float* __restrict__ colors,
-                                                                 uint32_t P, float ambient, float* __restrict__ image,
-                                                                 uint8_t* __restrict__ image_u8) {
-    const uint32_t r = blockIdx.x * kOverlayBlock + threadIdx.x;
+// where the overlay hit: the primitive's colour times the headlight on the hit's normal over the world's pixel; every other pixel
+// keeps its bits
+__global__ void __launch_bounds__(kCastBlock) k_overlay_shade(const float* __restrict__ rays_d, const int32_t* __restrict__ prim,
+                                                              const float* __restrict__ normal, uint32_t N, const float* __restrict__ colors,
+                                                              uint32_t P, float ambient, float* __restrict__ image, uint8_t* __restrict__ image_u8) {
+    const uint32_t r = blockIdx.x * kCastBlock + threadIdx.x;
     if (r >= N) return;
     const int32_t f = prim[r];
     if (f < 0 || (uint32_t)f >= P) return;
     const float dx = rays_d[3 * (size_t)r], dy = rays_d[3 * (size_t)r + 1], dz = rays_d[3 * (size_t)r + 2];
     const float nx = normal[3 * (size_t)r], ny = normal[3 * (size_t)r + 1], nz = normal[3 * (size_t)r + 2];
-    const float len = sqrtf(odot(nx, ny, nz, nx, ny, nz)) * sqrtf(odot(dx, dy, dz, dx, dy, dz));
-    const float c = len > 0.0f ? fminf(fabsf(odot(nx, ny, nz, dx, dy, dz)) / len, 1.0f) : 0.0f;
-    const float shade = ambient + (1.0f - ambient) * c;
+    const float shade = headlight(nx, ny, nz, dx, dy, dz, ambient);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float v = fminf(fmaxf(colors[3 * (size_t)f + k] * shade, 0.0f), 1.0f);
-        image[3 * (size_t)r + k] = v;
-        image_u8[3 * (size_t)r + k] = (uint8_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);
-    }
+    for (int k = 0; k < 3; k++) store_rgb(image, image_u8, r, k, fminf(fmaxf(colors[3 * (size_t)f + k] * shade, 0.0f), 1.0f));
 }
 
 }  // namespace ngp
@@ -252,17 +204,13 @@ int ngp_overlay_cast(const float* rays_o, const float* rays_d, uint64_t N, const
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(rays_o && rays_d && t && prim && normal, "overlay_cast: null pointer");
     NGP_REQUIRE(((uintptr_t)prims & 15) == 0, "overlay_cast: the primitive table must be 16-byte aligned");
-    uint32_t threads = (uint32_t)N;
-    if (frame_width) {
-        NGP_REQUIRE(N % frame_width == 0, "overlay_cast: frame_width %u does not divide N = %llu", frame_width, (unsigned long long)N);
-        const uint64_t tiles = (uint64_t)((frame_width + 7) / 8) * ((N / frame_width + 7) / 8);
-        if (tiles * 64 >= ((uint64_t)1 << 31)) frame_width = 0;      // (a hint: a frame too thin for tiles goes row-major)
-        else threads = (uint32_t)(tiles * 64);
-    }
+    uint32_t threads;
+    const int rc = cast_plan("overlay_cast", N, frame_width, threads);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("overlay_cast", s, (double)N * (double)P);
-    k_overlay_cast<<<div_up(threads, kOverlayBlock), kOverlayBlock, 0, s>>>(rays_o, rays_d, (uint32_t)N, reinterpret_cast<const float4*>(prims), P,
-                                                                           t_min, t_max, frame_width, t, prim, normal);
+    k_overlay_cast<<<div_up(threads, kCastBlock), kCastBlock, 0, s>>>(rays_o, rays_d, (uint32_t)N, reinterpret_cast<const float4*>(prims), P,
+                                                                     t_min, t_max, frame_width, t, prim, normal);
     return check_launch("overlay_cast");
 }
 
@@ -275,8 +223,8 @@ int ngp_overlay_shade(const float* rays_d, const int32_t* prim, const float* nor
     NGP_REQUIRE(rays_d && prim && normal && colors && image && image_u8, "overlay_shade: null pointer");
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("overlay_shade", s, (double)N);
-    k_overlay_shade<<<div_up((uint32_t)N, kOverlayBlock), kOverlayBlock, 0, s>>>(rays_d, prim, normal, (uint32_t)N, colors, P, ambient, image,
-                                                                                image_u8);
+    k_overlay_shade<<<div_up((uint32_t)N, kCastBlock), kCastBlock, 0, s>>>(rays_d, prim, normal, (uint32_t)N, colors, P, ambient, image,
+                                                                          image_u8);
     return check_launch("overlay_shade");
 }
 

@@ -1,13 +1,9 @@
 // raycast.hip -- rays against a triangle mesh (nerfsafetyvalidation_amd/world.py): the ground-truth camera of the safety-validation
 // loop, in the place of the Blender subprocess of the reference's second simulator (validation/simulators/BlenderSimulator.py:82,102).
 //
-// The hit rule (DESIGN.md "The ground-truth world"; world.py's numpy path is the same rule, float32, one rounding per operation; this
-// unit is compiled with -ffp-contract=off and holds no fmaf):
-//   per-triangle data v0, e1 = v1 - v0, e2 = v2 - v0 (packed once by the caller, three 16-byte rows per triangle);
-//   p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det (correctly rounded), s = o - v0, u = (s . p) * inv, q = s x e1,
-//   v = (d . q) * inv, t = (e2 . q) * inv; a . b = (ax bx + ay by) + az bz; (a x b).x = ay bz - az by, and cyclic;
-//   accept iff u >= 0 && v >= 0 && u + v <= 1 && t > t_min && t < t_max (NaN fails); the closest hit is the smallest t, equal t
-//   goes to the lowest triangle index.  A ray with a non-finite component or a zero direction is a miss.
+// The hit rule and the shading are world.py's docstring ("The hit rule", "Shading"); test_triangle and k_raycast_shade are that text in
+// float32 with one rounding per operation, in its order (this unit is compiled with -ffp-contract=off and holds no fmaf).  The
+// per-triangle data v0, e1, e2 are packed once by the caller, three 16-byte rows per triangle.
 // The grid only chooses WHICH triangles a ray is tested against; the arithmetic per (ray, triangle) is fixed.
 //
 // Acceleration structure: a uniform grid over the (padded) bounding box, built without atomics in the count -> scan -> emit form of
@@ -23,11 +19,10 @@
 // instead (bounded by F): the coverage argument needs the DDA's rounding to stay far below grid.grow, and that holds only for
 // ordinary rays near the box.
 // With frame_width the 64 lanes of a wave take an 8 x 8 pixel tile of the row-major frame, so a wave's rays walk the same cells.
-#include "ngp_common.hpp"
+#include "cast_common.hpp"
 
 namespace ngp {
 
-constexpr uint32_t kCastBlock = 256;
 constexpr uint32_t kMaxCellsPerAxis = 256;
 
 struct CastHit {
@@ -43,8 +38,6 @@ __device__ __forceinline__ Tri load_tri(const float4* __restrict__ tri_data, uin
     const float4 a = tri_data[3 * (size_t)f], b = tri_data[3 * (size_t)f + 1], c = tri_data[3 * (size_t)f + 2];
     return Tri{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
 }
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 // the hit rule for one (ray, triangle); updates `best` under (smallest t, then lowest index)
 __device__ __forceinline__ void test_triangle(const Tri& T, int32_t f, float ox, float oy, float oz, float dx, float dy, float dz, float t_min,
@@ -109,20 +102,6 @@ __global__ void __launch_bounds__(kCastBlock) k_bin_emit(const float4* __restric
                 pair_cell[k] = (int32_t)((x * G.n[1] + y) * G.n[2] + z);
                 pair_tri[k] = (int32_t)f;
             }
-}
-
-// ray index of this thread: row-major, or the 8 x 8 pixel tile form when the rays are whole rows of width W
-__device__ __forceinline__ bool ray_of_thread(uint32_t N, uint32_t W, uint32_t& ray) {
-    const uint32_t tid = blockIdx.x * kCastBlock + threadIdx.x;
-    if (W == 0) {
-        ray = tid;
-        return tid < N;
-    }
-    const uint32_t H = N / W, tiles_x = (W + 7) / 8;
-    const uint32_t tile = tid >> 6, lane = tid & 63u;
-    const uint32_t px = (tile % tiles_x) * 8 + (lane & 7u), py = (tile / tiles_x) * 8 + (lane >> 3);
-    ray = py * W + px;
-    return px < W && py < H;
 }
 
 __global__ void __launch_bounds__(kCastBlock) k_raycast(const float* __restrict__ rays_o, const float* __restrict__ rays_d, uint32_t N,
@@ -212,8 +191,7 @@ __global__ void __launch_bounds__(kCastBlock) k_raycast(const float* __restrict_
     out_v[r] = best.v;
 }
 
-// colour = (((1 - u) - v) c0 + u c1) + v c2 of the vertex colours (mid-grey without), times ambient + (1 - ambient) |n . d| / (|n| |d|)
-// with n = e1 x e2 (a headlight, two-sided), clamped to [0, 1]; a miss is the background; the uint8 copy is (uint8)(x * 255)
+// the barycentric blend of the vertex colours (mid-grey without) times the headlight on n = e1 x e2; a miss is the background
 __global__ void __launch_bounds__(kCastBlock) k_raycast_shade(const float* __restrict__ rays_d, const int32_t* __restrict__ prim,
                                                               const float* __restrict__ hit_u, const float* __restrict__ hit_v, uint32_t N,
                                                               const float4* __restrict__ tri_data, const int32_t* __restrict__ faces, uint32_t F,
@@ -236,17 +214,12 @@ __global__ void __launch_bounds__(kCastBlock) k_raycast_shade(const float* __res
         }
         const float dx = rays_d[3 * (size_t)r], dy = rays_d[3 * (size_t)r + 1], dz = rays_d[3 * (size_t)r + 2];
         const float nx = T.e1y * T.e2z - T.e1z * T.e2y, ny = T.e1z * T.e2x - T.e1x * T.e2z, nz = T.e1x * T.e2y - T.e1y * T.e2x;
-        const float len = sqrtf(dot3(nx, ny, nz, nx, ny, nz)) * sqrtf(dot3(dx, dy, dz, dx, dy, dz));
-        const float c = len > 0.0f ? fminf(fabsf(dot3(nx, ny, nz, dx, dy, dz)) / len, 1.0f) : 0.0f;
-        const float shade = ambient + (1.0f - ambient) * c;
+        const float shade = headlight(nx, ny, nz, dx, dy, dz, ambient);
 #pragma unroll
         for (int k = 0; k < 3; k++) rgb[k] = fminf(fmaxf(col[k] * shade, 0.0f), 1.0f);
     }
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        image[3 * (size_t)r + k] = rgb[k];
-        image_u8[3 * (size_t)r + k] = (uint8_t)(fminf(fmaxf(rgb[k], 0.0f), 1.0f) * 255.0f);
-    }
+    for (int k = 0; k < 3; k++) store_rgb(image, image_u8, r, k, rgb[k]);
 }
 
 static int cast_check_grid(const char* what, const ngp_raycast_grid* G) {
@@ -305,13 +278,9 @@ int ngp_raycast(const float* rays_o, const float* rays_d, uint64_t N, const ngp_
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(rays_o && rays_d && cell_start && pair_tri && tri_data && t && prim && u && v, "raycast: null pointer");
     NGP_REQUIRE(((uintptr_t)tri_data & 15) == 0, "raycast: tri_data must be 16-byte aligned");
-    uint32_t threads = (uint32_t)N;
-    if (frame_width) {
-        NGP_REQUIRE(N % frame_width == 0, "raycast: frame_width %u does not divide N = %llu", frame_width, (unsigned long long)N);
-        const uint64_t tiles = (uint64_t)((frame_width + 7) / 8) * ((N / frame_width + 7) / 8);
-        if (tiles * 64 >= ((uint64_t)1 << 31)) frame_width = 0;      // (a hint: a frame too thin for tiles goes row-major)
-        else threads = (uint32_t)(tiles * 64);
-    }
+    uint32_t threads;
+    rc = cast_plan("raycast", N, frame_width, threads);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("raycast", s, (double)N);
     k_raycast<<<div_up(threads, kCastBlock), kCastBlock, 0, s>>>(rays_o, rays_d, (uint32_t)N, *grid, cell_start, pair_tri, (uint32_t)P,

@@ -3,20 +3,10 @@
 // the cells that hold a mesh VERTEX; this unit marks every cell a TRIANGLE touches (a conservative surface voxelisation), so a
 // triangle larger than a cell leaves no hole.
 //
-// The rule (DESIGN.md "The ground-truth collision field"; world.py's numpy path is the same rule and the two agree cell for cell).
-// A vertex x (float32, the NeRF's axes) goes to the world frame by a signed permutation, w_a = sign_a * x[axis_a]: exact.  Everything
-// after that is float64, one IEEE rounding per operation (this unit is compiled with -ffp-contract=off and holds no fma):
-//   cell (i, j, k): centre c_a = start_a + (i_a + 0.5) / g, half-width h = 0.5 / g;
-//   face (v0, v1, v2): e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2 and n = e0 x e1 from the world vertices (not from the shifted ones: the
-//   same for every cell); v_k' = v_k - c;  a . b = (ax bx + ay by) + az bz, (a x b).x = ay bz - az by (and cyclic);
-//   the cell is marked iff no axis of the 13 separates (all strict: touching is overlap; a zero axis separates nothing):
-//     box axis a      min_k v'_ka > h  or  max_k v'_ka < -h
-//     the normal      |n . v_0'| > h ((|nx| + |ny|) + |nz|)
-//     u_i x e_j       p_k = a . v_k', r = h ((|ax| + |ay|) + |az|):  min_k p_k > r  or  max_k p_k < -r   (the zero component of a
-//                     drops out of both sums exactly, so they are written as the two-term sums they are)
-//   or one of the face's vertices lies in the cell: i_a = floor((w_a - start_a) * g), inside the box.
-// Candidates: per axis the cells floor((min_k w_ka - start_a) * g) - 1 .. floor((max_k w_ka - start_a) * g) + 1, clipped to the box --
-// a superset of the cells the face can overlap; which superset is tested changes no result.
+// The voxelisation rule -- the signed permutation into the world frame, the 13-axis separating test, the vertex cells, the candidate
+// cells -- is world.py's docstring ("The voxelisation rule"); vox_overlaps and vox_range are that text in float64 with one IEEE rounding
+// per operation, in its order (this unit is compiled with -ffp-contract=off and holds no fma).  The zero component of an axis u_i x e_j
+// drops out of both of its sums exactly, so they are written as the two-term sums they are.
 //
 // Work is split by (face, candidate cell) pair, not by face -- one face spanning the box does not serialise on a lane:
 //   k_voxel_count   one lane per face: its number of candidates; marks its vertices' cells

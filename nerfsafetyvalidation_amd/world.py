@@ -12,13 +12,22 @@ nerf.utils.get_rays (so a world frame and a NeRF frame of one pose are pixel-ali
 A mesh on a HIP device goes through csrc/raycast.hip (a uniform grid, one lane per ray) on the current stream; a CPU tensor or a numpy
 array through numpy: brute force over all triangles, chunked -- the package's CPU implementation, as mesh.isosurface has one.
 
-The hit rule is the specification; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
+This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip and DESIGN.md point
+here, and a change to a rule is made in this text, in the numpy path and in the kernel.
+
+The hit rule; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
     per triangle v0, e1 = v1 - v0, e2 = v2 - v0;  p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det, s = o - v0,
     u = (s . p) * inv, q = s x e1, v = (d . q) * inv, t = (e2 . q) * inv;  a . b = (ax bx + ay by) + az bz,
     (a x b).x = ay bz - az by (and cyclic);  accept iff u >= 0 and v >= 0 and u + v <= 1 and t_min < t < t_max (NaN fails);
     the closest hit is the smallest t, equal t goes to the lowest triangle index; a ray with a non-finite component or a zero
     direction misses.  A miss is t = +inf, prim = -1, u = v = 0.
 The grid only chooses which triangles a ray is tested against: no result depends on it, nor on frame_width.
+
+Shading, float32, one rounding per operation: colour = (((1 - u) - v) c0 + u c1) + v c2 of the hit triangle's vertex colours (mid-grey
+    without), times the headlight ambient + (1 - ambient) c, c = min(|n . d| / len, 1) with len = sqrt(n . n) sqrt(d . d) and c = 0
+    unless len > 0 -- two-sided, n = e1 x e2 and d as they are, not normalised -- clamped to [0, 1]; a miss is the background.  The
+    uint8 copy of a pixel is (uint8)(clamp(x, 0, 1) * 255).  The overlay's pixels take the same headlight, on the hit's normal, and
+    the same uint8 copy.
 
 The grid rule (grid_params): the vertices' bounding box padded by ext / 128 + S / 1024 on every side (ext its largest extent, S the
 largest of ext and the largest coordinate magnitude); `resolution=None` picks n_a = round(size_a * cbrt(4 F / volume)) cells on axis
@@ -34,7 +43,7 @@ hold a mesh vertex, which leaves holes wherever a triangle is larger than a cell
 
 A mesh on a HIP device goes through csrc/voxelize.hip on the current stream, a CPU world through voxelize_numpy; the two maps are equal.
 
-The voxelisation rule is the specification (written here once, implemented in voxelize_numpy and in csrc/voxelize.hip):
+The voxelisation rule (written here once, implemented in voxelize_numpy and in csrc/voxelize.hip):
     inputs: the world's vertices (float32, the NeRF's axes; the exact vertices, not tri_data: v0 + e1 is not v1) and faces, a
     collision.GridBox, and rot -- a signed permutation matrix (entries 0 or +-1, one per row and column; anything else is a ValueError),
     so that the inverse of collision.to_nerf, w_i = sum_j rot[i][j] x_j, is a copy or a negation: no rounding.
@@ -67,7 +76,8 @@ replay"), in the place of the Blender scene of validation/utils/viz_failures_ble
 A HIP world goes through csrc/overlay.hip, a CPU world through cast_overlay_numpy; the two agree bit for bit.  The primitive table
 holds 8 floats per primitive: kind, a.xyz, b.xyz, r -- kind 0 a capsule with the axis a-b and the radius r (a polyline of n points is
 n - 1 capsules), kind 1 an axis-aligned box with the centre a and the half extents b (r is not used by the rule).  Any other kind, a
-non-finite field or r <= 0 is a ValueError.  The overlay's hit rule per (ray, primitive), float32, one rounding per operation:
+non-finite field or r <= 0 is a ValueError.  The overlay's hit rule per (ray, primitive), float32, one rounding per operation
+(correctly rounded division and square root):
     x . y = (x0 y0 + x1 y1) + x2 y2;  (x X y)_0 = x1 y2 - x2 y1 (and cyclic);  dd = d . d (d is not normalised), inv_dd = 1 / dd
     re-centring on a point c: t0 = (d . (c - o)) inv_dd, o' = o + t0 d, p = o' - c;  an intersection is solved for o' and reported
         as t = t0 + t' (the cancellation of the quadratics scales with the primitive's size, not the camera's distance)
@@ -222,6 +232,15 @@ def hit_terms(o, d, tri_data, dtype=_f32):
     return det, u, v, t
 
 
+def _closest(ok, t):
+    """the closest accepted candidate of every ray: ok bool [R,P], t float32 [R,P] -> (hit bool [R], best float32 [R]: the smallest
+    accepted t, +inf on a miss; prim int64 [R]: the lowest index among the closest)"""
+    tm = np.where(ok, t, _f32(np.inf))
+    best = tm.min(1)
+    hit = ok.any(1)
+    return hit, np.where(hit, best, _f32(np.inf)), np.argmax(ok & (tm == best[:, None]), 1)
+
+
 def cast_numpy(o, d, tri_data, t_min=0.0, t_max=np.inf):
     """brute force by the hit rule, float32: o, d [N,3] -> {"t" float32 (+inf on a miss), "prim" int32 (-1), "u", "v" float32 (0)}"""
     o, d, tri_data = np.ascontiguousarray(o, _f32).reshape(-1, 3), np.ascontiguousarray(d, _f32).reshape(-1, 3), np.asarray(tri_data, _f32)
@@ -235,20 +254,34 @@ def cast_numpy(o, d, tri_data, t_min=0.0, t_max=np.inf):
         det, u, v, t = hit_terms(o[sl], d[sl], tri_data)
         with np.errstate(all="ignore"):
             ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= _f32(1.0)) & (t > t_min) & (t < t_max) & valid[sl, None]
-        tm = np.where(ok, t, _f32(np.inf))
-        best = tm.min(1)
-        hit = ok.any(1)
-        prim = np.argmax(ok & (tm == best[:, None]), 1)            # the lowest index among the closest
+        hit, out["t"][sl], prim = _closest(ok, t)
         rows = np.arange(prim.shape[0])
-        out["t"][sl] = np.where(hit, best, _f32(np.inf))
         out["prim"][sl] = np.where(hit, prim, -1)
         out["u"][sl] = np.where(hit, u[rows, prim], _f32(0))
         out["v"][sl] = np.where(hit, v[rows, prim], _f32(0))
     return out
 
 
+def _headlight(n, d, ambient):
+    """the shading rule's headlight: n, d three float32 [N] arrays each -> float32 [N]"""
+    with np.errstate(all="ignore"):
+        length = np.sqrt(_dot(n, n)) * np.sqrt(_dot(d, d))
+        cosine = np.where(length > 0, np.minimum(np.abs(_dot(n, d)) / length, _f32(1.0)), _f32(0)).astype(_f32)
+        return _f32(ambient) + (_f32(1.0) - _f32(ambient)) * cosine
+
+
+def _lit(col, shade):
+    """colours float32 [N,3] under the headlight, clamped to [0, 1]"""
+    return np.minimum(np.maximum(col * shade[:, None], _f32(0)), _f32(1.0))
+
+
+def _quantise(image):
+    """the uint8 copy of float32 pixels"""
+    return (np.clip(image, 0, 1) * _f32(255.0)).astype(np.uint8)
+
+
 def shade_numpy(d, prim, u, v, tri_data, faces, colors, bg, ambient):
-    """k_raycast_shade in numpy float32 -> (image float32 [N,3], image_u8 uint8 [N,3])"""
+    """the shading rule in numpy float32 (k_raycast_shade's bits) -> (image float32 [N,3], image_u8 uint8 [N,3])"""
     d, T = np.asarray(d, _f32).reshape(-1, 3), np.asarray(tri_data, _f32)
     prim = np.asarray(prim).reshape(-1)
     hit = prim >= 0
@@ -261,14 +294,10 @@ def shade_numpy(d, prim, u, v, tri_data, faces, colors, bg, ambient):
         c = np.asarray(colors, _f32)[np.asarray(faces)[f].astype(np.int64)]           # [N, 3 corners, 3]
         col = (w[:, None] * c[:, 0] + u[:, None] * c[:, 1]) + v[:, None] * c[:, 2]
     e1, e2 = [T[f, k] for k in range(4, 7)], [T[f, k] for k in range(8, 11)]
-    n, dc = _cross(e1, e2), [d[:, k] for k in range(3)]
     with np.errstate(all="ignore"):
-        length = np.sqrt(_dot(n, n)) * np.sqrt(_dot(dc, dc))
-        cosine = np.where(length > 0, np.minimum(np.abs(_dot(n, dc)) / length, _f32(1.0)), _f32(0)).astype(_f32)
-        shade = _f32(ambient) + (_f32(1.0) - _f32(ambient)) * cosine
-        rgb = np.minimum(np.maximum(col * shade[:, None], _f32(0)), _f32(1.0))
+        rgb = _lit(col, _headlight(_cross(e1, e2), [d[:, k] for k in range(3)], ambient))
     image = np.where(hit[:, None], rgb, np.asarray(bg, _f32)[None, :]).astype(_f32)
-    return image, (np.clip(image, 0, 1) * _f32(255.0)).astype(np.uint8)
+    return image, _quantise(image)
 
 
 def _bg3(bg_color):
@@ -416,12 +445,8 @@ def cast_overlay_numpy(o, d, prims, t_max=None, t_min=0.0):
         t, n = overlay_terms(o[sl], d[sl], q)
         with np.errstate(all="ignore"):
             ok = (t > t_min) & (t < far[sl, None]) & valid[sl, None]
-        tm = np.where(ok, t, _f32(np.inf))
-        best = tm.min(1)
-        hit = ok.any(1)
-        prim = np.argmax(ok & (tm == best[:, None]), 1)            # the lowest index among the closest
+        hit, out["t"][sl], prim = _closest(ok, t)
         rows = np.arange(prim.shape[0])
-        out["t"][sl] = np.where(hit, best, _f32(np.inf))
         out["prim"][sl] = np.where(hit, prim, -1)
         for k in range(3):
             out["normal"][sl, k] = np.where(hit, n[k][rows, prim], _f32(0))
@@ -436,14 +461,10 @@ def shade_overlay_numpy(d, prim, normal, colors, ambient, image, image_u8):
     hit = (prim >= 0) & (prim < col.shape[0])
     if not hit.any():
         return image, image_u8
-    nc, dc = [n[:, k] for k in range(3)], [d[:, k] for k in range(3)]
     with np.errstate(all="ignore"):
-        length = np.sqrt(_dot(nc, nc)) * np.sqrt(_dot(dc, dc))
-        cosine = np.where(length > 0, np.minimum(np.abs(_dot(nc, dc)) / length, _f32(1.0)), _f32(0)).astype(_f32)
-        shade = _f32(ambient) + (_f32(1.0) - _f32(ambient)) * cosine
-        rgb = np.minimum(np.maximum(col[np.where(hit, prim, 0)] * shade[:, None], _f32(0)), _f32(1.0)).astype(_f32)
+        rgb = _lit(col[np.where(hit, prim, 0)], _headlight([n[:, k] for k in range(3)], [d[:, k] for k in range(3)], ambient))
     image[hit] = rgb[hit]
-    image_u8[hit] = (np.clip(rgb[hit], 0, 1) * _f32(255.0)).astype(np.uint8)
+    image_u8[hit] = _quantise(rgb[hit])
     return image, image_u8
 
 
@@ -658,15 +679,33 @@ class MeshWorld:
         return occ.view(torch.bool)
 
     # ---- casting
-    def _rays(self, rays_o, rays_d):
-        tensors = isinstance(rays_o, torch.Tensor)
-        o = torch.as_tensor(rays_o).detach().to(self.device, torch.float32)
+    def _flat(self, who, rays_d, rays_o=None):
+        """what cast, shade and the overlay's two share on the way in: the directions [..., 3], with or without the origins ->
+        (o or None, d: float32 [N,3], contiguous, on the world's device; the leading shape; whether the rays came as tensors)"""
         d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
-        if o.shape != d.shape or o.dim() < 1 or o.shape[-1] != 3:
-            raise ValueError(f"MeshWorld.cast: rays_o and rays_d [..., 3] of one shape (got {tuple(o.shape)} and {tuple(d.shape)})")
-        if o.numel() // 3 >= 2 ** 31:
-            raise ValueError("MeshWorld.cast: N must be < 2^31")
-        return o.reshape(-1, 3).contiguous(), d.reshape(-1, 3).contiguous(), tuple(o.shape[:-1]), tensors
+        o = None
+        if rays_o is not None:
+            o = torch.as_tensor(rays_o).detach().to(self.device, torch.float32)
+            if o.shape != d.shape or o.dim() < 1 or o.shape[-1] != 3:
+                raise ValueError(f"MeshWorld.{who}: rays_o and rays_d [..., 3] of one shape (got {tuple(o.shape)} and {tuple(d.shape)})")
+            if o.numel() // 3 >= 2 ** 31:
+                raise ValueError(f"MeshWorld.{who}: N must be < 2^31")
+            o = o.reshape(-1, 3).contiguous()
+        return o, d.reshape(-1, 3).contiguous(), tuple(d.shape[:-1]), isinstance(rays_d if rays_o is None else rays_o, torch.Tensor)
+
+    @staticmethod
+    def _width(who, frame_width, N):
+        """the frame_width argument of the native casts (0: none)"""
+        if frame_width is not None and (int(frame_width) < 1 or N % int(frame_width)):
+            raise ValueError(f"MeshWorld.{who}: frame_width {frame_width} does not divide the {N} rays")
+        return int(frame_width or 0)
+
+    @staticmethod
+    def _back(a, shape, tensors):
+        """and on the way out: a flat per-ray result in `shape`, the rays' leading shape (+ (3,) for triples); a numpy result as a
+        tensor for tensor rays"""
+        a = a.reshape(shape)
+        return torch.from_numpy(a) if tensors and isinstance(a, np.ndarray) else a
 
     def cast(self, rays_o, rays_d, t_min=0.0, t_max=float("inf"), frame_width=None):
         """rays [..., 3] -> {"t" float32 (+inf on a miss), "prim" int32 (-1), "u", "v" float32} of shape [...], on the world's device
@@ -675,35 +714,29 @@ class MeshWorld:
         t_min, t_max = float(t_min), float(t_max)
         if t_min != t_min or t_max != t_max:
             raise ValueError("MeshWorld.cast: t_min / t_max is NaN")
-        o, d, shape, tensors = self._rays(rays_o, rays_d)
+        o, d, shape, tensors = self._flat("cast", rays_d, rays_o)
         N = o.shape[0]
-        if frame_width is not None and (int(frame_width) < 1 or N % int(frame_width)):
-            raise ValueError(f"MeshWorld.cast: frame_width {frame_width} does not divide the {N} rays")
+        width = self._width("cast", frame_width, N)
         if self.device.type != "cuda":
             out = cast_numpy(o.numpy(), d.numpy(), self.tri_data.numpy(), t_min, t_max)
-            out = {k: a.reshape(shape) for k, a in out.items()}
-            return {k: torch.from_numpy(a) for k, a in out.items()} if tensors else out
-        out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
-               "u": torch.empty(N, dtype=torch.float32, device=self.device), "v": torch.empty(N, dtype=torch.float32, device=self.device)}
-        if N:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().ngp_raycast(_lib.ptr(o), _lib.ptr(d), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
-                                                  _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_data), self.n_faces, t_min, t_max,
-                                                  int(frame_width or 0), _lib.ptr(out["t"]), _lib.ptr(out["prim"]), _lib.ptr(out["u"]),
-                                                  _lib.ptr(out["v"]), _lib.stream()), "raycast")
-        return {k: a.reshape(shape) for k, a in out.items()}
+        else:
+            out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+                   "u": torch.empty(N, dtype=torch.float32, device=self.device), "v": torch.empty(N, dtype=torch.float32, device=self.device)}
+            if N:
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().ngp_raycast(_lib.ptr(o), _lib.ptr(d), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
+                                                      _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_data), self.n_faces, t_min, t_max,
+                                                      width, _lib.ptr(out["t"]), _lib.ptr(out["prim"]), _lib.ptr(out["u"]), _lib.ptr(out["v"]),
+                                                      _lib.stream()), "raycast")
+        return {k: self._back(a, shape, tensors) for k, a in out.items()}
 
     def shade(self, rays_d, hit, bg_color=1.0, ambient=DEFAULT_AMBIENT):
         """a cast's result -> (image float32 [..., 3] in [0, 1], image_u8 uint8 [..., 3] = (uint8)(image * 255), Agent.get_img's
-        quantisation): the barycentric blend of the vertex colours (mid-grey without) times ambient + (1 - ambient) |n . d| / (|n| |d|),
-        a two-sided headlight; bg_color (a scalar or three values; white, the reference's white_bg) on a miss"""
+        quantisation) by the module's shading rule; bg_color (a scalar or three values; white, the reference's white_bg) on a miss"""
         if not 0.0 <= float(ambient) <= 1.0:
             raise ValueError("MeshWorld.shade: ambient must be in [0, 1]")
         bg = _bg3(bg_color)
-        tensors = isinstance(rays_d, torch.Tensor)
-        d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
-        shape = tuple(d.shape[:-1])
-        d = d.reshape(-1, 3).contiguous()
+        _, d, shape, tensors = self._flat("shade", rays_d)
         N = d.shape[0]
         prim, u, v = [torch.as_tensor(hit[k]).to(self.device).reshape(-1).contiguous() for k in ("prim", "u", "v")]
         if prim.shape[0] != N:
@@ -711,31 +744,38 @@ class MeshWorld:
         if self.device.type != "cuda":
             image, u8 = shade_numpy(d.numpy(), prim.numpy(), u.numpy(), v.numpy(), self.tri_data.numpy(), self.faces.numpy(),
                                     None if self.colors is None else self.colors.numpy(), bg, ambient)
-            image, u8 = image.reshape(shape + (3,)), u8.reshape(shape + (3,))
-            return (torch.from_numpy(image), torch.from_numpy(u8)) if tensors else (image, u8)
-        image = torch.empty(N, 3, dtype=torch.float32, device=self.device)
-        u8 = torch.empty(N, 3, dtype=torch.uint8, device=self.device)
-        if N:
-            bg_c = (ctypes.c_float * 3)(*[float(b) for b in bg])
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().ngp_raycast_shade(_lib.ptr(d), _lib.ptr(prim.to(torch.int32)), _lib.ptr(u.to(torch.float32)),
-                                                        _lib.ptr(v.to(torch.float32)), N, _lib.ptr(self.tri_data), _lib.ptr(self.faces), self.n_faces,
-                                                        _lib.ptr(self.colors), self.n_vertices, float(ambient), bg_c, _lib.ptr(image), _lib.ptr(u8),
-                                                        _lib.stream()), "raycast_shade")
-        return image.reshape(shape + (3,)), u8.reshape(shape + (3,))
+        else:
+            image = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+            u8 = torch.empty(N, 3, dtype=torch.uint8, device=self.device)
+            if N:
+                bg_c = (ctypes.c_float * 3)(*[float(b) for b in bg])
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().ngp_raycast_shade(_lib.ptr(d), _lib.ptr(prim.to(torch.int32)), _lib.ptr(u.to(torch.float32)),
+                                                            _lib.ptr(v.to(torch.float32)), N, _lib.ptr(self.tri_data), _lib.ptr(self.faces),
+                                                            self.n_faces, _lib.ptr(self.colors), self.n_vertices, float(ambient), bg_c,
+                                                            _lib.ptr(image), _lib.ptr(u8), _lib.stream()), "raycast_shade")
+        return self._back(image, shape + (3,), tensors), self._back(u8, shape + (3,), tensors)
 
-    def render(self, pose, intrinsics, H, W, bg_color=1.0, ambient=DEFAULT_AMBIENT):
-        """pose [4,4] cam2world (this package's camera convention) -> {"image" float32 [H,W,3], "image_u8" uint8 [H,W,3], "depth"
-        float32 [H,W] = t * |d| (+inf on a miss), "prim" int32 [H,W]} as tensors on the world's device.  The rays are
-        nerf.utils.get_rays' of the pose: pixel-aligned with the NeRF's frame of the same pose."""
+    def _frame(self, pose, intrinsics, H, W, bg_color, ambient):
+        """the mesh's part of a frame: nerf.utils.get_rays' rays of the pose, their cast and its shading -> (o, d, hit, image, image_u8)"""
         from .nerf.utils import get_rays
         pose = torch.as_tensor(pose).detach().to(self.device, torch.float32).reshape(1, 4, 4)
         rays = get_rays(pose, intrinsics, H, W)
         o, d = rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3)
         hit = self.cast(o, d, frame_width=W)
-        image, u8 = self.shade(d, hit, bg_color, ambient)
-        depth = hit["t"] * torch.linalg.vector_norm(d, dim=-1)
-        return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": hit["prim"].reshape(H, W)}
+        return (o, d, hit) + self.shade(d, hit, bg_color, ambient)
+
+    @staticmethod
+    def _frame_dict(H, W, d, t, prim, image, u8):
+        depth = t * torch.linalg.vector_norm(d, dim=-1)
+        return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": prim.reshape(H, W)}
+
+    def render(self, pose, intrinsics, H, W, bg_color=1.0, ambient=DEFAULT_AMBIENT):
+        """pose [4,4] cam2world (this package's camera convention) -> {"image" float32 [H,W,3], "image_u8" uint8 [H,W,3], "depth"
+        float32 [H,W] = t * |d| (+inf on a miss), "prim" int32 [H,W]} as tensors on the world's device.  The rays are
+        nerf.utils.get_rays' of the pose: pixel-aligned with the NeRF's frame of the same pose."""
+        _, d, hit, image, u8 = self._frame(pose, intrinsics, H, W, bg_color, ambient)
+        return self._frame_dict(H, W, d, hit["t"], hit["prim"], image, u8)
 
     # ---- the overlay: analytic primitives drawn into the world (the replay's failure view)
     def cast_overlay(self, rays_o, rays_d, prims, t_max=None, t_min=0.0, frame_width=None):
@@ -747,10 +787,9 @@ class MeshWorld:
         if t_min != t_min:
             raise ValueError("MeshWorld.cast_overlay: t_min is NaN")
         q = check_prims(prims)
-        o, d, shape, tensors = self._rays(rays_o, rays_d)
+        o, d, shape, tensors = self._flat("cast_overlay", rays_d, rays_o)
         N, P = o.shape[0], q.shape[0]
-        if frame_width is not None and (int(frame_width) < 1 or N % int(frame_width)):
-            raise ValueError(f"MeshWorld.cast_overlay: frame_width {frame_width} does not divide the {N} rays")
+        width = self._width("cast_overlay", frame_width, N)
         far = None
         if t_max is not None:
             far = torch.as_tensor(t_max).detach().to(self.device, torch.float32).reshape(-1).contiguous()
@@ -758,29 +797,26 @@ class MeshWorld:
                 raise ValueError("MeshWorld.cast_overlay: t_max is one value per ray")
         if self.device.type != "cuda":
             out = cast_overlay_numpy(o.numpy(), d.numpy(), q, None if far is None else far.numpy(), t_min)
-            out = {k: a.reshape(shape + a.shape[1:]) for k, a in out.items()}
-            return {k: torch.from_numpy(a) for k, a in out.items()} if tensors else out
-        out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
-               "normal": torch.empty(N, 3, dtype=torch.float32, device=self.device)}
-        if N:
-            with torch.cuda.device(self.device):
-                q_dev = torch.from_numpy(q).to(self.device) if P else None
-                _lib.check(_lib.lib().ngp_overlay_cast(_lib.ptr(o), _lib.ptr(d), N, q.ctypes.data if P else None, _lib.ptr(q_dev), P, t_min,
-                                                       _lib.ptr(far), int(frame_width or 0), _lib.ptr(out["t"]), _lib.ptr(out["prim"]),
-                                                       _lib.ptr(out["normal"]), _lib.stream()), "overlay_cast")
-        return {k: a.reshape(shape + tuple(a.shape[1:])) for k, a in out.items()}
+        else:
+            out = {"t": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+                   "normal": torch.empty(N, 3, dtype=torch.float32, device=self.device)}
+            if N:
+                with torch.cuda.device(self.device):
+                    q_dev = torch.from_numpy(q).to(self.device) if P else None
+                    _lib.check(_lib.lib().ngp_overlay_cast(_lib.ptr(o), _lib.ptr(d), N, q.ctypes.data if P else None, _lib.ptr(q_dev), P, t_min,
+                                                           _lib.ptr(far), width, _lib.ptr(out["t"]), _lib.ptr(out["prim"]),
+                                                           _lib.ptr(out["normal"]), _lib.stream()), "overlay_cast")
+        return {k: self._back(a, shape + (3,) if k == "normal" else shape, tensors) for k, a in out.items()}
 
     def shade_overlay(self, rays_d, hit, colors, image, image_u8, ambient=DEFAULT_AMBIENT):
         """a cast_overlay result drawn over a frame: where the overlay hit, the pixel of `image` (float32 [..., 3]) and `image_u8`
-        becomes colors[prim] (float [P,3]) times shade's two-sided headlight on the hit's normal, with the same uint8 quantisation;
+        becomes colors[prim] (float [P,3]) times the shading rule's headlight on the hit's normal, with the same uint8 copy;
         every other pixel keeps its bits -> new (image, image_u8), the inputs are not written"""
         if not 0.0 <= float(ambient) <= 1.0:
             raise ValueError("MeshWorld.shade_overlay: ambient must be in [0, 1]")
         col = np.ascontiguousarray(colors.detach().cpu().numpy() if isinstance(colors, torch.Tensor) else colors, _f32).reshape(-1, 3)
-        tensors = isinstance(image, torch.Tensor)
-        d = torch.as_tensor(rays_d).detach().to(self.device, torch.float32)
-        shape = tuple(d.shape[:-1])
-        d = d.reshape(-1, 3).contiguous()
+        _, d, shape, _ = self._flat("shade_overlay", rays_d)
+        tensors = isinstance(image, torch.Tensor)                       # (the frame decides what comes back, not the rays)
         N, P = d.shape[0], col.shape[0]
         prim = torch.as_tensor(hit["prim"]).to(self.device, torch.int32).reshape(-1).contiguous()
         normal = torch.as_tensor(hit["normal"]).to(self.device, torch.float32).reshape(-1, 3).contiguous()
@@ -790,14 +826,14 @@ class MeshWorld:
             raise ValueError("MeshWorld.shade_overlay: the hit record and the frame are not of these rays")
         if self.device.type != "cuda":
             img, u8 = shade_overlay_numpy(d.numpy(), prim.numpy(), normal.numpy(), col, ambient, img.numpy(), u8.numpy())
-            img, u8 = img.reshape(shape + (3,)), u8.reshape(shape + (3,))
-            return (torch.from_numpy(img), torch.from_numpy(u8)) if tensors else (img, u8)
-        img, u8 = img.clone().contiguous(), u8.clone().contiguous()
-        if N and P:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().ngp_overlay_shade(_lib.ptr(d), _lib.ptr(prim), _lib.ptr(normal), N, _lib.ptr(torch.from_numpy(col).to(self.device)),
-                                                        P, float(ambient), _lib.ptr(img), _lib.ptr(u8), _lib.stream()), "overlay_shade")
-        return img.reshape(shape + (3,)), u8.reshape(shape + (3,))
+        else:
+            img, u8 = img.clone().contiguous(), u8.clone().contiguous()
+            if N and P:
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().ngp_overlay_shade(_lib.ptr(d), _lib.ptr(prim), _lib.ptr(normal), N,
+                                                            _lib.ptr(torch.from_numpy(col).to(self.device)), P, float(ambient), _lib.ptr(img),
+                                                            _lib.ptr(u8), _lib.stream()), "overlay_shade")
+        return self._back(img, shape + (3,), tensors), self._back(u8, shape + (3,), tensors)
 
     def render_scene(self, pose, intrinsics, H, W, tubes=(), boxes=(), bg_color=1.0, ambient=DEFAULT_AMBIENT):
         """render() with analytic primitives in the scene -- the replay's failure view.  tubes: (points [n,3], radius, rgb) each;
@@ -805,15 +841,8 @@ class MeshWorld:
         primitives drawn over the world where they are nearer than the mesh, depth the nearer of the two, prim the MESH's triangle) plus
         "overlay_prim" int32 [H,W]: the primitive's index (tubes first, in the given order), -1 where the mesh or the background
         shows.  Without primitives every entry equals render()'s bit for bit."""
-        from .nerf.utils import get_rays
         prims, colors = overlay_prims(tubes, boxes)
-        pose = torch.as_tensor(pose).detach().to(self.device, torch.float32).reshape(1, 4, 4)
-        rays = get_rays(pose, intrinsics, H, W)
-        o, d = rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3)
-        hit = self.cast(o, d, frame_width=W)
-        image, u8 = self.shade(d, hit, bg_color, ambient)
+        o, d, hit, image, u8 = self._frame(pose, intrinsics, H, W, bg_color, ambient)
         over = self.cast_overlay(o, d, prims, t_max=hit["t"], frame_width=W)
         image, u8 = self.shade_overlay(d, over, colors, image, u8, ambient)
-        depth = torch.minimum(hit["t"], over["t"]) * torch.linalg.vector_norm(d, dim=-1)
-        return {"image": image.reshape(H, W, 3), "image_u8": u8.reshape(H, W, 3), "depth": depth.reshape(H, W), "prim": hit["prim"].reshape(H, W),
-                "overlay_prim": over["prim"].reshape(H, W)}
+        return {**self._frame_dict(H, W, d, torch.minimum(hit["t"], over["t"]), hit["prim"], image, u8), "overlay_prim": over["prim"].reshape(H, W)}

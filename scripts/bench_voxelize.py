@@ -27,24 +27,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-
-def event_ms(fn, repeats, warmup=3):
-    """ms of fn() between two events on the current stream, per repeat"""
-    for _ in range(warmup):
-        fn()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
+from bench_raycast import event_ms  # noqa: E402
 
 
 def host_ms(fn, repeats=1, sync=False):

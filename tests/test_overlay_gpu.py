@@ -89,7 +89,7 @@ def test_far_limits_mask_lanes_without_losing_them(world, device):
               "mixed": np.where(np.arange(N) % 3 == 0, f32(0), np.where(np.arange(N) % 3 == 1, f32(0.45), f32(np.inf))).astype(f32)}
     for name, far in limits.items():
         want = WO.cast_overlay_numpy(o, d, q, t_max=far)
-        for width in (None, OC.W):
+        for width in (None, OC.W, 35):      # (35: the last tile of every tile row holds lanes without a ray)
             same(world.cast_overlay(to, td, q, t_max=torch.from_numpy(far).to(device), frame_width=width), want)
         if name == "open":
             assert np.array_equal(want["prim"], free["prim"])
