@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -133,8 +134,7 @@ __global__ void __launch_bounds__(kUqThreads) k_uq_partial(const CT* __restrict_
     for (uint64_t i = t0; i < m; i += stride) acc[2] += (double)r[i];
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        double v = acc[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const double v = wave_sum_lane0(acc[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();

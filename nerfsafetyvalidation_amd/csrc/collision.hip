@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(kEdtBlock) k_edt_z(const uint8_t* __restrict__
             const uint32_t z = c0 + lane;
             const bool valid = z < Z;
             int v = (valid && occ[base + z]) ? (int)z : -1;
-#pragma unroll
+#pragma unroll      // (a max scan, and a min scan below: wave_ops.hpp's scans are add and mul)
             for (int off = 1; off < 64; off <<= 1) {
                 const int t = __shfl_up(v, off, 64);
                 if (lane >= off) v = max(v, t);

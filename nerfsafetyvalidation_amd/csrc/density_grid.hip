@@ -18,6 +18,7 @@
 //
 // All of it is HBM-streaming integer / compare work (4 B per cell and pass): no LDS tiling beyond the camera list, no MFMA.
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -109,8 +110,7 @@ __global__ void __launch_bounds__(kDgBlock) k_grid_possum(const float* __restric
     const uint32_t i = blockIdx.x * kDgBlock + threadIdx.x;
     double pos = 0.0;
     if (i < n) { const float g = grid[i]; pos = g > 0.0f ? (double)g : 0.0; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) pos += __shfl_down(pos, off, 64);
+    pos = wave_sum_lane0(pos);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = pos;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];

@@ -8,46 +8,18 @@
 // to sigma, or g itself.  DESIGN.md "Distortion regulariser" has the definitions.
 //
 // One WAVE per ray (four rays per 256-thread workgroup), lane l on sample base + l of a 64-sample chunk: the loads of a chunk are
-// consecutive addresses.  Inside a chunk the prefixes are Hillis-Steele scans over the 64 lanes (__shfl_up, six steps); between chunks
-// the running values travel in registers.  Bandwidth- and latency-bound: no LDS, no matrix pipe.  No atomics: a ray's sums are formed
-// by its own wave in an order that depends on its sample count alone, the mean over the rays in an order that depends on N alone --
-// two runs on the same inputs give the same bits, and so does any order of the table's rows.
+// consecutive addresses.  Inside a chunk the prefixes are wave_ops.hpp's scans over the 64 lanes; between chunks the running values
+// travel in registers.  Bandwidth- and latency-bound: no LDS, no matrix pipe.  No atomics: a ray's sums are formed by its own wave in an
+// order that depends on its sample count alone, the mean over the rays by mean_of_rays, the fixed-order mean (DESIGN.md "Cross-lane
+// arithmetic") -- two runs on the same inputs give the same bits, and so does any order of the table's rows.
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 namespace {
 
 constexpr int kDistBlock = 256;                     // four waves = four rays
-constexpr uint32_t kDistOneBlockRays = 16384;       // up to here one 1024-thread workgroup forms the mean (no workspace)
 constexpr float kStopT = 1e-4f;                     // composite_rays_train's early stop (raymarching.cu:560)
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {        // the same value in every lane, a fixed order
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float scan_add(float v, uint32_t lane) {      // inclusive prefix sum over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float u = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ float scan_mul(float v, uint32_t lane) {      // inclusive prefix product over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float u = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v *= u;
-    }
-    return v;
-}
-__device__ __forceinline__ float before(float inclusive, uint32_t lane, float first) {     // the neighbour's value: inclusive -> exclusive
-    const float u = __shfl_up(inclusive, 1, 64);
-    return lane == 0 ? first : u;
-}
-__device__ __forceinline__ float last_lane(float v) { return __shfl(v, 63, 64); }
 
 // The arrays of one call.  FROM_SIGMA: a = sigmas [M], b = deltas [M,2], c = scale per ray (indexed by the table's `index`; NULL = 1).
 // Otherwise: a = w [M], b = m [M], c = interval [M] (NULL: the scalar cs for every sample).
@@ -82,13 +54,13 @@ __device__ __forceinline__ RayChunk ray_chunk(const DistIn& in, size_t row, uint
         const float sg = on ? in.a[row + i] : 0.0f;
         const float2 d = on ? reinterpret_cast<const float2*>(in.b)[row + i] : make_float2(0.0f, 0.0f);
         const float alpha = 1.0f - expf(-sg * d.x);                  // (a lane that is off: exp(-0) = 1, alpha = 0)
-        const float P = scan_mul(1.0f - alpha, lane);
-        const float T_before = run.T * before(P, lane, 1.0f);
+        const float P = scan_inclusive<MulOp>(1.0f - alpha, lane);
+        const float T_before = run.T * shifted_in(P, lane, 1.0f);
         q.T_next = run.T * P;
         const unsigned long long crossed = __ballot(on && q.T_next < kStopT);
         const uint32_t stop_lane = crossed ? (uint32_t)__ffsll((long long)crossed) - 1u : 64u;
         q.live = on && lane <= stop_lane;
-        const float t = run.t + scan_add(d.y, lane);
+        const float t = run.t + scan_inclusive<AddOp>(d.y, lane);
         q.w = q.live ? alpha * T_before : 0.0f;
         q.m = q.live ? scale * t : 0.0f;
         q.delta = q.live ? scale * d.x : 0.0f;
@@ -105,9 +77,9 @@ __device__ __forceinline__ RayChunk ray_chunk(const DistIn& in, size_t row, uint
         q.T_next = 0.0f;
     }
     q.wm = q.w * q.m;
-    const float W = scan_add(q.w, lane), WM = scan_add(q.wm, lane);
-    q.Wpre = run.W + before(W, lane, 0.0f);
-    q.WMpre = run.WM + before(WM, lane, 0.0f);
+    const float W = scan_inclusive<AddOp>(q.w, lane), WM = scan_inclusive<AddOp>(q.wm, lane);
+    q.Wpre = run.W + shifted_in(W, lane, 0.0f);
+    q.WMpre = run.WM + shifted_in(WM, lane, 0.0f);
     run.W += last_lane(W);
     run.WM += last_lane(WM);
     return q;
@@ -188,7 +160,7 @@ __global__ void __launch_bounds__(kDistBlock) k_distortion_bwd(const float* __re
         if (FROM_SIGMA) {
             const float gw = g * q.w;
             if (count <= 64) S_total = wave_sum(gw);
-            const float S = scan_add(gw, lane);
+            const float S = scan_inclusive<AddOp>(gw, lane);
             const float S_after = S_total - (S_run + S);          // sum_{i>k} g_i w_i
             S_run += last_lane(S);
             if (q.live) grad[(size_t)offset + base + lane] = (seed * (q.dt * (g * q.T_next - S_after))) / rays_f;
@@ -196,54 +168,6 @@ __global__ void __launch_bounds__(kDistBlock) k_distortion_bwd(const float* __re
             if (q.live) grad[(size_t)offset + base + lane] = (seed * g) / rays_f;
         }
     }
-}
-
-// ---- mean over the rays: the order of ngp_photo_loss_forward -- the 64 slots of a group by the xor butterfly in float, lane l of one
-// wave adds the groups l, l + 64, ... in double, the butterfly over those 64 doubles -- a function of N alone.
-__device__ __forceinline__ void final_mean(const float* groups, uint32_t n_groups, uint32_t N, float* mean) {       // one whole wave
-    const uint32_t lane = threadIdx.x & 63;
-    double acc = 0.0;
-    for (uint32_t g = lane; g < n_groups; g += 64) acc += (double)groups[g];
-    acc = wave_sum(acc);
-    if (lane == 0) *mean = (float)(acc / (double)N);
-}
-
-__global__ void __launch_bounds__(1024) k_distortion_mean_one_block(const float* __restrict__ loss_rays, uint32_t N, float* __restrict__ mean) {
-    __shared__ float s_groups[kDistOneBlockRays / 64];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t rounds = (N + 1023) / 1024;
-    for (uint32_t r = 0; r < rounds; r++) {
-        const uint32_t i = r * 1024 + threadIdx.x;
-        const float v = wave_sum(i < N ? loss_rays[i] : 0.0f);
-        if (lane == 0) s_groups[r * 16 + wave] = v;
-    }
-    __syncthreads();
-    if (wave == 0) final_mean(s_groups, (N + 63) / 64, N, mean);
-}
-
-__global__ void __launch_bounds__(256) k_distortion_mean_groups(const float* __restrict__ loss_rays, uint32_t N, float* __restrict__ groups) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const float v = wave_sum(i < N ? loss_rays[i] : 0.0f);
-    if ((threadIdx.x & 63) == 0 && (i >> 6) < (N + 63) / 64) groups[i >> 6] = v;
-}
-
-__global__ void __launch_bounds__(64) k_distortion_mean_final(const float* __restrict__ groups, uint32_t n_groups, uint32_t N, float* __restrict__ mean) {
-    final_mean(groups, n_groups, N, mean);
-}
-
-int mean_of_rays(const float* loss_rays, uint32_t N, float* loss, void* workspace, size_t workspace_bytes, hipStream_t s, const char* what) {
-    const size_t need = ngp_distortion_workspace(N);
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("%s: workspace too small (%zu < %zu bytes)", what, workspace ? workspace_bytes : (size_t)0, need);
-        return NGP_EWORKSPACE;
-    }
-    if (!need) {
-        k_distortion_mean_one_block<<<1, 1024, 0, s>>>(loss_rays, N, loss);
-        return check_launch(what);
-    }
-    k_distortion_mean_groups<<<div_up(N, 256), 256, 0, s>>>(loss_rays, N, (float*)workspace);
-    k_distortion_mean_final<<<1, 64, 0, s>>>((const float*)workspace, div_up(N, 64), N, loss);
-    return check_launch(what);
 }
 
 constexpr uint32_t kDistMaxRays = 0x3FFFFFFFu;      // 3 N and 4 N stay 32-bit
@@ -255,7 +179,7 @@ using namespace ngp;
 
 extern "C" {
 
-size_t ngp_distortion_workspace(uint32_t N) { return N <= kDistOneBlockRays ? 0 : (size_t)div_up(N, 64) * sizeof(float); }
+size_t ngp_distortion_workspace(uint32_t N) { return mean_workspace(N); }
 
 int ngp_distortion_train_forward(const float* sigmas, const float* deltas, const int32_t* rays, const float* scale, uint32_t M, uint32_t N,
                                  float* loss_rays, float* totals, float* loss, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {

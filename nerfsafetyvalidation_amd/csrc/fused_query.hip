@@ -3,6 +3,7 @@
 // (collision.py, occupancy_from_density), and the trajectory planner's collision term with its backward (nav/quad_plot.py:216-249).
 // Every kernel is a template over the network policy of fused_net.hpp and is instantiated here only.
 #include "fused_net.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -158,8 +159,7 @@ __global__ void __launch_bounds__(256) k_network_density_bwd(NetArgs na, GridLev
         NET::density_vjp(na, Wb, lane, tape, gso, gx);
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-            gx[d] += __shfl_xor(gx[d], 16, 64);
-            gx[d] += __shfl_xor(gx[d], 32, 64);
+            gx[d] = quad_sum(gx[d]);
         }
         if (lane < 16 && valid) {
 #pragma unroll
@@ -184,6 +184,14 @@ struct PlanArgs {
 
 constexpr uint32_t kPlanThreads = 256;
 
+// sum of lanes 0..15 (every other lane holds 0), complete in lane 0.  (wave_sum<16>'s order, but with shuffle width 64 -- the other
+// lanes take part with their zeros -- and kept as written: with the header's width-16 form the planner kernels are scheduled differently)
+__device__ __forceinline__ float plan_lane_sum(float v) {
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 __device__ __forceinline__ void plan_load_rot(const PlanArgs& pa, float (&rot)[9]) {
 #pragma unroll
     for (int i = 0; i < 9; i++) rot[i] = pa.rot[i];
@@ -200,13 +208,6 @@ __device__ __forceinline__ void plan_point(const PlanArgs& pa, const float (&rot
     for (int i = 0; i < 3; i++) w[i] = R[3 * i] * bp[0] + R[3 * i + 1] * bp[1] + R[3 * i + 2] * bp[2] + p[i];
 #pragma unroll
     for (int j = 0; j < 3; j++) x[j] = w[0] * rot[j] + w[1] * rot[3 + j] + w[2] * rot[6 + j];
-}
-
-// sum of lanes 0..15 (every other lane holds 0), complete in lane 0
-__device__ __forceinline__ float plan_lane_sum(float v) {
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 template <class NET>
@@ -290,8 +291,7 @@ __global__ void __launch_bounds__(kPlanThreads) k_planner_collision_bwd(NetArgs 
         NET::density_vjp(na, Wb, lane, tape, gso, gx);
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-            gx[d] += __shfl_xor(gx[d], 16, 64);
-            gx[d] += __shfl_xor(gx[d], 32, 64);
+            gx[d] = quad_sum(gx[d]);
         }
         if (valid && lane < 16) {
             float gxr[3], gw[3];

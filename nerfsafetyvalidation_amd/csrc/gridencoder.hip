@@ -24,6 +24,7 @@
 #include <stdio.h>
 
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -792,12 +793,7 @@ __global__ void __launch_bounds__(NT) k_grid_bwd_bin(const _Float16* __restrict_
     __syncthreads();
     if (threadIdx.x < 64) {            // wave 0: exclusive scan of the 128 counts
         const uint32_t c0 = cnt[2 * lane], c1 = cnt[2 * lane + 1];
-        uint32_t incl = c0 + c1;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += up;
-        }
+        const uint32_t incl = scan_inclusive<AddOp>(c0 + c1, lane);
         off[2 * lane] = incl - c0 - c1;
         off[2 * lane + 1] = incl - c1;
     }

@@ -10,6 +10,7 @@
 // double: a float product is exact in double, so the cancellation in E[p^2] - mu^2 (against c2 = 9e-4) costs nothing (DESIGN.md
 // "Image-quality metrics").  -ffp-contract=off: the only fused multiply-adds are the explicit fma() calls.
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -39,13 +40,6 @@ __device__ __forceinline__ int reflect(int i, int n) {
     i = i < 0 ? -i : i;
     i = i >= n ? 2 * (n - 1) - i : i;
     return min(max(i, 0), n - 1);
-}
-
-template <typename T>
-__device__ __forceinline__ T iq_butterfly(T v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 __global__ void __launch_bounds__(kIqThreads) k_image_quality(const float* __restrict__ pred, const float* __restrict__ target,
@@ -145,7 +139,7 @@ __global__ void __launch_bounds__(kIqThreads) k_image_quality(const float* __res
     // fixed order: the 64 lanes of a wave by the xor butterfly, then the four waves in order
 #pragma unroll
     for (int q = 0; q < kIqSums; q++) {
-        const double v = iq_butterfly(sums[q]);
+        const double v = wave_sum(sums[q]);
         if ((tid & 63) == 0) s_red[tid >> 6][q] = v;
     }
     __syncthreads();
@@ -162,7 +156,7 @@ __global__ void __launch_bounds__(64 * kIqSums) k_image_quality_final(const doub
     const double* src = partials + ((size_t)b * kIqSums + q) * tiles;
     double acc = 0.0;
     for (uint32_t i = lane; i < tiles; i += 64) acc += src[i];
-    acc = iq_butterfly(acc);
+    acc = wave_sum(acc);
     if (lane == 0) stats[(size_t)b * 8 + q] = acc;
     if (threadIdx.x < 3) stats[(size_t)b * 8 + 5 + threadIdx.x] = threadIdx.x == 0 ? hw : 0.0;
 }

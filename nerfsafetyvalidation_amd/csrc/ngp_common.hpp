@@ -41,6 +41,16 @@ void prof_add_units(const char* name, double units);
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
+// ---- the fixed-order mean of N floats (train_data.hip; its order: DESIGN.md "Cross-lane arithmetic", device pieces in wave_ops.hpp) ----
+constexpr uint32_t kMeanOneBlockRays = 16384;      // up to here one 1024-thread workgroup forms the mean: one launch, no workspace
+constexpr uint32_t kMeanOneBlockThreads = 1024;
+constexpr uint32_t kMeanGroupThreads = 256;        // above: 256 values per workgroup into per-64 group sums, then one wave over the groups
+static inline size_t mean_workspace(uint32_t N) { return N <= kMeanOneBlockRays ? 0 : (size_t)div_up(N, 64) * sizeof(float); }
+// *mean = mean of values[0 .. N); mean_workspace(N) bytes of workspace (NGP_EWORKSPACE when it has fewer).  `what` names the caller in errors.
+int mean_of_rays(const float* values, uint32_t N, float* mean, void* workspace, size_t workspace_bytes, hipStream_t s, const char* what);
+// the last step alone, for a caller that formed the (N + 63) / 64 group sums in a pass of its own (N > kMeanOneBlockRays)
+int mean_of_groups(const float* groups, uint32_t N, float* mean, hipStream_t s, const char* what);
+
 // hipFuncSetAttribute(..., hipFuncAttributeMaxDynamicSharedMemorySize, bytes), once per (device, kernel): the attribute belongs to
 // the kernel's code object on ONE device, and render calls arrive from several host threads (pipeline.py) -- a plain
 // `static bool` guard is neither per device nor safe to race on.

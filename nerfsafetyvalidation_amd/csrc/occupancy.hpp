@@ -2,6 +2,7 @@
 // occupancy bits, the one-wave-per-ray window step, the slot scan.  Included by raymarching.hip, render_fused.hip and occupancy.hip only.
 #pragma once
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -412,12 +413,7 @@ __device__ __forceinline__ LatticeWindow probe_window(const Dda& s, float t, flo
 template <int THREADS>
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wave_tot) {
     const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += o;
-    }
+    const uint32_t incl = scan_inclusive<AddOp>(v, lane);
     if (lane == 63) wave_tot[wid] = incl;
     __syncthreads();
     uint32_t wave_off = 0;

@@ -141,9 +141,7 @@ __global__ void __launch_bounds__(kBlock) k_march_train_count(const float* __res
         counts[n] = num_steps;
     }
     // block reduction
-    uint32_t v = num_steps;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const uint32_t v = wave_sum_lane0(num_steps);
     if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -333,8 +331,7 @@ __global__ void __launch_bounds__(kBlock) k_march_train_write_wave(const float* 
     const uint32_t blk = n / kBlock, first = blk * kBlock;
     uint32_t before = 0;
     for (uint32_t i = first + lane; i < n; i += 64) before += counts[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+    before = wave_sum(before);
     const uint32_t point_index = base[0] + block_offsets[blk] + before;
     const uint32_t ray_index = base[1] + n;
     if (lane == 0 && ray_index < N) {
@@ -660,8 +657,7 @@ __global__ void __launch_bounds__(1024) k_get_rays_backward(const float* __restr
     }
 #pragma unroll
     for (int k = 0; k < 12; k++) {
-        float v = acc[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const float v = wave_sum_lane0(acc[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();

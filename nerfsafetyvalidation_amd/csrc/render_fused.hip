@@ -333,8 +333,8 @@ __global__ void __launch_bounds__(256) k_march_ahead(RenderArgs ra, float bound)
         }
         // [14] probes that found their 4x4x4 block empty, [15] probes in an occupied block that found their cell empty
         uint32_t ce = probes_coarse_empty, fe = probes_fine_empty;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { ce += (uint32_t)__shfl_xor((int)ce, off, 64); fe += (uint32_t)__shfl_xor((int)fe, off, 64); }
+        ce = wave_sum(ce);
+        fe = wave_sum(fe);
         if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__ballot(true))) {
             atomicAdd(ra.stamps + 14, (unsigned long long)ce);
             atomicAdd(ra.stamps + 15, (unsigned long long)fe);
@@ -477,7 +477,7 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
             }
             NGP_STAMP(0)
             // ---- 2. compact the wave's samples and run the network 16 at a time
-            uint32_t incl = cnt;
+            uint32_t incl = cnt;      // (wave_ops.hpp's scan_inclusive<AddOp> and last_lane, written out: k_render_iter must not change)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const uint32_t o = __shfl_up(incl, off, 64);
@@ -635,7 +635,7 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
             // composite_rays); in a multi-iteration launch a ray that completed steps_done samples entered iterations 0 .. steps_done / spec
             const uint32_t entered = (spec && !survive) ? (steps_done / spec + 1) * spec : n_step;
             uint32_t rm = active ? (emitted < entered ? emitted : entered) : 0u;
-#pragma unroll
+#pragma unroll      // (wave_sum, written out: k_render_iter must not change)
             for (int off = 32; off > 0; off >>= 1) rm += __shfl_xor(rm, off, 64);
             wave_samples = rm;
         }
@@ -789,7 +789,7 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
         tf += v >> 16;
         if (j < first) { pf += v & 0xffffu; ps += v >> 16; }
     }
-#pragma unroll
+#pragma unroll      // (three wave_sum_lane0, interleaved, and a fourth below: written out, k_render_compact must not change)
     for (int off = 32; off > 0; off >>= 1) {
         pf += __shfl_down(pf, off, 64);
         ps += __shfl_down(ps, off, 64);

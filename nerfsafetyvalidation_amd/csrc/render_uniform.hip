@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "fused_net.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -36,21 +37,14 @@ __device__ __forceinline__ bool weight_masked(float w) { return w > 1e-4f; }    
 // O(1) sums
 constexpr float kSpentTransmittance = 1e-10f;
 
-// inclusive scan (product or sum) over groups of W lanes; l = lane within the group
-template <int W, bool MUL>
-__device__ __forceinline__ float scan_inclusive(float v, uint32_t l) {
-#pragma unroll
-    for (int off = 1; off < W; off <<= 1) {
-        const float o = __shfl_up(v, off, W);
-        if (l >= (uint32_t)off) v = MUL ? v * o : v + o;
-    }
-    return v;
-}
 // cumprod(1 - alpha + 1e-15) of :209-210 over a tile of W samples, lane = sample: the transmittance in front of the lane's sample, given
 // `carry` = the product over the earlier tiles; tile_product is what the tile multiplies into carry
+// (the scan of k_trans_weights' chunk in sampling.hip, not shared with it: there the chunk also forms p from its arrays and is always
+// 64 wide; here the callers form p, W is 16 or 64, and carry moves on in the caller, which may stop the ray on it first.  The shift
+// and the broadcast stay written out: with the header's shifted_in / last_lane the compiler schedules the callers differently.)
 template <int W>
 __device__ __forceinline__ float tile_transmittance(float p, float carry, uint32_t l, float& tile_product) {
-    const float incl = scan_inclusive<W, true>(p, l);
+    const float incl = scan_inclusive<MulOp, W>(p, l);
     const float excl = __shfl_up(incl, 1, W);
     tile_product = __shfl(incl, W - 1, W);
     return carry * (l == 0 ? 1.0f : excl);
@@ -86,7 +80,7 @@ struct RaySums {
     }
     __device__ __forceinline__ void reduce16() {
 #pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
+        for (int off = 8; off > 0; off >>= 1) {      // six wave_sum<16> (wave_ops.hpp) interleaved step by step; as six calls the callers are scheduled differently
             ws += __shfl_xor(ws, off, 16); dep += __shfl_xor(dep, off, 16); agg += __shfl_xor(agg, off, 16);
             r += __shfl_xor(r, off, 16); g += __shfl_xor(g, off, 16); b += __shfl_xor(b, off, 16);
         }
@@ -244,9 +238,7 @@ __global__ void __launch_bounds__(256, NET::kF32 ? 2 : 4) k_render_uniform_x16(N
         }
         if (lane < 16 && live) sums.store(ray, weights_sum, depth, image, aggregated_density);
         if (stamps) {    // diagnostics (ngp_debug_set_stamps): depth indices walked by the group x 16 lanes, and those that carried a running ray
-            uint32_t mine = lane < 16 ? n_counted : 0u;
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 16);
+            const uint32_t mine = wave_sum<16>(lane < 16 ? n_counted : 0u);
             if (lane == 0) { atomicAdd(stamps + 12, (unsigned long long)n_iter * 16ull); atomicAdd(stamps + 13, (unsigned long long)mine); }
         }
     }
@@ -446,13 +438,13 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
             const uint32_t Tb = T - 1, Tw = T - 2;
             float sum = 0.0f;
             for (uint32_t t = lane; t < Tw; t += 64) sum += cdf[t + 1] + 1e-5f;      // :19-20
-#pragma unroll
+#pragma unroll      // (wave_ops.hpp's wave_sum, and last_lane below, written out: as calls k_render_upsample compiles to other instructions)
             for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
             float run = 0.0f;
             for (uint32_t t0 = 0; t0 < Tw; t0 += 64) {
                 const uint32_t t = t0 + lane;
                 const float pdf = t < Tw ? (cdf[t + 1] + 1e-5f) / sum : 0.0f;
-                const float incl = scan_inclusive<64, false>(pdf, lane);
+                const float incl = scan_inclusive<AddOp>(pdf, lane);
                 if (t < Tw) cdf[t + 1] = run + incl;                                 // :21
                 run += __shfl(incl, 63, 64);
             }
@@ -637,7 +629,7 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
             const float alpha = 1.0f - e, p = alpha_survival(alpha), w = alpha * Tr;
             const float g = on ? s_g[tt] : 0.0f;
             const float gw = on ? g * w : 0.0f;
-            float inc = gw;
+            float inc = gw;      // (scan_suffix<AddOp> and first_lane, and quad_sum in pass 2, written out: as calls k_render_uniform_bwd compiles to other instructions)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const float o = __shfl_down(inc, off, 64);
@@ -710,7 +702,7 @@ __global__ void __launch_bounds__(GW * 64, 1) k_render_uniform_bwd(NetArgs na, G
 #pragma unroll
         for (int d = 0; d < 3; d++) {
 #pragma unroll
-            for (int off = 8; off > 0; off >>= 1) { a_o[d] += __shfl_xor(a_o[d], off, 16); a_d[d] += __shfl_xor(a_d[d], off, 16); }
+            for (int off = 8; off > 0; off >>= 1) { a_o[d] += __shfl_xor(a_o[d], off, 16); a_d[d] += __shfl_xor(a_d[d], off, 16); }      // two wave_sum<16>, interleaved (as reduce16)
             if (lane == 0) { ga.grad_o[(size_t)ray * 3 + d] = a_o[d]; ga.grad_d[(size_t)ray * 3 + d] = a_d[d]; }
         }
         __builtin_amdgcn_wave_barrier();

@@ -16,6 +16,7 @@
 //
 // All of it is HBM-streaming fp32 work (4-16 B per sample): wave-level scans, a few KB of LDS, no MFMA.
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -80,6 +81,7 @@ __global__ void __launch_bounds__(kSmpBlock) k_uniform_samples_bwd(const float* 
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
+        // (two wave_sum_lane0 of wave_ops.hpp, interleaved: as two calls the kernel compiles to one instruction more)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) { go[k] += __shfl_down(go[k], off, 64); gd[k] += __shfl_down(gd[k], off, 64); }
         if (lane == 0) { grad_o[(size_t)ray * 3 + k] = go[k]; grad_d[(size_t)ray * 3 + k] = gd[k]; }
@@ -87,15 +89,6 @@ __global__ void __launch_bounds__(kSmpBlock) k_uniform_samples_bwd(const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- :206-210
-__device__ __forceinline__ float scan_mul_incl(float v, uint32_t lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float o = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v *= o;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(kSmpBlock) k_trans_weights(const float* __restrict__ z_vals, const float* __restrict__ sigmas,
                                                              const float* __restrict__ sample_dist, uint32_t N, uint32_t T, float density_scale,
                                                              float* __restrict__ weights) {
@@ -112,11 +105,10 @@ __global__ void __launch_bounds__(kSmpBlock) k_trans_weights(const float* __rest
         const float delta = tt + 1 < T ? z[tt + 1] - z[tt] : last;            // :206-207
         const float alpha = on ? 1.0f - expf(((-delta) * density_scale) * sg[tt]) : 0.0f;   // :208
         const float p = on ? (1.0f - alpha) + 1e-15f : 1.0f;                  // :209
-        const float incl = scan_mul_incl(p, lane);
-        const float excl = __shfl_up(incl, 1, 64);
-        const float Tr = carry * (lane == 0 ? 1.0f : excl);
+        const float incl = scan_inclusive<MulOp>(p, lane);
+        const float Tr = carry * shifted_in(incl, lane, 1.0f);
         if (on) weights[(size_t)ray * T + t] = alpha * Tr;                    // :210
-        carry *= __shfl(incl, 63, 64);
+        carry *= last_lane(incl);
     }
 }
 
@@ -134,17 +126,17 @@ __global__ void __launch_bounds__(kSmpBlock) k_trans_weights_bwd(const float* __
     const float* gw = grad_w + (size_t)ray * T;
     const float last = sample_dist[ray];
     float carry = 1.0f;
-    for (uint32_t t0 = 0; t0 < T; t0 += 64) {                                 // forward pass: T_j
+    // forward pass, T_j: k_trans_weights' chunk once more (as one shared device function both kernels compile to other instructions)
+    for (uint32_t t0 = 0; t0 < T; t0 += 64) {
         const uint32_t t = t0 + lane;
         const bool on = t < T;
         const uint32_t tt = on ? t : T - 1;
         const float delta = tt + 1 < T ? z[tt + 1] - z[tt] : last;
         const float alpha = on ? 1.0f - expf(((-delta) * density_scale) * sg[tt]) : 0.0f;
         const float p = on ? (1.0f - alpha) + 1e-15f : 1.0f;
-        const float incl = scan_mul_incl(p, lane);
-        const float excl = __shfl_up(incl, 1, 64);
-        if (on) Tr_s[t] = carry * (lane == 0 ? 1.0f : excl);
-        carry *= __shfl(incl, 63, 64);
+        const float incl = scan_inclusive<MulOp>(p, lane);
+        if (on) Tr_s[t] = carry * shifted_in(incl, lane, 1.0f);
+        carry *= last_lane(incl);
     }
     float suffix = 0.0f;                                                      // sum of g_i w_i over the later chunks
     const uint32_t n_chunks = (T + 63) / 64;
@@ -157,15 +149,10 @@ __global__ void __launch_bounds__(kSmpBlock) k_trans_weights_bwd(const float* __
         const float alpha = 1.0f - e, p = (1.0f - alpha) + 1e-15f;
         const float Tr = Tr_s[tt], g = on ? gw[tt] : 0.0f;
         const float gwv = on ? g * (alpha * Tr) : 0.0f;
-        float incl = gwv;                                                     // reverse inclusive scan: sum over lanes >= this one
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const float o = __shfl_down(incl, off, 64);
-            if (lane + (uint32_t)off < 64) incl += o;
-        }
+        const float incl = scan_suffix<AddOp>(gwv, lane);                     // sum over lanes >= this one
         const float later = suffix + (incl - gwv);
         if (on) grad_sigmas[(size_t)ray * T + t] = (g * Tr - later / p) * ((delta * density_scale) * e);
-        suffix += __shfl(incl, 0, 64);
+        suffix += first_lane(incl);
     }
 }
 
@@ -183,21 +170,15 @@ __global__ void __launch_bounds__(kSmpBlock) k_sample_pdf(const float* __restric
     const float* w = weights + (size_t)ray * Tw;
     float sum = 0.0f;
     for (uint32_t t = lane; t < Tw; t += 64) sum += w[t] + 1e-5f;             // :19-20
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    sum = wave_sum(sum);
     float carry = 0.0f;
     if (lane == 0) cdf[0] = 0.0f;                                             // :22
     for (uint32_t t0 = 0; t0 < Tw; t0 += 64) {
         const uint32_t t = t0 + lane;
         const float pdf = t < Tw ? (w[t] + 1e-5f) / sum : 0.0f;
-        float incl = pdf;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const float o = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += o;
-        }
+        const float incl = scan_inclusive<AddOp>(pdf, lane);
         if (t < Tw) cdf[t + 1] = carry + incl;                                // :21
-        carry += __shfl(incl, 63, 64);
+        carry += last_lane(incl);
     }
     __builtin_amdgcn_wave_barrier();
     const float* b = bins + (size_t)ray * Tb;

@@ -17,6 +17,7 @@
 // one partial per workgroup in the caller's workspace; k_sigma_fit_reduce sums the partials of workgroups w = seg, seg + 4, ... in
 // double per segment, the four segments in order, adds the prior terms and rounds once.  The loss is accumulated in double throughout.
 #include "fused_net.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
@@ -83,7 +84,7 @@ __global__ void __launch_bounds__(kFitThreads) k_sigma_fit(const float* __restri
 #pragma unroll
             for (int ub = 0; ub < 4; ub++) p = fmaf(w2[ub], fmaxf(hid[ub][r], 0.0f), p);
 #pragma unroll
-            for (int off = 1; off < 16; off <<= 1) p += __shfl_xor(p, off, 64);      // every lane of the q group ends with the same bits
+            for (int off = 1; off < 16; off <<= 1) p += __shfl_xor(p, off, 64);      // every lane of the q group ends with the same bits (ASCENDING offsets: not the order of wave_ops.hpp's wave_sum<16>)
             h0[r] = p;
         }
 #pragma unroll
@@ -118,13 +119,13 @@ __global__ void __launch_bounds__(kFitThreads) k_sigma_fit(const float* __restri
     }
 
     // ---- lanes -> wave -> workgroup, fixed order
-    for (int off = 32; off > 0; off >>= 1) loss += __shfl_down(loss, off, 64);
+    loss = wave_sum_lane0(loss);
     if (lane == 0) lds_loss[wave] = loss;
     if (GRAD) {
         float* buf = lds + wave * kFitPartial;
 #pragma unroll
         for (int ub = 0; ub < 4; ub++) {
-            float v = dw2[ub];
+            float v = dw2[ub];      // (wave_ops.hpp's quad_sum, written out: as a call k_sigma_fit<true> compiles to other instructions)
             v += __shfl_xor(v, 16, 64);
             v += __shfl_xor(v, 32, 64);
             if (q == 0) buf[kFitW1 + 16 * ub + c] = v;

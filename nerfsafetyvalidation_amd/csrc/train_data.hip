@@ -2,13 +2,11 @@
 // of the resident image store, the per-ray MSE with its mean and the error-map update, and the loss's gradient.  The reference spends a
 // dozen small torch operators and autograd nodes on this per step; here it is one launch each way.  Wave64, vector loads and stores only.
 #include "ngp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace ngp {
 
 constexpr uint32_t kStoreF32 = 0, kStoreF16 = 1, kStoreU8 = 2;
-constexpr uint32_t kLossOneBlockRays = 16384;      // up to here one 1024-thread workgroup does the whole loss (the training batch: one launch)
-constexpr uint32_t kLossOneBlockThreads = 1024;
-constexpr uint32_t kLossThreads = 256;             // above: 256 rays per workgroup, then k_photo_final
 
 __device__ __forceinline__ float round_half(float x) { return (float)(_Float16)x; }
 
@@ -61,23 +59,7 @@ __global__ void __launch_bounds__(256) k_train_targets(const void* __restrict__ 
 }
 
 // ---- photometric loss -------------------------------------------------------------------------------------------------------------
-// The order of the sum is a function of N alone: (1) the 64 rays of a group by the xor butterfly below, in float; (2) lane l of ONE
-// wave adds the groups l, l + 64, ... in double, in that order; (3) the same butterfly over the 64 lanes, in double.
-template <typename T>
-__device__ __forceinline__ T butterfly_sum(T v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ void final_mean(const float* groups, uint32_t n_groups, uint32_t N, float* mean) {   // one whole wave calls this
-    const uint32_t lane = threadIdx.x & 63;
-    double acc = 0.0;
-    for (uint32_t g = lane; g < n_groups; g += 64) acc += (double)groups[g];
-    acc = butterfly_sum(acc);
-    if (lane == 0) *mean = (float)(acc / (double)N);
-}
-
+// The mean over the rays is the fixed-order mean (DESIGN.md "Cross-lane arithmetic"), fused with the pass that forms the per-ray losses.
 template <typename P>
 __device__ __forceinline__ float ray_loss(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t i, uint32_t N, float* __restrict__ per_ray,
                                           float* __restrict__ error_row, uint32_t map_len, const int64_t* __restrict__ inds_coarse) {
@@ -94,32 +76,50 @@ __device__ __forceinline__ float ray_loss(const P* __restrict__ pred, const floa
 }
 
 template <typename P>
-__global__ void __launch_bounds__(kLossOneBlockThreads) k_photo_loss_one_block(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
+__global__ void __launch_bounds__(kMeanOneBlockThreads) k_photo_loss_one_block(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
                                                                               float* __restrict__ per_ray, float* __restrict__ mean,
                                                                               float* __restrict__ error_row, uint32_t map_len,
                                                                               const int64_t* __restrict__ inds_coarse) {
-    __shared__ float s_groups[kLossOneBlockRays / 64];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t rounds = ((N + kLossOneBlockThreads - 1) / kLossOneBlockThreads);
-    for (uint32_t r = 0; r < rounds; r++) {
-        const float v = butterfly_sum(ray_loss(pred, gt, r * kLossOneBlockThreads + threadIdx.x, N, per_ray, error_row, map_len, inds_coarse));
-        if (lane == 0) s_groups[r * (kLossOneBlockThreads / 64) + wave] = v;
-    }
-    __syncthreads();
-    if (wave == 0) final_mean(s_groups, ((N + 63) / 64), N, mean);
+    mean_one_block([&](uint32_t i) { return ray_loss(pred, gt, i, N, per_ray, error_row, map_len, inds_coarse); }, N, mean);
 }
 
 template <typename P>
-__global__ void __launch_bounds__(kLossThreads) k_photo_loss_groups(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
-                                                                    float* __restrict__ per_ray, float* __restrict__ error_row, uint32_t map_len,
-                                                                    const int64_t* __restrict__ inds_coarse, float* __restrict__ groups) {
-    const uint32_t i = blockIdx.x * kLossThreads + threadIdx.x;
-    const float v = butterfly_sum(ray_loss(pred, gt, i, N, per_ray, error_row, map_len, inds_coarse));
-    if ((threadIdx.x & 63) == 0 && (i >> 6) < ((N + 63) / 64)) groups[i >> 6] = v;
+__global__ void __launch_bounds__(kMeanGroupThreads) k_photo_loss_groups(const P* __restrict__ pred, const float* __restrict__ gt, uint32_t N,
+                                                                         float* __restrict__ per_ray, float* __restrict__ error_row, uint32_t map_len,
+                                                                         const int64_t* __restrict__ inds_coarse, float* __restrict__ groups) {
+    mean_groups([&](uint32_t i) { return ray_loss(pred, gt, i, N, per_ray, error_row, map_len, inds_coarse); }, N, groups);
 }
 
-__global__ void __launch_bounds__(64) k_photo_final(const float* __restrict__ groups, uint32_t n_groups, uint32_t N, float* __restrict__ mean) {
+// ---- the same mean over a plain float[N] (the distortion loss's per-ray values) ----
+__global__ void __launch_bounds__(kMeanOneBlockThreads) k_mean_one_block(const float* __restrict__ values, uint32_t N, float* __restrict__ mean) {
+    mean_one_block([&](uint32_t i) { return i < N ? values[i] : 0.0f; }, N, mean);
+}
+
+__global__ void __launch_bounds__(kMeanGroupThreads) k_mean_groups(const float* __restrict__ values, uint32_t N, float* __restrict__ groups) {
+    mean_groups([&](uint32_t i) { return i < N ? values[i] : 0.0f; }, N, groups);
+}
+
+__global__ void __launch_bounds__(64) k_mean_final(const float* __restrict__ groups, uint32_t n_groups, uint32_t N, float* __restrict__ mean) {
     final_mean(groups, n_groups, N, mean);
+}
+
+int mean_of_groups(const float* groups, uint32_t N, float* mean, hipStream_t s, const char* what) {
+    k_mean_final<<<1, 64, 0, s>>>(groups, div_up(N, 64), N, mean);
+    return check_launch(what);
+}
+
+int mean_of_rays(const float* values, uint32_t N, float* mean, void* workspace, size_t workspace_bytes, hipStream_t s, const char* what) {
+    const size_t need = mean_workspace(N);
+    if (need && (!workspace || workspace_bytes < need)) {
+        set_error("%s: workspace too small (%zu < %zu bytes)", what, workspace ? workspace_bytes : (size_t)0, need);
+        return NGP_EWORKSPACE;
+    }
+    if (!need) {
+        k_mean_one_block<<<1, kMeanOneBlockThreads, 0, s>>>(values, N, mean);
+        return check_launch(what);
+    }
+    k_mean_groups<<<div_up(N, kMeanGroupThreads), kMeanGroupThreads, 0, s>>>(values, N, (float*)workspace);
+    return mean_of_groups((const float*)workspace, N, mean, s, what);
 }
 
 template <typename P>
@@ -167,7 +167,7 @@ int ngp_train_targets(const void* store, int store_dtype, uint32_t C, uint64_t f
     return check_launch("train_targets");
 }
 
-size_t ngp_photo_loss_workspace(uint32_t N) { return N <= kLossOneBlockRays ? 0 : (size_t)div_up(N, 64) * sizeof(float); }
+size_t ngp_photo_loss_workspace(uint32_t N) { return mean_workspace(N); }
 
 int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, uint32_t N, float* per_ray, float* mean, float* error_row,
                            uint32_t map_len, const int64_t* inds_coarse, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
@@ -185,20 +185,19 @@ int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, ui
     ProfScope prof("photo_loss", s, (double)N);
     if (!need) {
         if (pred_dtype == 0)
-            k_photo_loss_one_block<float><<<1, kLossOneBlockThreads, 0, s>>>((const float*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
+            k_photo_loss_one_block<float><<<1, kMeanOneBlockThreads, 0, s>>>((const float*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
         else
-            k_photo_loss_one_block<_Float16><<<1, kLossOneBlockThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
+            k_photo_loss_one_block<_Float16><<<1, kMeanOneBlockThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
         return check_launch("photo_loss_forward");
     }
-    const uint32_t blocks = div_up(N, kLossThreads);
+    const uint32_t blocks = div_up(N, kMeanGroupThreads);
     if (pred_dtype == 0)
-        k_photo_loss_groups<float><<<blocks, kLossThreads, 0, s>>>((const float*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
+        k_photo_loss_groups<float><<<blocks, kMeanGroupThreads, 0, s>>>((const float*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
     else
-        k_photo_loss_groups<_Float16><<<blocks, kLossThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
+        k_photo_loss_groups<_Float16><<<blocks, kMeanGroupThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
     int rc = check_launch("photo_loss_forward");
     if (rc) return rc;
-    k_photo_final<<<1, 64, 0, s>>>((const float*)workspace, div_up(N, 64), N, mean);
-    return check_launch("photo_loss_forward (final)");
+    return mean_of_groups((const float*)workspace, N, mean, s, "photo_loss_forward (final)");
 }
 
 int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred, ngp_stream_t stream) {
