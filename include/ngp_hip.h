@@ -514,6 +514,38 @@ NGP_API int ngp_overlay_cast(const float* rays_o, const float* rays_d, uint64_t 
 NGP_API int ngp_overlay_shade(const float* rays_d, const int32_t* prim, const float* normal, uint64_t N, const float* colors, uint32_t P,
                               float ambient, float* image, uint8_t* image_u8, ngp_stream_t stream);
 
+/* The closest point of the mesh to every query point (csrc/closest.hip; MeshWorld.closest), on the grid ngp_raycast walks.
+ * tri_verts float [F,12], 16-byte aligned: the rows (v0, 0), (v1, 0), (v2, 0) of the EXACT vertices (not tri_data: v0 + e1 is not v1).
+ *   ngp_closest_point  points float [N,3] -> distance float [N], prim int32 [N], point float [N,3] by the closest-point rule of
+ *                      nerfsafetyvalidation_amd/world.py's docstring: per triangle the smallest of an interior candidate and three
+ *                      segment candidates, float32, one IEEE operation per step; the smallest finite d^2 wins, equal d^2 goes to the
+ *                      lowest triangle index; accepted iff sqrt(d^2) <= max_distance (+inf allowed, NaN refused).  A point with a
+ *                      non-finite component or without an accepted triangle is a miss: distance +inf, prim -1, point NaN.  A point
+ *                      with a component beyond grid.reach is tested against all F triangles.  tested uint32 [N] or null: the number
+ *                      of (point, triangle) pairs evaluated, a measurement.  No result depends on the grid.  N == 0 launches nothing.
+ * F, P, N < 2^31 (NGP_EINVAL otherwise, nothing launched).  No atomics, no workspace, no global state.
+ *
+ *   ngp_distance_stats the running statistics of a sequence of distances handed over in any number of calls: this call appends
+ *                      distance float [n] (device) to the `seen` elements of the earlier calls (seen == 0: a fresh sequence; the
+ *                      state need not be cleared).  state: ngp_distance_stats_state_bytes() bytes of device memory, the caller's,
+ *                      one per sequence.  thresholds_host: K <= NGP_DISTANCE_STATS_MAX_THRESHOLDS floats in host memory, the same
+ *                      in every call of a sequence.  stats double [16] (device), of ALL seen + n elements:
+ *                        [0] the number of finite entries  [1] their sum  [2] their sum of squares  [3] their maximum (0 without any)
+ *                        [4 + k] the number of finite entries <= thresholds[k]  (0 for k >= K)  [12] seen + n  [13..15] 0
+ *                      Fixed order, a function of an element's index in the sequence alone: the 64 elements of a group by the xor
+ *                      butterfly in double; lane l of one wave adds the groups l, l + 64, ... in that order; the butterfly over the
+ *                      64 lanes.  The same bits for any split of the sequence into calls.  Workspace:
+ *                      ngp_distance_stats_workspace(n) bytes, 8-byte aligned (NGP_EWORKSPACE when smaller).  n < 2^31 per call.
+ *                      No atomics.  Calls of one sequence go to one stream, in order. */
+#define NGP_DISTANCE_STATS_MAX_THRESHOLDS 8
+NGP_API int ngp_closest_point(const float* points, uint64_t N, const ngp_raycast_grid* grid, const int32_t* cell_start,
+                              const int32_t* pair_tri, uint64_t P, const float* tri_verts, uint32_t F, float max_distance, float* distance,
+                              int32_t* prim, float* point, uint32_t* tested, ngp_stream_t stream);
+NGP_API size_t ngp_distance_stats_state_bytes(void);
+NGP_API size_t ngp_distance_stats_workspace(uint64_t n);
+NGP_API int ngp_distance_stats(const float* distance, uint64_t n, uint64_t seen, const float* thresholds_host, uint32_t K, void* state,
+                               double* stats, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+
 /* NeRFRenderer.run (nerf/renderer.py:125-258) for upsample_steps == 0 and perturb == False (fp16 or fp32 network, ngp_model::precision): T uniform
  * samples per ray between nears and fars (lin = the T values of torch.linspace(0, 1, T), device memory), hash grid + sigma net
  * on every sample, transmittance scan, colour net where weight > 1e-4, and the per-ray sums.  Outputs: weights_sum [N],

@@ -153,6 +153,10 @@ SIGNATURES = {
     "ngp_voxelize_mark": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, C.c_uint64, C.c_uint64, _vp, _vp],
     "ngp_overlay_cast": [_vp, _vp, C.c_uint64, _vp, _vp, _u32, _f32, _vp, _u32, _vp, _vp, _vp, _vp],
     "ngp_overlay_shade": [_vp, _vp, _vp, C.c_uint64, _vp, _u32, _f32, _vp, _vp, _vp],
+    "ngp_closest_point": [_vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "ngp_distance_stats_state_bytes": [],
+    "ngp_distance_stats_workspace": [C.c_uint64],
+    "ngp_distance_stats": [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), _u32, _vp, _vp, _vp, _sz, _vp],
     "ngp_sift_workspace": [_u32, _u32],
     "ngp_sift_layer_offset": [_u32, _u32, _int, _int],
     "ngp_sift_octaves": [_u32, _u32],
@@ -186,7 +190,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
 
 _lib = None
 

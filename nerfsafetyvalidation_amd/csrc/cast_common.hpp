@@ -1,14 +1,26 @@
 // What the mesh cast and the overlay cast must compute with the same bits (the rules are nerfsafetyvalidation_amd/world.py's
 // docstring): the dot product's grouping, the thread -> ray mapping, the headlight, a pixel's two stores, and the host's
-// frame_width plan.  Included by raycast.hip and overlay.hip only.
+// frame_width plan; and what the mesh cast and the closest-point query (closest.hip) share: a triangle's three packed rows and the
+// grid check.  Included by raycast.hip, overlay.hip and closest.hip only.
 #pragma once
 #include "ngp_common.hpp"
 
 namespace ngp {
 
 constexpr uint32_t kCastBlock = 256;
+constexpr uint32_t kMaxCellsPerAxis = 256;
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// three 16-byte rows of a [F,12] table: tri_data's (v0, e1, e2) -- or, for closest.hip, tri_verts' (v0, v1, v2) under the same names
+struct Tri {
+    float v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z;
+};
+
+__device__ __forceinline__ Tri load_tri(const float4* __restrict__ tri_data, uint32_t f) {
+    const float4 a = tri_data[3 * (size_t)f], b = tri_data[3 * (size_t)f + 1], c = tri_data[3 * (size_t)f + 2];
+    return Tri{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
+}
 
 // ray index of this thread: row-major, or the 8 x 8 pixel tile form when the rays are whole rows of width W (a wave's rays then walk
 // the same cells).  false: this thread has no ray -- the caller's business: k_raycast returns, k_overlay_cast must not.
@@ -47,6 +59,17 @@ static inline int cast_plan(const char* what, uint64_t N, uint32_t& frame_width,
         const uint64_t tiles = (uint64_t)((frame_width + 7) / 8) * ((N / frame_width + 7) / 8);
         if (tiles * 64 >= ((uint64_t)1 << 31)) frame_width = 0;
         else threads = (uint32_t)(tiles * 64);
+    }
+    return NGP_OK;
+}
+
+static inline int cast_check_grid(const char* what, const ngp_raycast_grid* G) {
+    NGP_REQUIRE(G, "%s: null grid", what);
+    for (int a = 0; a < 3; a++) {
+        NGP_REQUIRE(G->n[a] >= 1 && G->n[a] <= kMaxCellsPerAxis, "%s: 1..%u cells per axis (got %u x %u x %u)", what, kMaxCellsPerAxis, G->n[0],
+                    G->n[1], G->n[2]);
+        NGP_REQUIRE(G->cell[a] > 0.0f && G->inv_cell[a] > 0.0f && G->grow[a] >= 0.0f && G->lo[a] == G->lo[a] && G->reach >= 0.0f,
+                    "%s: the grid needs positive finite cell sizes", what);
     }
     return NGP_OK;
 }

@@ -23,21 +23,10 @@
 
 namespace ngp {
 
-constexpr uint32_t kMaxCellsPerAxis = 256;
-
 struct CastHit {
     float t, u, v;
     int32_t prim;
 };
-
-struct Tri {
-    float v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z;
-};
-
-__device__ __forceinline__ Tri load_tri(const float4* __restrict__ tri_data, uint32_t f) {
-    const float4 a = tri_data[3 * (size_t)f], b = tri_data[3 * (size_t)f + 1], c = tri_data[3 * (size_t)f + 2];
-    return Tri{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
-}
 
 // the hit rule for one (ray, triangle); updates `best` under (smallest t, then lowest index)
 __device__ __forceinline__ void test_triangle(const Tri& T, int32_t f, float ox, float oy, float oz, float dx, float dy, float dz, float t_min,
@@ -220,17 +209,6 @@ __global__ void __launch_bounds__(kCastBlock) k_raycast_shade(const float* __res
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) store_rgb(image, image_u8, r, k, rgb[k]);
-}
-
-static int cast_check_grid(const char* what, const ngp_raycast_grid* G) {
-    NGP_REQUIRE(G, "%s: null grid", what);
-    for (int a = 0; a < 3; a++) {
-        NGP_REQUIRE(G->n[a] >= 1 && G->n[a] <= kMaxCellsPerAxis, "%s: 1..%u cells per axis (got %u x %u x %u)", what, kMaxCellsPerAxis, G->n[0],
-                    G->n[1], G->n[2]);
-        NGP_REQUIRE(G->cell[a] > 0.0f && G->inv_cell[a] > 0.0f && G->grow[a] >= 0.0f && G->lo[a] == G->lo[a] && G->reach >= 0.0f,
-                    "%s: the grid needs positive finite cell sizes", what);
-    }
-    return NGP_OK;
 }
 
 }  // namespace ngp

@@ -9,6 +9,12 @@
     save_mesh          extract_geometry of model.density over model.aabb_infer, written as a binary PLY
     write_ply/read_ply the binary PLY (optionally with uchar vertex colours) and its reader
     mesh_to_world      NeRF axes -> the world frame of collision.py's boxes (the inverse of collision.to_nerf)
+    surface_error      how far the mesh is from the true world's (world.MeshWorld): accuracy, completeness, F-score, Hausdorff,
+                         and the collision margin a planner needs (DESIGN.md "Surface error")
+    sample_surface     area-weighted surface samples, deterministic for a seed
+    distance_stats     count, sum, sum of squares, maximum and counts within thresholds of a distance array, in double, in one
+                         fixed order (csrc/closest.hip ngp_distance_stats on a HIP device, the same order in numpy on the CPU)
+    error_colors       per-vertex distances -> uint8 colours for write_ply
 
 The rule (DESIGN.md "Mesh export"): marching tetrahedra on the Kuhn split.  A lattice point is inside iff u > threshold (strict;
 NaN is outside).  Every cell is cut into the six tetrahedra around its (0,0,0)-(1,1,1) diagonal -- for the permutation (a, b, c) of
@@ -21,7 +27,10 @@ type), faces by (cell in C order, tetrahedron, triangle); triangle normals (righ
 With collision.py the mesh feeds the reference's createCollisionMap.py -> createSDF.py chain:
     occ = collision.occupancy_from_points(mesh_to_world(vertices), box); SignedDistanceField.from_occupancy(occ, box)
 """
+import ctypes
+import dataclasses
 import itertools
+import math
 import os
 import struct
 
@@ -29,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collision import PLANNER_ROT
+from .collision import PLANNER_ROT, to_nerf
 
 # edge type -> lattice offset (dx, dy, dz): 3 axis edges, 3 face diagonals, the body diagonal
 EDGE_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
@@ -361,3 +370,201 @@ def mesh_to_world(vertices, rot=PLANNER_ROT):
         return vertices[..., 0:1] * r[:, 0] + vertices[..., 1:2] * r[:, 1] + vertices[..., 2:3] * r[:, 2]
     r = np.asarray(rot, dtype=np.float64).reshape(3, 3)
     return np.asarray(vertices, dtype=np.float64) @ r.T
+
+
+# ------------------------------------------------------------------------------------------------------------- surface error
+MAX_THRESHOLDS = 8                                  # NGP_DISTANCE_STATS_MAX_THRESHOLDS
+MISS_COLOR = (255, 0, 255)                          # error_colors: a point without surface within max_distance
+ERROR_RAMP = ((0, 160, 0), (255, 255, 0), (255, 0, 0))      # error_colors: distance 0, vmax / 2, vmax and beyond
+
+
+def _check_thresholds(thresholds):
+    th = [float(t) for t in thresholds]
+    if len(th) > MAX_THRESHOLDS or any(t != t for t in th):
+        raise ValueError(f"distance_stats: at most {MAX_THRESHOLDS} thresholds, none NaN (got {th})")
+    return th
+
+
+def _fold64(a, op):
+    """the xor butterfly of 64 lanes as lane 0 sees it: offsets 32, 16, .. 1 over the last axis"""
+    for off in (32, 16, 8, 4, 2, 1):
+        a = op(a[..., :off], a[..., off:2 * off])
+    return a[..., 0]
+
+
+def distance_stats_numpy(distance, thresholds=()):
+    """ngp_distance_stats in numpy, the same order and so the same bits: element i sits in lane i % 64 of group i / 64; a group's 64
+    contributions (a non-finite or absent element contributes nothing) by the butterfly, in double; lane l adds the groups l,
+    l + 64, ... in that order; the butterfly over the lanes.  -> the dict distance_stats documents"""
+    th = _check_thresholds(thresholds)
+    d = np.ascontiguousarray(distance, np.float32).reshape(-1)
+    n = d.shape[0]
+    rows = 64 * max(1, -(-n // 4096))                                   # groups, padded to whole rounds of the 64 lanes
+    x = np.full(rows * 64, np.inf, np.float32)
+    x[:n] = d
+    x = x.reshape(rows, 64)
+    finite = x < np.float32(np.inf)                                       # (false for NaN)
+    v = np.where(finite, x, np.float32(0)).astype(np.float64)
+    terms = [finite.astype(np.float64), v, v * v, v] + [(finite & (x <= np.float32(t))).astype(np.float64) for t in th]
+    out = []
+    for q, t in enumerate(terms):
+        op = np.maximum if q == 3 else np.add
+        groups = _fold64(t, op).reshape(-1, 64)
+        acc = np.zeros(64, np.float64)
+        for row in groups:
+            acc = op(acc, row)
+        out.append(float(_fold64(acc, op)))
+    return {"n": n, "finite": int(out[0]), "sum": out[1], "sum_sq": out[2], "max": out[3], "within": tuple(int(c) for c in out[4:])}
+
+
+def distance_stats(distance, thresholds=(), splits=()):
+    """distance: float32 [N], a tensor (a HIP device: ngp_distance_stats on the current stream; the CPU: distance_stats_numpy) or
+    a numpy array -> {"n": N, "finite": the number of finite entries, "sum", "sum_sq", "max": of those, in double (max 0 without
+    any), "within": the number of finite entries <= each threshold}.  splits: indices at which the array is handed to the kernel in
+    separate launches; the result does not depend on them."""
+    th = _check_thresholds(thresholds)
+    if not isinstance(distance, torch.Tensor) or distance.device.type != "cuda":
+        return distance_stats_numpy(distance.detach().numpy() if isinstance(distance, torch.Tensor) else distance, th)
+    d = distance.detach().to(torch.float32).reshape(-1).contiguous()
+    n, lib = d.shape[0], _lib.lib()
+    cuts = [0] + sorted(int(c) for c in splits) + [n]
+    if cuts[1] < 0 or cuts[-2] > n:
+        raise ValueError(f"distance_stats: splits lie in 0 .. {n}")
+    th_c = (ctypes.c_float * max(1, len(th)))(*th)
+    with torch.cuda.device(d.device):
+        state = torch.empty(lib.ngp_distance_stats_state_bytes(), dtype=torch.uint8, device=d.device)
+        stats = torch.empty(16, dtype=torch.float64, device=d.device)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            if b - a >= 2 ** 31:
+                raise ValueError("distance_stats: fewer than 2^31 distances per launch; pass splits")
+            nbytes = lib.ngp_distance_stats_workspace(b - a)
+            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=d.device)
+            part = d[a:b]
+            _lib.check(lib.ngp_distance_stats(_lib.ptr(part) if b > a else None, b - a, a, th_c, len(th), _lib.ptr(state), _lib.ptr(stats),
+                                              _lib.ptr(ws), nbytes, _lib.stream()), "distance_stats")
+    out = stats.cpu().tolist()
+    return {"n": n, "finite": int(out[0]), "sum": out[1], "sum_sq": out[2], "max": out[3], "within": tuple(int(c) for c in out[4:4 + len(th)])}
+
+
+def sample_surface(vertices, faces, n, seed=0):
+    """n points of the surface, area-weighted: float32 [n,3] on the vertices' device (numpy in, numpy out).  Deterministic for a
+    seed, and the same on every device: the draw and its arithmetic run on the host in float64 -- three uniform draws per point
+    (u, r1, r2 [n] each, in this order) from torch.Generator().manual_seed(seed); the face is the first whose cumulative area (in
+    face order) exceeds u * the total, the point (1 - sqrt(r1)) v0 + sqrt(r1) (1 - r2) v1 + sqrt(r1) r2 v2, rounded to float32."""
+    as_numpy = not isinstance(vertices, torch.Tensor)
+    v = torch.as_tensor(np.asarray(vertices) if as_numpy else vertices.detach())
+    f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces.detach())
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0 or int(n) < 0:
+        raise ValueError(f"sample_surface: vertices [V,3], faces [F,3], n >= 0 (got {tuple(v.shape)}, {tuple(f.shape)}, {n})")
+    tri = v.to("cpu", torch.float32)[f.to("cpu").long()].to(torch.float64)
+    area = torch.linalg.vector_norm(torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), dim=1)
+    cdf = torch.cumsum(area, 0)
+    if not float(cdf[-1]) > 0:
+        raise ValueError("sample_surface: the mesh has no area")
+    gen = torch.Generator().manual_seed(int(seed))
+    u, r1, r2 = [torch.rand(int(n), generator=gen, dtype=torch.float64) for _ in range(3)]
+    face = torch.searchsorted(cdf, u * cdf[-1], right=True).clamp_max(f.shape[0] - 1)
+    su = r1.sqrt()
+    t = tri[face]
+    p = ((1.0 - su)[:, None] * t[:, 0] + (su * (1.0 - r2))[:, None] * t[:, 1] + (su * r2)[:, None] * t[:, 2]).to(torch.float32)
+    return p.numpy() if as_numpy else p.to(v.device)
+
+
+@dataclasses.dataclass
+class DirectionError:
+    """one direction of surface_error: n points, `misses` of them without surface within max_distance (or not finite); mean, rms and
+    max of the others' distances; within[tau] the number of points with distance <= tau; `distances` float32 [n] on the world's
+    device (+inf: a miss); `stats` the raw sums they come from (distance_stats' dict)"""
+    n: int
+    misses: int
+    mean: float
+    rms: float
+    max: float
+    within: dict
+    distances: torch.Tensor
+    stats: dict
+
+
+def _direction(distances, thresholds):
+    st = distance_stats(distances, thresholds)
+    k = st["finite"]
+    return DirectionError(st["n"], st["n"] - k, st["sum"] / k if k else math.nan, math.sqrt(st["sum_sq"] / k) if k else math.nan, st["max"],
+                          dict(zip(thresholds, st["within"])), distances, st)
+
+
+@dataclasses.dataclass
+class SurfaceError:
+    """accuracy: the given mesh's points against the world; completeness: the world's points against the given mesh.
+    precision[tau] = accuracy.within[tau] / accuracy.n, recall[tau] the same of completeness (a miss is not within),
+    f_score[tau] = 2 p r / (p + r) (0 when both are); hausdorff: the larger of the two maxima, max_distance when a point missed."""
+    accuracy: DirectionError
+    completeness: DirectionError
+    thresholds: tuple
+    max_distance: float
+    precision: dict
+    recall: dict
+    f_score: dict
+    hausdorff: float
+
+    def margin(self, q):
+        """the q-quantile (nearest rank: the smallest distance with a share >= q of the points at or below it, numpy's
+        `inverted_cdf`) of the completeness distances: the collision radius within which a share q of the true surface has surface
+        of the given mesh.  +inf when the quantile falls among the misses."""
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"SurfaceError.margin: q in [0, 1] (got {q})")
+        d = np.sort(self.completeness.distances.detach().cpu().numpy().reshape(-1))
+        if d.size == 0:
+            return math.nan
+        return float(d[min(d.size - 1, max(0, int(math.ceil(d.size * q - 1.0))))])
+
+
+def surface_error(vertices, faces, world, *, thresholds, max_distance, samples=None, seed=0, frame="nerf"):
+    """the distance between the surface of a mesh (vertices [V,3], faces [F,3]; the NeRF's axes, or frame="world": the planner's
+    frame, turned by collision.to_nerf like MeshWorld's) and the surface of `world` (a world.MeshWorld), both ways -> SurfaceError.
+    The points of a direction are the mesh's vertices, or with samples=n that many area-weighted surface samples (sample_surface
+    with `seed` for the given mesh, seed + 1 for the world).  max_distance truncates the search (world.MeshWorld.closest): a point
+    without surface within it is a miss.  Everything runs on the world's device: closest-point queries and statistics in HIP on a
+    HIP device, their numpy forms on the CPU."""
+    from .world import MeshWorld
+    if frame not in ("nerf", "world"):
+        raise ValueError(f"surface_error: frame is 'nerf' or 'world' (got {frame!r})")
+    th = tuple(_check_thresholds(thresholds))
+    max_distance = float(max_distance)
+    if max_distance != max_distance:
+        raise ValueError("surface_error: max_distance is NaN")
+    v = torch.as_tensor(np.asarray(vertices) if not isinstance(vertices, torch.Tensor) else vertices.detach()).to(world.device, torch.float32)
+    f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces.detach()).to(world.device)
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"surface_error: vertices [V,3] (got {tuple(v.shape)})")
+    if frame == "world":
+        v = to_nerf(v, PLANNER_ROT)
+    given = MeshWorld(v, f)
+    if samples is None:
+        from_given, from_world = given.vertices, world.vertices
+    else:
+        from_given = sample_surface(given.vertices, given.faces, samples, seed)
+        from_world = sample_surface(world.vertices, world.faces, samples, seed + 1)
+    accuracy = _direction(world.closest(from_given, max_distance)["distance"], th)
+    completeness = _direction(given.closest(from_world, max_distance)["distance"], th)
+    precision = {t: accuracy.within[t] / accuracy.n if accuracy.n else math.nan for t in th}
+    recall = {t: completeness.within[t] / completeness.n if completeness.n else math.nan for t in th}
+    f_score = {t: 2.0 * precision[t] * recall[t] / (precision[t] + recall[t]) if precision[t] + recall[t] > 0 else 0.0 for t in th}
+    hausdorff = max_distance if accuracy.misses or completeness.misses else max(accuracy.max, completeness.max)
+    return SurfaceError(accuracy, completeness, th, max_distance, precision, recall, f_score, hausdorff)
+
+
+def error_colors(distance, vmax):
+    """distances [N] (tensor or numpy) -> uint8 [N,3] for write_ply: ERROR_RAMP, linear between its three colours at 0, vmax / 2 and
+    vmax (beyond: the last), rounded to nearest; a non-finite distance (a miss) is MISS_COLOR"""
+    if not float(vmax) > 0:
+        raise ValueError("error_colors: vmax > 0")
+    d = np.asarray(distance.detach().cpu().numpy() if isinstance(distance, torch.Tensor) else distance, np.float64).reshape(-1)
+    ok = np.isfinite(d)
+    t = np.clip(np.where(ok, d, 0.0) / float(vmax), 0.0, 1.0) * 2.0
+    ramp = np.asarray(ERROR_RAMP, np.float64)
+    k = np.minimum(t.astype(np.int64), 1)
+    w = (t - k)[:, None]
+    rgb = np.rint(ramp[k] * (1.0 - w) + ramp[k + 1] * w).astype(np.uint8)
+    rgb[~ok] = MISS_COLOR
+    return rgb

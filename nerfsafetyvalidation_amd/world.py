@@ -12,8 +12,8 @@ nerf.utils.get_rays (so a world frame and a NeRF frame of one pose are pixel-ali
 A mesh on a HIP device goes through csrc/raycast.hip (a uniform grid, one lane per ray) on the current stream; a CPU tensor or a numpy
 array through numpy: brute force over all triangles, chunked -- the package's CPU implementation, as mesh.isosurface has one.
 
-This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip and DESIGN.md point
-here, and a change to a rule is made in this text, in the numpy path and in the kernel.
+This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip, csrc/closest.hip and
+DESIGN.md point here, and a change to a rule is made in this text, in the numpy path and in the kernel.
 
 The hit rule; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
     per triangle v0, e1 = v1 - v0, e2 = v2 - v0;  p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det, s = o - v0,
@@ -97,6 +97,35 @@ non-finite field or r <= 0 is a ValueError.  The overlay's hit rule per (ray, pr
     acceptance: accept iff t > t_min and t < t_max[ray] (NaN fails); the smallest t wins, equal t goes to the lowest primitive index;
         a ray with a non-finite component or a zero direction is a miss: t = +inf, prim = -1, normal = 0.
     t_max[ray] is the mesh cast's t of the same ray (+inf on a mesh miss): the depth merge with the world is part of the cast.
+
+The world is also what the NeRF's exported surface is measured against (mesh.surface_error; DESIGN.md "Surface error"): the closest
+point of the mesh to every query point.
+
+        .closest(points, max_distance=inf, coherent=None)              -> {"distance", "prim", "point"}
+    closest_numpy(points, vertices, faces, max_distance=inf)           -> the same, numpy: brute force over all triangles
+
+A HIP world goes through csrc/closest.hip (the cast's grid, one lane per point) on the current stream, a CPU world through
+closest_numpy; the two agree bit for bit.
+
+The closest-point rule; float32, one rounding per operation (correctly rounded division and square root), the hit rule's a . b and
+a x b.  It is defined on the EXACT vertices v0, v1, v2 = vertices[faces] (not tri_data: v0 + e1 is not v1), e1 = v1 - v0,
+e2 = v2 - v0, for every input, zero-area faces included.  Per (point p, triangle) the smallest of four candidate squared distances,
+in this order, a later candidate replacing an earlier one only when strictly smaller (NaN never replaces):
+    interior    n = e1 x e2, nn = n . n, s = p - v0, sn = s . n, b = ((s x e2) . n) / nn, c = ((e1 x s) . n) / nn;
+                a candidate iff nn > 0 and b >= 0 and c >= 0 and b + c <= 1 (NaN fails);
+                d2 = the larger of (sn sn) / nn and box2 (box2 when the first is NaN), box2 = g . g the squared distance from p to
+                the triangle's bounding box, g_a = max(max(min_k v_ka - p_a, p_a - max_k v_ka), 0) -- in exact arithmetic box2 is never
+                the larger; in float32 it keeps a sliver's cancellation from reporting a far triangle as near, which is what lets
+                the search below stop;  closest point p - (sn / nn) n
+    segments    v0 -> v1, v0 -> v2, v1 -> v2 (ab = e1, e2, v2 - v1; ap = s, s, p - v1):  den = ab . ab, x = (ap . ab) / den,
+                t = 0 when den == 0, else x;  then t = 0 unless t >= 0, t = 1 unless t <= 1;  r = ap - t ab, d2 = r . r;
+                closest point a + t ab, and b itself when t == 1 (so the closest point of a vertex is that vertex, bit for bit)
+    Across triangles the smallest d2 below +inf wins, an equal d2 goes to the lowest triangle index.
+    acceptance: distance = sqrt(d2) <= max_distance (+inf is allowed; NaN is a ValueError), max_distance rounded to float32.
+    A point with a non-finite component, or without an accepted triangle, is a miss: distance = +inf, prim = -1, point = NaN.
+The grid only chooses which triangles a point is tested against: no result depends on it, nor on `coherent` (the HIP path sorts
+the queries by grid cell before the launch and scatters the results back: a wave's lanes then search the same cells).
+A point with a component beyond REACH S is tested against every triangle.
 """
 import ctypes
 
@@ -115,6 +144,8 @@ DEFAULT_AMBIENT = 0.3
 GREY = 0.5
 _CHUNK_PAIRS = 1 << 20                              # (ray, triangle) pairs per chunk of the numpy path
 _VOXEL_CHUNK_PAIRS = 1 << 18                        # (face, candidate cell) pairs per chunk of voxelize_numpy
+_CLOSEST_CHUNK_PAIRS = 1 << 19                      # (point, triangle) pairs per chunk of closest_numpy
+COHERENT_MIN_POINTS = 1 << 15                       # MeshWorld.closest(coherent=None) sorts the queries by cell from here on
 MAX_PAIRS_PER_LAUNCH = 2 ** 31 - 1                  # ngp_voxelize_mark: pairs per call; a mesh with more is marked in several calls
 
 _f32 = np.float32
@@ -168,6 +199,19 @@ def pack_triangles(vertices, faces):
     else:
         out = np.zeros((idx.shape[0], 12), dtype=_f32)
     out[:, 0:3], out[:, 4:7], out[:, 8:11] = v0, v1 - v0, v2 - v0
+    return out
+
+
+def pack_vertices(vertices, faces):
+    """vertices float32 [V,3], faces integer [F,3] (numpy or tensors of one device) -> tri_verts float32 [F,12]: the rows (v0, 0),
+    (v1, 0), (v2, 0) of the exact vertices, the closest-point rule's table"""
+    xp = torch if isinstance(vertices, torch.Tensor) else np
+    idx = faces.long() if xp is torch else faces.astype(np.int64)
+    if xp is torch:
+        out = torch.zeros(idx.shape[0], 12, dtype=torch.float32, device=vertices.device)
+    else:
+        out = np.zeros((idx.shape[0], 12), dtype=_f32)
+    out[:, 0:3], out[:, 4:7], out[:, 8:11] = vertices[idx[:, 0]], vertices[idx[:, 1]], vertices[idx[:, 2]]
     return out
 
 
@@ -259,6 +303,69 @@ def cast_numpy(o, d, tri_data, t_min=0.0, t_max=np.inf):
         out["prim"][sl] = np.where(hit, prim, -1)
         out["u"][sl] = np.where(hit, u[rows, prim], _f32(0))
         out["v"][sl] = np.where(hit, v[rows, prim], _f32(0))
+    return out
+
+
+def closest_terms(p, tri, dtype=_f32):
+    """the closest-point rule's d2 and closest point for every (point, triangle) before acceptance: p [R,3], tri [F,3,3] (the exact
+    vertices) -> (d2 [R,F] (+inf: no candidate), point 3 x [R,F]) of `dtype` (float32: the rule itself; float64: the same formulas,
+    for error measurements)"""
+    p, T = np.asarray(p, dtype), np.asarray(tri, dtype)
+    pc = [p[:, None, k] for k in range(3)]
+    v0, v1, v2 = [[T[None, :, j, k] for k in range(3)] for j in range(3)]
+    inf, zero, one = dtype(np.inf), dtype(0), dtype(1)
+    with np.errstate(all="ignore"):
+        e1, e2 = [v1[k] - v0[k] for k in range(3)], [v2[k] - v0[k] for k in range(3)]
+        s = [pc[k] - v0[k] for k in range(3)]
+        n = _cross(e1, e2)
+        nn, sn = _dot(n, n), _dot(s, n)
+        b, c = _dot(_cross(s, e2), n) / nn, _dot(_cross(e1, s), n) / nn
+        inside = (nn > 0) & (b >= 0) & (c >= 0) & (b + c <= one)
+        g = [np.maximum(np.maximum(np.minimum(v0[k], np.minimum(v1[k], v2[k])) - pc[k], pc[k] - np.maximum(v0[k], np.maximum(v1[k], v2[k]))), zero)
+             for k in range(3)]
+        box2, plane2 = _dot(g, g), (sn * sn) / nn
+        d2 = np.where(inside, np.where(plane2 >= box2, plane2, box2), inf)
+        w = sn / nn
+        point = [np.where(inside, pc[k] - w * n[k], zero) for k in range(3)]
+        s1 = [pc[k] - v1[k] for k in range(3)]
+        e12 = [v2[k] - v1[k] for k in range(3)]
+        for ap, a, ab, end in ((s, v0, e1, v1), (s, v0, e2, v2), (s1, v1, e12, v2)):
+            den = _dot(ab, ab)
+            t = np.where(den == 0, zero, _dot(ap, ab) / den)
+            t = np.where(t >= 0, t, zero)
+            t = np.where(t <= one, t, one)
+            r = [ap[k] - t * ab[k] for k in range(3)]
+            sd = _dot(r, r)
+            take = sd < d2
+            d2 = np.where(take, sd, d2)
+            point = [np.where(take, np.where(t == one, end[k], a[k] + t * ab[k]), point[k]) for k in range(3)]
+    return d2.astype(dtype), [c.astype(dtype) for c in point]
+
+
+def closest_numpy(points, vertices, faces, max_distance=np.inf, dtype=_f32):
+    """brute force by the closest-point rule: points [N,3] -> {"distance" [N] (+inf on a miss), "prim" int32 [N] (-1), "point" [N,3]
+    (NaN)}.  dtype float32 is the rule; float64 evaluates the same formulas in double on the same float32 inputs."""
+    max_distance = dtype(max_distance)
+    if max_distance != max_distance:
+        raise ValueError("closest_numpy: max_distance is NaN")
+    p = np.ascontiguousarray(points, _f32).reshape(-1, 3)
+    tri = np.asarray(vertices, _f32).reshape(-1, 3)[np.asarray(faces).astype(np.int64).reshape(-1, 3)]
+    N, F = p.shape[0], tri.shape[0]
+    out = {"distance": np.full(N, np.inf, dtype), "prim": np.full(N, -1, np.int32), "point": np.full((N, 3), np.nan, dtype)}
+    valid = np.isfinite(p).all(1)
+    chunk = max(1, _CLOSEST_CHUNK_PAIRS // max(1, F))
+    for i0 in range(0, N, chunk):
+        sl = slice(i0, min(N, i0 + chunk))
+        d2, point = closest_terms(p[sl], tri, dtype)
+        some, best, prim = _closest((d2 < dtype(np.inf)) & valid[sl, None], d2)
+        with np.errstate(all="ignore"):
+            distance = np.sqrt(best)
+            hit = some & (distance <= max_distance)
+        rows = np.arange(prim.shape[0])
+        out["distance"][sl] = np.where(hit, distance, dtype(np.inf))
+        out["prim"][sl] = np.where(hit, prim, -1)
+        for k in range(3):
+            out["point"][sl, k] = np.where(hit, point[k][rows, prim], dtype(np.nan))
     return out
 
 
@@ -585,7 +692,7 @@ class MeshWorld:
     or None (mid-grey): tensors (the mesh lives on their device) or numpy arrays (the CPU path).  frame="world": the vertices are in
     the planner's world frame and are turned into the NeRF's axes first (collision.to_nerf with PLANNER_ROT).
     Attributes: device, n_vertices, n_faces, grid (grid_params' dict), dims (nx, ny, nz), pairs, mean_pairs_per_cell, and the
-    read-only tables tri_data, cell_start, pair_tri.  Shared freely between threads and streams: nothing is written after __init__."""
+    read-only tables tri_data, tri_verts, cell_start, pair_tri.  Shared freely between threads and streams: nothing is written after __init__."""
 
     def __init__(self, vertices, faces, colors=None, resolution=None, frame="nerf"):
         if frame not in ("nerf", "world"):
@@ -622,6 +729,7 @@ class MeshWorld:
         self.grid = grid_params(lo_hi[0], lo_hi[1], self.n_faces, resolution)
         self.dims = tuple(int(n) for n in self.grid["n"])
         self.tri_data = pack_triangles(self.vertices, self.faces)
+        self.tri_verts = pack_vertices(self.vertices, self.faces)
         if self.device.type == "cuda":
             self._build_hip()
         else:
@@ -677,6 +785,59 @@ class MeshWorld:
                                                  _lib.ptr(ends), base, min(int(pairs_per_launch), pairs - base), _lib.ptr(occ), _lib.stream()),
                            "voxelize_mark")
         return occ.view(torch.bool)
+
+    # ---- the closest point of the surface
+    def closest(self, points, max_distance=float("inf"), coherent=None, tested=False):
+        """points [..., 3] -> {"distance" float32 [...] (+inf on a miss), "prim" int32 [...] (-1), "point" float32 [..., 3] (NaN)} by the
+        module's closest-point rule, on the world's device (numpy arrays for numpy points on a CPU world).  max_distance: beyond it a
+        point is a miss -- and the search stops there, which is what keeps points far from the surface cheap.  coherent: sort the
+        queries by grid cell for the launch (None: from COHERENT_MIN_POINTS points on); a scheduling hint of the HIP path, the result
+        does not depend on it.  tested=True (HIP only) adds "tested" int32 [...]: the (point, triangle) pairs evaluated."""
+        max_distance = float(max_distance)
+        if max_distance != max_distance:
+            raise ValueError("MeshWorld.closest: max_distance is NaN")
+        tensors = isinstance(points, torch.Tensor)
+        p = (points.detach() if tensors else torch.from_numpy(np.array(points, dtype=_f32))).to(self.device, torch.float32)
+        if p.dim() < 1 or p.shape[-1] != 3:
+            raise ValueError(f"MeshWorld.closest: points [..., 3] (got {tuple(p.shape)})")
+        shape = tuple(p.shape[:-1])
+        p = p.reshape(-1, 3).contiguous()
+        N = p.shape[0]
+        if N >= 2 ** 31:
+            raise ValueError("MeshWorld.closest: N must be < 2^31")
+        if self.device.type != "cuda":
+            if tested:
+                raise ValueError("MeshWorld.closest: tested=True counts the HIP search's pairs; a CPU world tests all of them")
+            out = closest_numpy(p.numpy(), self.vertices.numpy(), self.faces.numpy(), max_distance)
+        else:
+            out = {"distance": torch.empty(N, dtype=torch.float32, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+                   "point": torch.empty(N, 3, dtype=torch.float32, device=self.device)}
+            if tested:
+                out["tested"] = torch.empty(N, dtype=torch.int32, device=self.device)
+            if N:
+                order = None
+                if coherent if coherent is not None else N >= COHERENT_MIN_POINTS:
+                    order = torch.argsort(self._cell_of(p), stable=True)
+                    p = p[order].contiguous()
+                raw = out if order is None else {k: torch.empty_like(a) for k, a in out.items()}
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().ngp_closest_point(_lib.ptr(p), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
+                                                            _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_verts), self.n_faces,
+                                                            max_distance, _lib.ptr(raw["distance"]), _lib.ptr(raw["prim"]), _lib.ptr(raw["point"]),
+                                                            _lib.ptr(raw.get("tested")), _lib.stream()), "closest_point")
+                if order is not None:
+                    for k in out:
+                        out[k][order] = raw[k]
+        return {k: self._back(a, shape + (3,) if k == "point" else shape, tensors) for k, a in out.items()}
+
+    def _cell_of(self, p):
+        """the grid cell (C order) of each point clamped to the grid box, int64 [N]: the key `closest` sorts coherent queries by"""
+        g = self.grid
+        lo = torch.from_numpy(g["lo"]).to(p.device)
+        n = torch.from_numpy(g["n"].astype(np.float32)).to(p.device)
+        c = ((torch.nan_to_num(p, nan=0.0, posinf=0.0, neginf=0.0) - lo) * torch.from_numpy(g["inv_cell"]).to(p.device)).floor()
+        c = torch.minimum(c.clamp_min(0.0), n - 1.0).to(torch.int64)
+        return (c[:, 0] * int(g["n"][1]) + c[:, 1]) * int(g["n"][2]) + c[:, 2]
 
     # ---- casting
     def _flat(self, who, rays_d, rays_o=None):
