@@ -415,6 +415,35 @@ NGP_API size_t ngp_edt_sq_workspace(uint32_t X, uint32_t Y, uint32_t Z);
 NGP_API int ngp_edt_sq(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, int32_t* d2, void* workspace, size_t workspace_bytes,
                        ngp_stream_t stream);
 
+/* Connected components of a C-order occupancy map (csrc/components.hip; the rule in full: nerfsafetyvalidation_amd/collision.py):
+ * occupied uint8 [X,Y,Z], non-zero = occupied.  Two occupied cells are neighbours when their offset is one of `connectivity`'s:
+ * 6, 18, 26 = the offsets of {-1,0,1}^3 \ 0 with at most 1, 2, 3 non-zero entries; 14 = +- the seven offsets of {0,1}^3 \ 0, the
+ * lattice edges of the isosurface's Kuhn split.  scipy.ndimage.label's result for the matching structure, numbering included:
+ *   ngp_label_components  labels int32 [X,Y,Z] = 0 on empty cells, else 1 + the rank of the cell's component, components ranked by the
+ *                         smallest C-order linear index of their cells; *n_components (int32, DEVICE memory) = their number.  A
+ *                         function of the input alone: the same bits on every call (integer min-atomics on a union-find forest whose
+ *                         links always point to a smaller index; the outcome does not depend on their order).  Six launches and a
+ *                         4-byte memset on `stream`, no host synchronisation.  Every device loop is bounded by the map's size; should
+ *                         one reach its bound (a corrupted workspace), *n_components is -1, -2 or -3 (the stage: tile, seams,
+ *                         flatten) and the labels are not valid -- ngp_component_stats refuses such an n with NGP_ELAUNCH and names
+ *                         the stage in ngp_last_error.
+ *   ngp_component_stats   for labels of n components (n: the value read back; n == 0 launches nothing): cells int64 [n] the number of
+ *                         cells, lo / hi int32 [n,3] the inclusive index bounding box, overlap int64 [n] (with truth uint8 [X,Y,Z],
+ *                         non-zero = marked; both may be null) the number of its cells that truth marks.  All device memory,
+ *                         overwritten.  Equal labels are reduced within the wave before the integer atomics (add, min, max).
+ * Every dimension >= 1, X * Y * Z < 2^31, connectivity one of the four: NGP_EINVAL otherwise, nothing launched.  workspace:
+ * ngp_label_components_workspace(X, Y, Z) bytes (host arithmetic; 0 for a size it refuses), 4-byte aligned (NGP_EWORKSPACE when
+ * smaller, nothing launched).  No global state: calls on different streams with their own workspaces do not interact.
+ * NGP_COMPONENTS_TILE_*: the cells per axis of the tile one workgroup labels in LDS (tests place their seams by it). */
+#define NGP_COMPONENTS_TILE_X 4
+#define NGP_COMPONENTS_TILE_Y 4
+#define NGP_COMPONENTS_TILE_Z 16
+NGP_API size_t ngp_label_components_workspace(uint32_t X, uint32_t Y, uint32_t Z);
+NGP_API int ngp_label_components(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, uint32_t connectivity, int32_t* labels,
+                                 int32_t* n_components, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+NGP_API int ngp_component_stats(const int32_t* labels, uint32_t X, uint32_t Y, uint32_t Z, int32_t n, const uint8_t* truth, int64_t* cells,
+                                int32_t* lo, int32_t* hi, int64_t* overlap, ngp_stream_t stream);
+
 /* Isosurface of a C-order scalar lattice u float [X,Y,Z] as an indexed, welded triangle mesh: marching tetrahedra on the Kuhn split
  * (six tetrahedra around every cell's (0,0,0)-(1,1,1) diagonal; DESIGN.md "Mesh export" fixes the rule and the output order).  A
  * lattice point is inside iff u > threshold (NaN is outside); every lattice edge (3 axis edges, 3 face diagonals, 1 body diagonal per

@@ -23,6 +23,7 @@ NGP_DBG_ONE_ITER_PER_LAUNCH, NGP_DBG_NO_TILES = 1 << 8, 1 << 13
 NGP_DBG_NO_PRE_VERDICT, NGP_DBG_WIDE_ITEMS, NGP_DBG_REPLAY_ONE_ITER = 1 << 14, 1 << 15, 1 << 16
 NGP_DBG_LANE_MARCH, NGP_DBG_PROBE_PER_SAMPLE = 1 << 17, 1 << 18
 NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
+NGP_COMPONENTS_TILE = (4, 4, 16)                                 # NGP_COMPONENTS_TILE_X / _Y / _Z: the tile ngp_label_components labels in LDS
 
 _vp, _u32, _f32, _int, _sz = C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_size_t
 
@@ -142,6 +143,9 @@ SIGNATURES = {
     "ngp_cell_max_density": [C.POINTER(ModelStruct), _vp, C.c_float, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
     "ngp_edt_sq_workspace": [_u32, _u32, _u32],
     "ngp_edt_sq": [_vp, _u32, _u32, _u32, _vp, _vp, _sz, _vp],
+    "ngp_label_components_workspace": [_u32, _u32, _u32],
+    "ngp_label_components": [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp],
+    "ngp_component_stats": [_vp, _u32, _u32, _u32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp],
     "ngp_isosurface_workspace": [_u32, _u32, _u32],
     "ngp_isosurface_count": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, _vp, _vp],
     "ngp_isosurface_emit": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _vp],
@@ -190,7 +194,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_label_components_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
 
 _lib = None
 

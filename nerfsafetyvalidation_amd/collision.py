@@ -22,7 +22,26 @@ Boxes: NerfSimulator looks values up with its own constants (`reference_box()`, 
 builds the map over a different box (`collision_map_box()`, shape (72, 96, 56)).  The reference therefore indexes a (72, 96, 56)
 field with the start and granularity of the other box; `SignedDistanceField.from_array(sdf, reference_box())` reproduces that
 (DESIGN.md, "The collision field").
+
+Connected components ("Connected components"): what tells a floater -- a blob of density attached to nothing, a phantom
+obstacle in the field above -- from an obstacle.
+
+    label_components     the labelling rule below                                      ngp_label_components (HIP); numpy on the CPU
+    component_table      cells, bounding box and overlap with a truth map per label    ngp_component_stats (HIP); numpy on the CPU
+    remove_floaters      drop components by size, rank or contact with the ground
+    floater_report       phantom components of a predicted map, missed ones of the truth
+
+The labelling rule.  Input: `occupied` [X, Y, Z] in C order, non-zero = occupied, X * Y * Z < 2^31, every dimension >= 1.  Two
+occupied cells are neighbours when their index offset is one of the connectivity's: for 6, 18 and 26 the offsets of {-1,0,1}^3 \\ 0
+with at most 1, 2 or 3 non-zero entries; for 14, +- the seven mesh.EDGE_OFFSETS ({0,1}^3 \\ 0), the lattice edges of the isosurface's
+Kuhn split -- the connectivity under which two inside lattice points share a marching-tetrahedra edge.  A component is a class of
+the transitive closure.  Output: `labels` int32 [X, Y, Z], 0 on empty cells and 1 + rank elsewhere, the components ranked by the
+smallest C-order linear index of their cells; `n`, their number.  This is scipy.ndimage.label(occupied, structure) for
+generate_binary_structure(3, 1 | 2 | 3) (6, 18, 26) or the 14-offset mask, numbering and dtype included -- a function of the input
+alone, the same on every call and on both paths.
 """
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -119,10 +138,14 @@ def cell_max_density(model, box, samples_per_axis=2, rot=PLANNER_ROT, chunk_poin
     return out
 
 
-def occupancy_from_density(model, box, thresh, samples_per_axis=2, rot=PLANNER_ROT):
+def occupancy_from_density(model, box, thresh, samples_per_axis=2, rot=PLANNER_ROT, min_cells=0, connectivity=26, grounded=None):
     """cell occupied <=> its largest sigma > thresh (strict, as packbits, raymarching.cu:286-288).  `thresh` is required: sigma
-    scales differ from model to model."""
-    return cell_max_density(model, box, samples_per_axis, rot) > float(thresh)
+    scales differ from model to model.  min_cells / connectivity / grounded: handed to remove_floaters, which then takes the
+    floaters out of the map (the defaults leave it as it is, and label nothing)."""
+    occ = cell_max_density(model, box, samples_per_axis, rot) > float(thresh)
+    if min_cells == 0 and grounded is None:
+        return occ
+    return remove_floaters(occ, connectivity=connectivity, min_cells=min_cells, grounded=grounded)[0]
 
 
 def occupancy_from_points(points, box):
@@ -174,6 +197,250 @@ def henge_fn(x, y, z):
     """the synthetic scene in the world (drone) frame: scene.henge_occupancy in the NeRF's axes, mapped as rollout.scene_collision
     does (_FLIP_YZ: NeRF = (y, z, x))"""
     return henge_occupancy(y, z, x)
+
+
+# ------------------------------------------------------------------ connected components
+CONNECTIVITIES = (6, 14, 18, 26)
+KUHN_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))     # = mesh.EDGE_OFFSETS (mesh imports this module)
+_STAGES = {-1: "tile", -2: "seams", -3: "flatten"}                  # ngp_label_components' n_components when a loop reached its bound
+
+
+def connectivity_offsets(connectivity):
+    """the neighbour offsets of a connectivity, both directions -> a list of (dx, dy, dz)"""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity is one of {CONNECTIVITIES} (got {connectivity!r})")
+    if connectivity == 14:
+        return [o for o in KUHN_OFFSETS] + [tuple(-v for v in o) for o in KUHN_OFFSETS]
+    most = {6: 1, 18: 2, 26: 3}[connectivity]
+    return [(dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1) if 0 < (dx != 0) + (dy != 0) + (dz != 0) <= most]
+
+
+def _check_map(occ, who):
+    if len(occ.shape) != 3:
+        raise ValueError(f"{who}: a 3-D map (got shape {tuple(occ.shape)})")
+    if min(occ.shape) < 1 or int(np.prod(occ.shape, dtype=np.int64)) >= 2 ** 31:
+        raise ValueError(f"{who}: every dimension >= 1 and X * Y * Z < 2^31 (got shape {tuple(occ.shape)})")
+
+
+def label_components_numpy(occ, connectivity=26):
+    """the labelling rule (module docstring) in numpy: array [X, Y, Z], non-zero = occupied -> (labels int32 [X, Y, Z], n).
+    The occupied cells, numbered in C order, are the nodes and every forward offset contributes its pairs of occupied cells as edges;
+    then rounds of hooking (the larger root of an edge's two ends under the smaller one, np.minimum.at) and pointer jumping to a
+    fixed point.  A path of k cells costs about log2(k) jumps, not k sweeps.  A component's root is its first cell in C order, so the
+    roots' order is the ranking."""
+    occ = np.asarray(occ)
+    _check_map(occ, "label_components")
+    forward = [o for o in connectivity_offsets(connectivity) if o > (0, 0, 0)]
+    inside = np.ascontiguousarray(occ != 0)
+    X, Y, Z = inside.shape
+    cells = np.flatnonzero(inside)
+    labels = np.zeros(inside.shape, dtype=np.int32)
+    if cells.size == 0:
+        return labels, 0
+    node = np.full(inside.size, -1, dtype=np.int64)
+    node[cells] = np.arange(cells.size)
+    node = node.reshape(inside.shape)
+    us, vs = [], []
+    for dx, dy, dz in forward:          # dx >= 0; the lower end a and the upper end b = a + offset
+        a = (slice(0, X - dx), slice(max(0, -dy), Y - max(0, dy)), slice(max(0, -dz), Z - max(0, dz)))
+        b = (slice(dx, X), slice(max(0, dy), Y + min(0, dy)), slice(max(0, dz), Z + min(0, dz)))
+        both = inside[a] & inside[b]
+        us.append(node[a][both])
+        vs.append(node[b][both])
+    u, v = np.concatenate(us), np.concatenate(vs)
+    parent = np.arange(cells.size)
+    while u.size:
+        pu, pv = parent[u], parent[v]
+        differ = pu != pv
+        if not differ.any():
+            break
+        u, v, pu, pv = u[differ], v[differ], pu[differ], pv[differ]
+        np.minimum.at(parent, np.maximum(pu, pv), np.minimum(pu, pv))          # parent is flat here: both are roots
+        while True:
+            jumped = parent[parent]
+            if np.array_equal(jumped, parent):
+                break
+            parent = jumped
+    roots = parent == np.arange(cells.size)
+    rank = np.cumsum(roots)
+    labels.reshape(-1)[cells] = rank[parent]
+    return labels, int(rank[-1])
+
+
+def _label_components_hip(occ, connectivity):
+    m = (occ != 0).to(torch.uint8).contiguous()
+    X, Y, Z = m.shape
+    lib = _lib.lib()
+    with torch.cuda.device(m.device):
+        labels = torch.empty(X, Y, Z, dtype=torch.int32, device=m.device)
+        n_dev = torch.empty(1, dtype=torch.int32, device=m.device)
+        ws_bytes = lib.ngp_label_components_workspace(X, Y, Z)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)
+        _lib.check(lib.ngp_label_components(_lib.ptr(m), X, Y, Z, connectivity, _lib.ptr(labels), _lib.ptr(n_dev), _lib.ptr(ws), ws_bytes,
+                                            _lib.stream()), "label_components")
+        n = int(n_dev.item())          # the call's one host read
+    if n < 0:
+        raise RuntimeError(f"label_components: a device loop reached its bound in stage '{_STAGES.get(n, n)}'; the labels are not valid")
+    return labels, n
+
+
+def label_components(occ, connectivity=26):
+    """the labelling rule (module docstring) -> (labels int32 [X, Y, Z], n: int).  A CUDA tensor goes through ngp_label_components on
+    the current stream and the labels stay on its device (one host read, of n); a CPU tensor or a numpy array goes through
+    label_components_numpy and the same kind comes back.  Any dtype (non-zero = occupied) and any strides."""
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"label_components: connectivity is one of {CONNECTIVITIES} (got {connectivity!r})")
+    _check_map(occ, "label_components")
+    if isinstance(occ, torch.Tensor):
+        if occ.is_cuda:
+            return _label_components_hip(occ.detach(), connectivity)
+        labels, n = label_components_numpy(occ.detach().numpy(), connectivity)
+        return torch.from_numpy(labels), n
+    return label_components_numpy(occ, connectivity)
+
+
+@dataclasses.dataclass
+class ComponentTable:
+    """per component (row c: label c + 1): `cells` int64 [n] the number of cells, `lo` / `hi` int32 [n, 3] the inclusive index
+    bounding box, `overlap` int64 [n] the number of its cells a truth map marks (None without one).  Tensors on the labels' device,
+    or numpy arrays for numpy labels."""
+    cells: object
+    lo: object
+    hi: object
+    overlap: object
+
+
+def component_table_numpy(labels, n, truth=None):
+    """component_table in numpy -> ComponentTable of arrays"""
+    labels = np.asarray(labels)
+    flat = labels.reshape(-1)
+    cells = np.bincount(flat, minlength=n + 1)[1:n + 1].astype(np.int64)
+    lo, hi = np.full((n, 3), np.iinfo(np.int32).max, dtype=np.int32), np.full((n, 3), -1, dtype=np.int32)
+    where = np.flatnonzero(flat)
+    which = flat[where] - 1
+    for d, coord in enumerate(np.unravel_index(where, labels.shape)):
+        np.minimum.at(lo[:, d], which, coord.astype(np.int32))
+        np.maximum.at(hi[:, d], which, coord.astype(np.int32))
+    overlap = None
+    if truth is not None:
+        marked = np.asarray(truth).reshape(-1)[where] != 0
+        overlap = np.bincount(which[marked], minlength=n).astype(np.int64)
+    return ComponentTable(cells, lo, hi, overlap)
+
+
+def component_table(labels, n, truth=None):
+    """labels int32 [X, Y, Z] of n components (label_components' pair), truth: a map of the same shape or None -> ComponentTable.
+    CUDA labels go through ngp_component_stats on the current stream and everything stays on the device (no host read); anything
+    else through numpy.  The values are the same."""
+    n = int(n)
+    if n < 0 or len(labels.shape) != 3:
+        raise ValueError(f"component_table: labels [X, Y, Z] and n >= 0 (got shape {tuple(labels.shape)}, n = {n})")
+    if truth is not None and tuple(truth.shape) != tuple(labels.shape):
+        raise ValueError(f"component_table: truth has the labels' shape (got {tuple(truth.shape)} and {tuple(labels.shape)})")
+    if not isinstance(labels, torch.Tensor):
+        return component_table_numpy(labels, n, None if truth is None else (truth.cpu().numpy() if isinstance(truth, torch.Tensor) else truth))
+    if not labels.is_cuda:
+        t = component_table_numpy(labels.numpy(), n, None if truth is None else torch.as_tensor(truth).cpu().numpy())
+        return ComponentTable(*[None if a is None else torch.from_numpy(a) for a in (t.cells, t.lo, t.hi, t.overlap)])
+    dev = labels.device
+    lab = labels.detach().to(torch.int32).contiguous()
+    marks = None if truth is None else (torch.as_tensor(truth).to(dev) != 0).to(torch.uint8).contiguous()
+    X, Y, Z = lab.shape
+    with torch.cuda.device(dev):
+        cells = torch.empty(n, dtype=torch.int64, device=dev)
+        lo, hi = torch.empty(n, 3, dtype=torch.int32, device=dev), torch.empty(n, 3, dtype=torch.int32, device=dev)
+        overlap = None if truth is None else torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().ngp_component_stats(_lib.ptr(lab), X, Y, Z, n, _lib.ptr(marks), _lib.ptr(cells), _lib.ptr(lo), _lib.ptr(hi),
+                                                  _lib.ptr(overlap), _lib.stream()), "component_stats")
+    return ComponentTable(cells, lo, hi, overlap)
+
+
+def _table_to_host(table):
+    """a ComponentTable as numpy arrays, with ONE device-to-host copy when it lives on a device"""
+    if not isinstance(table.cells, torch.Tensor):
+        return table
+    n = table.cells.shape[0]
+    cols = [table.cells.reshape(n, 1), table.lo.to(torch.int64), table.hi.to(torch.int64)]
+    if table.overlap is not None:
+        cols.append(table.overlap.reshape(n, 1))
+    packed = torch.cat(cols, 1).cpu().numpy()
+    return ComponentTable(packed[:, 0].copy(), packed[:, 1:4].astype(np.int32), packed[:, 4:7].astype(np.int32),
+                          None if table.overlap is None else packed[:, 7].copy())
+
+
+def _listing(table, pick):
+    """the report of the components `pick` (bool [n], host) of a host table"""
+    idx = np.flatnonzero(pick)
+    return {"count": int(idx.size), "labels": [int(i) + 1 for i in idx], "cells": [int(c) for c in table.cells[idx]],
+            "lo": [tuple(int(v) for v in row) for row in table.lo[idx]], "hi": [tuple(int(v) for v in row) for row in table.hi[idx]]}
+
+
+def _select_cells(labels, pick):
+    """bool [X, Y, Z]: the cells whose component `pick` (bool [n], host) selects, of the labels' kind"""
+    lut = np.concatenate([[False], np.asarray(pick, dtype=bool)])
+    if isinstance(labels, torch.Tensor):
+        return torch.from_numpy(lut).to(labels.device)[labels.long()]
+    return lut[labels]
+
+
+def remove_floaters(occ, *, connectivity=26, min_cells=0, keep_largest=None, grounded=None):
+    """occ [X, Y, Z] (tensor on any device, or numpy; non-zero = occupied) -> (cleaned, report).  A component (label_components with
+    `connectivity`) is KEPT iff all of: it has at least min_cells cells; it is among the keep_largest largest (ties: the lower label
+    first; None: no limit); with grounded = (axis, "lo" | "hi"), its bounding box reaches the first ("lo") or last ("hi") layer of
+    that axis -- a floater is what is attached to nothing.  cleaned: the map without the dropped components, of the input's kind,
+    dtype and device (the input itself when nothing is dropped).  report: {"n", "kept": {...}, "dropped": {...}}, each with
+    "count", "labels", "cells", "lo", "hi" (the inclusive index boxes).  One host read of n and one of the table."""
+    if len(occ.shape) != 3:
+        raise ValueError(f"remove_floaters: a 3-D map (got shape {tuple(occ.shape)})")
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"remove_floaters: connectivity is one of {CONNECTIVITIES} (got {connectivity!r})")
+    if int(min_cells) != min_cells or min_cells < 0:
+        raise ValueError(f"remove_floaters: min_cells is an integer >= 0 (got {min_cells!r})")
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 1):
+        raise ValueError(f"remove_floaters: keep_largest is None or an integer >= 1 (got {keep_largest!r})")
+    if grounded is not None:
+        if not (isinstance(grounded, (tuple, list)) and len(grounded) == 2 and grounded[0] in (0, 1, 2) and grounded[1] in ("lo", "hi")):
+            raise ValueError(f"remove_floaters: grounded is None or (axis in 0..2, 'lo' | 'hi') (got {grounded!r})")
+    labels, n = label_components(occ, connectivity)
+    table = _table_to_host(component_table(labels, n))
+    keep = table.cells >= int(min_cells)
+    if keep_largest is not None:
+        order = np.lexsort((np.arange(n), -table.cells))          # by size, largest first; ties by label
+        among = np.zeros(n, dtype=bool)
+        among[order[:int(keep_largest)]] = True
+        keep &= among
+    if grounded is not None:
+        axis, side = grounded
+        keep &= (table.lo[:, axis] == 0) if side == "lo" else (table.hi[:, axis] == occ.shape[axis] - 1)
+    report = {"n": n, "kept": _listing(table, keep), "dropped": _listing(table, ~keep)}
+    if keep.all():
+        return occ, report
+    kept_cells = _select_cells(labels, keep)
+    if isinstance(occ, torch.Tensor):
+        return torch.where(kept_cells, occ, torch.zeros_like(occ)), report
+    return np.where(kept_cells, occ, np.zeros_like(occ)), report
+
+
+def floater_report(pred, truth, connectivity=26):
+    """a predicted map (a NeRF-density map) against the truth map (occupancy_from_mesh), component by component ->
+    {"phantom": the components of pred without a single cell in truth (obstacles that do not exist: floaters),
+     "missed": the components of truth without a single cell in pred (whole obstacles the model does not see),
+     "pred_components", "truth_components": the two counts, "agreement": map_agreement(pred, truth)};
+    phantom and missed as remove_floaters' listings ("count", "labels", "cells", "lo", "hi").  Runs where pred lives."""
+    if tuple(pred.shape) != tuple(truth.shape):
+        raise ValueError(f"floater_report: maps of one shape (got {tuple(pred.shape)} and {tuple(truth.shape)})")
+    if isinstance(pred, torch.Tensor):
+        truth = torch.as_tensor(truth).to(pred.device)
+    else:
+        truth = truth.cpu().numpy() if isinstance(truth, torch.Tensor) else np.asarray(truth)
+    out = {}
+    for key, (a, b) in (("phantom", (pred, truth)), ("missed", (truth, pred))):
+        labels, n = label_components(a, connectivity)
+        table = _table_to_host(component_table(labels, n, b))
+        out[key] = _listing(table, table.overlap == 0)
+        out["pred_components" if key == "phantom" else "truth_components"] = n
+    out["agreement"] = map_agreement(pred, truth)
+    return out
 
 
 # ------------------------------------------------------------------ the distance transform

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collision import PLANNER_ROT, to_nerf
+from .collision import PLANNER_ROT, component_table, label_components, to_nerf
 
 # edge type -> lattice offset (dx, dy, dz): 3 axis edges, 3 face diagonals, the body diagonal
 EDGE_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
@@ -263,10 +263,33 @@ def _bounds(b):
     return (b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64))[:3]
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
+def drop_small_components(u, threshold, min_points):
+    """u [X,Y,Z] with the floaters taken out before the surface is cut: the inside points (u > threshold, strict, NaN outside, as
+    isosurface has it) that belong to a 14-connected component (collision.label_components; +- EDGE_OFFSETS, the Kuhn split's own
+    edges) of fewer than min_points points are set to `threshold`, which is outside; nothing else changes.  No kept inside point
+    shares a lattice edge with a changed one, so the kept surface keeps every vertex bit for bit, and its order.  Runs where u lives
+    (HIP for a CUDA tensor: one host read, of the number of components); the same kind comes back, u itself for min_points <= 1."""
+    if int(min_points) != min_points or min_points < 0:
+        raise ValueError(f"drop_small_components: min_points is an integer >= 0 (got {min_points!r})")
+    if min_points <= 1:
+        return u
+    is_tensor = isinstance(u, torch.Tensor)
+    thr = np.float32(threshold)
+    inside = (u.to(torch.float32) > float(thr)) if is_tensor else (np.asarray(u, dtype=np.float32) > thr)       # isosurface's own test
+    labels, n = label_components(inside, 14)
+    cells = component_table(labels, n).cells
+    if is_tensor:
+        small = torch.cat([torch.zeros(1, dtype=torch.bool, device=u.device), cells < int(min_points)])[labels.long()]
+        return torch.where(small, torch.full_like(u, float(thr)), u)
+    small = np.concatenate([[False], cells < int(min_points)])[labels]
+    return np.where(small, np.asarray(thr, dtype=u.dtype), u)
+
+
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, min_points=0):
     """-> (vertices [V,3] float64 numpy in the bounds' units, triangles [F,3] int32 numpy): the isosurface of extract_fields, scaled as
-    nerf/utils.py:181 scales mcubes' vertices: v / (resolution - 1) * (b_max - b_min) + b_min"""
-    u = extract_fields(bound_min, bound_max, resolution, query_func)
+    nerf/utils.py:181 scales mcubes' vertices: v / (resolution - 1) * (b_max - b_min) + b_min.  min_points: drop_small_components
+    first (0: the field as it is)."""
+    u = drop_small_components(extract_fields(bound_min, bound_max, resolution, query_func), threshold, min_points)
     v, f = isosurface(u, threshold)
     b_min, b_max = _bounds(bound_min), _bounds(bound_max)
     vertices = v.cpu().numpy().astype(np.float64) / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
@@ -345,9 +368,10 @@ def read_ply(path):
     return vrec["p"].astype(np.float32), frec["i"].astype(np.int32), (vrec["c"].copy() if colored else None)
 
 
-def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False):
+def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False, min_points=0):
     """Trainer.save_mesh (nerf/utils.py:533-553): the isosurface sigma = threshold of model.density over model.aabb_infer on a
-    resolution^3 lattice, written to save_path as a binary PLY -> (vertices float64 [V,3], triangles int32 [F,3])"""
+    resolution^3 lattice, written to save_path as a binary PLY -> (vertices float64 [V,3], triangles int32 [F,3]).  min_points:
+    components of fewer inside lattice points are left out (drop_small_components; 0: none)."""
     directory = os.path.dirname(save_path)
     if directory:
         os.makedirs(directory, exist_ok=True)
@@ -357,7 +381,7 @@ def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False):
         with torch.no_grad(), torch.autocast(device.type, dtype=torch.float16 if device.type == "cuda" else torch.bfloat16, enabled=fp16):
             return model.density(pts.to(device))["sigma"]
 
-    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], resolution, threshold, query_func)
+    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], resolution, threshold, query_func, min_points)
     write_ply(save_path, vertices, triangles)
     return vertices, triangles
 
