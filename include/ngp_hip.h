@@ -738,6 +738,17 @@ NGP_API int ngp_adam_step_dev(float* param, const float* grad, float* exp_avg, f
 NGP_API int ngp_train_targets(const void* store, int store_dtype, uint32_t C, uint64_t frame_base, uint32_t n_pix, const int64_t* inds,
                       uint32_t N, const float* bg, const float* table, int round_half, float* gt_rgb, ngp_stream_t stream);
 
+/* The depth targets of one batch of rays out of the resident 16-bit depth store (nerf/targets.py DepthStore), one thread per ray:
+ * store uint16 [n_img][n_pix] codes of z-depth along the optical axis; frame_base: index of the frame's first pixel in the store;
+ * inds int64 [N] pixel ids inside the frame (duplicates allowed), or NULL = pixels 0 .. N-1; W the frame's width (n_pix = H W).
+ *   code 0 -> 0 (no measurement),  code 65535 -> +inf (known empty),  else
+ *   target[k] = ((float)code * unit) * sqrt((x x + y y) + 1),   x = ((i + 0.5) - cx) / fx,  y = ((j + 0.5) - cy) / fy,  (i, j) = (pix % W, pix / W)
+ * -- the RAY DISTANCE of the pixel: its z-depth times the length of the direction get_rays forms for it before normalising, with
+ * unit = integer_depth_scale * opt.scale (one float).  Every operation is one fp32 operation.  An id outside [0, n_pix) reads nothing
+ * and gives 0.  target float [N]. */
+NGP_API int ngp_train_depth_targets(const uint16_t* store, uint64_t frame_base, uint32_t n_pix, uint32_t W, const int64_t* inds, uint32_t N,
+                            float fx, float fy, float cx, float cy, float unit, float* target, ngp_stream_t stream);
+
 /* MSELoss(reduction='none')(pred, gt).mean(-1) and its mean over the rays (utils.py:450,480) in one launch (two above 16384 rays):
  * pred [N,3] of pred_dtype 0 = f32 / 1 = f16, gt float [N,3] -> per_ray float [N] = ((d0^2 + d1^2) + d2^2) / 3, *mean (device float).
  * The mean is a fixed-order sum -- 64-ray groups by a butterfly, the groups in double, strided by 64 and by the same butterfly --
@@ -793,6 +804,48 @@ NGP_API int ngp_distortion_forward(const float* w, const float* m, const float* 
                            size_t workspace_bytes, ngp_stream_t stream);
 NGP_API int ngp_distortion_backward(const float* grad_loss, const float* w, const float* m, const float* interval, float interval_scalar,
                             const int32_t* rays, const float* totals, uint32_t M, uint32_t N, float* grad_w, ngp_stream_t stream);
+
+/* ---------------- depth supervision (DESIGN.md "Depth supervision") ---------------- */
+
+/* Per ray of a table rays int32 [N,3] = (index, offset, count) over packed sigmas [M] and deltas [M,2] = (dt, gap), with the composite
+ * rule ngp_distortion_train_* uses: alpha_i = 1 - exp(-sigma_i dt_i), T_0 = 1, T_{i+1} = T_i (1 - alpha_i), w_i = alpha_i T_i,
+ * t_i = sum_{k<=i} gap_k.  The ray ends behind the first sample with T_{i+1} < 1e-4, that sample included.  A ray with
+ * offset + count >= M is dropped.  Each ray has a target z = target[index], a ray distance in the units of t, and a per-ray
+ * scale[index] (NULL = 1; the renderer passes 1 / (far - near), as it does for the distortion term).
+ *   z == 0, or NaN, or negative: no measurement.  L_ray = 0, and every gradient row of the ray is left at the zeros handed in.
+ *   0 < z < +inf: a surface at z.   d = sum_live w_i t_i,   A = sum_{live, t_i < z - margin} w_i,
+ *                                   L_ray = a (scale (d - z))^2 + b A
+ *   z == +inf: known empty ray.     A = sum_live w_i,   L_ray = b A
+ * A is the opacity the ray has accumulated before the margin in front of the surface, 1 - T there: bounded by 1 and independent of how
+ * densely the ray was sampled, which is why it is linear in w and not a sum of w_i^2.
+ *   g_i = dL_ray / dw_i = 2 a scale^2 (d - z) t_i + b [t_i < z - margin]
+ *   dL_ray / dsigma_i = dt_i (T_{i+1} g_i - sum_{k>i, live} g_k w_k)        exact, the sample that stops the ray included
+ * *loss (device float) = sum over the slots of L_ray / N, over all N slots and not over the valid ones, by the fixed-order mean of
+ * ngp_photo_loss_forward.  a = weight_depth, b = weight_free and margin are host floats.
+ * loss_rays float [N]: L_ray at slot `index`;  parts float [N,2]: (d, A) at slot `index` (0, 0 for a ray without a measurement or a
+ * dropped one), which the backward call reads: its suffix sums are a total minus a prefix, the total being
+ * 2 a scale^2 (d - z) d + b A.  A row with index >= N is ignored; target and scale are read at a valid index only; the drop rule is
+ * applied before any row is read.  grad_sigmas[offset + k] = (*grad_loss / N) dL_ray / dsigma_k for live samples k; rows of dead
+ * samples, of rays that take no part and of no ray are NOT written: hand in zeros.  grad_loss is a device float.
+ * One wave per ray, prefix sums by wave scans, no LDS and no atomics: the same bits on every call and for every order of the table's
+ * rows.  workspace: ngp_depth_loss_workspace(N) bytes (0 up to 16384 rays).
+ *
+ * ngp_depth_loss_forward / _backward: the same on given w, t float [M]; every sample of a ray is live and a ray is dropped only when
+ * count == 0 or offset + count > M (a dense [B,T] input is the table (i, i T, T) with M = B T).
+ * grad_w[offset + k] = (*grad_loss / N) g_k; other rows are not written. */
+NGP_API size_t ngp_depth_loss_workspace(uint32_t N);
+NGP_API int ngp_depth_loss_train_forward(const float* sigmas, const float* deltas, const int32_t* rays, const float* target, const float* scale,
+                                 float margin, float weight_depth, float weight_free, uint32_t M, uint32_t N, float* loss_rays,
+                                 float* parts, float* loss, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+NGP_API int ngp_depth_loss_train_backward(const float* grad_loss, const float* sigmas, const float* deltas, const int32_t* rays,
+                                  const float* target, const float* scale, float margin, float weight_depth, float weight_free,
+                                  const float* parts, uint32_t M, uint32_t N, float* grad_sigmas, ngp_stream_t stream);
+NGP_API int ngp_depth_loss_forward(const float* w, const float* t, const int32_t* rays, const float* target, const float* scale, float margin,
+                           float weight_depth, float weight_free, uint32_t M, uint32_t N, float* loss_rays, float* parts, float* loss,
+                           void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+NGP_API int ngp_depth_loss_backward(const float* grad_loss, const float* w, const float* t, const int32_t* rays, const float* target,
+                            const float* scale, float margin, float weight_depth, float weight_free, const float* parts, uint32_t M,
+                            uint32_t N, float* grad_w, ngp_stream_t stream);
 
 /* ---------------- image quality (uncertainty/evaluation/image_metrics.py:79-135; nerf/utils.py PSNRMeter) ---------------- */
 

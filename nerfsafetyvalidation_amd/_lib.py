@@ -116,6 +116,7 @@ SIGNATURES = {
     "ngp_adam_advance_step": [_vp, _vp, _vp],
     "ngp_adam_step_dev": [_vp, _vp, _vp, _vp, C.c_uint64, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp],
     "ngp_train_targets": [_vp, _int, _u32, C.c_uint64, _u32, _vp, _u32, _vp, _vp, _int, _vp, _vp],
+    "ngp_train_depth_targets": [_vp, C.c_uint64, _u32, _u32, _vp, _u32, _f32, _f32, _f32, _f32, _f32, _vp, _vp],
     "ngp_photo_loss_workspace": [_u32],
     "ngp_photo_loss_forward": [_vp, _int, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp],
     "ngp_photo_loss_backward": [_vp, _int, _vp, _u32, _vp, _vp, _vp],
@@ -124,6 +125,11 @@ SIGNATURES = {
     "ngp_distortion_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "ngp_distortion_forward": [_vp, _vp, _vp, _f32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp],
     "ngp_distortion_backward": [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _vp, _vp],
+    "ngp_depth_loss_workspace": [_u32],
+    "ngp_depth_loss_train_forward": [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ngp_depth_loss_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _u32, _u32, _vp, _vp],
+    "ngp_depth_loss_forward": [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ngp_depth_loss_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _u32, _u32, _vp, _vp],
     "ngp_image_quality_workspace": [_u32, _u32, _u32],
     "ngp_image_quality": [_vp, _vp, _vp, _u32, _u32, _u32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f32, _vp, _vp, _vp, _sz, _vp],
     "ngp_cell_tables_bytes": [C.POINTER(ModelStruct), _u32],
@@ -194,7 +200,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_label_components_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_label_components_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_depth_loss_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
 
 _lib = None
 

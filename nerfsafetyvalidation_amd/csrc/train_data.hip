@@ -58,6 +58,26 @@ __global__ void __launch_bounds__(256) k_train_targets(const void* __restrict__ 
     out[2] = rgb[2];
 }
 
+// ---- depth targets ----------------------------------------------------------------------------------------------------------------
+// The chosen pixels' ray distances out of the 16-bit depth store (nerf/targets.py DepthStore), one thread per ray:
+//   code 0 -> 0 (no measurement), 65535 -> +inf (known empty), else t = ((float)code * unit) * |dir|,
+//   dir = ((i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, 1), the direction get_rays forms for pixel (i, j) before it normalises it.
+// Every operation is one fp32 operation.  An id outside [0, n_pix) reads nothing and gives 0.
+__global__ void __launch_bounds__(256) k_train_depth_targets(const uint16_t* __restrict__ store, uint64_t frame_base, uint32_t n_pix, uint32_t W,
+                                                             const int64_t* __restrict__ inds, uint32_t N, float fx, float fy, float cx, float cy,
+                                                             float unit, float* __restrict__ out) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= N) return;
+    const int64_t pix = inds ? inds[k] : (int64_t)k;
+    if (pix < 0 || pix >= (int64_t)n_pix) { out[k] = 0.0f; return; }
+    const uint32_t code = store[(size_t)frame_base + (size_t)pix];
+    if (code == 0u) { out[k] = 0.0f; return; }
+    if (code == 65535u) { out[k] = __builtin_inff(); return; }
+    const float x = (((float)((uint32_t)pix % W) + 0.5f) - cx) / fx;
+    const float y = (((float)((uint32_t)pix / W) + 0.5f) - cy) / fy;
+    out[k] = ((float)code * unit) * sqrtf((x * x + y * y) + 1.0f);
+}
+
 // ---- photometric loss -------------------------------------------------------------------------------------------------------------
 // The mean over the rays is the fixed-order mean (DESIGN.md "Cross-lane arithmetic"), fused with the pass that forms the per-ray losses.
 template <typename P>
@@ -165,6 +185,19 @@ int ngp_train_targets(const void* store, int store_dtype, uint32_t C, uint64_t f
     else { NGP_TARGETS(kStoreU8); }
 #undef NGP_TARGETS
     return check_launch("train_targets");
+}
+
+int ngp_train_depth_targets(const uint16_t* store, uint64_t frame_base, uint32_t n_pix, uint32_t W, const int64_t* inds, uint32_t N, float fx,
+                            float fy, float cx, float cy, float unit, float* target, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(store && target, "train_depth_targets: null pointer");
+    NGP_REQUIRE(W > 0 && n_pix % W == 0, "train_depth_targets: %u pixels are no whole rows of %u", n_pix, W);
+    NGP_REQUIRE(inds || N <= n_pix, "train_depth_targets: %u rays in pixel order but the frame has %u pixels", N, n_pix);
+    NGP_REQUIRE(((uintptr_t)store & 1) == 0, "train_depth_targets: the store must be 2-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_depth_targets", s, (double)N);
+    k_train_depth_targets<<<div_up(N, 256), 256, 0, s>>>(store, frame_base, n_pix, W, inds, N, fx, fy, cx, cy, unit, target);
+    return check_launch("train_depth_targets");
 }
 
 size_t ngp_photo_loss_workspace(uint32_t N) { return mean_workspace(N); }

@@ -59,6 +59,12 @@ def parse_args(argv=None):
     ### regularisation (not in the reference's entry point; its loss.py has the term)
     parser.add_argument('--lambda_distort', type=float, default=0, help="weight of the distortion loss on the ray weights (0 = off)")
 
+    ### depth supervision (not in the reference; DESIGN.md "Depth supervision").  The dataset names its maps with Instant-NGP's keys.
+    parser.add_argument('--lambda_depth', type=float, default=0, help="weight of the depth term: the squared miss of the expected ray distance (0 = off)")
+    parser.add_argument('--lambda_free', type=float, default=0, help="weight of the free-space term: the opacity in front of the measured surface (0 = off)")
+    parser.add_argument('--depth_margin', type=float, default=0.02,
+                        help="the free-space term ends this far in front of the surface, in scene units (0.02: about one cell of the 128^3 grid at bound 1)")
+
     ### evaluation (not in the reference)
     parser.add_argument('--ssim', action='store_true', help="also report SSIM at evaluation (after PSNR, which still picks the best checkpoint)")
 

@@ -8,7 +8,10 @@ What differs from the reference, and why:
     yields the reference's values (`code / 255` in float32, bit for bit; half where the reference holds half);
   * on a HIP device `collate` hands the Trainer the chosen pixel ids (`targets.PixelBatch`) instead of their gathered values, and
     ngp_train_targets reads them out of the store (`targets.fused_targets = False`, a CPU device or B > 1: the reference's gather);
-  * `rand_pose >= 0` (CLIP-guided training) is not ported."""
+  * `rand_pose >= 0` (CLIP-guided training) is not ported;
+  * depth supervision (not in the reference): frames may name a 16-bit `depth_path` with a top-level `integer_depth_scale`
+    (Instant-NGP's keys).  The maps are read only when `opt.lambda_depth > 0 or opt.lambda_free > 0`, kept as codes
+    (`targets.DepthStore`), and `collate` adds `depth`: the chosen pixels' ray distances (DESIGN.md "Depth supervision")."""
 import glob
 import json
 import os
@@ -18,7 +21,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import targets
-from .targets import ImageStore, PixelBatch
+from .targets import DepthBatch, DepthStore, ImageStore, PixelBatch
 from .utils import get_rays
 
 
@@ -61,6 +64,18 @@ def read_image(path):
         return np.array(im, dtype=np.uint8)
 
 
+def read_depth(path):
+    """uint16 [H, W] codes of a 16-bit greyscale file"""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("I;16", "I;16L", "I;16B", "I"):
+            raise ValueError(f"{path}: image mode {im.mode!r}; depth maps are 16-bit greyscale")
+        codes = np.array(im)
+    if codes.ndim != 2 or codes.min() < 0 or codes.max() > 65535:
+        raise ValueError(f"{path}: depth maps are 16-bit greyscale")
+    return codes.astype(np.uint16)
+
+
 def _resize_box(image, W, H):
     from PIL import Image
     return np.array(Image.fromarray(image).resize((W, H), Image.BOX), dtype=np.uint8)
@@ -82,6 +97,9 @@ class NeRFDataset:
 
         self.training = self.type in ['train', 'all', 'trainval']
         self.num_rays = self.opt.num_rays if self.training else -1
+
+        # depth maps are read only for the depth terms: with both weights 0 a dataset that has them loads exactly as one without
+        self.with_depth = getattr(opt, "lambda_depth", 0) > 0 or getattr(opt, "lambda_free", 0) > 0
 
         self.rand_pose = opt.rand_pose
         if self.rand_pose >= 0:
@@ -152,6 +170,7 @@ class NeRFDataset:
 
             self.poses = []
             images = []
+            depth_maps = []
             for f in frames:
                 f_path = os.path.join(self.root_path, f['file_path'])
                 if self.mode == 'blender' and '.' not in os.path.basename(f_path):
@@ -171,6 +190,17 @@ class NeRFDataset:
 
                 self.poses.append(pose)
                 images.append(image)
+
+                if self.with_depth:
+                    if 'depth_path' not in f:
+                        depth_maps.append(None)      # (an all-zero map: no measurement anywhere)
+                        continue
+                    if downscale != 1:
+                        raise NotImplementedError("depth maps together with downscale != 1 are not supported")
+                    codes = read_depth(os.path.join(self.root_path, f['depth_path']))
+                    if codes.shape != (self.H, self.W):
+                        raise ValueError(f"{f['depth_path']}: depth map of {codes.shape[1]} x {codes.shape[0]}, image of {self.W} x {self.H}")
+                    depth_maps.append(codes)
 
         self.poses = torch.from_numpy(np.stack(self.poses, axis=0))  # [N, 4, 4]
         self.images = None
@@ -210,6 +240,15 @@ class NeRFDataset:
 
         self.intrinsics = np.array([fl_x, fl_y, cx, cy])
 
+        self.depths = None
+        if self.with_depth and images is not None:
+            if any(m is not None for m in depth_maps) and 'integer_depth_scale' not in transform:
+                raise RuntimeError("frames name a depth_path but the transforms file has no integer_depth_scale")
+            codes = np.stack([np.zeros((self.H, self.W), dtype=np.uint16) if m is None else m for m in depth_maps], axis=0)
+            self.depths = DepthStore.from_codes(codes, self.H, self.W, float(transform.get('integer_depth_scale', 1.0)) * self.scale, self.intrinsics)
+            if self.preload:
+                self.depths = self.depths.to(self.device)
+
     def collate(self, index):
         B = len(index)  # a list of length 1
         poses = self.poses[index].to(self.device)  # [B, 4, 4]
@@ -233,6 +272,14 @@ class NeRFDataset:
                     images = torch.gather(images.view(B, -1, C), 1, torch.stack(C * [rays['inds']], -1))  # [B, N, 3/4]
                 results['images'] = images
 
+        if self.depths is not None:      # ray distances of the same pixels (0: no measurement, +inf: known empty)
+            if targets.fused_targets and self.device.type == 'cuda' and B == 1:
+                results['depth'] = DepthBatch(self.depths, index[0], rays['inds'] if self.training else None, self.device)
+            else:
+                codes = self.depths.codes(index).to(self.device)  # [B, H*W]
+                pix = rays['inds'] if self.training else torch.arange(self.H * self.W, device=self.device).expand(B, -1)
+                results['depth'] = targets.reference_depth_targets(torch.gather(codes, 1, pix), pix, self.W, self.depths.intrinsics, self.depths.unit)
+
         if error_map is not None:  # the trainer needs these to update the error map
             results['index'] = index
             results['inds_coarse'] = rays['inds_coarse']
@@ -247,19 +294,38 @@ class NeRFDataset:
         return loader
 
 
-def write_blender_dataset(path, poses_ngp, images_uint8, camera_angle_x, split, scale=1.0, offset=(0, 0, 0)):
+def write_blender_dataset(path, poses_ngp, images_uint8, camera_angle_x, split, scale=1.0, offset=(0, 0, 0), depths=None, integer_depth_scale=None):
     """Write `transforms_<split>.json` and `<split>/r_<i>.png` under `path` so that NeRFDataset(opt.scale = scale, opt.offset = offset)
     reads back `poses_ngp` [n,4,4] (this package's camera convention; exactly for scale = 1, offset = 0) and `images_uint8`
-    [n,H,W,3/4]."""
+    [n,H,W,3/4].
+
+    depths: float [n,H,W] z-depth along the optical axis, in the units of the WRITTEN poses (np.inf: known empty, NaN or <= 0: no
+    measurement), written as 16-bit greyscale `<split>/r_<i>_depth.png` of codes round(z / integer_depth_scale) (targets.encode_depth)
+    with Instant-NGP's keys: `depth_path` per frame, `integer_depth_scale` at the top level (default: the largest finite depth / 65534)."""
     from PIL import Image
     os.makedirs(os.path.join(path, split), exist_ok=True)
+    top = {"camera_angle_x": float(camera_angle_x)}
+    if depths is not None:
+        depths = np.asarray(depths, dtype=np.float64)
+        if depths.ndim != 3 or depths.shape[0] != len(images_uint8) or depths.shape[1:] != np.asarray(images_uint8[0]).shape[:2]:
+            raise ValueError("depths are float [n, H, W], one map per image")
+        if integer_depth_scale is None:
+            finite = depths[np.isfinite(depths) & (depths > 0)]
+            integer_depth_scale = float(finite.max()) / 65534 if finite.size else 1.0
+        top["integer_depth_scale"] = float(integer_depth_scale)
     frames = []
     for i, (pose, image) in enumerate(zip(np.asarray(poses_ngp, dtype=np.float32), np.asarray(images_uint8))):
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[-1] not in (3, 4):
             raise ValueError("images are uint8 [H, W, 3] or [H, W, 4]")
         Image.fromarray(np.ascontiguousarray(image)).save(os.path.join(path, split, f"r_{i}.png"))
         nerf = ngp_matrix_to_nerf(pose, scale=scale, offset=list(offset))
-        frames.append({"file_path": f"./{split}/r_{i}", "transform_matrix": [[float(v) for v in row] for row in nerf]})
+        frame = {"file_path": f"./{split}/r_{i}", "transform_matrix": [[float(v) for v in row] for row in nerf]}
+        if depths is not None:
+            codes = targets.encode_depth(depths[i], integer_depth_scale)
+            Image.fromarray(codes).save(       # (uint16 -> mode I;16)
+                os.path.join(path, split, f"r_{i}_depth.png"))
+            frame["depth_path"] = f"./{split}/r_{i}_depth.png"
+        frames.append(frame)
     with open(os.path.join(path, f"transforms_{split}.json"), "w") as f:
-        json.dump({"camera_angle_x": float(camera_angle_x), "frames": frames}, f, indent=1)
+        json.dump({**top, "frames": frames}, f, indent=1)
     return path

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, raymarching
-from ..loss import eff_distloss
+from ..loss import depth_loss, eff_distloss
 from . import sampling
 from .sampling import sample_pdf  # noqa: F401  (renderer.py:12-46: importable from here as in the reference)
 
@@ -188,6 +188,13 @@ class NeRFRenderer(nn.Module):
             # the distortion regulariser on the normalised depths, each sample with the interval its weight was formed with
             intervals = torch.cat([depths[:, 1:] - depths[:, :-1], last_interval.unsqueeze(-1)], dim=-1)
             extra["loss_distort"] = eff_distloss(weights, relative, intervals / span.unsqueeze(-1))
+        if self.training and torch.is_grad_enabled() and self._depth_terms(kwargs):
+            # depth supervision on the same weights; `depths` are ray distances, as the target is
+            target, margin = kwargs["depth_target"].reshape(-1).float(), kwargs.get("depth_margin", 0.0)
+            extra["loss_depth"] = depth_loss(weights, depths, target, margin, 1 / span, kwargs.get("lambda_depth", 0), kwargs.get("lambda_free", 0))
+            with torch.no_grad():
+                front = (depths < (target - margin).unsqueeze(-1)).to(weights.dtype)
+                extra["loss_depth_parts"] = self._depth_term_means((weights * depths).sum(dim=-1), (weights * front).sum(dim=-1), target, 1 / span)
         return {
             **extra,
             "depth": depth.view(*prefix),
@@ -221,9 +228,23 @@ class NeRFRenderer(nn.Module):
             return None
         return (C.c_float * 3)(*vals)
 
-    def _march_train(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays, distort=False):
+    @staticmethod
+    def _depth_terms(kwargs):
+        """depth supervision is on: the call carries `depth_target` and one of the two weights is positive"""
+        return kwargs.get("depth_target") is not None and (kwargs.get("lambda_depth", 0) > 0 or kwargs.get("lambda_free", 0) > 0)
+
+    @staticmethod
+    def _depth_term_means(d, A, target, scale):
+        """the mean over the rays of each term alone, [2] = ((scale (d - z))^2 on the rays with a surface, A), detached: for logging"""
+        with torch.no_grad():
+            surface = torch.isfinite(target) & (target > 0)
+            miss = torch.where(surface, scale * (d - torch.where(surface, target, torch.zeros_like(target))), torch.zeros_like(d))
+            return torch.stack([(miss * miss).mean(), torch.where(target > 0, A, torch.zeros_like(A)).mean()])
+
+    def _march_train(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays, distort=False, depth=None):
         """training branch (renderer.py:286-327): one march over all rays, one network call, one differentiable compositing;
-        `distort`: also the distortion regulariser of the same samples, on depths normalised by the ray's span (else None)"""
+        `distort`: also the distortion regulariser of the same samples, on depths normalised by the ray's span (else None);
+        `depth`: the call's kwargs when depth supervision is on -- the depth terms of the same samples (else None)"""
         counter = self.step_counter[self.local_step % 16]      # ring of the last 16 steps' sample counts (-> mean_count)
         counter.zero_()
         self.local_step += 1
@@ -236,7 +257,21 @@ class NeRFRenderer(nn.Module):
         if sigmas.dim() != 1:
             raise RuntimeError("run_cuda: the network must return one density per sample (residual stacks are not part of this path)")
         loss_distort = raymarching.distortion_rays_train(sigmas, deltas, rays, 1 / (fars - nears)) if distort else None
-        return (*raymarching.composite_rays_train(sigmas, rgbs, deltas, rays), sigmas, rgbs, loss_distort)
+        loss_depth = None
+        if depth is not None:
+            target, scale = self.march_depth_target(depth["depth_target"].reshape(-1), nears), 1 / (fars - nears)
+            term, _, parts = raymarching.depth_rays_train(sigmas, deltas, rays, target, depth.get("depth_margin", 0.0), scale,
+                                                          depth.get("lambda_depth", 0), depth.get("lambda_free", 0), return_rays=True)
+            loss_depth = (term, self._depth_term_means(parts[:, 0], parts[:, 1], target, scale))
+        return (*raymarching.composite_rays_train(sigmas, rgbs, deltas, rays), sigmas, rgbs, loss_distort, loss_depth)
+
+    @staticmethod
+    def march_depth_target(target, nears):
+        """A ray distance from the camera -> the units of the march's t_i = gap_0 + ... + gap_i, which count from the ray's near (the
+        march starts there and its first gap is its first step): z - near.  0 (no measurement) and +inf (known empty) stay; a surface
+        in front of the near plane is no measurement."""
+        rel = target.float() - nears
+        return torch.where(torch.isfinite(target) & (rel > 0), rel, torch.where(torch.isinf(target) & (target > 0), target.float(), torch.zeros_like(rel)))
 
     def _march_eval_operators(self, origins, directions, nears, fars, dt_gamma, max_steps, perturb):
         """eval branch, operator by operator (renderer.py:337-373) -- what the fused renderer (ngp_render_rays) replaces and is
@@ -275,11 +310,15 @@ class NeRFRenderer(nn.Module):
         backdrop = self._backdrop(origins, directions, bg_color)
         out = {}
         if self.training:
-            acc, depth, image, sigmas, rgbs, loss_distort = self._march_train(origins, directions, nears, fars, dt_gamma, max_steps, perturb,
-                                                                              force_all_rays, distort=torch.is_grad_enabled() and kwargs.get("lambda_distort", 0) > 0)
+            acc, depth, image, sigmas, rgbs, loss_distort, loss_depth = self._march_train(
+                origins, directions, nears, fars, dt_gamma, max_steps, perturb, force_all_rays,
+                distort=torch.is_grad_enabled() and kwargs.get("lambda_distort", 0) > 0,
+                depth=kwargs if torch.is_grad_enabled() and self._depth_terms(kwargs) else None)
             out["weights_sum"] = acc
             if loss_distort is not None:
                 out["loss_distort"] = loss_distort
+            if loss_depth is not None:
+                out["loss_depth"], out["loss_depth_parts"] = loss_depth
         else:
             fm = self.fused_model() if self.fused and not torch.is_grad_enabled() else None
             if fm is not None and not fm.f32:      # (the fused occupancy-grid loop exists for the fp16 network; fp32 takes the operators)

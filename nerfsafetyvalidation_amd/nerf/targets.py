@@ -9,7 +9,11 @@ Two forms of the same arithmetic:
     store (a quarter of the reference's fp32 store) and ngp_photo_loss_forward / _backward are one autograd node each way.
 
 `fused_targets` (module flag) selects the HIP form where it applies: a HIP device, one frame per batch, the criterion
-MSELoss(reduction='none').  Everything else takes the torch chain."""
+MSELoss(reduction='none').  Everything else takes the torch chain.
+
+Depth targets (DESIGN.md "Depth supervision") have the same two forms: `DepthStore` keeps a dataset's depth maps as 16-bit codes of
+z-depth, `reference_depth_targets` turns the chosen pixels' codes into ray distances with torch operators, and
+`training_depth_targets` (ngp_train_depth_targets) does the gather and the conversion in one launch."""
 import numpy as np
 import torch
 
@@ -96,6 +100,107 @@ class PixelBatch:
             return images
         C = images.shape[-1]
         return torch.gather(images.view(1, -1, C), 1, torch.stack(C * [self.inds], -1))
+
+
+# ------------------------------------------------------------------------------------------------ depth maps
+DEPTH_NONE, DEPTH_EMPTY = 0, 65535          # the two codes that are no distance: no measurement, known empty
+
+
+def encode_depth(depth, integer_depth_scale):
+    """float z-depth (any shape) -> uint16 codes: +inf -> 65535 (known empty), NaN or <= 0 -> 0 (no measurement), everything else
+    round(z / integer_depth_scale) clipped to 1 .. 65534"""
+    z = np.asarray(depth, dtype=np.float64)
+    finite = np.isfinite(z) & (z > 0)
+    codes = np.zeros(z.shape, dtype=np.uint16)
+    codes[finite] = np.clip(np.rint(z[finite] / float(integer_depth_scale)), 1, 65534).astype(np.uint16)
+    codes[np.isposinf(z)] = DEPTH_EMPTY
+    return codes
+
+
+class DepthStore:
+    """The dataset's depth maps as 16-bit codes [n_img, H*W] (held as int16 bit patterns: torch indexes those on every device),
+    resident on `data.device` like ImageStore.  A code k in 1 .. 65534 is the z-depth k * unit along the optical axis, in the units of
+    the loaded poses (unit = integer_depth_scale * opt.scale); 0 is no measurement, 65535 known empty.  `intrinsics` (fx, fy, cx, cy)
+    turn a pixel's z-depth into its ray distance."""
+
+    def __init__(self, data, H, W, unit, intrinsics):
+        assert data.dtype == torch.int16 and data.dim() == 2 and data.shape[1] == H * W
+        self.data, self.H, self.W, self.unit = data.contiguous(), H, W, float(np.float32(unit))
+        self.intrinsics = tuple(float(v) for v in intrinsics)
+
+    @classmethod
+    def from_codes(cls, codes, H, W, unit, intrinsics):
+        """codes: uint16 numpy [n_img, H, W]"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint16).reshape(codes.shape[0], H * W)
+        return cls(torch.from_numpy(codes.view(np.int16)), H, W, unit, intrinsics)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def nbytes(self):
+        return self.data.numel() * self.data.element_size()
+
+    def to(self, device):
+        return DepthStore(self.data.to(device), self.H, self.W, self.unit, self.intrinsics)
+
+    def codes(self, index):
+        """the codes of frames `index` as int32 [..., H*W] in 0 .. 65535"""
+        return self.data[index].to(torch.int32) & 0xFFFF
+
+
+def reference_depth_targets(codes, pix, W, intrinsics, unit):
+    """codes int [..., N] of the pixels `pix` (flat ids, same shape) -> float32 ray distances, by torch operators:
+    t = (code * unit) * |dir|, dir = ((i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, 1), the direction get_rays forms for the pixel before it
+    normalises it; code 0 -> 0, code 65535 -> +inf."""
+    fx, fy, cx, cy = intrinsics
+    x = (((pix % W).float() + 0.5) - cx) / fx
+    y = ((torch.div(pix, W, rounding_mode="floor").float() + 0.5) - cy) / fy
+    t = (codes.float() * unit) * torch.sqrt((x * x + y * y) + 1.0)
+    t = torch.where(codes == DEPTH_EMPTY, torch.full_like(t, float("inf")), t)
+    return torch.where(codes == DEPTH_NONE, torch.zeros_like(t), t)
+
+
+class DepthBatch:
+    """What `collate` hands over as `depth` when the HIP form applies: the store, the frame and the chosen pixels.  `materialize()`
+    builds the [1, N] tensor of ray distances the torch form gives."""
+
+    def __init__(self, store, frame, inds, device):
+        self.store, self.frame, self.inds, self.device = store, int(frame), inds, device
+
+    @property
+    def shape(self):
+        return torch.Size([1, self.store.H * self.store.W if self.inds is None else self.inds.shape[-1]])
+
+    def materialize(self):
+        st = self.store
+        codes = st.codes([self.frame]).to(self.device)
+        pix = torch.arange(st.H * st.W, device=self.device)[None] if self.inds is None else self.inds.reshape(1, -1)
+        return reference_depth_targets(torch.gather(codes, 1, pix), pix, st.W, st.intrinsics, st.unit)
+
+
+def training_depth_targets(batch):
+    """DepthBatch -> float32 [1, N] ray distances, one launch (ngp_train_depth_targets) straight from the 16-bit store"""
+    st, device = batch.store, batch.device
+    n_pix = st.H * st.W
+    if st.data.device == device:
+        data, base = st.data, batch.frame * n_pix
+    else:
+        data, base = st.data[batch.frame].to(device, non_blocking=True), 0
+    inds = None if batch.inds is None else batch.inds.reshape(-1).contiguous()
+    if inds is not None and inds.dtype != torch.int64:
+        raise RuntimeError("pixel ids must be int64")
+    N = n_pix if inds is None else int(inds.shape[0])
+    if base + n_pix > data.numel():
+        raise RuntimeError("the frame lies outside the depth store")
+    out = torch.empty(N, dtype=torch.float32, device=device)
+    fx, fy, cx, cy = st.intrinsics
+    _lib.check(_lib.lib().ngp_train_depth_targets(_lib.ptr(data), int(base), n_pix, st.W, _lib.ptr(inds), N, fx, fy, cx, cy, st.unit,
+                                                  _lib.ptr(out), _lib.stream()), "train_depth_targets")
+    return out.view(1, N)
 
 
 # ------------------------------------------------------------------------------------------------ the torch chain (the reference's text)

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from .. import checkpoint as _checkpoint
 from . import targets
-from .targets import PixelBatch
+from .targets import DepthBatch, PixelBatch
 from .utils import linear_to_srgb
 
 
@@ -266,7 +266,17 @@ class Trainer(object):
         else:
             gt_rgb = targets.reference_targets(images, bg_color, self.opt.color_space)
 
-        outputs = self.model.render(rays_o, rays_d, staged=False, bg_color=bg_color, perturb=True, force_all_rays=False, **vars(self.opt))
+        # depth supervision (opt-in): the targets of the same pixels as ray distances, by the fused launch or the torch form; the
+        # weights and the margin reach the renderer through vars(opt)
+        lam_depth, lam_free = getattr(self.opt, "lambda_depth", 0), getattr(self.opt, "lambda_free", 0)
+        extra = {}
+        if (lam_depth > 0 or lam_free > 0) and 'depth' in data:
+            depth = data['depth']
+            if isinstance(depth, DepthBatch):
+                depth = targets.training_depth_targets(depth) if targets.fused_targets else depth.materialize()
+            extra['depth_target'] = depth
+
+        outputs = self.model.render(rays_o, rays_d, staged=False, bg_color=bg_color, perturb=True, force_all_rays=False, **extra, **vars(self.opt))
 
         pred_rgb = outputs['image']
 
@@ -282,6 +292,12 @@ class Trainer(object):
         if lam > 0:
             self.last_loss_distort = outputs["loss_distort"]
             loss = loss + lam * self.last_loss_distort
+
+        # the depth terms, already weighted by lambda_depth and lambda_free (loss.depth_loss)
+        self.last_loss_depth = self.last_loss_depth_parts = None
+        if 'depth_target' in extra:
+            self.last_loss_depth, self.last_loss_depth_parts = outputs["loss_depth"], outputs["loss_depth_parts"]
+            loss = loss + self.last_loss_depth
 
         return pred_rgb, gt_rgb, loss
 
@@ -468,6 +484,8 @@ class Trainer(object):
                 writer.add_scalar("train/loss", loss_val, self.global_step)
                 if getattr(self, "last_loss_distort", None) is not None:
                     writer.add_scalar("train/loss_distort", self.last_loss_distort.item(), self.global_step)
+                if getattr(self, "last_loss_depth", None) is not None:
+                    writer.add_scalar("train/loss_depth", self.last_loss_depth.item(), self.global_step)
                 writer.add_scalar("train/lr", self.optimizer.param_groups[0]['lr'], self.global_step)
 
         if self.ema is not None:

@@ -23,7 +23,7 @@ from torch.amp import custom_bwd, custom_fwd
 from .. import _lib
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
-           "composite_rays_train", "distortion_rays_train", "march_rays", "composite_rays"]
+           "composite_rays_train", "distortion_rays_train", "depth_rays_train", "march_rays", "composite_rays"]
 
 USE_OCCUPANCY_LIN = True        # march_rays keeps derived copies of the occupancy bits per bitfield version (False: the plain kernel, for A/B)
 
@@ -262,6 +262,64 @@ def distortion_rays_train(sigmas, deltas, rays, scale=None, return_rays=False):
     else:
         loss, loss_rays = _distortion_rays_train.apply(sigmas, deltas, rays, scale)
     return (loss, loss_rays) if return_rays else loss
+
+
+class _depth_rays_train(Function):
+    @staticmethod
+    @_fwd32
+    def forward(ctx, sigmas, deltas, rays, target, scale, margin, weight_depth, weight_free):
+        sigmas, deltas, rays = sigmas.float().contiguous(), deltas.float().contiguous(), rays.contiguous()
+        target = target.float().contiguous()
+        scale = None if scale is None else scale.float().contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        if target.numel() != N or (scale is not None and scale.numel() != N):
+            raise RuntimeError("depth_rays_train: target and scale hold one value per ray slot")
+        loss_rays = torch.zeros(N, dtype=sigmas.dtype, device=sigmas.device)
+        parts = torch.zeros(N, 2, dtype=sigmas.dtype, device=sigmas.device)
+        loss = torch.zeros((), dtype=sigmas.dtype, device=sigmas.device)
+        L = _lib.lib()
+        nbytes = L.ngp_depth_loss_workspace(N)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=sigmas.device) if nbytes else None
+        _lib.check(L.ngp_depth_loss_train_forward(_lib.ptr(sigmas), _lib.ptr(deltas), _lib.ptr(rays), _lib.ptr(target), _lib.ptr(scale), margin,
+                                                  weight_depth, weight_free, M, N, _lib.ptr(loss_rays), _lib.ptr(parts), _lib.ptr(loss),
+                                                  _lib.ptr(ws), nbytes, _lib.stream()), "depth_loss_train_forward")
+        ctx.save_for_backward(sigmas, deltas, rays, target, scale, parts)
+        ctx.dims, ctx.consts = [M, N], (margin, weight_depth, weight_free)
+        ctx.mark_non_differentiable(loss_rays, parts)
+        return loss, loss_rays, parts
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_loss, _grad_loss_rays, _grad_parts):
+        sigmas, deltas, rays, target, scale, parts = ctx.saved_tensors
+        M, N = ctx.dims
+        grad_sigmas = torch.zeros_like(sigmas)      # rows of dead samples, of rays that take no part and of no ray read 0
+        _lib.check(_lib.lib().ngp_depth_loss_train_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(sigmas), _lib.ptr(deltas),
+                                                            _lib.ptr(rays), _lib.ptr(target), _lib.ptr(scale), *ctx.consts, _lib.ptr(parts),
+                                                            M, N, _lib.ptr(grad_sigmas), _lib.stream()), "depth_loss_train_backward")
+        return grad_sigmas, None, None, None, None, None, None, None
+
+
+def depth_rays_train(sigmas, deltas, rays, target, margin, scale=None, weight_depth=1.0, weight_free=1.0, return_rays=False):
+    """Depth supervision on march_rays_train's packed samples -> scalar, differentiable in sigmas (csrc/depth_loss.hip).
+
+    sigmas [M], deltas [M,2] = (dt, gap), rays int32 [N,3] = (index, offset, count), target [N] and scale [N] per ray slot (scale
+    None = 1; the renderer passes 1 / (far - near)).  The composite rule is distortion_rays_train's, and so are the stop
+    (T_{i+1} < 1e-4, that sample included) and the drop rule (offset + count >= M); t_i = gap_0 + ... + gap_i.  With z = target[index],
+    a = weight_depth, b = weight_free (`loss.py` has the same definitions for dense weights):
+        z == 0, NaN or negative   no measurement: L_ray = 0, no gradient
+        0 < z < +inf              d = sum w_i t_i,  A = sum_{t_i < z - margin} w_i,  L_ray = a (scale (d - z))^2 + b A
+        z == +inf                 known empty ray: A = sum w_i,  L_ray = b A
+    The result is sum(L_ray) / N over ALL N rows of the table.  The gradient is exact for every live sample, the one that stops the
+    ray included.  No atomics: the same bits on every call and for every order of the table's rows.
+    return_rays: also return L_ray [N] and parts [N,2] = (d, A) per slot (not differentiable)."""
+    if rays.shape[0] == 0:
+        loss = sigmas.float().sum() * 0
+        loss_rays, parts = sigmas.new_zeros(0, dtype=torch.float32), sigmas.new_zeros(0, 2, dtype=torch.float32)
+    else:
+        loss, loss_rays, parts = _depth_rays_train.apply(sigmas, deltas, rays, target, scale, float(margin), float(weight_depth),
+                                                         float(weight_free))
+    return (loss, loss_rays, parts) if return_rays else loss
 
 
 # ---------------------------------------------------------------- inference
