@@ -79,6 +79,13 @@ NGP_API int ngp_morton3D_invert(const int32_t* indices, uint32_t N, int32_t* coo
 /* raymarching.cu:294-302 packbits; N = number of output BYTES */
 NGP_API int ngp_packbits(const float* grid, uint32_t N, float density_thresh, uint8_t* bitfield, ngp_stream_t stream);
 
+/* The occupancy grid of the marches below, of ngp_render_rays and of the density-grid maintenance: C cascades (1 <= C <= 8) of H^3
+ * cells, cell (level, x, y, z) at bit level * H^3 + morton3D(x, y, z) of the bitfield, LSB first in a byte.  H must be a POWER OF TWO
+ * in [2, 1024]: the Morton code of a cell stays below H^3 only then (H = 48: morton3D(47, 47, 47) = 233 471 against 110 592 cells), so
+ * any other H would index past the level and past the buffer.  ngp_march_rays, ngp_march_rays_lin, ngp_march_rays_train,
+ * ngp_render_rays, ngp_mark_untrained_grid, ngp_density_grid_update and ngp_density_grid_finish return NGP_EINVAL on the host for
+ * anything else, name the sizes in ngp_last_error(), launch nothing and leave their outputs untouched. */
+
 /* raymarching.cu:486-495 march_rays_train.  Slots are handed out by an exclusive
  * prefix sum in ray order (deterministic member of the reference's atomicAdd
  * permutation set).  counter[0] += total samples, counter[1] += N, as the
@@ -295,7 +302,7 @@ typedef struct ngp_model {
     float density_scale;
     const uint8_t* density_bitfield; /* [C*H^3/8]                                         */
     uint32_t cascade;             /* C                                                    */
-    uint32_t grid_size;           /* H (128)                                              */
+    uint32_t grid_size;           /* H (128): a power of two in [2, 1024]                 */
     const void* cell_tables;      /* optional (may be NULL): per-cell corner records of the first cell_levels levels, */
     uint32_t cell_levels;         /* built by ngp_build_cell_tables; the fused kernels use the records when this is 12 */
     const void* packed_weights;   /* the two blobs as MFMA fragments (ngp_pack_weights; ngp_packed_weights_bytes() bytes of device
@@ -653,7 +660,8 @@ NGP_API int ngp_merge_sorted(const float* z_a, const float* z_b, uint32_t N, uin
 /* ---------------- density-grid maintenance (nerf/renderer.py:388-544): the producer of density_bitfield ---------------- */
 
 /* mark_untrained_grid (:388-449): cells of density_grid [cascade, H^3] (Morton order) whose centre no camera sees become -1.
- * poses [n_cams,4,4] cam2world (device).  workspace: only for more than 2048 cameras (cascade * H^3 * 4 bytes), else NULL. */
+ * poses [n_cams,4,4] cam2world (device).  workspace: only for more than 2048 cameras (cascade * H^3 * 4 bytes), else NULL.
+ * H: a power of two in [2, 1024], cascade in [1, 8] (see ngp_march_rays_train), here and in ngp_density_grid_update / _finish. */
 NGP_API int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float fx, float fy, float cx, float cy, float bound, uint32_t cascade,
                             uint32_t H, float* density_grid, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 /* sample positions of update_extra_state (:479-485, :512-520): coords int32 [n,3] cell coordinates, or NULL = every cell in the

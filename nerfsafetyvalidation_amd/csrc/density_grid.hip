@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(kDgBlock) k_packbits_dev(const float* __restri
 }
 
 static bool grid_dims_ok(uint32_t cascade, uint32_t H) {
-    return cascade >= 1 && cascade <= 8 && H >= 2 && H <= 1024 && (H * H * H) % 8 == 0;
+    return cascade >= 1 && cascade <= 8 && grid_size_ok(H);      // (a power of two >= 2: H^3 cells fill whole bytes of the bitfield)
 }
 
 }  // namespace ngp
@@ -163,7 +163,7 @@ extern "C" {
 int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float fx, float fy, float cx, float cy, float bound, uint32_t cascade, uint32_t H,
                             float* density_grid, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
     NGP_REQUIRE(density_grid && (poses || n_cams == 0), "mark_untrained_grid: null pointer");
-    NGP_REQUIRE(grid_dims_ok(cascade, H), "mark_untrained_grid: unsupported cascade / grid size (%u, %u)", cascade, H);
+    NGP_REQUIRE(grid_dims_ok(cascade, H), "mark_untrained_grid: unsupported cascade / grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", cascade, H);
     hipStream_t s = (hipStream_t)stream;
     const uint32_t H3 = H * H * H, cells = cascade * H3;
     // the scalars of :436-438 as torch hands Python floats to a float32 kernel: cx / fx in double, rounded once
@@ -204,7 +204,8 @@ size_t ngp_density_grid_workspace(uint32_t cascade, uint32_t H) {
 int ngp_density_grid_update(float* density_grid, uint32_t cascade, uint32_t H, uint32_t cas, const int32_t* indices, const float* sigmas, uint32_t n,
                             float density_scale, float decay, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
     NGP_REQUIRE(density_grid && workspace && (n == 0 || (indices && sigmas)), "density_grid_update: null pointer");
-    NGP_REQUIRE(grid_dims_ok(cascade, H) && cas < cascade, "density_grid_update: unsupported cascade / grid size");
+    NGP_REQUIRE(grid_dims_ok(cascade, H) && cas < cascade,
+                "density_grid_update: unsupported cascade / grid size C=%u H=%u, level %u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", cascade, H, cas);
     NGP_REQUIRE(workspace_bytes >= ngp_density_grid_workspace(cascade, H) && ((uintptr_t)workspace & 7) == 0,
                 "density_grid_update: workspace too small or misaligned (%zu < %zu bytes)", workspace_bytes, ngp_density_grid_workspace(cascade, H));
     hipStream_t s = (hipStream_t)stream;
@@ -219,7 +220,7 @@ int ngp_density_grid_update(float* density_grid, uint32_t cascade, uint32_t H, u
 int ngp_density_grid_finish(const float* density_grid, uint32_t cascade, uint32_t H, float density_thresh, float* mean_thresh, uint8_t* bitfield,
                             void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
     NGP_REQUIRE(density_grid && mean_thresh && bitfield && workspace, "density_grid_finish: null pointer");
-    NGP_REQUIRE(grid_dims_ok(cascade, H), "density_grid_finish: unsupported cascade / grid size");
+    NGP_REQUIRE(grid_dims_ok(cascade, H), "density_grid_finish: unsupported cascade / grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", cascade, H);
     NGP_REQUIRE(workspace_bytes >= ngp_density_grid_workspace(cascade, H) && ((uintptr_t)workspace & 7) == 0, "density_grid_finish: workspace too small or misaligned");
     NGP_REQUIRE(((uintptr_t)density_grid & 15) == 0, "density_grid_finish: the density grid must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;

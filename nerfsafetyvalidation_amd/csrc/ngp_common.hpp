@@ -107,5 +107,11 @@ __device__ __forceinline__ uint32_t expand_bits10(uint32_t v) {
 __device__ __forceinline__ uint32_t morton3D_cell(uint32_t x, uint32_t y, uint32_t z) {
     return expand_bits10(x) | (expand_bits10(y) << 1) | (expand_bits10(z) << 2);
 }
+// The grid sizes of the occupancy grid and the density grid: a power of two in [2, 1024].  A cell's index is level * H^3 +
+// morton3D(x, y, z), and the Morton code stays below H^3 only then (H = 48: morton3D(47, 47, 47) = 233 471 against 110 592 cells), so
+// with any other H a march would read, and mark_untrained_grid write, past the level and past the buffer.  The reference has the same
+// defect and only ever uses 128; here every entry point refuses on the host.
+inline bool grid_size_ok(uint32_t H) { return H >= 2 && H <= 1024 && (H & (H - 1)) == 0; }
+#define NGP_GRID_SIZE_RULE "H must be a power of two in [2, 1024]: cells are indexed by morton3D(x, y, z), which exceeds H^3 otherwise"
 
 }  // namespace ngp

@@ -179,6 +179,8 @@ struct Dda {
     }
     // :378-380.  The reference's `0.5 * (...) * H` is a double product; for a power-of-two H it only rescales the
     // float value fmaf(v, rb, 1) by 2^k, which is exact in float as well, so the double detour is skipped.
+    // (Every entry point refuses any other H on the host -- grid_size_ok, ngp_common.hpp -- so the double branch is never taken.  It
+    // stays: without it the render loop's march kernels compile to other code, measured 1 % slower on the frame benchmark.)
     __device__ __forceinline__ int cell(float v, float mip_rbound) const {
         const float a = fmaf(v, mip_rbound, 1.0f);
         const float s = h_pow2 ? a * halfH : (float)(0.5 * (double)a * Hd);
@@ -293,7 +295,12 @@ struct Dda {
     // `occupied_until` (optional): when the probe finds its cell occupied, the time up to which every later position of the ray is
     // CERTAIN to be located in this same cell by the reference's arithmetic -- the cell's exit time less the rounding allowance of
     // jump_block (all three axes counted: a generous bound).  A position before it moves towards each exit face and stays eight ulps of a
-    // coordinate short of it, so its cell indices are these; the cascade level changes only at cube surfaces, which are cell faces.
+    // coordinate short of it, so its cell indices are these.  The cascade level must not change inside the cell either: it changes at the
+    // cube surfaces |p| = 2^k, and those are faces of this level's cells only when the cells tile the cube of half size 2^level
+    // (mip_bound == 2^level: the surfaces lie at cell coordinates H/4, 3H/4, 0 and H).  Where mip_bound is the scene bound instead --
+    // the top cascade of a non-power-of-two bound (bound 1.5, H 64: |x| = 1 is at cell coordinate 53.33), or a level above
+    // log2(bound), which only a position clamped onto the box selects (bound 8, C 8) -- a surface cuts through cells, the next position
+    // may belong to a finer level whose cell is empty, and nothing is certain: *occupied_until = t (jump_block refuses the same case).
     // The march can take its samples up to there without probing (the samples' own arithmetic -- t, dt, t += dt -- is untouched).
     __device__ __forceinline__ bool probe_lin(float& t, float& x, float& y, float& z, float& dt, const uint32_t* coarse,
                                               float* occupied_until = nullptr) const {
@@ -312,7 +319,8 @@ struct Dda {
                 const float tt = t + fminf(tx, fminf(ty, tz));
                 const float g = fmaf(tt, 9.5367431640625e-7f, (fabsf(rdx) + fabsf(rdy) + fabsf(rdz)) * jump_guard);
                 const float until = tt - g;
-                *occupied_until = until > t ? until : t;          // (NaN / infinite allowances: nothing is certain)
+                // (NaN / infinite allowances, or a cell that a cascade surface cuts through: nothing is certain)
+                *occupied_until = (until > t && mip_bound == (float)(1 << level)) ? until : t;
             }
         } else if (const_dt && block_jump && jump_block(t, x, y, z, level, mip_bound, nx, ny, nz)) {
             return false;

@@ -757,7 +757,8 @@ int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t
                          ngp_stream_t stream) {
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter, "march_rays_train: null pointer");
-    NGP_REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 1024, "march_rays_train: unsupported cascade/grid size C=%u H=%u", C, H);
+    NGP_REQUIRE(C >= 1 && C <= 8 && grid_size_ok(H), "march_rays_train: unsupported cascade/grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")",
+                C, H);
     if (!workspace || workspace_bytes < ngp_march_rays_train_workspace(N)) {
         set_error("march_rays_train: workspace of %zu bytes needed, %zu given", ngp_march_rays_train_workspace(N), workspace_bytes);
         return NGP_EWORKSPACE;
@@ -855,7 +856,7 @@ static int march_rays_impl(uint32_t n_alive, uint32_t n_step, const int32_t* ray
     if (M_padded == 0 || n_step == 0) return NGP_OK;
     NGP_REQUIRE(rays_alive && rays_t && rays_o && rays_d && grid && fars && xyzs && dirs && deltas, "march_rays: null pointer");
     NGP_REQUIRE((uint64_t)n_alive * n_step <= M_padded, "march_rays: M_padded=%u smaller than n_alive*n_step", M_padded);
-    NGP_REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 1024, "march_rays: unsupported cascade/grid size C=%u H=%u", C, H);
+    NGP_REQUIRE(C >= 1 && C <= 8 && grid_size_ok(H), "march_rays: unsupported cascade/grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", C, H);
     hipStream_t s = (hipStream_t)stream;
     Pcg32 rng;
     rng.seed((uint64_t)perturb);  // raymarching.cu:819

@@ -1289,8 +1289,8 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     const ActiveRender active_render;
     NGP_REQUIRE(rays_o && rays_d && nears && fars && weights_sum && depth && image, "render_rays: null pointer");
     NGP_REQUIRE(model && model->density_bitfield, "render_rays: model has no density bitfield");
-    NGP_REQUIRE(model->cascade >= 1 && model->cascade <= 8 && model->grid_size >= 2 && model->grid_size <= 1024,
-                "render_rays: unsupported cascade/grid size");
+    NGP_REQUIRE(model->cascade >= 1 && model->cascade <= 8 && grid_size_ok(model->grid_size),
+                "render_rays: unsupported cascade/grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", model->cascade, model->grid_size);
     hipStream_t s = (hipStream_t)stream;
     const DebugState dbg = debug_snapshot(ctx);   // ONE snapshot per call (see DebugState)
     NetArgs na;
