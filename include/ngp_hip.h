@@ -56,6 +56,10 @@ typedef void* ngp_stream_t;
 #define NGP_API
 #endif
 
+/* The number ngp_version() returns; it changes with every incompatible change of this header, and a binding compares it at load.
+ *   101: ngp_network_density has a `geo_feat` argument, ngp_model has `precision` (both were added under 100, unrecorded). */
+#define NGP_ABI_VERSION 101
+
 NGP_API const char* ngp_last_error(void);
 NGP_API int ngp_version(void);
 /* number of HIP devices visible (does not create a context on this image) */

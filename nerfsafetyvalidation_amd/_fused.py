@@ -217,7 +217,7 @@ class FusedModel:
             lib = _lib.lib()
             m = self._struct(None)
             packed = torch.empty(lib.ngp_packed_weights_bytes(), dtype=torch.uint8, device=self.device)
-            _lib.check(lib.ngp_pack_weights(C.byref(m), _lib.ptr(packed), _lib.stream()), "pack_weights")
+            _lib.call("pack_weights", C.byref(m), packed)
             torch.cuda.current_stream(self.device).synchronize()   # other streams may render with it next
             self._packed = packed
 
@@ -241,9 +241,7 @@ class FusedModel:
         sigmas = torch.empty(M, dtype=torch.float32, device=xyzs.device)
         rgbs = torch.empty(M, 3, dtype=torch.float32, device=xyzs.device)
         m = self._struct(None)
-        lib = _lib.lib()
-        _lib.check(lib.ngp_network_forward(C.byref(m), _lib.ptr(xyzs), _lib.ptr(dirs), M, _lib.ptr(sigmas), _lib.ptr(rgbs), _lib.stream()),
-                   "network_forward")
+        _lib.call("network_forward", C.byref(m), xyzs, dirs, M, sigmas, rgbs)
         return sigmas, rgbs
 
     def network_density(self, xyzs, want_geo=False):
@@ -255,7 +253,7 @@ class FusedModel:
         sigmas = torch.empty(M, dtype=torch.float32, device=xyzs.device)
         geo = torch.empty(M, 15, dtype=torch.float32, device=xyzs.device) if want_geo else None
         m = self._struct(None)
-        _lib.check(_lib.lib().ngp_network_density(C.byref(m), _lib.ptr(xyzs), M, _lib.ptr(sigmas), _lib.ptr(geo), _lib.stream()), "network_density")
+        _lib.call("network_density", C.byref(m), xyzs, M, sigmas, geo)
         return (sigmas, geo) if want_geo else sigmas
 
     def cell_max_density(self, start, granularity, shape, samples_per_axis, rot):
@@ -267,8 +265,7 @@ class FusedModel:
         out = torch.empty(X, Y, Z, dtype=torch.float32, device=self.device)
         st = (C.c_float * 3)(*[float(v) for v in start])
         r = (C.c_float * 9)(*[float(v) for v in torch.as_tensor(rot, dtype=torch.float32).reshape(9).tolist()])
-        _lib.check(_lib.lib().ngp_cell_max_density(C.byref(self._struct(None)), st, float(granularity), X, Y, Z, int(samples_per_axis), r,
-                                                   _lib.ptr(out), _lib.stream()), "cell_max_density")
+        _lib.call("cell_max_density", C.byref(self._struct(None)), st, float(granularity), X, Y, Z, int(samples_per_axis), r, out)
         return out
 
     def _ensure_packed_bwd(self):
@@ -278,7 +275,7 @@ class FusedModel:
             with self._ctx_lock:
                 if self._packed_bwd is None:
                     buf = torch.empty(lib.ngp_packed_weights_bwd_bytes(), dtype=torch.uint8, device=self.device)
-                    _lib.check(lib.ngp_pack_weights_bwd(C.byref(self._struct(None)), _lib.ptr(buf), _lib.stream()), "pack_weights_bwd")
+                    _lib.call("pack_weights_bwd", C.byref(self._struct(None)), buf)
                     torch.cuda.current_stream(self.device).synchronize()
                     self._packed_bwd = buf
         return self._packed_bwd
@@ -293,8 +290,7 @@ class FusedModel:
         f32 = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
         gx = torch.empty(M, 3, dtype=torch.float32, device=xyzs.device)
         m = self._struct(None)
-        _lib.check(_lib.lib().ngp_network_density_backward(C.byref(m), _lib.ptr(packed_bwd), _lib.ptr(xyzs), M, _lib.ptr(f32(g_sigma)),
-                                                           _lib.ptr(f32(g_geo)), _lib.ptr(gx), _lib.stream()), "network_density_backward")
+        _lib.call("network_density_backward", C.byref(m), packed_bwd, xyzs, M, f32(g_sigma), f32(g_geo), gx)
         return gx
 
     def planner_collision(self, rot_matrix, pos, body, rot):
@@ -303,8 +299,7 @@ class FusedModel:
         self._ensure_packed()
         S, B = rot_matrix.shape[0], body.shape[0]
         out = torch.empty(S, dtype=torch.float32, device=rot_matrix.device)
-        _lib.check(_lib.lib().ngp_planner_collision(C.byref(self._struct(None)), _lib.ptr(rot_matrix), _lib.ptr(pos), _lib.ptr(body),
-                                                    _lib.ptr(rot), S, B, _lib.ptr(out), _lib.stream()), "planner_collision")
+        _lib.call("planner_collision", C.byref(self._struct(None)), rot_matrix, pos, body, rot, S, B, out)
         return out
 
     def planner_collision_backward(self, rot_matrix, pos, body, rot, g):
@@ -315,9 +310,7 @@ class FusedModel:
         g = g.float().contiguous()
         g_pos = torch.empty(S, 3, dtype=torch.float32, device=rot_matrix.device)
         g_rot = torch.empty(S, 3, 3, dtype=torch.float32, device=rot_matrix.device)
-        _lib.check(_lib.lib().ngp_planner_collision_backward(C.byref(self._struct(None)), _lib.ptr(packed_bwd), _lib.ptr(rot_matrix), _lib.ptr(pos),
-                                                             _lib.ptr(body), _lib.ptr(rot), S, B, _lib.ptr(g), _lib.ptr(g_pos), _lib.ptr(g_rot),
-                                                             _lib.stream()), "planner_collision_backward")
+        _lib.call("planner_collision_backward", C.byref(self._struct(None)), packed_bwd, rot_matrix, pos, body, rot, S, B, g, g_pos, g_rot)
         return g_pos, g_rot
 
     def _pad_value(self):
@@ -343,7 +336,7 @@ class FusedModel:
             if ent is not None:
                 lib.ngp_render_ctx_destroy(ent[0])
             h = C.c_void_p()
-            _lib.check(lib.ngp_render_ctx_create(N, C.byref(h)), "render_ctx_create")
+            _lib.call("render_ctx_create", N, C.byref(h))
             ent = [h, N]
             with self._ctx_lock:
                 self._ctxs[key] = ent
@@ -364,18 +357,15 @@ class FusedModel:
         last_c = torch.empty(N + 128, 3, dtype=torch.float32, device=dev) if want_last else None
         stats = _lib.RenderStats()
         m = self._struct(bitfield)
-        lib = _lib.lib()
         ctx = self._context(N)
         need_stats = want_stats or want_last
-        _lib.check(lib.ngp_render_ctx_set_frame_width(ctx, int(frame_width or 0)), "render_ctx_set_frame_width")
+        _lib.call("render_ctx_set_frame_width", ctx, int(frame_width or 0))
         if self.debug is not None:
             flags, stamps, hashes = self.debug
-            _lib.check(lib.ngp_render_ctx_set_debug(ctx, 1, int(flags), _lib.ptr(stamps), _lib.ptr(hashes)), "render_ctx_set_debug")
-        _lib.check(lib.ngp_render_rays(ctx, C.byref(m), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears.contiguous()),
-                                       _lib.ptr(fars.contiguous()), N, float(dt_gamma), int(max_steps), int(perturb), _lib.ptr(weights_sum),
-                                       _lib.ptr(depth), _lib.ptr(image), _lib.ptr(last_s), _lib.ptr(last_c),
-                                       self._pad_value() if want_last else None, C.byref(stats) if need_stats else None, 0, _lib.stream()),
-                   "render_rays")
+            _lib.call("render_ctx_set_debug", ctx, 1, int(flags), stamps, hashes)
+        _lib.call("render_rays", ctx, C.byref(m), rays_o, rays_d, nears.contiguous(), fars.contiguous(), N, float(dt_gamma), int(max_steps),
+                  int(perturb), weights_sum, depth, image, last_s, last_c, self._pad_value() if want_last else None,
+                  C.byref(stats) if need_stats else None, 0)
         sigmas = rgbs = None
         if need_stats:
             self._tls.stats = {"samples_marched": int(stats.samples_marched), "samples_slots": int(stats.samples_slots),
@@ -400,10 +390,8 @@ class FusedModel:
         sigmas = torch.empty(n_dump * T, 1, dtype=torch.float32, device=dev)
         rgbs = torch.empty(n_dump, T, 3, dtype=torch.float32, device=dev)
         m = self._struct(None)
-        lib = _lib.lib()
-        _lib.check(lib.ngp_render_uniform(C.byref(m), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears.contiguous()), _lib.ptr(fars.contiguous()),
-                                          N, T, _lib.ptr(lin), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
-                                          dump_begin, _lib.ptr(sigmas), _lib.ptr(rgbs), int(frame_width or 0), _lib.stream()), "render_uniform")
+        _lib.call("render_uniform", C.byref(m), rays_o, rays_d, nears.contiguous(), fars.contiguous(), N, T, lin, out[0], out[1], out[2],
+                  out[3], dump_begin, sigmas, rgbs, int(frame_width or 0))
         return out[0], out[1], out[2], out[3], sigmas, rgbs
 
     def _linspace(self, lo, hi, n):
@@ -438,20 +426,15 @@ class FusedModel:
         sigmas = torch.empty(n_dump * (T + U), 1, dtype=torch.float32, device=dev)
         rgbs = torch.empty(n_dump, T + U, 3, dtype=torch.float32, device=dev)
         m = self._struct(None)
-        lib = _lib.lib()
-        wbytes = lib.ngp_render_upsample_workspace(N, T, U)
-        work = torch.empty((wbytes + 3) // 4, dtype=torch.float32, device=dev) if wbytes else None
-        _lib.check(lib.ngp_render_upsample(C.byref(m), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears.contiguous()), _lib.ptr(fars.contiguous()),
-                                           N, T, U, _lib.ptr(lin), _lib.ptr(u), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
-                                           _lib.ptr(out[3]), dump_begin, _lib.ptr(sigmas), _lib.ptr(rgbs), int(frame_width or 0), _lib.ptr(work), wbytes,
-                                           _lib.stream()), "render_upsample")
+        work, wbytes = _lib.workspace("render_upsample", N, T, U, device=dev)
+        _lib.call("render_upsample", C.byref(m), rays_o, rays_d, nears.contiguous(), fars.contiguous(), N, T, U, lin, u, out[0], out[1],
+                  out[2], out[3], dump_begin, sigmas, rgbs, int(frame_width or 0), work, wbytes)
         return out[0], out[1], out[2], out[3], sigmas, rgbs
 
     def render_uniform_backward(self, rays_o, rays_d, nears, fars, num_steps, g_image, g_depth=None, g_ws=None, g_agg=None):
         """vector-Jacobian product of render_uniform w.r.t. the rays, map frozen (ngp_render_uniform_backward): upstream gradients of
         image (before the background mix) [N,3], depth / weights_sum / aggregated_density [N] (None = zero) -> grad_rays_o, grad_rays_d"""
         self._ensure_cells()
-        lib = _lib.lib()
         self._ensure_packed_bwd()
         N, T, dev = rays_o.shape[0], int(num_steps), rays_o.device
         lin = self._linspace(0.0, 1.0, T)
@@ -459,10 +442,8 @@ class FusedModel:
         go = torch.empty(N, 3, dtype=torch.float32, device=dev)
         gd = torch.empty(N, 3, dtype=torch.float32, device=dev)
         m = self._struct(None)
-        _lib.check(lib.ngp_render_uniform_backward(C.byref(m), _lib.ptr(self._packed_bwd), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears.contiguous()),
-                                                   _lib.ptr(fars.contiguous()), N, T, _lib.ptr(lin), _lib.ptr(f32(g_image)), _lib.ptr(f32(g_depth)),
-                                                   _lib.ptr(f32(g_ws)), _lib.ptr(f32(g_agg)), _lib.ptr(go), _lib.ptr(gd), _lib.stream()),
-                   "render_uniform_backward")
+        _lib.call("render_uniform_backward", C.byref(m), self._packed_bwd, rays_o, rays_d, nears.contiguous(), fars.contiguous(), N, T, lin,
+                  f32(g_image), f32(g_depth), f32(g_ws), f32(g_agg), go, gd)
         return go, gd
 
     def uniform_backward_fits(self, num_steps):

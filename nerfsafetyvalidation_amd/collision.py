@@ -270,14 +270,11 @@ def label_components_numpy(occ, connectivity=26):
 def _label_components_hip(occ, connectivity):
     m = (occ != 0).to(torch.uint8).contiguous()
     X, Y, Z = m.shape
-    lib = _lib.lib()
     with torch.cuda.device(m.device):
         labels = torch.empty(X, Y, Z, dtype=torch.int32, device=m.device)
         n_dev = torch.empty(1, dtype=torch.int32, device=m.device)
-        ws_bytes = lib.ngp_label_components_workspace(X, Y, Z)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)
-        _lib.check(lib.ngp_label_components(_lib.ptr(m), X, Y, Z, connectivity, _lib.ptr(labels), _lib.ptr(n_dev), _lib.ptr(ws), ws_bytes,
-                                            _lib.stream()), "label_components")
+        ws, ws_bytes = _lib.workspace("label_components", X, Y, Z, device=m.device)
+        _lib.call("label_components", m, X, Y, Z, connectivity, labels, n_dev, ws, ws_bytes)
         n = int(n_dev.item())          # the call's one host read
     if n < 0:
         raise RuntimeError(f"label_components: a device loop reached its bound in stage '{_STAGES.get(n, n)}'; the labels are not valid")
@@ -350,8 +347,7 @@ def component_table(labels, n, truth=None):
         cells = torch.empty(n, dtype=torch.int64, device=dev)
         lo, hi = torch.empty(n, 3, dtype=torch.int32, device=dev), torch.empty(n, 3, dtype=torch.int32, device=dev)
         overlap = None if truth is None else torch.empty(n, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib().ngp_component_stats(_lib.ptr(lab), X, Y, Z, n, _lib.ptr(marks), _lib.ptr(cells), _lib.ptr(lo), _lib.ptr(hi),
-                                                  _lib.ptr(overlap), _lib.stream()), "component_stats")
+        _lib.call("component_stats", lab, X, Y, Z, n, marks, cells, lo, hi, overlap)
     return ComponentTable(cells, lo, hi, overlap)
 
 
@@ -452,11 +448,9 @@ def edt_sq(occ):
     dev = occ.device if occ.is_cuda else torch.device("cuda", torch.cuda.current_device())
     m = occ.to(dev, torch.uint8).contiguous()
     X, Y, Z = m.shape
-    lib = _lib.lib()
     d2 = torch.empty(X, Y, Z, dtype=torch.int32, device=dev)
-    ws_bytes = lib.ngp_edt_sq_workspace(X, Y, Z)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _lib.check(lib.ngp_edt_sq(_lib.ptr(m), X, Y, Z, _lib.ptr(d2), _lib.ptr(ws), ws_bytes, _lib.stream()), "edt_sq")
+    ws, ws_bytes = _lib.workspace("edt_sq", X, Y, Z, device=dev)
+    _lib.call("edt_sq", m, X, Y, Z, d2, ws, ws_bytes)
     return d2
 
 

@@ -259,7 +259,7 @@ using namespace ngp;
 extern "C" {
 
 const char* ngp_last_error(void) { return g_err; }
-int ngp_version(void) { return 100; }
+int ngp_version(void) { return NGP_ABI_VERSION; }
 
 int ngp_device_count(void) {
     int n = 0;

@@ -18,15 +18,8 @@ RECOMPUTE_ACTIVATIONS = True     # (this build; False: keep forward_buffer as th
 
 def launch_forward(inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, forward_buffer, outputs, planes=False):
     """planes: inputs are level planes (ngp_ffmlp_forward_planes); forward_buffer None: no activations kept (row inputs: the inference call)"""
-    lib = _lib.lib()
-    if planes:
-        fn, what = lib.ngp_ffmlp_forward_planes, "ffmlp_forward_planes"
-    elif forward_buffer is not None:
-        fn, what = lib.ngp_ffmlp_forward, "ffmlp_forward"
-    else:
-        fn, what = lib.ngp_ffmlp_inference, "ffmlp_inference"
-    _lib.check(fn(_lib.ptr(inputs), _lib.ptr(weights), B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation,
-                  _lib.ptr(forward_buffer), _lib.ptr(outputs), _lib.stream()), what)
+    name = "ffmlp_forward_planes" if planes else "ffmlp_forward" if forward_buffer is not None else "ffmlp_inference"
+    _lib.call(name, inputs, weights, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, forward_buffer, outputs)
 
 
 def launch_backward(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation, output_activation, calc_grad_inputs, planes=False):
@@ -39,12 +32,9 @@ def launch_backward(grad, inputs, weights, forward_buffer, B, input_dim, output_
     backward_buffer = torch.empty(num_layers, B, hidden_dim, device=grad.device, dtype=grad.dtype) if bbytes else None
     # split-K partials of the weight gradients: this call's own scratch from torch's (stream-aware) caching allocator, so
     # backward passes running concurrently on other streams never share it
-    wbytes = lib.ngp_ffmlp_backward_workspace(B, input_dim, hidden_dim, num_layers)
-    work = torch.empty((wbytes + 3) // 4, dtype=torch.float32, device=grad.device)
-    fn = lib.ngp_ffmlp_backward_planes if planes else lib.ngp_ffmlp_backward
-    _lib.check(fn(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(weights), _lib.ptr(forward_buffer), B, input_dim, output_dim, hidden_dim, num_layers, activation,
-                  output_activation, int(calc_grad_inputs), _lib.ptr(backward_buffer), _lib.ptr(grad_inputs), _lib.ptr(grad_weights), _lib.ptr(work), wbytes,
-                  _lib.stream()), "ffmlp_backward")
+    work, wbytes = _lib.workspace("ffmlp_backward", B, input_dim, hidden_dim, num_layers, device=grad.device)
+    _lib.call("ffmlp_backward_planes" if planes else "ffmlp_backward", grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim,
+              num_layers, activation, output_activation, int(calc_grad_inputs), backward_buffer, grad_inputs, grad_weights, work, wbytes)
     return grad_inputs, grad_weights
 
 
@@ -113,10 +103,10 @@ class FFMLP(nn.Module):
         self.num_parameters = hidden_dim * (input_dim + hidden_dim * (num_layers - 1) + self.padded_output_dim)
         self.weights = nn.Parameter(torch.zeros(self.num_parameters))
         self.reset_parameters()
-        _lib.check(_lib.lib().ngp_ffmlp_allocate_splitk(self.num_layers + 1), "allocate_splitk")
+        _lib.call("ffmlp_allocate_splitk", self.num_layers + 1)
 
     def cleanup(self):
-        _lib.check(_lib.lib().ngp_ffmlp_free_splitk(), "free_splitk")
+        _lib.call("ffmlp_free_splitk")
 
     def __repr__(self):
         return (f"FFMLP: input_dim={self.input_dim} output_dim={self.output_dim} hidden_dim={self.hidden_dim} "

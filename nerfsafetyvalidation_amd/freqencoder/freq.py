@@ -17,8 +17,7 @@ class _freq_encoder(Function):
         if output_dim != input_dim + 2 * input_dim * degree:
             raise ValueError(f"freq_encode: output_dim {output_dim} is not input_dim (1 + 2 degree) = {input_dim + 2 * input_dim * degree}")
         outputs = torch.empty(B, output_dim, dtype=inputs.dtype, device=inputs.device)
-        _lib.check(_lib.lib().ngp_freq_encode_forward(_lib.ptr(inputs), _lib.ptr(outputs), B, input_dim, degree, _lib.stream()),
-                   "freq_encode_forward")
+        _lib.call("freq_encode_forward", inputs, outputs, B, input_dim, degree)
         # the inputs alone: the backward recomputes sin / cos from them (the reference keeps the [B, output_dim] outputs, freq.py:31)
         ctx.save_for_backward(inputs)
         ctx.dims = [B, input_dim, degree]
@@ -33,8 +32,7 @@ class _freq_encoder(Function):
         (inputs,) = ctx.saved_tensors
         B, input_dim, degree = ctx.dims
         grad_inputs = torch.empty_like(inputs)  # written, not accumulated
-        _lib.check(_lib.lib().ngp_freq_encode_backward(_lib.ptr(grad), _lib.ptr(inputs), B, input_dim, degree, _lib.ptr(grad_inputs),
-                                                       _lib.stream()), "freq_encode_backward")
+        _lib.call("freq_encode_backward", grad, inputs, B, input_dim, degree, grad_inputs)
         return grad_inputs, None, None
 
 

@@ -83,7 +83,7 @@ class DerivedTables:
             nbytes = lib.ngp_cell_tables_bytes(C.byref(m), 12)
             if 0 < nbytes <= min(budget_gb * (1 << 30), free / 3):
                 cells = torch.empty(nbytes, dtype=torch.uint8, device=self.emb16.device)
-                _lib.check(lib.ngp_build_cell_tables(C.byref(m), 12, _lib.ptr(cells), _lib.stream()), "build_cell_tables")
+                _lib.call("build_cell_tables", C.byref(m), 12, cells)
                 torch.cuda.current_stream(self.emb16.device).synchronize()   # other streams may read it next
                 for sid in self._streams:                                    # (streams that already use the table will read the records too)
                     if sid != torch.cuda.current_stream(self.emb16.device).cuda_stream:
@@ -144,30 +144,25 @@ def _table_for_call(embeddings, offsets, B, D, C, L, S, H, gridtype, align_corne
 def launch_forward(inputs, embeddings, offsets_host, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners, cells, cell_levels, strides=None):
     """The native forward call.  outputs: the operator's level-major [L, B, C], or, with strides = (level_stride, point_stride) in
     elements, wherever those put a (level, point) pair (ngp_grid_encode_forward_strided).  dy_dx None: no input gradient is prepared."""
-    lib, calc, code = _lib.lib(), int(dy_dx is not None), _lib.dtype_code(embeddings)
+    calc, code = int(dy_dx is not None), _lib.dtype_code(embeddings)
+    args = (inputs, embeddings, offsets_host, outputs, B, D, C, L, S, H, calc, dy_dx, gridtype, int(align_corners), code, cells, cell_levels)
     if strides is None:
-        rc = lib.ngp_grid_encode_forward(_lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(outputs), B, D, C, L, S, H, calc, _lib.ptr(dy_dx),
-                                         gridtype, int(align_corners), code, _lib.ptr(cells), cell_levels, _lib.stream())
+        _lib.call("grid_encode_forward", *args)
     else:
-        rc = lib.ngp_grid_encode_forward_strided(_lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(outputs), B, D, C, L, S, H, calc, _lib.ptr(dy_dx),
-                                                 gridtype, int(align_corners), code, _lib.ptr(cells), cell_levels, strides[0], strides[1], _lib.stream())
-    _lib.check(rc, "grid_encode_forward")
+        _lib.call("grid_encode_forward_strided", *args, strides[0], strides[1])
 
 
 def launch_backward(grad, inputs, embeddings, offsets_host, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners, strides=None):
     """The native backward call, `grad` laid out as launch_forward's outputs.  grad_embeddings None: frozen table; dy_dx and grad_inputs None: no
     input gradient.  The scratch of the binned table-gradient scatter (large fp16 batches only) is this call's own, from torch's stream-aware allocator."""
-    lib, calc, code = _lib.lib(), int(grad_inputs is not None), _lib.dtype_code(embeddings)
-    wbytes = lib.ngp_grid_encode_backward_workspace(B, D, C, L, code) if grad_embeddings is not None else 0
-    work = torch.empty(wbytes, dtype=torch.uint8, device=grad.device) if wbytes else None
+    calc, code = int(grad_inputs is not None), _lib.dtype_code(embeddings)
+    work, wbytes = _lib.workspace("grid_encode_backward", B, D, C, L, code, device=grad.device) if grad_embeddings is not None else (None, 0)
+    args = (grad, inputs, embeddings, offsets_host, grad_embeddings, B, D, C, L, S, H, calc, dy_dx, grad_inputs, gridtype, int(align_corners), code,
+            work, wbytes)
     if strides is None:
-        rc = lib.ngp_grid_encode_backward(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(grad_embeddings), B, D, C, L, S, H, calc,
-                                          _lib.ptr(dy_dx), _lib.ptr(grad_inputs), gridtype, int(align_corners), code, _lib.ptr(work), wbytes, _lib.stream())
+        _lib.call("grid_encode_backward", *args)
     else:
-        rc = lib.ngp_grid_encode_backward_strided(_lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings), offsets_host, _lib.ptr(grad_embeddings), B, D, C, L, S, H,
-                                                  calc, _lib.ptr(dy_dx), _lib.ptr(grad_inputs), gridtype, int(align_corners), code, _lib.ptr(work), wbytes,
-                                                  strides[0], strides[1], _lib.stream())
-    _lib.check(rc, "grid_encode_backward")
+        _lib.call("grid_encode_backward_strided", *args, strides[0], strides[1])
 
 
 class _grid_encode(Function):

@@ -87,12 +87,8 @@ class _DistLossHIP(Function):
         loss_rays = torch.zeros(B, dtype=torch.float32, device=dev)
         totals = torch.zeros(B, 2, dtype=torch.float32, device=dev)
         loss = torch.zeros((), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        nbytes = L.ngp_distortion_workspace(B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        _lib.check(L.ngp_distortion_forward(_lib.ptr(w2), _lib.ptr(m2), _lib.ptr(iv), float(interval_scalar), _lib.ptr(rays), B * T, B,
-                                            _lib.ptr(loss_rays), _lib.ptr(totals), _lib.ptr(loss), _lib.ptr(ws), nbytes, _lib.stream()),
-                   "distortion_forward")
+        ws, nbytes = _lib.workspace("distortion", B, device=dev)
+        _lib.call("distortion_forward", w2, m2, iv, float(interval_scalar), rays, B * T, B, loss_rays, totals, loss, ws, nbytes)
         ctx.save_for_backward(w2, m2, iv, rays, totals)
         ctx.interval_scalar, ctx.shape = float(interval_scalar), w.shape
         return loss
@@ -103,9 +99,7 @@ class _DistLossHIP(Function):
         w2, m2, iv, rays, totals = ctx.saved_tensors
         B, T = w2.shape
         grad_w = torch.empty_like(w2)               # every row belongs to a ray and every sample is live: all of it is written
-        _lib.check(_lib.lib().ngp_distortion_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(w2), _lib.ptr(m2), _lib.ptr(iv),
-                                                      ctx.interval_scalar, _lib.ptr(rays), _lib.ptr(totals), B * T, B, _lib.ptr(grad_w),
-                                                      _lib.stream()), "distortion_backward")
+        _lib.call("distortion_backward", grad_loss.float().contiguous(), w2, m2, iv, ctx.interval_scalar, rays, totals, B * T, B, grad_w)
         return grad_w.view(ctx.shape), None, None, None
 
 
@@ -152,12 +146,9 @@ class _DepthLossHIP(Function):
         loss_rays = torch.zeros(B, dtype=torch.float32, device=dev)
         parts = torch.zeros(B, 2, dtype=torch.float32, device=dev)
         loss = torch.zeros((), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        nbytes = L.ngp_depth_loss_workspace(B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        _lib.check(L.ngp_depth_loss_forward(_lib.ptr(w2), _lib.ptr(t2), _lib.ptr(rays), _lib.ptr(z), _lib.ptr(sc), margin, weight_depth,
-                                            weight_free, B * T, B, _lib.ptr(loss_rays), _lib.ptr(parts), _lib.ptr(loss), _lib.ptr(ws), nbytes,
-                                            _lib.stream()), "depth_loss_forward")
+        ws, nbytes = _lib.workspace("depth_loss", B, device=dev)
+        _lib.call("depth_loss_forward", w2, t2, rays, z, sc, margin, weight_depth, weight_free, B * T, B, loss_rays, parts, loss, ws,
+                  nbytes)
         ctx.save_for_backward(w2, t2, rays, z, sc, parts)
         ctx.consts, ctx.shape = (margin, weight_depth, weight_free), w.shape
         return loss
@@ -168,9 +159,7 @@ class _DepthLossHIP(Function):
         w2, t2, rays, z, sc, parts = ctx.saved_tensors
         B, T = w2.shape
         grad_w = torch.zeros_like(w2)               # the rows of a ray without a measurement are not written
-        _lib.check(_lib.lib().ngp_depth_loss_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(w2), _lib.ptr(t2), _lib.ptr(rays),
-                                                      _lib.ptr(z), _lib.ptr(sc), *ctx.consts, _lib.ptr(parts), B * T, B, _lib.ptr(grad_w),
-                                                      _lib.stream()), "depth_loss_backward")
+        _lib.call("depth_loss_backward", grad_loss.float().contiguous(), w2, t2, rays, z, sc, *ctx.consts, parts, B * T, B, grad_w)
         return grad_w.view(ctx.shape), None, None, None, None, None, None
 
 

@@ -200,14 +200,11 @@ def _isosurface_hip(u, threshold):
         raise ValueError(f"isosurface: X * Y * Z must be < 2^31 (got {u.numel()})")
     u = u.to(torch.float32).contiguous()
     X, Y, Z = u.shape
-    lib = _lib.lib()
     with torch.cuda.device(u.device):
-        ws_bytes = lib.ngp_isosurface_workspace(X, Y, Z)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device)
+        ws, ws_bytes = _lib.workspace("isosurface", X, Y, Z, device=u.device)
         state = torch.empty(3, dtype=torch.int64, device=u.device)      # V, F, any(+-inf): one host read for all three
         state[2] = torch.isinf(u).any()
-        _lib.check(lib.ngp_isosurface_count(_lib.ptr(u), X, Y, Z, float(threshold), _lib.ptr(ws), ws_bytes, _lib.ptr(state), _lib.stream()),
-                   "isosurface_count")
+        _lib.call("isosurface_count", u, X, Y, Z, float(threshold), ws, ws_bytes, state)
         V, F, bad = (int(v) for v in state.tolist())
         if bad:
             raise ValueError("isosurface: the field holds +-inf")
@@ -216,8 +213,7 @@ def _isosurface_hip(u, threshold):
         vertices = torch.empty(V, 3, dtype=torch.float32, device=u.device)
         faces = torch.empty(F, 3, dtype=torch.int32, device=u.device)
         if V or F:
-            _lib.check(lib.ngp_isosurface_emit(_lib.ptr(u), X, Y, Z, float(threshold), _lib.ptr(ws), ws_bytes, V, F, _lib.ptr(vertices),
-                                               _lib.ptr(faces), _lib.stream()), "isosurface_emit")
+            _lib.call("isosurface_emit", u, X, Y, Z, float(threshold), ws, ws_bytes, V, F, vertices, faces)
     return vertices, faces
 
 
@@ -461,11 +457,8 @@ def distance_stats(distance, thresholds=(), splits=()):
         for a, b in zip(cuts[:-1], cuts[1:]):
             if b - a >= 2 ** 31:
                 raise ValueError("distance_stats: fewer than 2^31 distances per launch; pass splits")
-            nbytes = lib.ngp_distance_stats_workspace(b - a)
-            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=d.device)
-            part = d[a:b]
-            _lib.check(lib.ngp_distance_stats(_lib.ptr(part) if b > a else None, b - a, a, th_c, len(th), _lib.ptr(state), _lib.ptr(stats),
-                                              _lib.ptr(ws), nbytes, _lib.stream()), "distance_stats")
+            ws, nbytes = _lib.workspace("distance_stats", b - a, device=d.device)
+            _lib.call("distance_stats", d[a:b] if b > a else None, b - a, a, th_c, len(th), state, stats, ws, nbytes)
     out = stats.cpu().tolist()
     return {"n": n, "finite": int(out[0]), "sum": out[1], "sum_sq": out[2], "max": out[3], "within": tuple(int(c) for c in out[4:4 + len(th)])}
 

@@ -27,15 +27,13 @@ def sift_interest_mask(img_rgb, kernel_size=5, dil_iter=3, device=None, return_p
     rgb = _frame(img_rgb, device)
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     lib = _lib.lib()
-    ws_bytes = lib.ngp_sift_workspace(H, W)
-    if ws_bytes == 0:
+    ws, ws_bytes = _lib.workspace("sift", H, W, device=rgb.device)
+    if ws is None:
         raise ValueError(f"features: unsupported frame size {H} x {W} (each side in [8, 16384], 20 H W < 2^32)")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=rgb.device)
     points = torch.empty(W, H, dtype=torch.uint8, device=rgb.device)
     mask = torch.empty(W, H, dtype=torch.uint8, device=rgb.device)
     count = torch.empty(1, dtype=torch.int32, device=rgb.device)
-    _lib.check(lib.ngp_sift_interest_mask(_lib.ptr(rgb), H, W, int(kernel_size), int(dil_iter), _lib.ptr(points), _lib.ptr(mask),
-                                          _lib.ptr(count), _lib.ptr(ws), ws_bytes, _lib.stream()), "sift_interest_mask")
+    _lib.call("sift_interest_mask", rgb, H, W, int(kernel_size), int(dil_iter), points, mask, count, ws, ws_bytes)
     out = {"points": points, "mask": mask, "count": count}
     if return_pyramid:
         pyr = []

@@ -19,8 +19,7 @@ from .renderer import NeRFRenderer
 def _launch_sigma_color_input(h, dirs, B):
     sigma = torch.empty(B, dtype=torch.float32, device=h.device)
     cin = torch.empty(h.shape[0], 32, dtype=torch.float16, device=h.device)
-    _lib.check(_lib.lib().ngp_ff_sigma_color_input(_lib.ptr(h), _lib.ptr(dirs), B, h.shape[0], _lib.ptr(sigma), _lib.ptr(cin), _lib.stream()),
-               "ff_sigma_color_input")
+    _lib.call("ff_sigma_color_input", h, dirs, B, h.shape[0], sigma, cin)
     return sigma, cin
 
 
@@ -28,20 +27,19 @@ def _launch_sigma_color_input_backward(h, g_sigma, g_cin, B):
     g_sigma = g_sigma.contiguous().float() if g_sigma is not None else None
     g_cin = g_cin.contiguous().half() if g_cin is not None else None
     g_h = torch.empty_like(h)
-    _lib.check(_lib.lib().ngp_ff_sigma_color_input_backward(_lib.ptr(h), _lib.ptr(g_sigma), _lib.ptr(g_cin), B, h.shape[0], _lib.ptr(g_h),
-                                                            _lib.stream()), "ff_sigma_color_input_backward")
+    _lib.call("ff_sigma_color_input_backward", h, g_sigma, g_cin, B, h.shape[0], g_h)
     return g_h
 
 
 def _launch_rgb(o16, B):
     rgb = torch.empty(B, 3, dtype=torch.float16, device=o16.device)
-    _lib.check(_lib.lib().ngp_ff_rgb(_lib.ptr(o16), B, _lib.ptr(rgb), _lib.stream()), "ff_rgb")
+    _lib.call("ff_rgb", o16, B, rgb)
     return rgb
 
 
 def _launch_rgb_backward(g, rgb, B_pad):
     g_o = torch.empty(B_pad, 16, dtype=torch.float16, device=rgb.device)
-    _lib.check(_lib.lib().ngp_ff_rgb_backward(_lib.ptr(g.contiguous().half()), _lib.ptr(rgb), rgb.shape[0], B_pad, _lib.ptr(g_o), _lib.stream()), "ff_rgb_backward")
+    _lib.call("ff_rgb_backward", g.contiguous().half(), rgb, rgb.shape[0], B_pad, g_o)
     return g_o
 
 

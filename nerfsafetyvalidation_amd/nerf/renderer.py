@@ -104,9 +104,9 @@ class NeRFRenderer(nn.Module):
 
     def invalidate_fused(self):
         """Drop the fused renderer's fp16 snapshot of the parameters (table, weight blobs, per-cell records).  The snapshot is
-        keyed on the parameters' (data_ptr, _version) -- every torch in-place op and this package's Adam bump it -- but writes
-        through `.data` (torch_ema's copy_to / restore in the reference Trainer, nerf/utils.py:846-850,932-933) or raw pointers do
-        not: call this after such a write.  Entering training mode and load_state_dict call it themselves."""
+        keyed on the parameters' (data_ptr, _version) -- every torch in-place op and every write of this package's library calls
+        (_lib.call's `wrote=`) bump it -- but a caller's writes through `.data` (torch_ema's copy_to / restore in the reference
+        Trainer, nerf/utils.py:846-850,932-933) do not: call this after such a write.  Entering training mode and load_state_dict call it themselves."""
         from .. import _fused
         from ..gridencoder.grid import invalidate_derived
         with _fused.CACHE_LOCK:
@@ -331,8 +331,7 @@ class NeRFRenderer(nn.Module):
         if bg3 is not None and not self.training and not torch.is_grad_enabled() and image.is_cuda and image.dtype == torch.float32:
             # the two lines below in one launch, in place (image / depth are this call's own tensors): same operations, same roundings
             image, depth, acc = image.contiguous(), depth.contiguous(), acc.contiguous()
-            _lib.check(_lib.lib().ngp_finish_rays(_lib.ptr(image), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(nears.contiguous()),
-                                                  _lib.ptr(fars.contiguous()), bg3, image.shape[0], _lib.stream()), "finish_rays")
+            _lib.call("finish_rays", image, depth, acc, nears.contiguous(), fars.contiguous(), bg3, image.shape[0])
         else:
             image = image + (1 - acc).unsqueeze(-1) * backdrop
             depth = (depth - nears).clamp(min=0) / (fars - nears)    # renderer.py:326 / :376
@@ -341,8 +340,7 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------ density grid maintenance (renderer.py:388-544)
     def _grid_workspace(self):
-        nbytes = _lib.lib().ngp_density_grid_workspace(self.cascade, self.grid_size)
-        return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.density_grid.device), nbytes
+        return _lib.workspace("density_grid", self.cascade, self.grid_size, device=self.density_grid.device)
 
     @torch.no_grad()
     def mark_untrained_grid(self, poses, intrinsic, S=64):
@@ -355,8 +353,8 @@ class NeRFRenderer(nn.Module):
         cams = torch.as_tensor(np.asarray(poses) if not torch.is_tensor(poses) else poses, dtype=torch.float32).to(device).contiguous()
         fx, fy, cx, cy = [float(v) for v in intrinsic]
         work, nbytes = self._grid_workspace()
-        _lib.check(_lib.lib().ngp_mark_untrained_grid(_lib.ptr(cams), cams.shape[0], fx, fy, cx, cy, float(self.bound), self.cascade, self.grid_size,
-                                                      _lib.ptr(self.density_grid), _lib.ptr(work), nbytes, _lib.stream()), "mark_untrained_grid")
+        _lib.call("mark_untrained_grid", cams, cams.shape[0], fx, fy, cx, cy, float(self.bound), self.cascade, self.grid_size,
+                  self.density_grid, work, nbytes, wrote=(self.density_grid,))
 
     def _grid_sigmas(self, points):
         """density of the grid's sample points [n,3] -> sigma [n] f32: the fused encode + sigma-net kernel when the model has one
@@ -377,7 +375,7 @@ class NeRFRenderer(nn.Module):
         sigma, two launches apply it; mean, threshold and the bitfield follow without a host round trip."""
         if not self.cuda_ray:
             return
-        lib, H, device = _lib.lib(), self.grid_size, self.density_grid.device
+        H, device = self.grid_size, self.density_grid.device
         work, nbytes = self._grid_workspace()
         sweep = self.iter_density < 16
         for cas in range(self.cascade):
@@ -393,15 +391,13 @@ class NeRFRenderer(nn.Module):
             noise = _Draws.jitter(n, device).float().contiguous()
             points = torch.empty(n, 3, dtype=torch.float32, device=device)
             cells = torch.empty(n, dtype=torch.int32, device=device)
-            _lib.check(lib.ngp_density_grid_points(_lib.ptr(coords), n, H, float(min(2 ** cas, self.bound)), _lib.ptr(noise), _lib.ptr(points),
-                                                   _lib.ptr(cells), _lib.stream()), "density_grid_points")
+            _lib.call("density_grid_points", coords, n, H, float(min(2 ** cas, self.bound)), noise, points, cells)
             sigmas = self._grid_sigmas(points)
-            _lib.check(lib.ngp_density_grid_update(_lib.ptr(self.density_grid), self.cascade, H, cas, _lib.ptr(cells), _lib.ptr(sigmas), n,
-                                                   float(self.density_scale), float(decay), _lib.ptr(work), nbytes, _lib.stream()),
-                       "density_grid_update")
+            _lib.call("density_grid_update", self.density_grid, self.cascade, H, cas, cells, sigmas, n, float(self.density_scale),
+                      float(decay), work, nbytes, wrote=(self.density_grid,))
         mean_thresh = torch.empty(2, dtype=torch.float32, device=device)
-        _lib.check(lib.ngp_density_grid_finish(_lib.ptr(self.density_grid), self.cascade, H, float(self.density_thresh), _lib.ptr(mean_thresh),
-                                               _lib.ptr(self.density_bitfield), _lib.ptr(work), nbytes, _lib.stream()), "density_grid_finish")
+        _lib.call("density_grid_finish", self.density_grid, self.cascade, H, float(self.density_thresh), mean_thresh, self.density_bitfield,
+                  work, nbytes, wrote=(self.density_grid, self.density_bitfield))
         self.mean_density = mean_thresh[0].item()                                  # the one synchronisation (:533)
         self.iter_density += 1
 

@@ -29,8 +29,7 @@ def _rays_backward(ctx, grad_xyzs):
     rays_o, rays_d, z_vals = ctx.saved_tensors
     N, T = z_vals.shape
     go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
-    _lib.check(_lib.lib().ngp_uniform_samples_backward(_lib.ptr(grad_xyzs.float().contiguous()), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z_vals),
-                                                       N, T, ctx.box, _lib.ptr(go), _lib.ptr(gd), _lib.stream()), "uniform_samples_backward")
+    _lib.call("uniform_samples_backward", grad_xyzs.float().contiguous(), rays_o, rays_d, z_vals, N, T, ctx.box, go, gd)
     return go, gd
 
 
@@ -42,8 +41,7 @@ class _UniformSamples(Function):
         ctx.box = _aabb_host(aabb)
         z_vals = torch.empty(N, T, dtype=torch.float32, device=rays_o.device)
         xyzs = torch.empty(N, T, 3, dtype=torch.float32, device=rays_o.device)
-        _lib.check(_lib.lib().ngp_uniform_samples(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(nears), _lib.ptr(fars), N, T, T, _lib.ptr(lin),
-                                                  _lib.ptr(noise), None, ctx.box, _lib.ptr(z_vals), _lib.ptr(xyzs), _lib.stream()), "uniform_samples")
+        _lib.call("uniform_samples", rays_o, rays_d, nears, fars, N, T, T, lin, noise, None, ctx.box, z_vals, xyzs)
         ctx.save_for_backward(rays_o, rays_d, z_vals)
         ctx.mark_non_differentiable(z_vals)        # nears / fars come from a no_grad block in the reference (:141): constants
         return z_vals, xyzs
@@ -61,8 +59,7 @@ class _SamplesAt(Function):
         N, T = z_vals.shape
         ctx.box = _aabb_host(aabb)
         xyzs = torch.empty(N, T, 3, dtype=torch.float32, device=rays_o.device)
-        _lib.check(_lib.lib().ngp_uniform_samples(_lib.ptr(rays_o), _lib.ptr(rays_d), None, None, N, T, 0, None, None, _lib.ptr(z_vals), ctx.box, None,
-                                                  _lib.ptr(xyzs), _lib.stream()), "uniform_samples")
+        _lib.call("uniform_samples", rays_o, rays_d, None, None, N, T, 0, None, None, z_vals, ctx.box, None, xyzs)
         ctx.save_for_backward(rays_o, rays_d, z_vals)
         return xyzs
 
@@ -91,8 +88,7 @@ class _TransmittanceWeights(Function):
         z_vals, sigmas, sample_dist = z_vals.float().contiguous(), sigmas.float().contiguous(), sample_dist.float().contiguous()
         N, T = z_vals.shape
         weights = torch.empty(N, T, dtype=torch.float32, device=z_vals.device)
-        _lib.check(_lib.lib().ngp_transmittance_weights(_lib.ptr(z_vals), _lib.ptr(sigmas), _lib.ptr(sample_dist), N, T, float(density_scale),
-                                                        _lib.ptr(weights), _lib.stream()), "transmittance_weights")
+        _lib.call("transmittance_weights", z_vals, sigmas, sample_dist, N, T, float(density_scale), weights)
         ctx.save_for_backward(z_vals, sigmas, sample_dist)
         ctx.density_scale = float(density_scale)
         return weights
@@ -102,9 +98,7 @@ class _TransmittanceWeights(Function):
         z_vals, sigmas, sample_dist = ctx.saved_tensors
         N, T = z_vals.shape
         gs = torch.empty_like(sigmas)
-        _lib.check(_lib.lib().ngp_transmittance_weights_backward(_lib.ptr(grad_w.float().contiguous()), _lib.ptr(z_vals), _lib.ptr(sigmas),
-                                                                 _lib.ptr(sample_dist), N, T, ctx.density_scale, _lib.ptr(gs), _lib.stream()),
-                   "transmittance_weights_backward")
+        _lib.call("transmittance_weights_backward", grad_w.float().contiguous(), z_vals, sigmas, sample_dist, N, T, ctx.density_scale, gs)
         return None, gs, None, None
 
 
@@ -126,8 +120,7 @@ def sample_pdf(bins, weights, n_samples, det=False):
         # sorted draws: the same set of samples as the reference's unsorted ones (it sorts them right after, :187), already in order
         u = torch.rand(N, n_samples, device=dev).sort(dim=-1).values.contiguous()
     out = torch.empty(N, n_samples, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().ngp_sample_pdf(_lib.ptr(bins), _lib.ptr(weights), N, Tb, _lib.ptr(u), 0 if det else 1, n_samples, _lib.ptr(out),
-                                         _lib.stream()), "sample_pdf")
+    _lib.call("sample_pdf", bins, weights, N, Tb, u, 0 if det else 1, n_samples, out)
     return out
 
 
@@ -140,5 +133,5 @@ def merge_sorted(z_a, z_b):
     Tb = z_b.shape[1]
     z = torch.empty(N, Ta + Tb, dtype=torch.float32, device=z_a.device)
     index = torch.empty(N, Ta + Tb, dtype=torch.int64, device=z_a.device)
-    _lib.check(_lib.lib().ngp_merge_sorted(_lib.ptr(z_a), _lib.ptr(z_b), N, Ta, Tb, _lib.ptr(z), _lib.ptr(index), _lib.stream()), "merge_sorted")
+    _lib.call("merge_sorted", z_a, z_b, N, Ta, Tb, z, index)
     return z, index

@@ -198,8 +198,7 @@ def training_depth_targets(batch):
         raise RuntimeError("the frame lies outside the depth store")
     out = torch.empty(N, dtype=torch.float32, device=device)
     fx, fy, cx, cy = st.intrinsics
-    _lib.check(_lib.lib().ngp_train_depth_targets(_lib.ptr(data), int(base), n_pix, st.W, _lib.ptr(inds), N, fx, fy, cx, cy, st.unit,
-                                                  _lib.ptr(out), _lib.stream()), "train_depth_targets")
+    _lib.call("train_depth_targets", data, int(base), n_pix, st.W, inds, N, fx, fy, cx, cy, st.unit, out)
     return out.view(1, N)
 
 
@@ -242,8 +241,8 @@ def gather_targets(store, frame_base, n_pix, inds, bg, table=None, round_half=Fa
     if (frame_base + n_pix) * store.shape[-1] > store.numel():
         raise RuntimeError("the frame lies outside the image store")
     gt = torch.empty(N, 3, dtype=torch.float32, device=store.device)
-    _lib.check(_lib.lib().ngp_train_targets(_lib.ptr(store), _STORE_CODES[store.dtype], store.shape[-1], int(frame_base), int(n_pix), _lib.ptr(inds),
-                                            N, _lib.ptr(bg), _lib.ptr(table), int(bool(round_half)), _lib.ptr(gt), _lib.stream()), "train_targets")
+    _lib.call("train_targets", store, _STORE_CODES[store.dtype], store.shape[-1], int(frame_base), int(n_pix), inds, N, bg, table,
+              int(bool(round_half)), gt)
     return gt
 
 
@@ -273,27 +272,21 @@ def photo_loss_forward(pred, gt, error_row=None, inds_coarse=None):
     dev = pred.device
     per_ray = torch.empty(N, dtype=torch.float32, device=dev)
     mean = torch.empty((), dtype=torch.float32, device=dev)
-    lib = _lib.lib()
-    nbytes = lib.ngp_photo_loss_workspace(N)
-    work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
+    work, nbytes = _lib.workspace("photo_loss", N, device=dev)
     if error_row is not None:
         if error_row.dtype != torch.float32 or inds_coarse is None or inds_coarse.dtype != torch.int64 or inds_coarse.numel() != N:
             raise RuntimeError("the error-map row is float32 and inds_coarse int64 [N]")
         inds_coarse = inds_coarse.reshape(-1).contiguous()
-    _lib.check(lib.ngp_photo_loss_forward(_lib.ptr(pred), _lib.dtype_code(pred), _lib.ptr(gt), N, _lib.ptr(per_ray), _lib.ptr(mean),
-                                          _lib.ptr(error_row), 0 if error_row is None else error_row.numel(),
-                                          _lib.ptr(inds_coarse) if error_row is not None else None, _lib.ptr(work), nbytes, _lib.stream()),
-               "photo_loss_forward")
-    if error_row is not None:
-        torch.autograd.graph.increment_version(error_row)
+    _lib.call("photo_loss_forward", pred, _lib.dtype_code(pred), gt, N, per_ray, mean, error_row,
+              0 if error_row is None else error_row.numel(), inds_coarse if error_row is not None else None, work, nbytes,
+              wrote=() if error_row is None else (error_row,))
     return per_ray, mean
 
 
 def photo_loss_backward(pred, gt, g):
     """grad_pred = g * 2 (pred - gt) / (3 N), g a 0-dim float32 tensor on the device"""
     grad = torch.empty_like(pred)
-    _lib.check(_lib.lib().ngp_photo_loss_backward(_lib.ptr(pred), _lib.dtype_code(pred), _lib.ptr(gt), pred.numel() // 3, _lib.ptr(g), _lib.ptr(grad),
-                                                  _lib.stream()), "photo_loss_backward")
+    _lib.call("photo_loss_backward", pred, _lib.dtype_code(pred), gt, pred.numel() // 3, g, grad)
     return grad
 
 

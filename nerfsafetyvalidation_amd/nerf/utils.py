@@ -39,9 +39,7 @@ class _RaysKernel(torch.autograd.Function):
         n_pix = H * W if inds is None else inds.shape[0]
         rays_o = torch.empty(B, n_pix, 3, dtype=torch.float32, device=poses.device)
         rays_d = torch.empty(B, n_pix, 3, dtype=torch.float32, device=poses.device)
-        lib = _lib.lib()
-        _lib.check(lib.ngp_get_rays(_lib.ptr(poses), B, fx, fy, cx, cy, H, W, _lib.ptr(inds), n_pix, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                                    _lib.stream()), "get_rays")
+        _lib.call("get_rays", poses, B, fx, fy, cx, cy, H, W, inds, n_pix, rays_o, rays_d)
         ctx.geom = (B, fx, fy, cx, cy, H, W, n_pix)
         ctx.inds = inds
         return rays_o, rays_d
@@ -53,8 +51,7 @@ class _RaysKernel(torch.autograd.Function):
         gd = None if grad_d is None else grad_d.float().contiguous()
         ref = go if go is not None else gd
         grad_poses = torch.empty(B, 4, 4, dtype=torch.float32, device=ref.device)
-        _lib.check(_lib.lib().ngp_get_rays_backward(_lib.ptr(go), _lib.ptr(gd), B, fx, fy, cx, cy, H, W, _lib.ptr(ctx.inds), n_pix,
-                                                    _lib.ptr(grad_poses), _lib.stream()), "get_rays_backward")
+        _lib.call("get_rays_backward", go, gd, B, fx, fy, cx, cy, H, W, ctx.inds, n_pix, grad_poses)
         return grad_poses, None, None, None, None
 
 

@@ -28,7 +28,6 @@ class Adam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def _step_on_device(self):
-        lib = _lib.lib()
         found_inf = getattr(self, "found_inf", None)      # set by GradScaler.step around this call (device float tensors), else absent
         grad_scale = getattr(self, "grad_scale", None)
         advanced = False
@@ -48,13 +47,11 @@ class Adam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] = self._dev_step               # (torch's state layout: state_dict() saves it per tensor)
                 if not advanced:
-                    _lib.check(lib.ngp_adam_advance_step(_lib.ptr(self._dev_step), _lib.ptr(found_inf), _lib.stream()), "adam_advance_step")
+                    _lib.call("adam_advance_step", self._dev_step, found_inf, wrote=(self._dev_step,))
                     advanced = True
                 g = p.grad.contiguous()
-                _lib.check(lib.ngp_adam_step_dev(_lib.ptr(p), _lib.ptr(g), _lib.ptr(st["exp_avg"]), _lib.ptr(st["exp_avg_sq"]), p.numel(),
-                                                 float(group["lr"]), float(b1), float(b2), float(group["eps"]), _lib.ptr(self._dev_step),
-                                                 _lib.ptr(grad_scale), _lib.ptr(found_inf), _lib.stream()), "adam_step_dev")
-                torch.autograd.graph.increment_version(p)
+                _lib.call("adam_step_dev", p, g, st["exp_avg"], st["exp_avg_sq"], p.numel(), float(group["lr"]), float(b1), float(b2),
+                          float(group["eps"]), self._dev_step, grad_scale, found_inf, wrote=(p, st["exp_avg"], st["exp_avg_sq"]))
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
@@ -65,7 +62,6 @@ class Adam(torch.optim.Optimizer):
         if self.device_step:
             self._step_on_device()
             return loss
-        lib = _lib.lib()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -84,10 +80,6 @@ class Adam(torch.optim.Optimizer):
                 g = p.grad.contiguous()
                 if not p.is_contiguous():
                     raise RuntimeError("Adam (HIP): parameters must be contiguous")
-                _lib.check(lib.ngp_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(st["exp_avg"]), _lib.ptr(st["exp_avg_sq"]), p.numel(),
-                                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(st["step"]),
-                                             float(grad_scale), _lib.stream()), "adam_step")
-                # the kernel wrote through the raw pointer: tell autograd (and every cache keyed on `_version`, e.g. the fused
-                # renderer's fp16 snapshot, _fused.FusedModel.valid_for) that the parameter changed
-                torch.autograd.graph.increment_version(p)
+                _lib.call("adam_step", p, g, st["exp_avg"], st["exp_avg_sq"], p.numel(), float(group["lr"]), float(b1), float(b2),
+                          float(group["eps"]), int(st["step"]), float(grad_scale), wrote=(p, st["exp_avg"], st["exp_avg_sq"]))    # (the fused renderer's fp16 snapshot, _fused.FusedModel.valid_for, is keyed on p._version)
         return loss

@@ -50,9 +50,7 @@ class _near_far_from_aabb(Function):
         N = rays_o.shape[0]
         nears = torch.empty(N, dtype=rays_o.dtype, device=rays_o.device)
         fars = torch.empty(N, dtype=rays_o.dtype, device=rays_o.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_near_far_from_aabb(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, min_near,
-                                            _lib.ptr(nears), _lib.ptr(fars), _lib.stream()), "near_far_from_aabb")
+        _lib.call("near_far_from_aabb", rays_o, rays_d, aabb, N, min_near, nears, fars)
         return nears, fars
 
 
@@ -67,9 +65,7 @@ class _sph_from_ray(Function):
         rays_o, rays_d = _rays(rays_o, rays_d)
         N = rays_o.shape[0]
         coords = torch.empty(N, 2, dtype=rays_o.dtype, device=rays_o.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_sph_from_ray(_lib.ptr(rays_o), _lib.ptr(rays_d), radius, N, _lib.ptr(coords), _lib.stream()),
-                   "sph_from_ray")
+        _lib.call("sph_from_ray", rays_o, rays_d, radius, N, coords)
         return coords
 
 
@@ -83,8 +79,7 @@ class _morton3D(Function):
         coords = _dev(coords).int().contiguous()
         N = coords.shape[0]
         indices = torch.empty(N, dtype=torch.int32, device=coords.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_morton3D(_lib.ptr(coords), N, _lib.ptr(indices), _lib.stream()), "morton3D")
+        _lib.call("morton3D", coords, N, indices)
         return indices
 
 
@@ -98,8 +93,7 @@ class _morton3D_invert(Function):
         indices = _dev(indices).int().contiguous()
         N = indices.shape[0]
         coords = torch.empty(N, 3, dtype=torch.int32, device=indices.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_morton3D_invert(_lib.ptr(indices), N, _lib.ptr(coords), _lib.stream()), "morton3D_invert")
+        _lib.call("morton3D_invert", indices, N, coords)
         return coords
 
 
@@ -114,10 +108,10 @@ class _packbits(Function):
         grid = _dev(grid).contiguous()
         C, H3 = grid.shape[0], grid.shape[1]
         N = C * H3 // 8
+        wrote = () if bitfield is None else (bitfield,)
         if bitfield is None:
             bitfield = torch.empty(N, dtype=torch.uint8, device=grid.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_packbits(_lib.ptr(grid), N, thresh, _lib.ptr(bitfield), _lib.stream()), "packbits")
+        _lib.call("packbits", grid, N, thresh, bitfield, wrote=wrote)
         return bitfield
 
 
@@ -145,16 +139,12 @@ class _march_rays_train(Function):
         dirs = torch.zeros(M, 3, dtype=dt, device=dev)
         deltas = torch.zeros(M, 2, dtype=dt, device=dev)
         rays = torch.empty(N, 3, dtype=torch.int32, device=dev)
+        wrote = () if step_counter is None else (step_counter,)
         if step_counter is None:
             step_counter = torch.zeros(2, dtype=torch.int32, device=dev)
-        L = _lib.lib()
-        ws_bytes = L.ngp_march_rays_train_workspace(N)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.ngp_march_rays_train(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(density_bitfield), bound, dt_gamma,
-                                          max_steps, N, C, H, M, _lib.ptr(nears.contiguous()), _lib.ptr(fars.contiguous()),
-                                          _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(deltas), _lib.ptr(rays),
-                                          _lib.ptr(step_counter), int(perturb), _lib.ptr(ws), ws_bytes, _lib.stream()),
-                   "march_rays_train")
+        ws, ws_bytes = _lib.workspace("march_rays_train", N, device=dev)
+        _lib.call("march_rays_train", rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M, nears.contiguous(),
+                  fars.contiguous(), xyzs, dirs, deltas, rays, step_counter, int(perturb), ws, ws_bytes, wrote=wrote)
         if force_all_rays or mean_count <= 0:
             m = step_counter[0].item()  # D2H sync, as in the reference (:219)
             if align > 0:
@@ -178,10 +168,7 @@ class _composite_rays_train(Function):
         weights_sum = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
         depth = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
         image = torch.empty(N, 3, dtype=sigmas.dtype, device=sigmas.device)
-        L = _lib.lib()
-        _lib.check(L.ngp_composite_rays_train_forward(_lib.ptr(sigmas), _lib.ptr(rgbs), _lib.ptr(deltas), _lib.ptr(rays), M, N,
-                                                      _lib.ptr(weights_sum), _lib.ptr(depth), _lib.ptr(image),
-                                                      _lib.stream()), "composite_rays_train_forward")
+        _lib.call("composite_rays_train_forward", sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image)
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image)
         ctx.dims = [M, N]
         return weights_sum, depth, image
@@ -194,21 +181,12 @@ class _composite_rays_train(Function):
         sigmas, rgbs, deltas, rays, weights_sum, depth, image = ctx.saved_tensors
         M, N = ctx.dims
         grad_sigmas, grad_rgbs = torch.zeros_like(sigmas), torch.zeros_like(rgbs)
-        L = _lib.lib()
-        _lib.check(L.ngp_composite_rays_train_backward(_lib.ptr(grad_weights_sum), _lib.ptr(grad_image), _lib.ptr(sigmas),
-                                                       _lib.ptr(rgbs), _lib.ptr(deltas), _lib.ptr(rays),
-                                                       _lib.ptr(weights_sum), _lib.ptr(image), M, N, _lib.ptr(grad_sigmas),
-                                                       _lib.ptr(grad_rgbs), _lib.stream()),
-                   "composite_rays_train_backward")
+        _lib.call("composite_rays_train_backward", grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                  grad_sigmas, grad_rgbs)
         return grad_sigmas, grad_rgbs, None, None
 
 
 composite_rays_train = _composite_rays_train.apply
-
-
-def _distortion_workspace(L, N, device):
-    nbytes = L.ngp_distortion_workspace(N)
-    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), nbytes
 
 
 class _distortion_rays_train(Function):
@@ -221,11 +199,8 @@ class _distortion_rays_train(Function):
         loss_rays = torch.zeros(N, dtype=sigmas.dtype, device=sigmas.device)
         totals = torch.zeros(N, 2, dtype=sigmas.dtype, device=sigmas.device)
         loss = torch.zeros((), dtype=sigmas.dtype, device=sigmas.device)
-        L = _lib.lib()
-        ws, ws_bytes = _distortion_workspace(L, N, sigmas.device)
-        _lib.check(L.ngp_distortion_train_forward(_lib.ptr(sigmas), _lib.ptr(deltas), _lib.ptr(rays), _lib.ptr(scale), M, N, _lib.ptr(loss_rays),
-                                                  _lib.ptr(totals), _lib.ptr(loss), _lib.ptr(ws), ws_bytes, _lib.stream()),
-                   "distortion_train_forward")
+        ws, ws_bytes = _lib.workspace("distortion", N, device=sigmas.device)
+        _lib.call("distortion_train_forward", sigmas, deltas, rays, scale, M, N, loss_rays, totals, loss, ws, ws_bytes)
         ctx.save_for_backward(sigmas, deltas, rays, scale, totals)
         ctx.dims = [M, N]
         ctx.mark_non_differentiable(loss_rays)
@@ -237,9 +212,7 @@ class _distortion_rays_train(Function):
         sigmas, deltas, rays, scale, totals = ctx.saved_tensors
         M, N = ctx.dims
         grad_sigmas = torch.zeros_like(sigmas)      # rows of dead samples, of dropped rays and of no ray read 0
-        _lib.check(_lib.lib().ngp_distortion_train_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(sigmas), _lib.ptr(deltas),
-                                                            _lib.ptr(rays), _lib.ptr(scale), _lib.ptr(totals), M, N, _lib.ptr(grad_sigmas),
-                                                            _lib.stream()), "distortion_train_backward")
+        _lib.call("distortion_train_backward", grad_loss.float().contiguous(), sigmas, deltas, rays, scale, totals, M, N, grad_sigmas)
         return grad_sigmas, None, None, None
 
 
@@ -277,12 +250,9 @@ class _depth_rays_train(Function):
         loss_rays = torch.zeros(N, dtype=sigmas.dtype, device=sigmas.device)
         parts = torch.zeros(N, 2, dtype=sigmas.dtype, device=sigmas.device)
         loss = torch.zeros((), dtype=sigmas.dtype, device=sigmas.device)
-        L = _lib.lib()
-        nbytes = L.ngp_depth_loss_workspace(N)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=sigmas.device) if nbytes else None
-        _lib.check(L.ngp_depth_loss_train_forward(_lib.ptr(sigmas), _lib.ptr(deltas), _lib.ptr(rays), _lib.ptr(target), _lib.ptr(scale), margin,
-                                                  weight_depth, weight_free, M, N, _lib.ptr(loss_rays), _lib.ptr(parts), _lib.ptr(loss),
-                                                  _lib.ptr(ws), nbytes, _lib.stream()), "depth_loss_train_forward")
+        ws, nbytes = _lib.workspace("depth_loss", N, device=sigmas.device)
+        _lib.call("depth_loss_train_forward", sigmas, deltas, rays, target, scale, margin, weight_depth, weight_free, M, N, loss_rays,
+                  parts, loss, ws, nbytes)
         ctx.save_for_backward(sigmas, deltas, rays, target, scale, parts)
         ctx.dims, ctx.consts = [M, N], (margin, weight_depth, weight_free)
         ctx.mark_non_differentiable(loss_rays, parts)
@@ -294,9 +264,8 @@ class _depth_rays_train(Function):
         sigmas, deltas, rays, target, scale, parts = ctx.saved_tensors
         M, N = ctx.dims
         grad_sigmas = torch.zeros_like(sigmas)      # rows of dead samples, of rays that take no part and of no ray read 0
-        _lib.check(_lib.lib().ngp_depth_loss_train_backward(_lib.ptr(grad_loss.float().contiguous()), _lib.ptr(sigmas), _lib.ptr(deltas),
-                                                            _lib.ptr(rays), _lib.ptr(target), _lib.ptr(scale), *ctx.consts, _lib.ptr(parts),
-                                                            M, N, _lib.ptr(grad_sigmas), _lib.stream()), "depth_loss_train_backward")
+        _lib.call("depth_loss_train_backward", grad_loss.float().contiguous(), sigmas, deltas, rays, target, scale, *ctx.consts, parts, M,
+                  N, grad_sigmas)
         return grad_sigmas, None, None, None, None, None, None, None
 
 
@@ -333,8 +302,7 @@ _OCC_LIN_MAX = 8
 
 
 def _occupancy_lin(density_bitfield, C, H):
-    L = _lib.lib()
-    nbytes = L.ngp_occupancy_lin_bytes(C, H)
+    nbytes = _lib.lib().ngp_occupancy_lin_bytes(C, H)
     if not nbytes or not density_bitfield.is_cuda or density_bitfield.data_ptr() % 8 or density_bitfield.dtype != torch.uint8:
         return None
     stream = _lib.stream()
@@ -348,7 +316,7 @@ def _occupancy_lin(density_bitfield, C, H):
                 return buf
             del _OCC_LIN[key]
     buf = torch.empty(nbytes, dtype=torch.uint8, device=density_bitfield.device)      # (torch allocations are 512-byte aligned)
-    _lib.check(L.ngp_build_occupancy_lin(_lib.ptr(density_bitfield), C, H, _lib.ptr(buf), nbytes, stream), "build_occupancy_lin")
+    _lib.call("build_occupancy_lin", density_bitfield, C, H, buf, nbytes, stream=stream)
     with _OCC_LIN_LOCK:
         _OCC_LIN[key] = (weakref.ref(density_bitfield), density_bitfield._version, density_bitfield.data_ptr(), buf)
         while len(_OCC_LIN) > _OCC_LIN_MAX:
@@ -370,18 +338,13 @@ class _march_rays(Function):
         xyzs = torch.empty(M, 3, dtype=dt, device=dev)
         dirs = torch.empty(M, 3, dtype=dt, device=dev)
         deltas = torch.empty(M, 2, dtype=dt, device=dev)
-        L = _lib.lib()
         occ = _occupancy_lin(density_bitfield, C, H) if USE_OCCUPANCY_LIN else None
         if occ is not None:
-            _lib.check(L.ngp_march_rays_lin(n_alive, n_step, _lib.ptr(rays_alive), _lib.ptr(rays_t), _lib.ptr(rays_o),
-                                            _lib.ptr(rays_d), bound, dt_gamma, max_steps, C, H, _lib.ptr(density_bitfield),
-                                            _lib.ptr(near), _lib.ptr(far), _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(deltas),
-                                            int(perturb), M, _lib.ptr(occ), _lib.stream()), "march_rays_lin")
+            _lib.call("march_rays_lin", n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H,
+                      density_bitfield, near, far, xyzs, dirs, deltas, int(perturb), M, occ)
         else:
-            _lib.check(L.ngp_march_rays(n_alive, n_step, _lib.ptr(rays_alive), _lib.ptr(rays_t), _lib.ptr(rays_o),
-                                        _lib.ptr(rays_d), bound, dt_gamma, max_steps, C, H, _lib.ptr(density_bitfield),
-                                        _lib.ptr(near), _lib.ptr(far), _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(deltas),
-                                        int(perturb), M, _lib.stream()), "march_rays")
+            _lib.call("march_rays", n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, density_bitfield,
+                      near, far, xyzs, dirs, deltas, int(perturb), M)
         return xyzs, dirs, deltas
 
 
@@ -394,10 +357,8 @@ class _composite_rays(Function):
     def forward(ctx, n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image):
         """raymarching.py:340-359.  Updates rays_alive, rays_t, weights_sum, depth, image IN PLACE; returns ()."""
         sigmas, rgbs = sigmas.float().contiguous(), rgbs.float().contiguous()
-        L = _lib.lib()
-        _lib.check(L.ngp_composite_rays(n_alive, n_step, _lib.ptr(rays_alive), _lib.ptr(rays_t), _lib.ptr(sigmas),
-                                        _lib.ptr(rgbs), _lib.ptr(deltas), _lib.ptr(weights_sum), _lib.ptr(depth),
-                                        _lib.ptr(image), _lib.stream()), "composite_rays")
+        _lib.call("composite_rays", n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
+                  wrote=(rays_alive, rays_t, weights_sum, depth, image))
         return tuple()
 
 

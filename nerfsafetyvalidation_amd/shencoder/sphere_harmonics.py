@@ -17,9 +17,7 @@ class _sh_encoder(Function):
         output_dim = degree ** 2
         outputs = torch.empty(B, output_dim, dtype=inputs.dtype, device=inputs.device)
         dy_dx = torch.empty(B, input_dim * output_dim, dtype=inputs.dtype, device=inputs.device) if calc_grad_inputs else None
-        lib = _lib.lib()
-        _lib.check(lib.ngp_sh_encode_forward(_lib.ptr(inputs), _lib.ptr(outputs), B, input_dim, degree, int(calc_grad_inputs),
-                                             _lib.ptr(dy_dx), _lib.stream()), "sh_encode_forward")
+        _lib.call("sh_encode_forward", inputs, outputs, B, input_dim, degree, int(calc_grad_inputs), dy_dx)
         if dy_dx is None:
             dy_dx = torch.empty(1, dtype=inputs.dtype, device=inputs.device)
         ctx.save_for_backward(inputs, dy_dx)
@@ -36,9 +34,7 @@ class _sh_encoder(Function):
         inputs, dy_dx = ctx.saved_tensors
         B, input_dim, degree = ctx.dims
         grad_inputs = torch.zeros_like(inputs)  # the kernel accumulates (shencoder.cu:379)
-        lib = _lib.lib()
-        _lib.check(lib.ngp_sh_encode_backward(_lib.ptr(grad), _lib.ptr(inputs), B, input_dim, degree, _lib.ptr(dy_dx),
-                                              _lib.ptr(grad_inputs), _lib.stream()), "sh_encode_backward")
+        _lib.call("sh_encode_backward", grad, inputs, B, input_dim, degree, dy_dx, grad_inputs)
         return grad_inputs, None, None
 
 

@@ -72,15 +72,15 @@ def image_quality_stats(preds, target, mask=None, channels_last=False, return_ma
             preds, target = preds.contiguous(), target.contiguous()
         if mask is not None:
             mask = mask.detach().to(device=preds.device, dtype=torch.float32).contiguous()
-        lib = _lib.lib()
         stats = torch.empty(B, 8, dtype=torch.float64, device=preds.device)
-        wbytes = lib.ngp_image_quality_workspace(B, H, W)
-        work = torch.empty(max(wbytes // 8, 1), dtype=torch.float64, device=preds.device)
+        work, wbytes = _lib.workspace("image_quality", B, H, W, device=preds.device)
+        if work is None:              # a frame size the library refuses: a buffer all the same, so that its message names the reason
+            work = torch.empty(8, dtype=torch.uint8, device=preds.device)
         ssim_map = torch.empty(B, H, W, dtype=torch.float32, device=preds.device) if return_map else None
         sb, sc, sy, sx = preds.stride()
         with torch.cuda.device(preds.device):
-            _lib.check(lib.ngp_image_quality(preds.data_ptr(), target.data_ptr(), _lib.ptr(mask), B, H, W, sb, sc, sy, sx, float(data_range),
-                                             _lib.ptr(ssim_map), _lib.ptr(stats), _lib.ptr(work), wbytes, _lib.stream()), "image_quality")
+            _lib.call("image_quality", preds.data_ptr(), target.data_ptr(), mask, B, H, W, sb, sc, sy, sx, float(data_range), ssim_map,
+                      stats, work, wbytes)
         return stats, ssim_map
 
     # host tensors: the same recipe with torch operators at the inputs' dtype

@@ -51,18 +51,18 @@ class _Density(nn.Module):
 
 def sigma_fit_eval(features, y, theta, prior_mean, prior_std, mode, max_workgroups=0):
     """csrc/sigma_fit.hip on device tensors: features [n,32], y [n], theta [3072] (float32) -> (loss float64 0-dim tensor, grad [3072] or None)"""
-    lib = _lib.lib()
     n = features.shape[0]
     if features.dtype != torch.float32 or features.shape[1:] != (32,) or y.dtype != torch.float32 or y.numel() != n or theta.dtype != torch.float32 or theta.numel() != 3072:
         raise RuntimeError("sigma_fit_eval: features float32 [n,32], y float32 [n], theta float32 [3072]")
     if not (features.is_contiguous() and y.is_contiguous() and theta.is_contiguous()) or not (features.device == y.device == theta.device):
         raise RuntimeError("sigma_fit_eval: features, y and theta must be contiguous tensors on one device")
-    wbytes = lib.ngp_sigma_fit_workspace(n, max_workgroups)
-    work = torch.empty(max(wbytes // 8, 1), dtype=torch.float64, device=features.device)
+    work, wbytes = _lib.workspace("sigma_fit", n, max_workgroups, device=features.device)
+    if work is None:                  # a max_workgroups the library refuses: a buffer all the same, so that its message names the reason
+        work = torch.empty(8, dtype=torch.uint8, device=features.device)
     loss = torch.empty((), dtype=torch.float64, device=features.device)
     grad = torch.empty(3072, dtype=torch.float32, device=features.device) if mode != MODE_LOSS else None
-    _lib.check(lib.ngp_sigma_fit_eval(_lib.ptr(features), _lib.ptr(y), n, _lib.ptr(theta), float(prior_mean), float(prior_std) ** 2, mode,
-                                      max_workgroups, _lib.ptr(work), wbytes, _lib.ptr(loss), _lib.ptr(grad), _lib.stream()), "sigma_fit_eval")
+    _lib.call("sigma_fit_eval", features, y, n, theta, float(prior_mean), float(prior_std) ** 2, mode, max_workgroups, work, wbytes, loss,
+              grad)
     return loss, grad
 
 
@@ -209,7 +209,6 @@ class BayesianLaplace:
         return theta.detach(), hist.cpu().numpy(), bool(improved), min_loss
 
     def _fit_fused(self, X_p, y, theta_init, lrs, min_loss):
-        lib = _lib.lib()
         dev = theta_init.device
         feat = self._encode(X_p)
         n = feat.shape[0]
@@ -218,15 +217,11 @@ class BayesianLaplace:
         hist = torch.empty(len(lrs), dtype=torch.float32, device=dev)
         improved = torch.zeros(1, dtype=torch.int32, device=dev)
         min_loss = min_loss.clone()
-        wbytes = lib.ngp_sigma_fit_workspace(n, 0)
-        work = torch.empty(wbytes // 8, dtype=torch.float64, device=dev)
+        work, wbytes = _lib.workspace("sigma_fit", n, 0, device=dev)
         mode = MODE_FULL_GRAD if self.likelihood_gradient else MODE_PRIOR_GRAD
-        args = (_lib.ptr(feat), _lib.ptr(y), n, _lib.ptr(theta), self.prior_mean, self.prior_std ** 2, mode, 0, _lib.ptr(work), wbytes,
-                _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v))
-        tail = (_lib.ptr(min_loss), _lib.ptr(improved), _lib.ptr(hist))
-        stream = _lib.stream()
+        args = (feat, y, n, theta, self.prior_mean, self.prior_std ** 2, mode, 0, work, wbytes, grad, m, v)
         for k, lr in enumerate(lrs):               # launches only; the one read-back follows the loop
-            _lib.check(lib.ngp_sigma_fit_step(*args, lr, k + 1, *tail, k, stream), "sigma_fit_step")
+            _lib.call("sigma_fit_step", *args, lr, k + 1, min_loss, improved, hist, k)
         return theta, hist.cpu().numpy(), bool(int(improved.item())), min_loss
 
     # ---- results ---------------------------------------------------------------------------------------------------------

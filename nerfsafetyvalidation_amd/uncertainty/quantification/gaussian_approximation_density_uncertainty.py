@@ -26,12 +26,9 @@ def density_statistics(c, d, r):
     r = r.float().contiguous()
     if c.shape[-1] != 3 or c.numel() != 3 * d.numel():
         raise RuntimeError(f"density_statistics: c {tuple(c.shape)} must hold 3 colour values per density sample ({d.numel()} samples)")
-    lib = _lib.lib()
-    wbytes = lib.ngp_uq_stats_workspace()
-    work = torch.empty(wbytes // 8, dtype=torch.float64, device=d.device)
+    work, wbytes = _lib.workspace("uq_stats", device=d.device)
     stats = torch.empty(8, dtype=torch.float64, device=d.device)
-    _lib.check(lib.ngp_uq_stats(_lib.ptr(c), 1 if c.dtype == torch.float16 else 0, _lib.ptr(d), d.numel(), _lib.ptr(r), r.numel(),
-                                _lib.ptr(stats), _lib.ptr(work), wbytes, _lib.stream()), "uq_stats")
+    _lib.call("uq_stats", c, 1 if c.dtype == torch.float16 else 0, d, d.numel(), r, r.numel(), stats, work, wbytes)
     A, B, sum_r, m, sum_d, sum_d2, n, _ = stats.cpu().tolist()      # the one synchronisation
     mean_d = sum_d / n if n else float("nan")
     var = (sum_d2 - n * mean_d * mean_d) / (n - 1) if n > 1 else float("nan")   # torch.std: unbiased

@@ -739,13 +739,12 @@ class MeshWorld:
         self.mean_pairs_per_cell = self.pairs / float(np.prod(self.dims))
 
     def _build_hip(self):
-        lib, F = _lib.lib(), self.n_faces
+        F = self.n_faces
         self._grid_c = _grid_struct(self.grid)
         n_cells = int(np.prod(self.dims))
         with torch.cuda.device(self.device):
             counts = torch.empty(F, dtype=torch.int32, device=self.device)
-            _lib.check(lib.ngp_raycast_bin_count(_lib.ptr(self.tri_data), F, ctypes.byref(self._grid_c), _lib.ptr(counts), _lib.stream()),
-                       "raycast_bin_count")
+            _lib.call("raycast_bin_count", self.tri_data, F, ctypes.byref(self._grid_c), counts)
             ends = torch.cumsum(counts, 0, dtype=torch.int64)
             P = int(ends[-1])
             if P >= 2 ** 31:
@@ -753,8 +752,7 @@ class MeshWorld:
             offsets = (ends - counts).contiguous()
             pair_cell = torch.empty(P, dtype=torch.int32, device=self.device)
             pair_tri = torch.empty(P, dtype=torch.int32, device=self.device)
-            _lib.check(lib.ngp_raycast_bin_emit(_lib.ptr(self.tri_data), F, ctypes.byref(self._grid_c), _lib.ptr(offsets), P, _lib.ptr(pair_cell),
-                                                _lib.ptr(pair_tri), _lib.stream()), "raycast_bin_emit")
+            _lib.call("raycast_bin_emit", self.tri_data, F, ctypes.byref(self._grid_c), offsets, P, pair_cell, pair_tri)
             cells, order = torch.sort(pair_cell, stable=True)
             self.pair_tri = pair_tri[order].contiguous()
             self.cell_start = torch.searchsorted(cells, torch.arange(n_cells + 1, dtype=torch.int32, device=self.device)).to(torch.int32).contiguous()
@@ -772,18 +770,16 @@ class MeshWorld:
             return torch.from_numpy(voxelize_numpy(vw, self.faces.numpy(), box))
         if not 1 <= int(pairs_per_launch) <= MAX_PAIRS_PER_LAUNCH:
             raise ValueError(f"MeshWorld.occupancy: pairs_per_launch is 1 .. {MAX_PAIRS_PER_LAUNCH}")
-        lib, b = _lib.lib(), _voxel_box_struct(box, rot)
+        b = _voxel_box_struct(box, rot)
         with torch.cuda.device(self.device):
             occ = torch.empty(box.shape, dtype=torch.uint8, device=self.device)
             counts = torch.empty(self.n_faces, dtype=torch.int32, device=self.device)
-            _lib.check(lib.ngp_voxelize_count(_lib.ptr(self.vertices), self.n_vertices, _lib.ptr(self.faces), self.n_faces, ctypes.byref(b),
-                                              _lib.ptr(occ), _lib.ptr(counts), _lib.stream()), "voxelize_count")
+            _lib.call("voxelize_count", self.vertices, self.n_vertices, self.faces, self.n_faces, ctypes.byref(b), occ, counts)
             ends = torch.cumsum(counts, 0, dtype=torch.int64)
             pairs = int(ends[-1])
             for base in range(0, pairs, int(pairs_per_launch)):
-                _lib.check(lib.ngp_voxelize_mark(_lib.ptr(self.vertices), self.n_vertices, _lib.ptr(self.faces), self.n_faces, ctypes.byref(b),
-                                                 _lib.ptr(ends), base, min(int(pairs_per_launch), pairs - base), _lib.ptr(occ), _lib.stream()),
-                           "voxelize_mark")
+                _lib.call("voxelize_mark", self.vertices, self.n_vertices, self.faces, self.n_faces, ctypes.byref(b), ends, base,
+                          min(int(pairs_per_launch), pairs - base), occ)
         return occ.view(torch.bool)
 
     # ---- the closest point of the surface
@@ -821,10 +817,8 @@ class MeshWorld:
                     p = p[order].contiguous()
                 raw = out if order is None else {k: torch.empty_like(a) for k, a in out.items()}
                 with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().ngp_closest_point(_lib.ptr(p), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
-                                                            _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_verts), self.n_faces,
-                                                            max_distance, _lib.ptr(raw["distance"]), _lib.ptr(raw["prim"]), _lib.ptr(raw["point"]),
-                                                            _lib.ptr(raw.get("tested")), _lib.stream()), "closest_point")
+                    _lib.call("closest_point", p, N, ctypes.byref(self._grid_c), self.cell_start, self.pair_tri, self.pairs, self.tri_verts,
+                              self.n_faces, max_distance, raw["distance"], raw["prim"], raw["point"], raw.get("tested"))
                 if order is not None:
                     for k in out:
                         out[k][order] = raw[k]
@@ -885,10 +879,8 @@ class MeshWorld:
                    "u": torch.empty(N, dtype=torch.float32, device=self.device), "v": torch.empty(N, dtype=torch.float32, device=self.device)}
             if N:
                 with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().ngp_raycast(_lib.ptr(o), _lib.ptr(d), N, ctypes.byref(self._grid_c), _lib.ptr(self.cell_start),
-                                                      _lib.ptr(self.pair_tri), self.pairs, _lib.ptr(self.tri_data), self.n_faces, t_min, t_max,
-                                                      width, _lib.ptr(out["t"]), _lib.ptr(out["prim"]), _lib.ptr(out["u"]), _lib.ptr(out["v"]),
-                                                      _lib.stream()), "raycast")
+                    _lib.call("raycast", o, d, N, ctypes.byref(self._grid_c), self.cell_start, self.pair_tri, self.pairs, self.tri_data,
+                              self.n_faces, t_min, t_max, width, out["t"], out["prim"], out["u"], out["v"])
         return {k: self._back(a, shape, tensors) for k, a in out.items()}
 
     def shade(self, rays_d, hit, bg_color=1.0, ambient=DEFAULT_AMBIENT):
@@ -911,10 +903,8 @@ class MeshWorld:
             if N:
                 bg_c = (ctypes.c_float * 3)(*[float(b) for b in bg])
                 with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().ngp_raycast_shade(_lib.ptr(d), _lib.ptr(prim.to(torch.int32)), _lib.ptr(u.to(torch.float32)),
-                                                            _lib.ptr(v.to(torch.float32)), N, _lib.ptr(self.tri_data), _lib.ptr(self.faces),
-                                                            self.n_faces, _lib.ptr(self.colors), self.n_vertices, float(ambient), bg_c,
-                                                            _lib.ptr(image), _lib.ptr(u8), _lib.stream()), "raycast_shade")
+                    _lib.call("raycast_shade", d, prim.to(torch.int32), u.to(torch.float32), v.to(torch.float32), N, self.tri_data,
+                              self.faces, self.n_faces, self.colors, self.n_vertices, float(ambient), bg_c, image, u8)
         return self._back(image, shape + (3,), tensors), self._back(u8, shape + (3,), tensors)
 
     def _frame(self, pose, intrinsics, H, W, bg_color, ambient):
@@ -964,9 +954,8 @@ class MeshWorld:
             if N:
                 with torch.cuda.device(self.device):
                     q_dev = torch.from_numpy(q).to(self.device) if P else None
-                    _lib.check(_lib.lib().ngp_overlay_cast(_lib.ptr(o), _lib.ptr(d), N, q.ctypes.data if P else None, _lib.ptr(q_dev), P, t_min,
-                                                           _lib.ptr(far), width, _lib.ptr(out["t"]), _lib.ptr(out["prim"]),
-                                                           _lib.ptr(out["normal"]), _lib.stream()), "overlay_cast")
+                    _lib.call("overlay_cast", o, d, N, q.ctypes.data if P else None, q_dev, P, t_min, far, width, out["t"], out["prim"],
+                              out["normal"])
         return {k: self._back(a, shape + (3,) if k == "normal" else shape, tensors) for k, a in out.items()}
 
     def shade_overlay(self, rays_d, hit, colors, image, image_u8, ambient=DEFAULT_AMBIENT):
@@ -991,9 +980,7 @@ class MeshWorld:
             img, u8 = img.clone().contiguous(), u8.clone().contiguous()
             if N and P:
                 with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().ngp_overlay_shade(_lib.ptr(d), _lib.ptr(prim), _lib.ptr(normal), N,
-                                                            _lib.ptr(torch.from_numpy(col).to(self.device)), P, float(ambient), _lib.ptr(img),
-                                                            _lib.ptr(u8), _lib.stream()), "overlay_shade")
+                    _lib.call("overlay_shade", d, prim, normal, N, torch.from_numpy(col).to(self.device), P, float(ambient), img, u8)
         return self._back(img, shape + (3,), tensors), self._back(u8, shape + (3,), tensors)
 
     def render_scene(self, pose, intrinsics, H, W, tubes=(), boxes=(), bg_color=1.0, ambient=DEFAULT_AMBIENT):

@@ -1,5 +1,6 @@
-"""The C ABI: every function declared in include/ngp_hip.h is exported by libngp_hip.so and bound (with argtypes)
-by the ctypes layer.  No compute calls: runs without a GPU."""
+"""The C ABI: every function declared in include/ngp_hip.h is exported by libngp_hip.so and bound by the ctypes layer with the
+argument and return types of its prototype, and the package enters the library through _lib.call alone.  No compute calls: runs
+without a GPU."""
 import ctypes
 import os
 import re
@@ -13,6 +14,60 @@ def declared():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"NGP_API\s+[\w\s\*]+?\b(ngp_\w+)\s*\(", text)))
+
+
+def prototypes():
+    """name -> (return type, [parameter type, ...]) of every NGP_API prototype, types as the header spells them (no parameter names)"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"NGP_API\s+([\w\s\*]+?)\b(ngp_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else [p if p.endswith("*") else re.sub(r"\s*\b\w+$", "", p) for p in params])
+    return out
+
+
+_C_SCALARS = {"int": ("int", 4), "int32_t": ("int", 4), "int64_t": ("int", 8), "uint32_t": ("uint", 4), "uint64_t": ("uint", 8), "size_t": ("uint", 8),
+              "float": ("float", 4), "double": ("float", 8)}
+
+
+def header_kind(ctype):
+    """(class, bytes, is the stream) of a C parameter or return type"""
+    if ctype == "ngp_stream_t":
+        return "pointer", 8, True
+    if "*" in ctype:
+        return "pointer", 8, False
+    return _C_SCALARS[ctype] + (False,)         # KeyError: a type this test does not know yet -- teach it, do not skip it
+
+
+def ctypes_kind(t, stream_type):
+    """the same triple of a ctypes type, by kind and ctypes.sizeof (c_int is c_int32 and c_size_t is c_uint64 here: class identity says nothing)"""
+    if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)):
+        assert ctypes.sizeof(t) == 8
+        return "pointer", 8, issubclass(t, stream_type)
+    assert issubclass(t, ctypes._SimpleCData), t
+    code = t._type_
+    kind = "float" if code in "fd" else "int" if code in "bhilq" else "uint" if code in "BHILQ" else None
+    assert kind is not None, t
+    return kind, ctypes.sizeof(t), False
+
+
+def table_mismatches(signatures, restypes, stream_type):
+    """every disagreement between the header's prototypes and a signature table, as text"""
+    wrong = []
+    for name, (ret, params) in prototypes().items():
+        if name not in signatures:
+            wrong.append(f"{name}: no entry")
+            continue
+        argtypes = signatures[name]
+        if len(argtypes) != len(params):
+            wrong.append(f"{name}: {len(params)} parameters in the header, {len(argtypes)} in the table")
+            continue
+        for i, (c, t) in enumerate(zip(params, argtypes)):
+            if header_kind(c) != ctypes_kind(t, stream_type):
+                wrong.append(f"{name}: parameter {i} is `{c}` {header_kind(c)} in the header, {t.__name__} {ctypes_kind(t, stream_type)} in the table")
+        if header_kind(ret)[:2] != ctypes_kind(restypes.get(name, ctypes.c_int), stream_type)[:2] or (ret == "const char*") != (restypes.get(name) is ctypes.c_char_p):
+            wrong.append(f"{name}: returns `{ret}` in the header, {restypes.get(name, ctypes.c_int).__name__} in the table")
+    return wrong
 
 
 def test_header_declares_the_four_reference_modules():
@@ -89,6 +144,65 @@ def test_backward_plans_answer_as_before_the_refactor(monkeypatch):
         assert lib.ngp_ffmlp_backward_workspace(B, 32, 64, 2) == partials * P * 4
     for B, nbytes in ((131071, 0), (131072, 276824064), (1 << 25, 3225944064)):
         assert lib.ngp_grid_encode_backward_workspace(B, 3, 2, 16, _lib.NGP_F16) == nbytes
+
+
+def test_signature_table_matches_the_header():
+    """Every prototype against its SIGNATURES / _RESTYPES entry: the number of parameters, per parameter the class (pointer, signed or
+    unsigned integer, floating point) and the width, the return type (int, size_t, const char*), and the slot the table marks as the
+    stream is the one the header declares ngp_stream_t.  A table with one argument dropped or one uint32 widened is caught."""
+    from nerfsafetyvalidation_amd import _lib
+    protos = prototypes()
+    assert sorted(protos) == declared() == sorted(_lib.SIGNATURES)
+    assert {r for r, _ in protos.values()} == {"int", "size_t", "const char*"}
+    assert not set(_lib._RESTYPES) - set(_lib.SIGNATURES)
+    wrong = table_mismatches(_lib.SIGNATURES, _lib._RESTYPES, _lib.StreamPtr)
+    assert not wrong, "\n".join(wrong)
+    # the stream: the last parameter wherever there is one, as _lib.call relies on
+    with_stream = [n for n, (_, params) in protos.items() if "ngp_stream_t" in params]
+    assert len(with_stream) > 80 and all(protos[n][1].index("ngp_stream_t") == len(protos[n][1]) - 1 for n in with_stream)
+    # the check itself: it sees a dropped argument, a widened integer, a stream mark in the wrong place and a wrong return type
+    broken = dict(_lib.SIGNATURES)
+    broken["ngp_packbits"] = broken["ngp_packbits"][:-2] + broken["ngp_packbits"][-1:]
+    broken["ngp_morton3D"] = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, _lib.StreamPtr]
+    broken["ngp_sph_from_ray"] = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint32, _lib.StreamPtr, ctypes.c_void_p]
+    found = table_mismatches(broken, {**_lib._RESTYPES, "ngp_version": ctypes.c_size_t}, _lib.StreamPtr)
+    assert sorted(f.split(":")[0] for f in found) == ["ngp_morton3D", "ngp_packbits", "ngp_sph_from_ray", "ngp_sph_from_ray", "ngp_version"], found
+
+
+def test_abi_version_is_one_number():
+    from nerfsafetyvalidation_amd import _lib
+    (in_header,) = re.findall(r"^#define NGP_ABI_VERSION (\d+)$", open(HEADER).read(), flags=re.M)
+    assert int(in_header) == _lib.ABI_VERSION == _lib.lib().ngp_version()
+
+
+def test_call_raises_with_the_name_the_code_and_the_library_message():
+    import pytest
+    import torch
+    from nerfsafetyvalidation_amd import _lib
+    with pytest.raises(RuntimeError) as err:
+        _lib.call("debug_disable_march_queue", 1 << 4)
+    text = str(err.value)
+    assert "debug_disable_march_queue" in text and "code -1" in text and "unknown debug flag bits" in text
+    assert _lib.call("debug_disable_march_queue", 0) is None
+    # a host tensor is refused before the library is entered (the function's name is resolved first: a wrong name is an AttributeError)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        _lib.call("morton3D", torch.zeros(3, dtype=torch.int32), 1, torch.zeros(1, dtype=torch.int32))
+    with pytest.raises(AttributeError):
+        _lib.call("no_such_function")
+    with pytest.raises(TypeError, match="takes no stream"):
+        _lib.call("debug_disable_march_queue", 0, stream=0)
+    with pytest.raises(TypeError, match="ngp_morton3D takes 3 arguments and the stream; 4 given"):      # (a stream passed by hand, as before)
+        _lib.call("morton3D", None, 0, None, 0)
+
+
+def test_package_enters_the_library_through_call_alone():
+    """_lib.check( -- the hand-written protocol -- occurs in the package only inside _lib.py"""
+    pkg = os.path.join(ROOT, "nerfsafetyvalidation_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for fn in files:
+            path = os.path.join(dirpath, fn)
+            if fn.endswith(".py") and path != os.path.join(pkg, "_lib.py"):
+                assert "_lib.check(" not in open(path).read(), path
 
 
 def test_product_never_imports_the_oracle():

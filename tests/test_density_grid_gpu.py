@@ -110,6 +110,41 @@ def test_update_extra_state_golden(device):
     assert 0.1 < changed < 0.6
 
 
+def test_update_extra_state_is_a_new_version_of_the_bitfield(device):
+    """update_extra_state writes density_bitfield through its raw pointer (ngp_density_grid_finish).  That is a new version of the
+    tensor: march_rays, which keeps derived copies of the occupancy bits per (tensor, version), must march the new bits afterwards."""
+    from nerfsafetyvalidation_amd import _lib, raymarching
+    from nerfsafetyvalidation_amd.raymarching import raymarching as rm
+    f = np.load(os.path.join(G, "density_grid.npz"))
+    net = _model(f, device)
+    H, bound = int(f["grid_size"]), float(f["bound"])
+    assert _lib.lib().ngp_occupancy_lin_bytes(net.cascade, H) > 0
+    g = (torch.arange(8, dtype=torch.float32, device=device) + 0.5) / 8 * 1.6 - 0.8           # 64 rays along +z through the box
+    xy = torch.stack(torch.meshgrid(g, g, indexing="ij"), -1).reshape(-1, 2) * bound
+    rays_o = torch.cat([xy, torch.full((64, 1), -3 * bound, device=device)], 1).contiguous()
+    rays_d = torch.tensor([[0.0, 0.0, 1.0]], device=device).repeat(64, 1)
+    aabb = torch.tensor([-bound] * 3 + [bound] * 3, dtype=torch.float32, device=device)
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, 0.2)
+    alive = torch.arange(64, dtype=torch.int32, device=device)
+    args = lambda: (64, 2, alive, nears.clone(), rays_o, rays_d, bound, net.density_bitfield, net.cascade, H, nears, fars, 128,   # noqa: E731
+                    False, 0.0, 1024)
+    assert int((raymarching.march_rays(*args())[2][:, 0] > 0).sum()) == 0                     # the empty bitfield, and its derived copies
+    before = (net.density_bitfield._version, net.density_grid._version)
+    torch.manual_seed(int(f["full1_seed"]))
+    net.update_extra_state()
+    assert net.density_bitfield._version > before[0] and net.density_grid._version > before[1]
+    assert bool(net.density_bitfield.any())
+    out = {}
+    try:
+        for lin in (True, False):
+            rm.USE_OCCUPANCY_LIN = lin
+            out[lin] = [t.clone() for t in raymarching.march_rays(*args())]
+    finally:
+        rm.USE_OCCUPANCY_LIN = True
+    for a, b in zip(out[True], out[False]):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
 def test_update_extra_state_through_the_fused_density_kernel(device):
     """fp16 backbone under autocast: update_extra_state queries sigma through ngp_network_density (no per-cell records are built);
     the result agrees with the same sweep through the network's own density() up to the fp16 network's noise"""

@@ -48,6 +48,19 @@ def test_native_library_is_loaded(device):
     assert "libngp_hip.so" in maps
 
 
+def test_call_refuses_a_non_contiguous_tensor_and_workspace_sizes_by_the_query(device):
+    from nerfsafetyvalidation_amd import _lib
+    coords = torch.zeros(3, 8, dtype=torch.int32, device=device).t()         # [8,3], strides (1, 8)
+    assert not coords.is_contiguous()
+    with pytest.raises(RuntimeError, match="contiguous"):
+        _lib.call("morton3D", coords, 8, torch.empty(8, dtype=torch.int32, device=device))
+    # a query that answers 0 gives no buffer (the fp32 table gradient uses none); one that answers n gives n bytes on the device
+    assert _lib.workspace("grid_encode_backward", 1 << 20, 3, 2, 16, _lib.NGP_F32, device=device) == (None, 0)
+    buf, nbytes = _lib.workspace("march_rays_train", 1000, device=device)
+    assert nbytes == _lib.lib().ngp_march_rays_train_workspace(1000) > 0
+    assert buf.dtype == torch.uint8 and buf.shape == (nbytes,) and buf.device == torch.device(device) and buf.data_ptr() % 256 == 0
+
+
 def test_near_far_bit_exact(device):
     from nerfsafetyvalidation_amd import raymarching
     rng = np.random.default_rng(0)
@@ -163,6 +176,53 @@ def test_march_rays_follows_the_bitfield_it_is_given(device):
             del tmp
     finally:
         rm.USE_OCCUPANCY_LIN = True
+
+
+def _march_both_ways(args):
+    """march_rays(*args) with the derived copies of the occupancy bits and with the plain kernel -> {True: outputs, False: outputs}"""
+    from nerfsafetyvalidation_amd import raymarching
+    from nerfsafetyvalidation_amd.raymarching import raymarching as rm
+    out = {}
+    try:
+        for lin in (True, False):
+            rm.USE_OCCUPANCY_LIN = lin
+            out[lin] = [t.clone() for t in raymarching.march_rays(*args)]
+    finally:
+        rm.USE_OCCUPANCY_LIN = True
+    return out
+
+
+def _rays_through_box(n_side, bound, device):
+    """n_side^2 parallel rays along +z through the middle of the box, from outside it -> (rays_o, rays_d, nears, fars, alive)"""
+    from nerfsafetyvalidation_amd import raymarching
+    g = (np.arange(n_side, dtype=np.float32) + 0.5) / n_side * 1.6 - 0.8
+    xy = np.stack(np.meshgrid(g, g, indexing="ij"), -1).reshape(-1, 2) * bound
+    rays_o = _t(np.concatenate([xy, np.full((len(xy), 1), -3 * bound, np.float32)], 1).astype(np.float32), device)
+    rays_d = _t(np.tile(np.array([[0, 0, 1]], np.float32), (len(xy), 1)), device)
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, _t(np.array([-bound] * 3 + [bound] * 3, np.float32), device), 0.05)
+    return rays_o, rays_d, nears, fars, torch.arange(len(xy), dtype=torch.int32, device=device)
+
+
+def test_march_rays_sees_a_bitfield_written_through_its_pointer(device):
+    """packbits(grid, thresh, bitfield) writes the caller's bitfield through its raw pointer: the write must count as a new version of
+    the tensor, or march_rays goes on with the derived copies of the bits it marched before (the smallest grid that has them: C = 1,
+    H = 16, a 512-byte bitfield; march_cases.CONFIGS[7])."""
+    import march_cases as MC
+    from nerfsafetyvalidation_amd import raymarching
+    cfg = MC.CONFIGS[7]
+    assert (cfg.C, cfg.H) == (1, 16) and MC.lin_bytes(cfg.C, cfg.H) > 0
+    rays_o, rays_d, nears, fars, alive = _rays_through_box(8, cfg.bound, device)
+    bf = torch.zeros(cfg.C * cfg.H ** 3 // 8, dtype=torch.uint8, device=device)
+    assert bf.numel() == 512
+    args = (alive.numel(), 2, alive, nears.clone(), rays_o, rays_d, cfg.bound, bf, cfg.C, cfg.H, nears, fars, 128, False, cfg.dt_gamma, cfg.max_steps)
+    assert int((raymarching.march_rays(*args)[2][:, 0] > 0).sum()) == 0          # empty grid, derived copies built: no sample
+    version = bf._version
+    raymarching.packbits(torch.ones(cfg.C, cfg.H ** 3, device=device), 0.5, bf)
+    assert bf._version > version and bool((bf == 255).all())
+    out = _march_both_ways(args)
+    for a, b in zip(out[True], out[False]):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert bool((out[True][2][:, 0] > 0).any())
 
 
 @pytest.mark.parametrize("max_steps", [16, 48, 100, 4096])
