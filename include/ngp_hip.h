@@ -362,6 +362,23 @@ NGP_API int ngp_render_ctx_destroy(ngp_render_ctx* ctx);
  * ignored, because march_rays seeds its jitter with the list index, raymarching.cu:819). */
 NGP_API int ngp_render_ctx_set_frame_width(ngp_render_ctx* ctx, uint32_t width);
 
+/* Diagnostics: switches of the launch sizing for this context's calls (0 = the default).  A context's own word,
+ * apart from the debug flag word of enum ngp_debug_flag, whose set of bits is frozen.  Results do not depend on it; any other bit
+ * is refused with NGP_EINVAL. */
+#define NGP_SCHED_NO_FORECAST 1u    /* multi-iteration launches are sized by the recent death rate alone, not by the saturation forecast of the live rays */
+NGP_API int ngp_render_ctx_set_schedule_flags(ngp_render_ctx* ctx, uint32_t flags);
+
+/* Schedule counters of the context's most recent ngp_render_rays call -> out[0..7] (all zero before the first call).  Synchronises
+ * the stream of that call, which must still exist.
+ *   [0] launches that covered several reference iterations, failed their verification and were rolled back (ngp_render_stats::replayed)
+ *   [1] network samples evaluated in those launches and discarded with them
+ *   [2] reserved (0)
+ *   [3] launches that the saturation forecast made smaller than the death rate alone would have (NGP_SCHED_NO_FORECAST: 0)
+ *   [4] the last multi-iteration launch: deaths forecast before its last verified iteration, [5] deaths counted there
+ *   [6] multi-iteration launches run (rolled-back ones included)
+ *   [7] reserved (0) */
+NGP_API int ngp_render_ctx_schedule_stats(ngp_render_ctx* ctx, uint64_t* out);
+
 /* rays_o/rays_d [N,3] f32, nears/fars [N] f32 (from ngp_near_far_from_aabb).
  * Outputs weights_sum [N], depth [N], image [N,3] f32: the accumulated values BEFORE the
  * background mix / depth normalisation of renderer.py:375-378 (done by the caller as in the

@@ -151,6 +151,7 @@ class FusedModel:
         self._packed = None      # the two weight blobs as MFMA fragments (ngp_pack_weights), packed with the cell tables
         self._packed_bwd = None  # ... and transposed, for the fused backward of `run` (ngp_pack_weights_bwd), on first use
         self.debug = None        # (flags, stamps tensor or None, sample-hash tensor or None): diagnostics state of THIS model's contexts
+        self.schedule_flags = None   # diagnostics: NGP_SCHED_* switches of the launch sizing (ngp_render_ctx_set_schedule_flags; 0 = back to the default)
 
     # ---- construction from the two backbones ---------------------------------------------------------
     @classmethod
@@ -327,6 +328,27 @@ class FusedModel:
         """statistics of the calling thread's last render"""
         return getattr(self._tls, "stats", None)
 
+    SCHEDULE_STATS = ("rolled_back", "discarded_samples", "reserved_2", "forecast_sized", "forecast_deaths", "counted_deaths",
+                      "multi_iteration_launches", "reserved_7")
+
+    def schedule_stats(self):
+        """schedule counters of the calling thread's last render (ngp_render_ctx_schedule_stats; waits for its stream): how its
+        multi-iteration launches were sized and what the rolled-back ones cost.  None before the thread's first render"""
+        with self._ctx_lock:
+            ent = self._ctxs.get(threading.get_ident())
+        if ent is None:
+            return None
+        out = (C.c_uint64 * 8)()
+        _lib.call("render_ctx_schedule_stats", ent[0], out)
+        return dict(zip(self.SCHEDULE_STATS, (int(v) for v in out)))
+
+    def reset_context(self):
+        """destroys the calling thread's render context: its next render starts with a new one"""
+        with self._ctx_lock:
+            ent = self._ctxs.pop(threading.get_ident(), None)
+        if ent is not None:
+            _lib.lib().ngp_render_ctx_destroy(ent[0])
+
     def _context(self, N):
         lib = _lib.lib()
         key = threading.get_ident()
@@ -363,6 +385,8 @@ class FusedModel:
         if self.debug is not None:
             flags, stamps, hashes = self.debug
             _lib.call("render_ctx_set_debug", ctx, 1, int(flags), stamps, hashes)
+        if self.schedule_flags is not None:
+            _lib.call("render_ctx_set_schedule_flags", ctx, int(self.schedule_flags))
         _lib.call("render_rays", ctx, C.byref(m), rays_o, rays_d, nears.contiguous(), fars.contiguous(), N, float(dt_gamma), int(max_steps),
                   int(perturb), weights_sum, depth, image, last_s, last_c, self._pad_value() if want_last else None,
                   C.byref(stats) if need_stats else None, 0)

@@ -25,6 +25,7 @@ NGP_DBG_NO_BLOCK_JUMP, NGP_DBG_NO_COARSE, NGP_DBG_NO_SLOW_SORT, NGP_DBG_NO_LIN =
 NGP_DBG_ONE_ITER_PER_LAUNCH, NGP_DBG_NO_TILES = 1 << 8, 1 << 13
 NGP_DBG_NO_PRE_VERDICT, NGP_DBG_WIDE_ITEMS, NGP_DBG_REPLAY_ONE_ITER = 1 << 14, 1 << 15, 1 << 16
 NGP_DBG_LANE_MARCH, NGP_DBG_PROBE_PER_SAMPLE = 1 << 17, 1 << 18
+NGP_SCHED_NO_FORECAST = 1                                        # ngp_render_ctx_set_schedule_flags (a context's own word, not the debug flag word)
 NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
 NGP_COMPONENTS_TILE = (4, 4, 16)                                 # NGP_COMPONENTS_TILE_X / _Y / _Z: the tile ngp_label_components labels in LDS
 
@@ -151,6 +152,8 @@ SIGNATURES = {
     "ngp_render_ctx_create": [_u32, C.POINTER(_vp)],
     "ngp_render_ctx_destroy": [_vp],
     "ngp_render_ctx_set_frame_width": [_vp, _u32],
+    "ngp_render_ctx_set_schedule_flags": [_vp, _u32],
+    "ngp_render_ctx_schedule_stats": [_vp, C.POINTER(C.c_uint64)],
     "ngp_render_rays": [_vp, C.POINTER(ModelStruct), _vp, _vp, _vp, _vp, _u32, _f32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                         C.POINTER(C.c_float), C.POINTER(RenderStats), _int, _st],
     "ngp_network_forward": [C.POINTER(ModelStruct), _vp, _vp, _u32, _vp, _vp, _st],

@@ -40,6 +40,7 @@
 #include <atomic>
 
 #include "fused_net.hpp"
+#include "launch_plan.hpp"
 #include "occupancy.hpp"
 
 namespace ngp {
@@ -59,6 +60,11 @@ struct Ctl {
     uint32_t iters, last_n_alive, last_n_step, pad;
     unsigned long long samples_marched, samples_slots;
     uint32_t spec, rollbacks, backoff, rsv;   // see "several reference iterations per launch" below
+    // schedule diagnostics (ngp_render_ctx_schedule_stats): accumulated by k_render_compact, nothing in the loop reads them back
+    unsigned long long discarded;             // network samples of the launches that were rolled back
+    uint32_t fc_sized, spec_launches;         // launches the saturation forecast made smaller; multi-iteration launches run
+    uint32_t fc_pred, fc_actual;              // last multi-iteration launch: deaths forecast / counted before its last verified iteration
+    uint32_t plan_pred, plan_headroom, plan_rate, plan_k_rate;   // the plan of the launch this state starts (trace, fc_pred)
 };
 
 // Several reference iterations per launch.  While more than half of the N rays are alive the reference's schedule is
@@ -72,19 +78,20 @@ struct Ctl {
 // loads it), the alive list is handed on unchanged and the iteration is run again on its own -- a wrong guess costs one
 // launch, never a result.  Not used with perturb (the jitter of an iteration is seeded with the ray's index in that
 // iteration's list).
-constexpr uint32_t kSpecK = 8;            // most reference iterations per launch
+// (kSpecK, the most reference iterations per launch, and the sizing rule are launch_plan.hpp's)
 constexpr uint32_t kSpecMarginDiv = 16;   // first launch: entered only if n_alive - N/2 > N / kSpecMarginDiv
 // largest q for which a launch covers several iterations (K * q <= 8 samples per ray and launch, K >= 2)
 constexpr uint32_t kSpecMaxQ = 8;
 constexpr uint32_t kSpecMaxSamples = 32;  // samples per ray and launch in the n_step >= 5 regimes (k_render_compact's cap_hi)
 constexpr uint32_t kSpecMidSamples = 8;   // ... and in the n_step 2..4 regimes (its cap_mid_max)
-constexpr uint32_t kSpecSafetyX2 = 1;     // later launches: sized for kSpecSafetyX2 / 2 x the recent death rate (+ 4 sigma + 16 rays).  1.5 x until
-                                          // a failed launch came to be replayed as its verified prefix: a wrong guess now costs the discarded
-                                          // launch only, and the larger launches win (bound-2 frame: 49.5 -> 41.8 launches, 4.80 -> 4.48 ms)
 constexpr int kDeathShards = 64;
 // per launch parity: [kDeathShards][kSpecK] deaths per iteration (k_render_iter) | [kDeathShards][kSpecK] rays whose MARCH runs out of
-// samples in that iteration (k_march_ahead: known before the network runs, see truncate_launch)
-constexpr uint32_t kDeathWords = 2u * kDeathShards * kSpecK;
+// samples in that iteration (k_march_ahead: known before the network runs, see truncate_launch) | [kDeathShards][kForecastBuckets]
+// the saturation forecast of the launch's survivors (k_render_iter step 4 -> the sizing code of k_render_compact, nothing else).
+// The first two blocks are cleared right before a multi-iteration launch uses them, the forecast before EVERY launch -- always the
+// other parity's, never the buffer the running k_render_compact's blocks are reading (DESIGN "A race found by sharing the GPU").
+constexpr uint32_t kForecastAt = 2u * kDeathShards * kSpecK;
+constexpr uint32_t kDeathWords = kForecastAt + kDeathShards * kForecastBuckets;
 // work-queue heads: one per shard (chunk c belongs to shard c & 7), each on its own 128-byte line, two sets (ping-pong with Ctl)
 struct QueueHeads { uint32_t head[8][32]; };
 
@@ -129,6 +136,7 @@ struct RenderArgs {
     uint32_t pre_verdict;             // k_march_ahead counts the rays whose march runs out per iteration (truncate_launch); 0: diagnostics
     uint32_t wave_march_max;          // launches of at most this many rays march one WAVE per ray (march_ahead_wave); 0: never
     uint32_t cell_runs;               // k_march_ahead: the samples that follow a probe's in the same occupied cell are taken without probing
+    uint32_t forecast;                // k_render_iter leaves the saturation forecast of its survivors (death_shards + kForecastAt); 0: diagnostics
 };
 
 // Work items of k_render_iter: W consecutive entries of the alive list, one wave each.  64 while the list fills the chip's wave slots
@@ -477,7 +485,7 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
             }
             NGP_STAMP(0)
             // ---- 2. compact the wave's samples and run the network 16 at a time
-            uint32_t incl = cnt;      // (wave_ops.hpp's scan_inclusive<AddOp> and last_lane, written out: k_render_iter must not change)
+            uint32_t incl = cnt;      // (wave_ops.hpp's scan_inclusive<AddOp> and last_lane, written out since the refactor that compared ISA)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const uint32_t o = __shfl_up(incl, off, 64);
@@ -630,14 +638,34 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
                 if (lane == 0 && cdead) atomicAdd(&ra.death_shards[ds + m], cdead);
             }
         }
+        if (ra.forecast) {
+            // Saturation forecast, for the sizing of the NEXT launch only (k_render_compact, plan_launch): after how many further samples
+            // does this survivor's T = 1 - ws fall below 1e-4 if the opacity of its last sample persists?  1 .. 8 are counted per wave
+            // (ballots, as the deaths are) into the launch's forecast shards; anything later, and rays whose last sample was empty, are not.
+            // (that sample's sigma and dt are still in the wave's slab: a survivor composited the last slot of the last sub-pass)
+            uint32_t fb = 0;
+            const uint32_t last_slot = lane * kCh + (n_step - 1u) % (uint32_t)kCh;
+            const float alpha_last = survive ? 1.0f - expf(-S.sig[last_slot] * S.dt[last_slot]) : 0.0f;
+            if (alpha_last > 0.0f) {
+                const float x = ceilf(__logf(1e-4f / (1.0f - ws)) / __logf(1.0f - alpha_last));
+                if (x <= (float)kForecastBuckets) fb = x < 1.0f ? 1u : (uint32_t)x;     // (NaN: not counted)
+            }
+            if (__any(fb != 0u)) {
+                uint32_t* fc = ra.death_shards + kForecastAt + ((blockIdx.x * kWaves + wid) % kDeathShards) * kForecastBuckets;
+                for (uint32_t s = 1; s <= kForecastBuckets; s++) {
+                    const uint32_t n = (uint32_t)__popcll(__ballot(fb == s));
+                    if (lane == 0 && n) atomicAdd(&fc[s - 1], n);
+                }
+            }
+        }
         {
             // samples the reference marches for this ray: all of every iteration it enters alive (march_rays runs before
             // composite_rays); in a multi-iteration launch a ray that completed steps_done samples entered iterations 0 .. steps_done / spec
             const uint32_t entered = (spec && !survive) ? (steps_done / spec + 1) * spec : n_step;
             uint32_t rm = active ? (emitted < entered ? emitted : entered) : 0u;
-#pragma unroll      // (wave_sum, written out: k_render_iter must not change)
+#pragma unroll      // (wave_sum, written out since the refactor that compared ISA)
             for (int off = 32; off > 0; off >>= 1) rm += __shfl_xor(rm, off, 64);
-            wave_samples = rm;
+            wave_samples = (uint32_t)__builtin_amdgcn_readfirstlane((int)rm);   // (wave-uniform after the reduction: the running total stays scalar)
         }
         wave_total += wave_samples;
         // padding rows of the reference's [M_padded] tensors (M += 128 - M % 128), written by the last chunk's wave
@@ -711,7 +739,7 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
     if (g >= n_blocks) return;
     const uint32_t first = g * 8;
     // ---- a launch that covered several reference iterations is verified first (every block reaches the same verdict) ----
-    __shared__ uint32_t deaths[kSpecK], exhausted[kSpecK];
+    __shared__ uint32_t deaths[kSpecK], exhausted[kSpecK], forecast[kForecastBuckets];
     __shared__ uint32_t verdict_bad, verdict_keep;
     if (threadIdx.x < kSpecK) {
         uint32_t d = 0, x = 0;
@@ -722,32 +750,28 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
             }
         deaths[threadIdx.x] = d;
         exhausted[threadIdx.x] = x;
+    } else if (threadIdx.x >= 64 && threadIdx.x < 128 && g == n_blocks - 1) {   // the forecast: read by the sizing code below, nothing else
+        const uint32_t* f = death_shards + kForecastAt + (threadIdx.x - 64u) * kForecastBuckets;      // (wave 1, a shard per lane)
+#pragma unroll
+        for (uint32_t b = 0; b < kForecastBuckets; b++) {
+            const uint32_t sum = wave_sum(f[b]);
+            if (threadIdx.x == 64) forecast[b] = sum;
+        }
     }
     __syncthreads();
     truncate_launch(c, exhausted, N);          // the launch k_render_iter actually ran (same counts, same cut)
     if (threadIdx.x == 0) {
-        // K = c.n_step / q reference iterations of q = c.spec samples each: n_alive(i + j) = n_alive(i) - deaths before j.  Each must
-        // have been run with n_step = clamp(N // n_alive, 1, 8) == q, and the loop would have stopped at the first empty list.
-        // `keep`: the iterations before the first violation.  They WERE the reference's (every ray was processed exactly as the
-        // reference processes it up to there, so their death counts are the true ones): a launch of just those verifies for certain.
-        uint32_t bad = 0, keep = 0;
-        if (c.spec) {
-            const uint32_t q = c.spec, K = c.n_step / q;
-            uint32_t alive = c.n_alive;
-            keep = K;
-            for (uint32_t j = 0; j < K; j++) {
-                if (alive == 0) break;                            // the reference stops here; the rest of the launch had no ray to touch
-                const uint32_t want_q = N / alive;
-                if (j > 0 && (want_q < 1 ? 1u : (want_q > 8 ? 8u : want_q)) != q) { bad = 1; keep = j; break; }
-                alive -= deaths[j];
-                // the caller wants the reference's last-iteration tensors: that iteration has to run on its own (bit 1 of spec_allowed)
-                if ((spec_allowed & 2u) && alive == 0) { bad = 1; keep = j; break; }
-            }
-        }
-        verdict_bad = bad;
-        verdict_keep = keep;
+        // K = c.n_step / q reference iterations of q = c.spec samples each, judged by launch_verdict (launch_plan.hpp); bit 1 of
+        // spec_allowed: the caller wants the reference's last-iteration tensors, so that iteration has to run on its own
+        LaunchVerdict v = {0u, 0u};
+        if (c.spec) v = launch_verdict(N, c.n_alive, c.spec, c.n_step / c.spec, deaths, (spec_allowed & 2u) != 0u);
+        verdict_bad = v.bad;
+        verdict_keep = v.keep;
     }
     __syncthreads();
+    // the other parity's forecast shards start every launch at zero (its death counts: only a multi-iteration launch's, below)
+    if (g == n_blocks - 1)
+        for (uint32_t i = kForecastAt + threadIdx.x; i < kDeathWords; i += 256) death_next[i] = 0;
     if (verdict_bad) {
         // ROLLBACK: the launch was not equivalent to the reference's iterations.  Every ray it processed gets the state it
         // started from back, the alive list is handed on unchanged, and the iteration is run again on its own.
@@ -762,12 +786,23 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
         if (g == n_blocks - 1 && threadIdx.x == 0) {
             Ctl n = c;
             n.rollbacks = c.rollbacks + 1;
+            {   // schedule diagnostics: what the discarded launch cost, and how its forecast compared
+                unsigned long long lost = 0;
+                for (int i = 0; i < kStatShards; i++) lost += stat_shards_rw[i];
+                n.discarded = c.discarded + lost;
+                n.spec_launches = c.spec_launches + 1;
+                uint32_t before_last = 0;
+                for (uint32_t j = 0; j + 1 < c.n_step / c.spec; j++) before_last += deaths[j];
+                n.fc_pred = c.plan_pred;
+                n.fc_actual = before_last;
+                n.plan_pred = 0; n.plan_headroom = 0; n.plan_rate = 0; n.plan_k_rate = 0;   // (the replay is not a guess)
+            }
             if (verdict_keep >= 2 && !(spec_allowed & 4u)) {
-                // the iterations before the violation again, as one launch: certain to verify (see `keep` above)
+                // the iterations before the violation again, as one launch: certain to verify (see launch_verdict's `keep`)
                 n.spec = c.spec;
                 n.n_step = verdict_keep * c.spec;
                 n.backoff = 0;
-                for (uint32_t i = 0; i < kDeathWords; i++) death_next[i] = 0;     // (the other parity's buffer: nobody reads it now)
+                for (uint32_t i = 0; i < kForecastAt; i++) death_next[i] = 0;     // (the other parity's buffer: nobody reads it now)
             } else {
                 n.spec = 0;
                 const uint32_t ns = c.n_alive ? N / c.n_alive : 8;
@@ -789,7 +824,7 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
         tf += v >> 16;
         if (j < first) { pf += v & 0xffffu; ps += v >> 16; }
     }
-#pragma unroll      // (three wave_sum_lane0, interleaved, and a fourth below: written out, k_render_compact must not change)
+#pragma unroll      // (three wave_sum_lane0, interleaved, and a fourth below: written out since the refactor that compared ISA)
     for (int off = 32; off > 0; off >>= 1) {
         pf += __shfl_down(pf, off, 64);
         ps += __shfl_down(ps, off, 64);
@@ -852,36 +887,35 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
             n.iters = c.iters + it;
             n.samples_slots = slots;
             n.step = c.step + it * q;
+            n.spec_launches = c.spec_launches + 1;                // schedule diagnostics: how the launch's forecast compared
+            uint32_t before_last = 0;
+            for (uint32_t j = 0; j + 1 < K; j++) before_last += deaths[j];
+            n.fc_pred = c.plan_pred;
+            n.fc_actual = before_last;
         }
-        uint32_t ns = n.n_alive ? N / n.n_alive : 8;
-        n.n_step = ns < 1 ? 1 : (ns > 8 ? 8 : ns);
+        n.n_step = schedule_n_step(N, n.n_alive);
         n.done = (n.n_alive == 0 || n.step >= max_steps) ? 1 : 0;
-        // The next launch may cover several reference iterations of q = n_step samples (K * q <= 8): as many as the recent death
-        // rate (plus four standard deviations of a count that size) leaves room for above the n_alive at which the reference's
-        // n_step changes (N // n_alive == q  <=>  n_alive > N / (q + 1)).  A wrong guess costs one launch (rollback above).
+        // The next launch may cover several reference iterations of q = n_step samples: as many as plan_launch (launch_plan.hpp)
+        // finds room for above the n_alive at which the reference's n_step changes, judged by the recent death rate and by the
+        // saturation forecast k_render_iter left of this launch's survivors (bit 3 of spec_allowed, diagnostics: by the rate
+        // alone).  A wrong guess costs one launch (rollback above).
         n.spec = 0;
+        n.plan_pred = 0; n.plan_headroom = 0; n.plan_rate = 0; n.plan_k_rate = 0;
         if (n.backoff) n.backoff--;
         else if (spec_allowed && !n.done && n.n_step <= kSpecMaxQ && (n.n_step == 8 || n.n_alive > N / (n.n_step + 1))) {
             const uint32_t q = n.n_step;
             const bool own_last = (spec_allowed & 2u) != 0;     // the last iteration must not be part of such a launch
             uint32_t room = (max_steps - n.step) / q;
             if (own_last && room) room--;
-            const uint32_t headroom = n.n_alive - (q == 8 ? 0u : N / (q + 1)) - 1;
-            uint32_t sq = 0;
-            while ((unsigned long long)(sq + 1) * (sq + 1) <= recent) sq++;
-            const unsigned long long rate = (unsigned long long)recent + 4ull * sq + 16ull;
-            uint32_t K = (uint32_t)((unsigned long long)headroom * 2u / (kSpecSafetyX2 * rate));
-            // at most 8 samples per ray and launch while n_step is small; in the n_step >= 5 regimes (few rays, every launch
-            // latency-bound) up to kSpecMaxSamples.  With n_step = 8 the guess cannot fail: N // n_alive only grows as rays die.
-            const uint32_t cap_mid = 8u * q < cap_mid_max ? 8u * q : cap_mid_max;      // (n_alive <= N / q: at most 8 N samples per launch)
-            const uint32_t cap_samples = q == 1 ? 8u : (q <= 4 ? cap_mid : cap_hi);
-            const uint32_t capK = cap_samples / q < kSpecK ? cap_samples / q : kSpecK;
-            K = (q == 8 && !own_last) ? capK : (K < capK ? K : capK);
-            K = K < room ? K : room;
-            if (K >= 2) { n.spec = q; n.n_step = K * q; }
+            const LaunchPlan p = plan_launch(N, n.n_alive, q, recent, (spec_allowed & 8u) ? nullptr : forecast, room, cap_mid_max, cap_hi, own_last);
+            if (p.K < p.K_rate && p.K_rate >= 2) n.fc_sized = c.fc_sized + 1;
+            if (p.K >= 2) {
+                n.spec = q; n.n_step = p.K * q;
+                n.plan_pred = p.forecast; n.plan_headroom = p.headroom; n.plan_rate = p.rate; n.plan_k_rate = p.K_rate;
+            }
         }
         if (n.spec)   // the next launch counts deaths per iteration: its buffer (not the one this kernel's blocks are reading) starts at zero
-            for (uint32_t i = 0; i < kDeathWords; i++) death_next[i] = 0;
+            for (uint32_t i = 0; i < kForecastAt; i++) death_next[i] = 0;
         *nxt = n;
         for (int i = 0; i < 8; i++) nxt_heads->head[i][0] = 0;
         publish_status(host_slot, n, seq, fin_host, call_tag);
@@ -982,6 +1016,9 @@ using namespace ngp;
 struct ngp_render_ctx {
     uint32_t max_rays = 0;
     uint32_t frame_width = 0;               // ngp_render_ctx_set_frame_width: rays are the pixels of row-major frames this wide (0: unknown)
+    uint32_t sched_flags = 0;               // ngp_render_ctx_set_schedule_flags: NGP_SCHED_* switches of the launch sizing (diagnostics)
+    const void* last_ctl = nullptr;         // the device state after the last launch of the most recent call, and its stream
+    hipStream_t last_stream = nullptr;      // (ngp_render_ctx_schedule_stats)
     int32_t* alive[2] = {nullptr, nullptr};
     int32_t* staging = nullptr;
     uint32_t* chunk_count = nullptr;
@@ -1074,6 +1111,26 @@ int ngp_render_ctx_create(uint32_t max_rays, ngp_render_ctx** out) {
 int ngp_render_ctx_set_frame_width(ngp_render_ctx* ctx, uint32_t width) {
     NGP_REQUIRE(ctx, "render_ctx_set_frame_width: null context");
     ctx->frame_width = width;
+    return NGP_OK;
+}
+
+int ngp_render_ctx_set_schedule_flags(ngp_render_ctx* ctx, uint32_t flags) {
+    NGP_REQUIRE(ctx, "render_ctx_set_schedule_flags: null context");
+    NGP_REQUIRE((flags & ~NGP_SCHED_NO_FORECAST) == 0, "render_ctx_set_schedule_flags: unknown bits 0x%x", flags);
+    ctx->sched_flags = flags;
+    return NGP_OK;
+}
+
+int ngp_render_ctx_schedule_stats(ngp_render_ctx* ctx, uint64_t* out) {
+    NGP_REQUIRE(ctx && out, "render_ctx_schedule_stats: null pointer");
+    Ctl fin = {};
+    if (ctx->last_ctl &&
+        (hipStreamSynchronize(ctx->last_stream) != hipSuccess || hipMemcpy(&fin, ctx->last_ctl, sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("render_ctx_schedule_stats: %s", hipGetErrorString(hipGetLastError()));
+        return NGP_ELAUNCH;
+    }
+    out[0] = fin.rollbacks; out[1] = fin.discarded; out[2] = 0; out[3] = fin.fc_sized;
+    out[4] = fin.fc_pred; out[5] = fin.fc_actual; out[6] = fin.spec_launches; out[7] = 0;
     return NGP_OK;
 }
 
@@ -1188,6 +1245,34 @@ static void enqueue_launch(ngp_render_ctx* ctx, const NetArgs& na, const GridLev
                                                        ctx->backup, ctx->rays_t, ra.weights_sum, ra.depth, ra.image, ra.sample_hash, ctx->stat_shards,
                                                        ctx->death_shards + (size_t)(cur ^ 1) * kDeathWords, ra.wave_slots, kSpecMidSamples,
                                                        kSpecMaxSamples, ctx->fin_dev, call_tag);
+}
+
+// NGP_TRACE_SCHEDULE: one line per multi-iteration launch -- its plan (K iterations of q samples, what the death rate alone would have
+// taken, the headroom, the per-iteration guess, the forecast deaths before the last verified iteration), what happened (deaths and
+// march-exhausted rays per iteration) and whether it was rolled back.  Waits for the launch: the trace serialises host
+// and device, the schedule itself is the device's and does not change.
+static void trace_launch(const ngp_render_ctx* ctx, hipStream_t s, uint32_t launch, uint32_t call_tag) {
+    const uint32_t cur = launch & 1;
+    Ctl in = {}, out = {};
+    uint32_t words[kDeathWords];
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&in, ctx->ctl + cur, sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&out, ctx->ctl + (cur ^ 1), sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(words, ctx->death_shards + (size_t)cur * kDeathWords, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess)
+        return;
+    if (in.done || !in.spec) return;
+    const uint32_t q = in.spec, K = in.n_step / q;
+    char deaths[128] = "", gone[128] = "";
+    size_t nd = 0, ng = 0;
+    for (uint32_t j = 0; j < K && j < kSpecK; j++) {
+        uint32_t d = 0, x = 0;
+        for (int sh = 0; sh < kDeathShards; sh++) { d += words[sh * kSpecK + j]; x += words[kDeathShards * kSpecK + sh * kSpecK + j]; }
+        nd += (size_t)snprintf(deaths + nd, sizeof(deaths) - nd, "%s%u", j ? "," : "", d);
+        ng += (size_t)snprintf(gone + ng, sizeof(gone) - ng, "%s%u", j ? "," : "", x);
+    }
+    fprintf(stderr, "[ngp] plan {\"call\": %u, \"launch\": %u, \"n_alive\": %u, \"q\": %u, \"K\": %u, \"K_rate\": %u, \"headroom\": %u, \"rate\": %u, "
+            "\"forecast\": %u, \"deaths\": [%s], \"exhausted\": [%s], \"cut_short\": %u, \"rolled_back\": %u, \"n_alive_after\": %u}\n",
+            call_tag, launch + 1, in.n_alive, q, K, in.plan_k_rate, in.plan_headroom, in.plan_rate, in.plan_pred, deaths, gone, out.rsv - in.rsv,
+            out.rollbacks - in.rollbacks, out.n_alive);
 }
 
 // Consumes every status word that has already landed (known -> launched); blocks only when the host is kLookahead launches ahead.
@@ -1308,8 +1393,9 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     }
     // several reference iterations per launch (see Ctl), not with jitter.  bit 0: launches may cover several iterations; bit 1: the last
     // iteration runs on its own (its tensors are wanted); bit 2 (diagnostics): a failed launch is replayed as ONE iteration instead of
-    // its verified prefix
-    const uint32_t spec_allowed = (!dbg.spec_off() && perturb == 0) ? (1u | (last_sigmas ? 2u : 0u) | (dbg.prefix_replay_off() ? 4u : 0u)) : 0u;
+    // its verified prefix; bit 3 (diagnostics): launches are sized by the death rate alone, not by the saturation forecast
+    const uint32_t spec_allowed = (!dbg.spec_off() && perturb == 0)
+                                      ? (1u | (last_sigmas ? 2u : 0u) | (dbg.prefix_replay_off() ? 4u : 0u) | ((ctx->sched_flags & NGP_SCHED_NO_FORECAST) ? 8u : 0u)) : 0u;
     // scheduling hint (ngp_render_ctx_set_frame_width): whole rows of 4x4-pixel tiles only; not with jitter (seeded with the list index)
     const uint32_t fw = ctx->frame_width;
     const uint32_t tile_w = (perturb == 0 && !dbg.tile_off() && fw >= 4 && fw % 4 == 0 && N % (4 * fw) == 0) ? fw : 0u;
@@ -1324,6 +1410,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     ra.last_sigmas = last_sigmas; ra.last_rgbs = last_rgbs;
     if (pad_value_host) { ra.pad_sigma = pad_value_host[0]; ra.pad_r = pad_value_host[1]; ra.pad_g = pad_value_host[2]; ra.pad_b = pad_value_host[3]; }
     fill_render_args(ctx, model, dbg, N, dt_gamma, max_steps, perturb, ra);
+    ra.forecast = (spec_allowed && !(ctx->sched_flags & NGP_SCHED_NO_FORECAST)) ? 1u : 0u;         // (ngp_render_ctx_set_schedule_flags)
     const bool lin = choose_occupancy(ctx, model, dbg, s, ra);
     if ((ra.sort_slow || tile_w) && last_sigmas) {
         // regrouped alive list + last-iteration tensors requested: collect per-ray records, restore the row order afterwards
@@ -1352,6 +1439,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     while (!done) {
         enqueue_launch(ctx, na, lv, ra, iter_kernel, lds, lin, ub, launched, spec_allowed, call_tag, s);
         launched++;
+        if (trace) trace_launch(ctx, s, launched - 1, call_tag);
         rc = consume_status(ctx, s, launched, call_tag, trace, known, ub, done);
         if (rc) return rc;
         if (launched > 2u * max_steps + 16u) {  // cannot happen: every launch advances step by >= 1 or is the rollback of one that did
@@ -1361,6 +1449,8 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     }
     ctx->seq_base += launched;
     const Ctl* last = ctx->ctl + (launched & 1);   // the state after the last launch (done is sticky)
+    ctx->last_ctl = last;
+    ctx->last_stream = s;
     if (ra.dump_rec) {
         const uint32_t nb = div_up(N, 256);
         k_dump_count<<<nb, 256, 0, s>>>(ctx->dump_iter, N, last, ctx->chunk_count);
