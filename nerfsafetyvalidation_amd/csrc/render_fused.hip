@@ -54,36 +54,8 @@ constexpr size_t kLinMaxBytes = 4u << 20;  // linear copy of the occupancy bitfi
 constexpr int kLookahead = 4;             // iterations the host may enqueue beyond the last status it has seen
 constexpr int kRing = 8;
 
-// device-side loop state (ping-pong pair); also the pinned status record
-struct Ctl {
-    uint32_t n_alive, n_step, step, done;
-    uint32_t iters, last_n_alive, last_n_step, pad;
-    unsigned long long samples_marched, samples_slots;
-    uint32_t spec, rollbacks, backoff, rsv;   // see "several reference iterations per launch" below
-    // schedule diagnostics (ngp_render_ctx_schedule_stats): accumulated by k_render_compact, nothing in the loop reads them back
-    unsigned long long discarded;             // network samples of the launches that were rolled back
-    uint32_t fc_sized, spec_launches;         // launches the saturation forecast made smaller; multi-iteration launches run
-    uint32_t fc_pred, fc_actual;              // last multi-iteration launch: deaths forecast / counted before its last verified iteration
-    uint32_t plan_pred, plan_headroom, plan_rate, plan_k_rate;   // the plan of the launch this state starts (trace, fc_pred)
-};
-
-// Several reference iterations per launch.  While more than half of the N rays are alive the reference's schedule is
-// n_step = clamp(N // n_alive, 1, 8) = 1: one sample per ray and iteration, for dozens of iterations (50 of the 56 of an 800x800
-// Stonehenge frame), each paying a launch, the per-ray state round trip and a compaction for a single sample.  A launch with
-// `spec` = q set covers K = n_step / q consecutive reference iterations of q samples each: per ray it emulates the iteration
-// boundaries exactly (march restarts from the re-accumulated rays_t, raymarching.cu:727,848) and the per-iteration death
-// counts give the n_alive sequence, so iterations / samples_slots / step are the reference's.  That is valid only if
-// N // n_alive stays q through the K iterations.  K is GUESSED from the recent death rate and the launch is VERIFIED afterwards
-// by k_render_compact: on a violation every ray gets back the state the launch started from (each wave saves it when it
-// loads it), the alive list is handed on unchanged and the iteration is run again on its own -- a wrong guess costs one
-// launch, never a result.  Not used with perturb (the jitter of an iteration is seeded with the ray's index in that
-// iteration's list).
-// (kSpecK, the most reference iterations per launch, and the sizing rule are launch_plan.hpp's)
-constexpr uint32_t kSpecMarginDiv = 16;   // first launch: entered only if n_alive - N/2 > N / kSpecMarginDiv
-// largest q for which a launch covers several iterations (K * q <= 8 samples per ray and launch, K >= 2)
-constexpr uint32_t kSpecMaxQ = 8;
-constexpr uint32_t kSpecMaxSamples = 32;  // samples per ray and launch in the n_step >= 5 regimes (k_render_compact's cap_hi)
-constexpr uint32_t kSpecMidSamples = 8;   // ... and in the n_step 2..4 regimes (its cap_mid_max)
+// The loop state (struct Ctl), the schedule of "several reference iterations per launch" and every transition of it are
+// launch_plan.hpp's: one integer state machine, host and device, which tests/test_launch_plan_cpu.py runs whole on the CPU.
 constexpr int kDeathShards = 64;
 // per launch parity: [kDeathShards][kSpecK] deaths per iteration (k_render_iter) | [kDeathShards][kSpecK] rays whose MARCH runs out of
 // samples in that iteration (k_march_ahead: known before the network runs, see truncate_launch) | [kDeathShards][kForecastBuckets]
@@ -146,30 +118,6 @@ struct RenderArgs {
 // a launch derive W from the launch's n_alive.
 __host__ __device__ __forceinline__ uint32_t item_width(uint32_t n_alive, uint32_t wave_slots) {
     return n_alive >= 64u * wave_slots ? 64u : (n_alive >= 32u * wave_slots ? 32u : 16u);
-}
-// A multi-iteration launch that cannot pass its verification is cut short BEFORE the network runs.  k_march_ahead knows, for every
-// ray, in which of the launch's iterations its march runs out of samples (the ray dies there at the latest): those counts are a lower
-// bound of the deaths per iteration, and N // n_alive only grows as rays die, so an iteration whose n_step already differs from q
-// under the lower bound differs for certain.  The launch then covers the iterations before it (one iteration: an ordinary launch);
-// k_render_iter and k_render_compact both apply this to their copy of the launch's Ctl, from the same counts.  Cameras outside the
-// scene box (BASELINE configs[3]) lose most rays in the first iteration: without this the first launch of every frame ran the
-// network on up to eight samples per ray, failed its verification and was run again.
-// `exhausted[j]`: rays whose march ends in iteration j of the launch (summed over the shards).
-__device__ __forceinline__ void truncate_launch(Ctl& c, const uint32_t* exhausted, uint32_t N) {
-    if (!c.spec) return;
-    const uint32_t q = c.spec, K = c.n_step / q;
-    uint32_t alive = c.n_alive, ok = K;
-    for (uint32_t j = 0; j < K; j++) {
-        if (alive == 0) break;                                    // (the reference stops here: nothing left to violate)
-        const uint32_t want_q = N / alive;
-        if (j > 0 && (want_q < 1 ? 1u : (want_q > 8 ? 8u : want_q)) != q) { ok = j; break; }
-        alive -= exhausted[j] < alive ? exhausted[j] : alive;
-    }
-    if (ok < K) {
-        if (ok <= 1) { c.spec = 0; c.n_step = q; }
-        else c.n_step = ok * q;
-        c.rsv += 1;                                               // (diagnostics: launches cut short)
-    }
 }
 // an upper bound of the items of a launch whose n_alive is at most `ub`
 static uint32_t items_bound(uint32_t ub, uint32_t wave_slots) {
@@ -683,45 +631,53 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
     if (lane == 0 && wave_total) atomicAdd(&ra.stat_shards[(blockIdx.x * kWaves + wid) % kStatShards], wave_total);
 }
 
-// stitch chunk survivor lists -> next alive list; advance the reference's schedule (renderer.py:347-373).
+// stitch chunk survivor lists -> next alive list; its last thread advances the reference's schedule (renderer.py:347-373; finish_launch).
 // One 256-thread block per 8 chunks (512 alive entries): wave w copies chunks 2w, 2w+1 of its block.  Survivors come in two
 // classes per chunk (fast: stored from the front, slow: stored from the back, see k_render_iter); the next list is
 // [all slow survivors in order | all fast survivors in order].  With no slow survivors this is the reference's stable
 // compaction rays_alive[rays_alive >= 0].
 // What the host needs while it enqueues iterations ahead -- how many rays are left and whether the loop has ended -- goes
-// straight into its pinned, coherent status ring as ONE 64-bit word (sequence number << 32 | done << 31 | n_alive), written
+// straight into its pinned, coherent status ring as ONE 64-bit word (pack_status), written
 // with a relaxed system-scope store: no copy, no event, and no release fence (a fence writes the XCD's L2 back, ~10 us at the
 // end of this short kernel).  Everything else the host reads from the device state after the loop.
-// A state that ends the loop also leaves the counters the host reports (ngp_render_stats) in four more pinned words, each carrying a
-// tag in its upper 16 bits that names the render CALL (bit 15 set + a per-context call counter: the run-ahead no-op launches of the
-// previous call may still be writing their own, older tag when this call starts; the host takes a word once it carries this call's
-// tag -- every launch of a call that publishes a finished state writes the same values, so there is nothing to tear) -- the host then needs neither a stream
-// synchronize nor a copy of the device state at the end of a frame, and the caller can enqueue the next frame's work at once.
+// A state that ends the loop also leaves the counters the host reports (ngp_render_stats) in four more pinned words (pack_fin), each
+// tagged with the render CALL: the run-ahead no-op launches of the previous call may still be writing their own, older tag when this
+// call starts; the host takes the words once they carry this call's tag -- every launch of a call that publishes a finished state
+// writes the same values, so there is nothing to tear -- the host then needs neither a stream synchronize nor a copy of the device
+// state at the end of a frame, and the caller can enqueue the next frame's work at once.
 __device__ __forceinline__ void publish_status(unsigned long long* host_slot, const Ctl& n, uint32_t seq, unsigned long long* fin = nullptr,
                                                uint32_t call_tag = 0) {
     if (!host_slot) return;
     if (n.done && fin) {
-        const unsigned long long tag = (unsigned long long)(0x8000u | (call_tag & 0x7FFFu)) << 48;
-        __hip_atomic_store(fin + 0, tag | (n.samples_marched & 0xFFFFFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(fin + 1, tag | (n.samples_slots & 0xFFFFFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(fin + 2, tag | ((unsigned long long)(n.iters & 0xFFFFFFu) << 24) | (n.rollbacks & 0xFFFFFFu), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(fin + 3, tag | ((unsigned long long)n.last_n_alive << 8) | (n.last_n_step & 0xFFu), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
+        unsigned long long w[4];
+        pack_fin(n, call_tag, w);
+        for (int i = 0; i < 4; i++) __hip_atomic_store(fin + i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    const unsigned long long w = ((unsigned long long)seq << 32) | ((unsigned long long)(n.done ? 1u : 0u) << 31) | (n.n_alive & 0x7FFFFFFFu);
-    __hip_atomic_store(host_slot, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host_slot, pack_status(seq, n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// (Plain __restrict__ pointer arguments, not one struct by value: members of a struct cannot carry the qualifier, the uniform loads
+//  of the launch's state and counts then become vector loads, and the kernel took 2.5 x as long -- DESIGN "One place for the schedule".)
 __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ cur, Ctl* __restrict__ nxt, const int32_t* __restrict__ staging,
                                                          const uint32_t* __restrict__ chunk_count, int32_t* __restrict__ alive_out, uint32_t N,
-                                                         uint32_t max_steps, const unsigned long long* __restrict__ stat_shards,
-                                                         QueueHeads* __restrict__ nxt_heads, unsigned long long* __restrict__ host_slot, uint32_t seq,
-                                                         const uint32_t* __restrict__ death_shards, uint32_t spec_allowed, const int32_t* __restrict__ alive_in,
+                                                         uint32_t max_steps, unsigned long long* stat_shards, QueueHeads* __restrict__ nxt_heads,
+                                                         unsigned long long* __restrict__ host_slot, uint32_t seq,
+                                                         const uint32_t* __restrict__ death_shards, uint32_t flags, const int32_t* __restrict__ alive_in,
                                                          const float4* __restrict__ backup, float* __restrict__ rays_t, float* __restrict__ weights_sum,
                                                          float* __restrict__ depth, float* __restrict__ image, uint32_t* __restrict__ sample_hash,
-                                                         unsigned long long* stat_shards_rw, uint32_t* __restrict__ death_next, uint32_t wave_slots,
-                                                         uint32_t cap_mid_max, uint32_t cap_hi, unsigned long long* __restrict__ fin_host, uint32_t call_tag) {
+                                                         uint32_t* __restrict__ death_next, uint32_t wave_slots,
+                                                         unsigned long long* __restrict__ fin_host, uint32_t call_tag) {
+    // The last thread of a launch hands the loop on: the next launch's counters start at zero, its state is stored and published.
+    // (This launch's death counts are NOT cleared here: the other blocks of the kernel are still reading them for their verdict.
+    // Launches alternate between two buffers; a buffer is cleared right before a multi-iteration launch uses it.)
+    const auto hand_on = [&](const Ctl& n) {
+        for (int i = 0; i < kStatShards; i++) stat_shards[i] = 0ull;       // per-launch sample counts: folded into n (or discarded)
+        if (n.spec)   // the next launch counts deaths per iteration
+            for (uint32_t i = 0; i < kForecastAt; i++) death_next[i] = 0;
+        *nxt = n;
+        for (int i = 0; i < 8; i++) nxt_heads->head[i][0] = 0;
+        publish_status(host_slot, n, seq, fin_host, call_tag);
+    };
     __shared__ uint32_t red[3][4];
     __shared__ uint32_t off_f[9], off_s[9];
     Ctl c = *cur;
@@ -761,10 +717,9 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
     __syncthreads();
     truncate_launch(c, exhausted, N);          // the launch k_render_iter actually ran (same counts, same cut)
     if (threadIdx.x == 0) {
-        // K = c.n_step / q reference iterations of q = c.spec samples each, judged by launch_verdict (launch_plan.hpp); bit 1 of
-        // spec_allowed: the caller wants the reference's last-iteration tensors, so that iteration has to run on its own
+        // K = c.n_step / q reference iterations of q = c.spec samples each, judged by launch_verdict (launch_plan.hpp)
         LaunchVerdict v = {0u, 0u};
-        if (c.spec) v = launch_verdict(N, c.n_alive, c.spec, c.n_step / c.spec, deaths, (spec_allowed & 2u) != 0u);
+        if (c.spec) v = launch_verdict(N, c.n_alive, c.spec, c.n_step / c.spec, deaths, (flags & kPlanOwnLast) != 0u);
         verdict_bad = v.bad;
         verdict_keep = v.keep;
     }
@@ -784,37 +739,9 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
             alive_out[e] = ray;
         }
         if (g == n_blocks - 1 && threadIdx.x == 0) {
-            Ctl n = c;
-            n.rollbacks = c.rollbacks + 1;
-            {   // schedule diagnostics: what the discarded launch cost, and how its forecast compared
-                unsigned long long lost = 0;
-                for (int i = 0; i < kStatShards; i++) lost += stat_shards_rw[i];
-                n.discarded = c.discarded + lost;
-                n.spec_launches = c.spec_launches + 1;
-                uint32_t before_last = 0;
-                for (uint32_t j = 0; j + 1 < c.n_step / c.spec; j++) before_last += deaths[j];
-                n.fc_pred = c.plan_pred;
-                n.fc_actual = before_last;
-                n.plan_pred = 0; n.plan_headroom = 0; n.plan_rate = 0; n.plan_k_rate = 0;   // (the replay is not a guess)
-            }
-            if (verdict_keep >= 2 && !(spec_allowed & 4u)) {
-                // the iterations before the violation again, as one launch: certain to verify (see launch_verdict's `keep`)
-                n.spec = c.spec;
-                n.n_step = verdict_keep * c.spec;
-                n.backoff = 0;
-                for (uint32_t i = 0; i < kForecastAt; i++) death_next[i] = 0;     // (the other parity's buffer: nobody reads it now)
-            } else {
-                n.spec = 0;
-                const uint32_t ns = c.n_alive ? N / c.n_alive : 8;
-                n.n_step = ns < 1 ? 1 : (ns > 8 ? 8 : ns);
-                n.backoff = 2;                                    // the next two iterations run one per launch
-            }
-            // (this launch's death counts are NOT cleared here: the other blocks of this kernel are still reading them for their
-            //  verdict.  Launches alternate between two buffers; a buffer is cleared right before a multi-iteration launch uses it.)
-            for (int i = 0; i < kStatShards; i++) stat_shards_rw[i] = 0ull;   // the discarded launch's sample counts
-            *nxt = n;
-            for (int i = 0; i < 8; i++) nxt_heads->head[i][0] = 0;
-            publish_status(host_slot, n, seq, fin_host, call_tag);
+            unsigned long long lost = 0;                          // what the discarded launch cost
+            for (int i = 0; i < kStatShards; i++) lost += stat_shards[i];
+            hand_on(finish_launch(c, {1u, verdict_keep}, deaths, forecast, c.n_alive, lost, N, max_steps, flags, kSpecMidSamples, kSpecMaxSamples));
         }
         return;
     }
@@ -853,80 +780,18 @@ __global__ void __launch_bounds__(256) k_render_compact(const Ctl* __restrict__ 
         if (lane < ns) alive_out[prefix_s + off_s[ci] + lane] = staging[(size_t)(first + ci) * W + W - 1 - lane];
         if (lane < nf) alive_out[total_s + prefix_f + off_f[ci] + lane] = staging[(size_t)(first + ci) * W + lane];
     }
-    unsigned long long marched = threadIdx.x < (uint32_t)kStatShards ? stat_shards_rw[threadIdx.x] : 0ull;   // kStatShards == 64: wave 0
+    unsigned long long marched = threadIdx.x < (uint32_t)kStatShards ? stat_shards[threadIdx.x] : 0ull;   // kStatShards == 64: wave 0
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) marched += __shfl_down(marched, off, 64);
-    if (g == n_blocks - 1 && threadIdx.x == 0) {
-        Ctl n = c;
-        n.samples_marched = c.samples_marched + marched;          // per-launch counters: folded in here, reset below
-        for (int i = 0; i < kStatShards; i++) stat_shards_rw[i] = 0ull;
-        n.n_alive = total_s + prefix_f + off_f[8];
-        uint32_t recent = c.n_alive - n.n_alive;   // deaths per reference iteration, most recent observation
-        if (!c.spec) {
-            n.last_n_alive = c.n_alive;
-            n.last_n_step = c.n_step;
-            n.iters = c.iters + 1;
-            n.samples_slots = c.samples_slots + (unsigned long long)c.n_alive * c.n_step;
-            n.step = c.step + c.n_step;
-        } else {
-            const uint32_t q = c.spec, K = c.n_step / q;
-            uint32_t alive = c.n_alive, d_last = 0, d_prev = 0;
-            unsigned long long slots = c.samples_slots;
-            uint32_t it = 0;
-            for (uint32_t j = 0; j < K; j++) {
-                if (alive == 0) break;                            // iterations the reference does not run
-                slots += (unsigned long long)alive * q;
-                it++;
-                n.last_n_alive = alive;
-                n.last_n_step = q;
-                alive -= deaths[j];
-                d_prev = d_last;
-                d_last = deaths[j];
-            }
-            recent = d_last > d_prev ? d_last : d_prev;            // the launch's last two iterations
-            n.iters = c.iters + it;
-            n.samples_slots = slots;
-            n.step = c.step + it * q;
-            n.spec_launches = c.spec_launches + 1;                // schedule diagnostics: how the launch's forecast compared
-            uint32_t before_last = 0;
-            for (uint32_t j = 0; j + 1 < K; j++) before_last += deaths[j];
-            n.fc_pred = c.plan_pred;
-            n.fc_actual = before_last;
-        }
-        n.n_step = schedule_n_step(N, n.n_alive);
-        n.done = (n.n_alive == 0 || n.step >= max_steps) ? 1 : 0;
-        // The next launch may cover several reference iterations of q = n_step samples: as many as plan_launch (launch_plan.hpp)
-        // finds room for above the n_alive at which the reference's n_step changes, judged by the recent death rate and by the
-        // saturation forecast k_render_iter left of this launch's survivors (bit 3 of spec_allowed, diagnostics: by the rate
-        // alone).  A wrong guess costs one launch (rollback above).
-        n.spec = 0;
-        n.plan_pred = 0; n.plan_headroom = 0; n.plan_rate = 0; n.plan_k_rate = 0;
-        if (n.backoff) n.backoff--;
-        else if (spec_allowed && !n.done && n.n_step <= kSpecMaxQ && (n.n_step == 8 || n.n_alive > N / (n.n_step + 1))) {
-            const uint32_t q = n.n_step;
-            const bool own_last = (spec_allowed & 2u) != 0;     // the last iteration must not be part of such a launch
-            uint32_t room = (max_steps - n.step) / q;
-            if (own_last && room) room--;
-            const LaunchPlan p = plan_launch(N, n.n_alive, q, recent, (spec_allowed & 8u) ? nullptr : forecast, room, cap_mid_max, cap_hi, own_last);
-            if (p.K < p.K_rate && p.K_rate >= 2) n.fc_sized = c.fc_sized + 1;
-            if (p.K >= 2) {
-                n.spec = q; n.n_step = p.K * q;
-                n.plan_pred = p.forecast; n.plan_headroom = p.headroom; n.plan_rate = p.rate; n.plan_k_rate = p.K_rate;
-            }
-        }
-        if (n.spec)   // the next launch counts deaths per iteration: its buffer (not the one this kernel's blocks are reading) starts at zero
-            for (uint32_t i = 0; i < kForecastAt; i++) death_next[i] = 0;
-        *nxt = n;
-        for (int i = 0; i < 8; i++) nxt_heads->head[i][0] = 0;
-        publish_status(host_slot, n, seq, fin_host, call_tag);
-    }
+    if (g == n_blocks - 1 && threadIdx.x == 0)
+        hand_on(finish_launch(c, {0u, 0u}, deaths, forecast, total_s + prefix_f + off_f[8], marched, N, max_steps, flags, kSpecMidSamples, kSpecMaxSamples));
 }
 
 __global__ void __launch_bounds__(256) k_render_init(uint32_t N, const float* __restrict__ nears, float* __restrict__ rays_t,
                                                       int32_t* __restrict__ alive, float* __restrict__ weights_sum, float* __restrict__ depth,
                                                       float* __restrict__ image, Ctl* __restrict__ ctl, uint32_t max_steps,
                                                       uint32_t* __restrict__ sample_hash, unsigned long long* __restrict__ stat_shards,
-                                                      QueueHeads* __restrict__ heads, uint32_t* __restrict__ death_shards, uint32_t spec_allowed,
+                                                      QueueHeads* __restrict__ heads, uint32_t* __restrict__ death_shards, uint32_t flags,
                                                       uint32_t tile_w) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
     if (n < (uint32_t)kStatShards) stat_shards[n] = 0ull;
@@ -947,15 +812,7 @@ __global__ void __launch_bounds__(256) k_render_init(uint32_t N, const float* __
         image[(size_t)n * 3] = 0; image[(size_t)n * 3 + 1] = 0; image[(size_t)n * 3 + 2] = 0;
     }
     if (n == 0) {
-        Ctl c = {};
-        c.n_alive = N;
-        c.n_step = 1;  // clamp(N // N, 1, 8)
-        c.done = (N == 0 || max_steps == 0) ? 1 : 0;
-        const uint32_t room = (spec_allowed & 2u) ? (max_steps ? max_steps - 1 : 0) : max_steps;   // bit 1: the last iteration runs on its own
-        if (spec_allowed && !c.done && N > N / 2 + N / kSpecMarginDiv && room >= 2) {   // see Ctl: several iterations per launch
-            c.spec = 1;
-            c.n_step = room < kSpecK ? room : kSpecK;
-        }
+        const Ctl c = loop_begin(N, max_steps, flags);
         ctl[0] = c;
         ctl[1] = c;
     }
@@ -1209,7 +1066,7 @@ static IterKernel choose_iter_kernel(const NetArgs& na, const GridLevels& lv) {
 // Enqueues launch number `launched` of a call: the march, the network over its samples, the compaction that publishes its status word.
 // `ub`: the host's upper bound of the launch's n_alive.
 static void enqueue_launch(ngp_render_ctx* ctx, const NetArgs& na, const GridLevels& lv, RenderArgs& ra, IterKernel iter_kernel, size_t lds,
-                           bool lin, uint32_t ub, uint32_t launched, uint32_t spec_allowed, uint32_t call_tag, hipStream_t s) {
+                           bool lin, uint32_t ub, uint32_t launched, uint32_t plan_flags, uint32_t call_tag, hipStream_t s) {
     const uint32_t cur = launched & 1;
     const uint32_t chunks = items_bound(ub, ra.wave_slots);     // work items of the launch, at most
     // persistent: resident workgroups pull chunks from a queue.  k_render_iter at two workgroups per CU holds every vector register and
@@ -1238,13 +1095,11 @@ static void enqueue_launch(ngp_render_ctx* ctx, const NetArgs& na, const GridLev
         ProfScope pk("k_render_iter", s, 0);
         iter_kernel<<<blocks, kThreads, lds, s>>>(na, lv, ra);
     }
-    k_render_compact<<<div_up(chunks, 8), 256, 0, s>>>(ctx->ctl + cur, ctx->ctl + (cur ^ 1), ctx->staging, ctx->chunk_count,
-                                                       ctx->alive[cur ^ 1], ra.n_rays, ra.max_steps, ctx->stat_shards, ctx->heads + (cur ^ 1),
-                                                       ctx->status_dev + launched % kRing, ctx->seq_base + launched + 1,
-                                                       ctx->death_shards + (size_t)cur * kDeathWords, spec_allowed, ctx->alive[cur],
-                                                       ctx->backup, ctx->rays_t, ra.weights_sum, ra.depth, ra.image, ra.sample_hash, ctx->stat_shards,
-                                                       ctx->death_shards + (size_t)(cur ^ 1) * kDeathWords, ra.wave_slots, kSpecMidSamples,
-                                                       kSpecMaxSamples, ctx->fin_dev, call_tag);
+    k_render_compact<<<div_up(chunks, 8), 256, 0, s>>>(ra.ctl, ctx->ctl + (cur ^ 1), ra.staging, ra.chunk_count, ctx->alive[cur ^ 1], ra.n_rays,
+                                                       ra.max_steps, ra.stat_shards, ctx->heads + (cur ^ 1), ctx->status_dev + launched % kRing,
+                                                       ctx->seq_base + launched + 1, ra.death_shards, plan_flags, ra.alive_in, ra.backup, ra.rays_t,
+                                                       ra.weights_sum, ra.depth, ra.image, ra.sample_hash,
+                                                       ctx->death_shards + (size_t)(cur ^ 1) * kDeathWords, ra.wave_slots, ctx->fin_dev, call_tag);
 }
 
 // NGP_TRACE_SCHEDULE: one line per multi-iteration launch -- its plan (K iterations of q samples, what the death rate alone would have
@@ -1284,10 +1139,10 @@ static int consume_status(const ngp_render_ctx* ctx, hipStream_t s, uint32_t lau
         volatile unsigned long long* slot = ctx->status + known % kRing;
         const uint32_t want_seq = ctx->seq_base + known + 1;
         unsigned long long w = *slot;
-        if ((uint32_t)(w >> 32) != want_seq) {
+        if (unpack_status(w).seq != want_seq) {
             if (!must_wait) break;
             uint32_t spins = 0;
-            while ((uint32_t)((w = *slot) >> 32) != want_seq) {
+            while (unpack_status(w = *slot).seq != want_seq) {
                 // every 2^20 polls (tens of milliseconds: far longer than any launch) make sure the stream is still alive.  Rarely,
                 // because the query is not free on the device side: the runtime answers it with a marker packet in the queue, and the
                 // kernels behind it start ~6 us late -- at every 4096 polls that was one gap per launch (kernel timeline, round 3)
@@ -1297,7 +1152,7 @@ static int consume_status(const ngp_render_ctx* ctx, hipStream_t s, uint32_t lau
                         set_error("render_rays: %s", hipGetErrorString(q));
                         return NGP_ELAUNCH;
                     }
-                    if (q == hipSuccess && (uint32_t)(*slot >> 32) != want_seq) {   // everything ran, nothing was published: cannot happen
+                    if (q == hipSuccess && unpack_status(*slot).seq != want_seq) {   // everything ran, nothing was published: cannot happen
                         set_error("render_rays: the device finished without publishing iteration %u", known);
                         return NGP_ELAUNCH;
                     }
@@ -1306,9 +1161,10 @@ static int consume_status(const ngp_render_ctx* ctx, hipStream_t s, uint32_t lau
             }
         }
         known++;
-        ub = (uint32_t)w & 0x7FFFFFFFu;
-        if (trace) fprintf(stderr, "[ngp] call %u launch %u: n_alive %u%s\n", call_tag, known, ub, ((w >> 31) & 1ull) ? " done" : "");
-        if ((w >> 31) & 1ull) { done = true; break; }
+        const LoopStatus st = unpack_status(w);
+        ub = st.n_alive;
+        if (trace) fprintf(stderr, "[ngp] call %u launch %u: n_alive %u%s\n", call_tag, known, ub, st.done ? " done" : "");
+        if (st.done) { done = true; break; }
     }
     return NGP_OK;
 }
@@ -1324,21 +1180,9 @@ static int read_counters(const ngp_render_ctx* ctx, hipStream_t s, const Ctl* la
         volatile unsigned long long* f = ctx->fin;
         unsigned long long w[4] = {0, 0, 0, 0};
         for (uint32_t spin = 0; spin < 200000u && !have_fin; spin++) {
-            bool all = true;
-            for (int i = 0; i < 4; i++) {
-                w[i] = f[i];
-                all = all && (w[i] >> 48) == (0x8000u | call_tag);
-            }
-            have_fin = all;
+            for (int i = 0; i < 4; i++) w[i] = f[i];
+            have_fin = unpack_fin(w, call_tag, fin);
             if (!have_fin) __builtin_ia32_pause();
-        }
-        if (have_fin) {
-            fin.samples_marched = w[0] & 0xFFFFFFFFFFFFull;
-            fin.samples_slots = w[1] & 0xFFFFFFFFFFFFull;
-            fin.iters = (uint32_t)((w[2] >> 24) & 0xFFFFFFu);
-            fin.rollbacks = (uint32_t)(w[2] & 0xFFFFFFu);
-            fin.last_n_alive = (uint32_t)((w[3] >> 8) & 0xFFFFFFFFu);
-            fin.last_n_step = (uint32_t)(w[3] & 0xFFu);
         }
     }
     if ((stats_host && !have_fin) || sync) {
@@ -1391,18 +1235,17 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
         k_pack_weights<<<div_up(n_packed, 256), 256, 0, s>>>((const _Float16*)model->sigma_weights, na.sig_mm,
                                                              (const _Float16*)model->color_weights, na.col_mm, ctx->packed);
     }
-    // several reference iterations per launch (see Ctl), not with jitter.  bit 0: launches may cover several iterations; bit 1: the last
-    // iteration runs on its own (its tensors are wanted); bit 2 (diagnostics): a failed launch is replayed as ONE iteration instead of
-    // its verified prefix; bit 3 (diagnostics): launches are sized by the death rate alone, not by the saturation forecast
-    const uint32_t spec_allowed = (!dbg.spec_off() && perturb == 0)
-                                      ? (1u | (last_sigmas ? 2u : 0u) | (dbg.prefix_replay_off() ? 4u : 0u) | ((ctx->sched_flags & NGP_SCHED_NO_FORECAST) ? 8u : 0u)) : 0u;
+    // several reference iterations per launch (launch_plan.hpp), not with jitter
+    const uint32_t plan_flags = (!dbg.spec_off() && perturb == 0)
+                                    ? (kPlanMulti | (last_sigmas ? kPlanOwnLast : 0u) | (dbg.prefix_replay_off() ? kPlanReplayOne : 0u) |
+                                       ((ctx->sched_flags & NGP_SCHED_NO_FORECAST) ? kPlanNoForecast : 0u)) : 0u;
     // scheduling hint (ngp_render_ctx_set_frame_width): whole rows of 4x4-pixel tiles only; not with jitter (seeded with the list index)
     const uint32_t fw = ctx->frame_width;
     const uint32_t tile_w = (perturb == 0 && !dbg.tile_off() && fw >= 4 && fw % 4 == 0 && N % (4 * fw) == 0) ? fw : 0u;
     // (the grid also has to cover the loop's own counters -- both death-count buffers -- however few rays there are)
     const uint32_t init_threads = N > 2u * kDeathWords ? N : 2u * kDeathWords;
     k_render_init<<<div_up(init_threads, 256), 256, 0, s>>>(N, nears, ctx->rays_t, ctx->alive[0], weights_sum, depth, image, ctx->ctl, max_steps,
-                                                 dbg.sample_hash, ctx->stat_shards, ctx->heads, ctx->death_shards, spec_allowed, tile_w);
+                                                 dbg.sample_hash, ctx->stat_shards, ctx->heads, ctx->death_shards, plan_flags, tile_w);
 
     RenderArgs ra = {};
     ra.rays_o = rays_o; ra.rays_d = rays_d; ra.fars = fars;
@@ -1410,7 +1253,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     ra.last_sigmas = last_sigmas; ra.last_rgbs = last_rgbs;
     if (pad_value_host) { ra.pad_sigma = pad_value_host[0]; ra.pad_r = pad_value_host[1]; ra.pad_g = pad_value_host[2]; ra.pad_b = pad_value_host[3]; }
     fill_render_args(ctx, model, dbg, N, dt_gamma, max_steps, perturb, ra);
-    ra.forecast = (spec_allowed && !(ctx->sched_flags & NGP_SCHED_NO_FORECAST)) ? 1u : 0u;         // (ngp_render_ctx_set_schedule_flags)
+    ra.forecast = ((plan_flags & kPlanMulti) && !(plan_flags & kPlanNoForecast)) ? 1u : 0u;         // (ngp_render_ctx_set_schedule_flags)
     const bool lin = choose_occupancy(ctx, model, dbg, s, ra);
     if ((ra.sort_slow || tile_w) && last_sigmas) {
         // regrouped alive list + last-iteration tensors requested: collect per-ray records, restore the row order afterwards
@@ -1437,7 +1280,7 @@ int ngp_render_rays(ngp_render_ctx* ctx, const ngp_model* model, const float* ra
     uint32_t known = 0;       // iterations whose resulting status the host has read
     bool done = false;
     while (!done) {
-        enqueue_launch(ctx, na, lv, ra, iter_kernel, lds, lin, ub, launched, spec_allowed, call_tag, s);
+        enqueue_launch(ctx, na, lv, ra, iter_kernel, lds, lin, ub, launched, plan_flags, call_tag, s);
         launched++;
         if (trace) trace_launch(ctx, s, launched - 1, call_tag);
         rc = consume_status(ctx, s, launched, call_tag, trace, known, ub, done);
