@@ -57,8 +57,22 @@ typedef void* ngp_stream_t;
 #endif
 
 /* The number ngp_version() returns; it changes with every incompatible change of this header, and a binding compares it at load.
- *   101: ngp_network_density has a `geo_feat` argument, ngp_model has `precision` (both were added under 100, unrecorded). */
-#define NGP_ABI_VERSION 101
+ *   101: ngp_network_density has a `geo_feat` argument, ngp_model has `precision` (both were added under 100, unrecorded).
+ *   102: ngp_mark_untrained_grid_workspace is new; ngp_density_grid_update, ngp_density_grid_finish, ngp_uq_stats and
+ *        ngp_mark_untrained_grid return NGP_EWORKSPACE, no longer NGP_EINVAL, for a workspace that is too small. */
+#define NGP_ABI_VERSION 102
+
+/* Caller-owned workspaces.  Every `workspace` / `workspace_bytes` pair below is checked by one rule, against the size its
+ * ngp_*_workspace() function answers (which the entry point carves with the very code that measured it):
+ *   nothing needed (the size function answers 0)                             -> not looked at, NULL is fine
+ *   workspace_bytes smaller than needed (NULL with 0 bytes included)         -> NGP_EWORKSPACE, "<entry point>: workspace too small
+ *                                                                               (<given> < <needed> bytes)" in ngp_last_error()
+ *   enough bytes, but the pointer is NULL or not aligned as the entry states -> NGP_EINVAL
+ * and nothing is launched in either case.  This holds for ngp_march_rays_train (16-byte aligned), ngp_edt_sq, ngp_label_components,
+ * ngp_sift_interest_mask, ngp_mark_untrained_grid, ngp_photo_loss_forward, the ngp_distortion_* and ngp_depth_loss_* forwards
+ * (4-byte), ngp_isosurface_count / _emit, ngp_distance_stats, ngp_density_grid_update / _finish, ngp_uq_stats, ngp_sigma_fit_* and
+ * ngp_image_quality (8-byte).  Not for ngp_render_upsample, ngp_grid_encode_backward* and ngp_ffmlp_backward*, where the workspace
+ * given chooses the route. */
 
 NGP_API const char* ngp_last_error(void);
 NGP_API int ngp_version(void);
@@ -93,7 +107,8 @@ NGP_API int ngp_packbits(const float* grid, uint32_t N, float density_thresh, ui
 /* raymarching.cu:486-495 march_rays_train.  Slots are handed out by an exclusive
  * prefix sum in ray order (deterministic member of the reference's atomicAdd
  * permutation set).  counter[0] += total samples, counter[1] += N, as the
- * reference's atomics leave them.  workspace: ngp_march_rays_train_workspace(N) bytes. */
+ * reference's atomics leave them.  workspace: ngp_march_rays_train_workspace(N) bytes, 16-byte aligned
+ * (NGP_EWORKSPACE when smaller). */
 NGP_API size_t ngp_march_rays_train_workspace(uint32_t N);
 NGP_API int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                          uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
@@ -681,8 +696,11 @@ NGP_API int ngp_merge_sorted(const float* z_a, const float* z_b, uint32_t N, uin
 /* ---------------- density-grid maintenance (nerf/renderer.py:388-544): the producer of density_bitfield ---------------- */
 
 /* mark_untrained_grid (:388-449): cells of density_grid [cascade, H^3] (Morton order) whose centre no camera sees become -1.
- * poses [n_cams,4,4] cam2world (device).  workspace: only for more than 2048 cameras (cascade * H^3 * 4 bytes), else NULL.
+ * poses [n_cams,4,4] cam2world (device).  workspace: ngp_mark_untrained_grid_workspace(n_cams, cascade, H) bytes, 4-byte aligned:
+ * 0 up to 2048 cameras (one launch; NULL is fine), a flag word per cell (cascade * H^3 * 4 bytes) carried between the launches above
+ * that, and 0 for a grid the call refuses.  NGP_EWORKSPACE when smaller.
  * H: a power of two in [2, 1024], cascade in [1, 8] (see ngp_march_rays_train), here and in ngp_density_grid_update / _finish. */
+NGP_API size_t ngp_mark_untrained_grid_workspace(uint32_t n_cams, uint32_t cascade, uint32_t H);
 NGP_API int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float fx, float fy, float cx, float cy, float bound, uint32_t cascade,
                             uint32_t H, float* density_grid, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 /* sample positions of update_extra_state (:479-485, :512-520): coords int32 [n,3] cell coordinates, or NULL = every cell in the
@@ -691,7 +709,9 @@ NGP_API int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float f
 NGP_API int ngp_density_grid_points(const int32_t* coords, uint32_t n, uint32_t H, float cascade_bound, const float* noise, float* xyzs,
                             int32_t* indices, ngp_stream_t stream);
 /* :489-491 + :531-532 for one cascade: tmp[indices] = sigmas * density_scale (duplicates: the LAST sample wins, as PyTorch's CPU
- * index_put_), then grid = max(grid * decay, tmp) where both are >= 0.  workspace: ngp_density_grid_workspace(cascade, H) bytes. */
+ * index_put_), then grid = max(grid * decay, tmp) where both are >= 0.  workspace: ngp_density_grid_workspace(cascade, H) bytes, 8-byte
+ * aligned, shared with ngp_density_grid_finish: H^3 scatter words, then cascade * ceil(H^3 / 256) partial sums (NGP_EWORKSPACE when
+ * smaller, from either call). */
 NGP_API size_t ngp_density_grid_workspace(uint32_t cascade, uint32_t H);
 NGP_API int ngp_density_grid_update(float* density_grid, uint32_t cascade, uint32_t H, uint32_t cas, const int32_t* indices, const float* sigmas,
                             uint32_t n, float density_scale, float decay, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
@@ -706,7 +726,8 @@ NGP_API int ngp_density_grid_finish(const float* density_grid, uint32_t cascade,
  * reductions + .item() per scipy.minimize evaluation.  c [n,3] per-sample colours (dtype code 0 = f32,
  * 1 = f16), d [n] f32 per-sample densities, r [m] f32 rendered colour values.  stats (device, 8 doubles):
  *   [0] sum c^2 d^2   [1] sum c d   [2] sum r   [3] m   [4] sum d   [5] sum d^2   [6] n   [7] 0
- * accumulated in double in a fixed order (deterministic).  workspace: ngp_uq_stats_workspace() bytes of device memory. */
+ * accumulated in double in a fixed order (deterministic).  workspace: ngp_uq_stats_workspace() bytes of device memory, 8-byte aligned
+ * (NGP_EWORKSPACE when smaller). */
 NGP_API size_t ngp_uq_stats_workspace(void);
 NGP_API int ngp_uq_stats(const void* c, int c_dtype, const float* d, uint64_t n, const float* r, uint64_t m, double* stats,
                  void* workspace, size_t workspace_bytes, ngp_stream_t stream);

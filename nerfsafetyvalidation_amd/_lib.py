@@ -29,7 +29,7 @@ NGP_SCHED_NO_FORECAST = 1                                        # ngp_render_ct
 NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
 NGP_COMPONENTS_TILE = (4, 4, 16)                                 # NGP_COMPONENTS_TILE_X / _Y / _Z: the tile ngp_label_components labels in LDS
 
-ABI_VERSION = 101                                                # NGP_ABI_VERSION of the header this table mirrors; lib() compares
+ABI_VERSION = 102                                               # NGP_ABI_VERSION of the header this table mirrors; lib() compares
 
 _vp, _u32, _f32, _int, _sz = C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_size_t
 
@@ -196,6 +196,7 @@ SIGNATURES = {
     "ngp_transmittance_weights_backward": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _st],
     "ngp_sample_pdf": [_vp, _vp, _u32, _u32, _vp, _int, _u32, _vp, _st],
     "ngp_merge_sorted": [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _st],
+    "ngp_mark_untrained_grid_workspace": [_u32, _u32, _u32],
     "ngp_mark_untrained_grid": [_vp, _u32, _f32, _f32, _f32, _f32, _f32, _u32, _u32, _vp, _vp, _sz, _st],
     "ngp_density_grid_points": [_vp, _u32, _u32, _f32, _vp, _vp, _vp, _st],
     "ngp_density_grid_workspace": [_u32, _u32],
@@ -215,7 +216,7 @@ SIGNATURES = {
     "ngp_prof_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
 }
 _RESTYPES = {"ngp_render_uniform_backward_lds": _sz, "ngp_cell_tables_bytes": _sz, "ngp_packed_weights_bytes": _sz, "ngp_packed_weights_bwd_bytes": _sz, "ngp_grid_encode_backward_workspace": _sz,
-             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_label_components_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_depth_loss_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
+             "ngp_ffmlp_backward_workspace": _sz, "ngp_ffmlp_backward_buffer_bytes": _sz, "ngp_render_upsample_workspace": _sz, "ngp_density_grid_workspace": _sz, "ngp_mark_untrained_grid_workspace": _sz, "ngp_last_error": C.c_char_p, "ngp_march_rays_train_workspace": _sz, "ngp_uq_stats_workspace": _sz, "ngp_sigma_fit_workspace": _sz, "ngp_occupancy_lin_bytes": _sz, "ngp_edt_sq_workspace": _sz, "ngp_label_components_workspace": _sz, "ngp_isosurface_workspace": _sz, "ngp_sift_workspace": _sz, "ngp_sift_layer_offset": _sz, "ngp_photo_loss_workspace": _sz, "ngp_image_quality_workspace": _sz, "ngp_distortion_workspace": _sz, "ngp_depth_loss_workspace": _sz, "ngp_distance_stats_state_bytes": _sz, "ngp_distance_stats_workspace": _sz}
 
 _lib = None
 

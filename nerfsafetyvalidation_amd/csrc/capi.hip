@@ -267,28 +267,32 @@ int ngp_device_count(void) {
     return n;
 }
 
-size_t ngp_uq_stats_workspace(void) { return (size_t)kUqBlocks * 5 * sizeof(double); }
+// [kUqBlocks][5] partial sums, one row per workgroup of k_uq_partial
+static double* uq_layout(Carver& c) { return c.take<double>((size_t)kUqBlocks * 5); }
+size_t ngp_uq_stats_workspace(void) { Carver c; uq_layout(c); return c.bytes(); }
 
 int ngp_uq_stats(const void* c, int c_dtype, const float* d, uint64_t n, const float* r, uint64_t m, double* stats, void* workspace,
                  size_t workspace_bytes, ngp_stream_t stream) {
-    NGP_REQUIRE(stats && workspace, "uq_stats: null pointer");
+    NGP_REQUIRE(stats, "uq_stats: null pointer");
     NGP_REQUIRE((c && d) || n == 0, "uq_stats: null sample buffers");
     NGP_REQUIRE(r || m == 0, "uq_stats: null rendered-colour buffer");
-    NGP_REQUIRE(workspace_bytes >= ngp_uq_stats_workspace(), "uq_stats: workspace too small (%zu < %zu bytes)", workspace_bytes,
-                ngp_uq_stats_workspace());
+    int rc = check_workspace("uq_stats", workspace, workspace_bytes, ngp_uq_stats_workspace(), 8);
+    if (rc) return rc;
     NGP_REQUIRE(c_dtype == 0 || c_dtype == 1, "uq_stats: colour dtype must be 0 (f32) or 1 (f16)");
+    Carver carver(workspace);
+    double* const partial = uq_layout(carver);
     hipStream_t s = (hipStream_t)stream;
     const uint64_t work = n > m ? n : m;
     uint32_t blocks = (uint32_t)((work + kUqThreads - 1) / kUqThreads);
     blocks = blocks < 1 ? 1 : blocks > kUqBlocks ? kUqBlocks : blocks;
     ProfScope prof("uq_stats", s, (double)work);
     if (c_dtype == 0)
-        k_uq_partial<float><<<blocks, kUqThreads, 0, s>>>((const float*)c, d, n, r, m, (double*)workspace);
+        k_uq_partial<float><<<blocks, kUqThreads, 0, s>>>((const float*)c, d, n, r, m, partial);
     else
-        k_uq_partial<_Float16><<<blocks, kUqThreads, 0, s>>>((const _Float16*)c, d, n, r, m, (double*)workspace);
-    int rc = check_launch("uq_stats");
+        k_uq_partial<_Float16><<<blocks, kUqThreads, 0, s>>>((const _Float16*)c, d, n, r, m, partial);
+    rc = check_launch("uq_stats");
     if (rc) return rc;
-    k_uq_final<<<1, 64, 0, s>>>((const double*)workspace, blocks, n, m, stats);
+    k_uq_final<<<1, 64, 0, s>>>(partial, blocks, n, m, stats);
     return check_launch("uq_stats (final)");
 }
 

@@ -285,9 +285,12 @@ int ngp_closest_point(const float* points, uint64_t N, const ngp_raycast_grid* g
 
 size_t ngp_distance_stats_state_bytes(void) { return sizeof(StatsState); }
 
+// [n / 64 + 2][kStatsQ] partial sums: a call's groups run from the open group of what was seen to the open group of the total
+static double* distance_stats_layout(Carver& c, uint64_t n) { return c.take<double>((size_t)(n / 64 + 2) * kStatsQ); }
+
 size_t ngp_distance_stats_workspace(uint64_t n) {
     if (n >= ((uint64_t)1 << 31)) return 0;
-    return (size_t)(n / 64 + 2) * kStatsQ * sizeof(double);
+    Carver c; distance_stats_layout(c, n); return c.bytes();
 }
 
 int ngp_distance_stats(const float* distance, uint64_t n, uint64_t seen, const float* thresholds_host, uint32_t K, void* state, double* stats,
@@ -304,11 +307,10 @@ int ngp_distance_stats(const float* distance, uint64_t n, uint64_t seen, const f
         th.tau[k] = k < K ? thresholds_host[k] : 0.0f;
         NGP_REQUIRE(th.tau[k] == th.tau[k], "distance_stats: threshold %u is NaN", k);
     }
-    const size_t need = ngp_distance_stats_workspace(n);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) {
-        set_error("distance_stats: workspace too small or not 8-byte aligned (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace("distance_stats", workspace, workspace_bytes, ngp_distance_stats_workspace(n), 8);
+    if (rc) return rc;
+    Carver c(workspace);
+    double* const partial = distance_stats_layout(c, n);
     // the groups this call touches: from the open group of what was seen to the (open) group of the total
     const uint64_t g_first = seen / 64, total = seen + n;
     const uint32_t n_groups = (uint32_t)((total + 63) / 64 - g_first);       // <= n / 64 + 2
@@ -316,11 +318,11 @@ int ngp_distance_stats(const float* distance, uint64_t n, uint64_t seen, const f
     ProfScope prof("distance_stats", s, (double)n);
     if (n_groups) {
         k_distance_stats<<<div_up(n_groups, kStatsBlock / 64), kStatsBlock, 0, s>>>(distance, seen, n, g_first, n_groups, th,
-                                                                                   (const StatsState*)state, (double*)workspace);
-        int rc = check_launch("distance_stats");
+                                                                                   (const StatsState*)state, partial);
+        rc = check_launch("distance_stats");
         if (rc) return rc;
     }
-    k_distance_stats_carry<<<1, 64 * kStatsQ, 0, s>>>(distance, seen, n, g_first, n_groups, (const double*)workspace, (StatsState*)state, stats);
+    k_distance_stats_carry<<<1, 64 * kStatsQ, 0, s>>>(distance, seen, n, g_first, n_groups, partial, (StatsState*)state, stats);
     return check_launch("distance_stats (carry)");
 }
 

@@ -137,6 +137,16 @@ static uint32_t edt_blocks(uint32_t threads) {
     return b > 4096 ? 4096 : (b ? b : 1);
 }
 
+struct EdtWs {
+    int32_t* mid;                  // [n] the middle pass's output
+    uint16_t *stk_s, *stk_t;       // [n] each: the envelope's stacks
+};
+static EdtWs edt_layout(Carver& c, size_t n) {
+    const EdtWs w = {c.take<int32_t>(n), c.take<uint16_t>(n), c.take<uint16_t>(n)};
+    c.pad(64);                     // no kernel touches it: kept so that the size stays what it was
+    return w;
+}
+
 }  // namespace ngp
 
 using namespace ngp;
@@ -144,8 +154,7 @@ using namespace ngp;
 extern "C" {
 
 size_t ngp_edt_sq_workspace(uint32_t X, uint32_t Y, uint32_t Z) {
-    const size_t n = (size_t)X * Y * Z;
-    return n * 4 + 2 * (n * 2) + 64;          // the middle pass's output, then the two uint16 stacks
+    Carver c; edt_layout(c, (size_t)X * Y * Z); return c.bytes();
 }
 
 int ngp_edt_sq(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, int32_t* d2, void* workspace, size_t workspace_bytes,
@@ -154,22 +163,18 @@ int ngp_edt_sq(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, int3
                 "edt_sq: every dimension must be in [1, %u] (got %u x %u x %u)", kEdtMaxDim, X, Y, Z);
     const size_t n = (size_t)X * Y * Z;
     NGP_REQUIRE(n < ((size_t)1 << 31), "edt_sq: X * Y * Z must be < 2^31 (got %zu)", n);
-    NGP_REQUIRE(occupied && d2 && workspace, "edt_sq: null pointer");
-    NGP_REQUIRE(((uintptr_t)workspace & 3) == 0, "edt_sq: workspace must be 4-byte aligned");
-    if (workspace_bytes < ngp_edt_sq_workspace(X, Y, Z)) {
-        set_error("edt_sq: workspace too small (%zu < %zu bytes)", workspace_bytes, ngp_edt_sq_workspace(X, Y, Z));
-        return NGP_EWORKSPACE;
-    }
+    NGP_REQUIRE(occupied && d2, "edt_sq: null pointer");
+    int rc = check_workspace("edt_sq", workspace, workspace_bytes, ngp_edt_sq_workspace(X, Y, Z), 4);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    int32_t* mid = reinterpret_cast<int32_t*>(workspace);
-    uint16_t* stk_s = reinterpret_cast<uint16_t*>(mid + n);
-    uint16_t* stk_t = stk_s + n;
+    Carver c(workspace);
+    const EdtWs w = edt_layout(c, n);
     ProfScope prof("edt_sq", s, (double)n);
     // pass 1 (Z) -> d2; pass 2 (Y): d2 -> mid, lines (x, z); pass 3 (X): mid -> d2, lines (y, z)
     const uint32_t zlines = X * Y;
     k_edt_z<<<div_up(zlines, kEdtBlock / 64) > 4096 ? 4096 : div_up(zlines, kEdtBlock / 64), kEdtBlock, 0, s>>>(occupied, zlines, Z, d2);
-    k_edt_env<<<edt_blocks(X * Z), kEdtBlock, 0, s>>>(d2, mid, X * Z, Z, (size_t)Y * Z, Z, Y, stk_s, stk_t);
-    k_edt_env<<<edt_blocks(Y * Z), kEdtBlock, 0, s>>>(mid, d2, Y * Z, Y * Z, n, (size_t)Y * Z, X, stk_s, stk_t);
+    k_edt_env<<<edt_blocks(X * Z), kEdtBlock, 0, s>>>(d2, w.mid, X * Z, Z, (size_t)Y * Z, Z, Y, w.stk_s, w.stk_t);
+    k_edt_env<<<edt_blocks(Y * Z), kEdtBlock, 0, s>>>(w.mid, d2, Y * Z, Y * Z, n, (size_t)Y * Z, X, w.stk_s, w.stk_t);
     return check_launch("edt_sq");
 }
 

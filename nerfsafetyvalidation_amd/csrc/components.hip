@@ -403,6 +403,21 @@ static bool cc_size_ok(uint32_t X, uint32_t Y, uint32_t Z) {
 }
 constexpr size_t kCcHeader = 64;      // the error word, padded
 
+struct CcWs {
+    int32_t *err, *parent;      // the error word; [n] the union-find forest, later the ranks
+    uint32_t* sums;             // [scan_blocks] roots per block of kScanCells cells
+    uint32_t scan_blocks;
+};
+static CcWs cc_layout(Carver& c, uint32_t n) {
+    CcWs w;
+    w.scan_blocks = div_up(n, kScanCells);
+    w.err = c.take<int32_t>(1);
+    c.pad(kCcHeader - sizeof(int32_t));      // keeps `parent` on a 64-byte line of its own; no kernel touches it
+    w.parent = c.take<int32_t>(n);
+    w.sums = c.take<uint32_t>(w.scan_blocks);
+    return w;
+}
+
 }  // namespace ngp
 
 using namespace ngp;
@@ -411,8 +426,7 @@ extern "C" {
 
 size_t ngp_label_components_workspace(uint32_t X, uint32_t Y, uint32_t Z) {
     if (!cc_size_ok(X, Y, Z)) return 0;
-    const size_t n = (size_t)X * Y * Z;
-    return kCcHeader + n * 4 + (size_t)div_up((uint32_t)n, kScanCells) * 4;      // error word, parent, block counts
+    Carver c; cc_layout(c, X * Y * Z); return c.bytes();
 }
 
 int ngp_label_components(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32_t Z, uint32_t connectivity, int32_t* labels,
@@ -420,22 +434,19 @@ int ngp_label_components(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32
     NGP_REQUIRE(cc_size_ok(X, Y, Z), "label_components: every dimension >= 1 and X * Y * Z < 2^31 (got %u x %u x %u)", X, Y, Z);
     const uint32_t fwd = forward_mask(connectivity);
     NGP_REQUIRE(fwd != 0, "label_components: connectivity is 6, 14, 18 or 26 (got %u)", connectivity);
-    NGP_REQUIRE(occupied && labels && n_components && workspace, "label_components: null pointer");
-    NGP_REQUIRE(((uintptr_t)workspace & 3) == 0, "label_components: workspace must be 4-byte aligned");
-    if (workspace_bytes < ngp_label_components_workspace(X, Y, Z)) {
-        set_error("label_components: workspace too small (%zu < %zu bytes)", workspace_bytes, ngp_label_components_workspace(X, Y, Z));
-        return NGP_EWORKSPACE;
-    }
+    NGP_REQUIRE(occupied && labels && n_components, "label_components: null pointer");
+    int rc = check_workspace("label_components", workspace, workspace_bytes, ngp_label_components_workspace(X, Y, Z), 4);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t n = X * Y * Z;
-    int32_t* err = reinterpret_cast<int32_t*>(workspace);
-    int32_t* parent = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + kCcHeader);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(parent + n);
+    Carver c(workspace);
+    const CcWs w = cc_layout(c, n);
+    int32_t *const err = w.err, *const parent = w.parent;
     const uint32_t tiles_x = div_up(X, kTX), tiles_y = div_up(Y, kTY), tiles_z = div_up(Z, kTZ);
     const uint64_t tiles = (uint64_t)tiles_x * tiles_y * tiles_z;
     NGP_REQUIRE(tiles < ((uint64_t)1 << 31), "label_components: %llu tiles of %u x %u x %u cells do not fit one launch", (unsigned long long)tiles,
                 kTX, kTY, kTZ);
-    const uint32_t cell_blocks = div_up(n, kCcBlock), scan_blocks = div_up(n, kScanCells);
+    const uint32_t cell_blocks = div_up(n, kCcBlock), scan_blocks = w.scan_blocks;
     if (hipMemsetAsync(err, 0, sizeof(int32_t), s) != hipSuccess) return check_launch("label_components");
     {
         ProfScope prof("cc_tile", s, (double)n);
@@ -447,12 +458,12 @@ int ngp_label_components(const uint8_t* occupied, uint32_t X, uint32_t Y, uint32
     }
     {
         ProfScope prof("cc_flatten", s, (double)n);
-        k_cc_flatten<<<scan_blocks, kCcBlock, 0, s>>>(n, parent, labels, sums, err);
+        k_cc_flatten<<<scan_blocks, kCcBlock, 0, s>>>(n, parent, labels, w.sums, err);
     }
     {
         ProfScope prof("cc_rank", s, (double)n);
-        k_cc_scan<<<1, kScanBlock, 0, s>>>(sums, scan_blocks, err, n_components);
-        k_cc_rank<<<scan_blocks, kCcBlock, 0, s>>>(n, labels, sums, parent);
+        k_cc_scan<<<1, kScanBlock, 0, s>>>(w.sums, scan_blocks, err, n_components);
+        k_cc_rank<<<scan_blocks, kCcBlock, 0, s>>>(n, labels, w.sums, parent);
         k_cc_relabel<<<cell_blocks, kCcBlock, 0, s>>>(n, parent, labels);
     }
     return check_launch("label_components");

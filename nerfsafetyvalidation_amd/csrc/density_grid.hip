@@ -154,11 +154,37 @@ static bool grid_dims_ok(uint32_t cascade, uint32_t H) {
     return cascade >= 1 && cascade <= 8 && grid_size_ok(H);      // (a power of two >= 2: H^3 cells fill whole bytes of the bitfield)
 }
 
+// ngp_density_grid_update and ngp_density_grid_finish share one workspace
+struct GridWs {
+    unsigned long long* tmp;      // [H^3] the update's scatter target (order-preserving float bits)
+    double* partial;              // [cascade * per_level] the finish's partial sums of the positive cells
+    uint32_t per_level;           // k_grid_possum's workgroups per level
+};
+static GridWs grid_layout(Carver& c, uint32_t cascade, uint32_t H) {
+    GridWs w;
+    const size_t H3 = (size_t)H * H * H;
+    w.per_level = (uint32_t)((H3 + kDgBlock - 1) / kDgBlock);
+    w.tmp = c.take<unsigned long long>(H3);
+    w.partial = c.take<double>((size_t)cascade * w.per_level);
+    c.pad(64);      // no kernel touches it: kept so that the size stays what it was for H >= 8
+    return w;
+}
+
+// ngp_mark_untrained_grid: one flag word per cell, carried between camera batches; a single batch needs none
+static uint32_t* mark_layout(Carver& c, uint32_t n_cams, uint32_t cascade, uint32_t H) {
+    return c.take<uint32_t>(n_cams > kMaxCams ? (size_t)cascade * H * H * H : 0);
+}
+
 }  // namespace ngp
 
 using namespace ngp;
 
 extern "C" {
+
+size_t ngp_mark_untrained_grid_workspace(uint32_t n_cams, uint32_t cascade, uint32_t H) {
+    if (!grid_dims_ok(cascade, H)) return 0;
+    Carver c; mark_layout(c, n_cams, cascade, H); return c.bytes();
+}
 
 int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float fx, float fy, float cx, float cy, float bound, uint32_t cascade, uint32_t H,
                             float* density_grid, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
@@ -169,12 +195,10 @@ int ngp_mark_untrained_grid(const float* poses, uint32_t n_cams, float fx, float
     // the scalars of :436-438 as torch hands Python floats to a float32 kernel: cx / fx in double, rounded once
     const float kx = (float)((double)cx / (double)fx), ky = (float)((double)cy / (double)fy);
     const uint32_t n_batches = n_cams ? div_up(n_cams, kMaxCams) : 1;
-    uint32_t* seen = nullptr;
-    if (n_batches > 1) {
-        NGP_REQUIRE(workspace && workspace_bytes >= (size_t)cells * 4, "mark_untrained_grid: %u cameras need a workspace of %zu bytes", n_cams,
-                    (size_t)cells * 4);
-        seen = reinterpret_cast<uint32_t*>(workspace);
-    }
+    int rc = check_workspace("mark_untrained_grid", workspace, workspace_bytes, ngp_mark_untrained_grid_workspace(n_cams, cascade, H), 4);
+    if (rc) return rc;
+    Carver c(n_batches > 1 ? workspace : nullptr);
+    uint32_t* const seen = mark_layout(c, n_cams, cascade, H);      // (NULL for a single batch)
     ensure_dynamic_lds((const void*)k_mark_untrained, (int)(kMaxCams * 12 * sizeof(float)));
     for (uint32_t b = 0; b < n_batches; b++) {
         const uint32_t c0 = b * kMaxCams, nc = n_cams - c0 < kMaxCams ? n_cams - c0 : kMaxCams;
@@ -197,20 +221,20 @@ int ngp_density_grid_points(const int32_t* coords, uint32_t n, uint32_t H, float
 }
 
 size_t ngp_density_grid_workspace(uint32_t cascade, uint32_t H) {
-    const size_t H3 = (size_t)H * H * H;
-    return H3 * 8 + (size_t)div_up((uint32_t)(cascade * H3), kDgBlock) * 8 + 64;
+    Carver c; grid_layout(c, cascade, H); return c.bytes();
 }
 
 int ngp_density_grid_update(float* density_grid, uint32_t cascade, uint32_t H, uint32_t cas, const int32_t* indices, const float* sigmas, uint32_t n,
                             float density_scale, float decay, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
-    NGP_REQUIRE(density_grid && workspace && (n == 0 || (indices && sigmas)), "density_grid_update: null pointer");
+    NGP_REQUIRE(density_grid && (n == 0 || (indices && sigmas)), "density_grid_update: null pointer");
     NGP_REQUIRE(grid_dims_ok(cascade, H) && cas < cascade,
                 "density_grid_update: unsupported cascade / grid size C=%u H=%u, level %u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", cascade, H, cas);
-    NGP_REQUIRE(workspace_bytes >= ngp_density_grid_workspace(cascade, H) && ((uintptr_t)workspace & 7) == 0,
-                "density_grid_update: workspace too small or misaligned (%zu < %zu bytes)", workspace_bytes, ngp_density_grid_workspace(cascade, H));
+    int rc = check_workspace("density_grid_update", workspace, workspace_bytes, ngp_density_grid_workspace(cascade, H), 8);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t H3 = H * H * H;
-    unsigned long long* tmp = reinterpret_cast<unsigned long long*>(workspace);
+    Carver c(workspace);
+    unsigned long long* const tmp = grid_layout(c, cascade, H).tmp;
     if (hipMemsetAsync(tmp, 0, (size_t)H3 * 8, s) != hipSuccess) return check_launch("density_grid_update (memset)");
     if (n) k_grid_scatter<<<div_up(n, kDgBlock), kDgBlock, 0, s>>>(indices, sigmas, n, density_scale, tmp, H3);
     k_grid_ema<<<div_up(H3, kDgBlock), kDgBlock, 0, s>>>(density_grid + (size_t)cas * H3, tmp, H3, decay);
@@ -219,16 +243,18 @@ int ngp_density_grid_update(float* density_grid, uint32_t cascade, uint32_t H, u
 
 int ngp_density_grid_finish(const float* density_grid, uint32_t cascade, uint32_t H, float density_thresh, float* mean_thresh, uint8_t* bitfield,
                             void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
-    NGP_REQUIRE(density_grid && mean_thresh && bitfield && workspace, "density_grid_finish: null pointer");
+    NGP_REQUIRE(density_grid && mean_thresh && bitfield, "density_grid_finish: null pointer");
     NGP_REQUIRE(grid_dims_ok(cascade, H), "density_grid_finish: unsupported cascade / grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")", cascade, H);
-    NGP_REQUIRE(workspace_bytes >= ngp_density_grid_workspace(cascade, H) && ((uintptr_t)workspace & 7) == 0, "density_grid_finish: workspace too small or misaligned");
+    int rc = check_workspace("density_grid_finish", workspace, workspace_bytes, ngp_density_grid_workspace(cascade, H), 8);
+    if (rc) return rc;
     NGP_REQUIRE(((uintptr_t)density_grid & 15) == 0, "density_grid_finish: the density grid must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const uint32_t H3 = H * H * H, cells = cascade * H3;
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<unsigned long long*>(workspace) + H3);
-    const uint32_t per = div_up(H3, kDgBlock);
-    for (uint32_t c = 0; c < cascade; c++) k_grid_possum<<<per, kDgBlock, 0, s>>>(density_grid + (size_t)c * H3, H3, partial + (size_t)c * per);
-    k_grid_mean_thresh<<<1, 1024, 0, s>>>(partial, cascade * per, (double)cells, density_thresh, mean_thresh);
+    Carver carver(workspace);
+    const GridWs w = grid_layout(carver, cascade, H);
+    for (uint32_t c = 0; c < cascade; c++)
+        k_grid_possum<<<w.per_level, kDgBlock, 0, s>>>(density_grid + (size_t)c * H3, H3, w.partial + (size_t)c * w.per_level);
+    k_grid_mean_thresh<<<1, 1024, 0, s>>>(w.partial, cascade * w.per_level, (double)cells, density_thresh, mean_thresh);
     k_packbits_dev<<<div_up(div_up(cells / 8, 4), kDgBlock), kDgBlock, 0, s>>>(density_grid, cells / 8, mean_thresh + 1, bitfield);
     return check_launch("density_grid_finish");
 }

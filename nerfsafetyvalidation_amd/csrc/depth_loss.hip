@@ -113,6 +113,8 @@ int ngp_depth_loss_train_forward(const float* sigmas, const float* deltas, const
     NGP_REQUIRE(sigmas && deltas && rays && target && loss_rays && parts && loss, "depth_loss_train_forward: null pointer");
     NGP_REQUIRE(N <= kRayMaxRays, "depth_loss_train_forward: too many rays");
     NGP_REQUIRE(((uintptr_t)deltas & 7) == 0, "depth_loss_train_forward: deltas must be 8-byte aligned");
+    int rc = check_workspace("depth_loss_train_forward", workspace, workspace_bytes, mean_workspace(N), alignof(float));      // before anything is launched
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("depth_loss_train_forward", s, M);
     const RayIn in = {sigmas, deltas, nullptr, 0.0f};
@@ -142,6 +144,8 @@ int ngp_depth_loss_forward(const float* w, const float* t, const int32_t* rays, 
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(w && t && rays && target && loss_rays && parts && loss, "depth_loss_forward: null pointer");
     NGP_REQUIRE(N <= kRayMaxRays, "depth_loss_forward: too many rays");
+    int rc = check_workspace("depth_loss_forward", workspace, workspace_bytes, mean_workspace(N), alignof(float));      // before anything is launched
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("depth_loss_forward", s, M);
     const RayIn in = {w, t, nullptr, 0.0f};

@@ -102,6 +102,8 @@ int ngp_distortion_train_forward(const float* sigmas, const float* deltas, const
     NGP_REQUIRE(sigmas && deltas && rays && loss_rays && totals && loss, "distortion_train_forward: null pointer");
     NGP_REQUIRE(N <= kRayMaxRays, "distortion_train_forward: too many rays");
     NGP_REQUIRE(((uintptr_t)deltas & 7) == 0, "distortion_train_forward: deltas must be 8-byte aligned");
+    int rc = check_workspace("distortion_train_forward", workspace, workspace_bytes, mean_workspace(N), alignof(float));      // before anything is launched
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("distortion_train_forward", s, M);
     const RayIn in = {sigmas, deltas, scale, 0.0f};
@@ -128,6 +130,8 @@ int ngp_distortion_forward(const float* w, const float* m, const float* interval
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(w && m && rays && loss_rays && totals && loss, "distortion_forward: null pointer");
     NGP_REQUIRE(N <= kRayMaxRays, "distortion_forward: too many rays");
+    int rc = check_workspace("distortion_forward", workspace, workspace_bytes, mean_workspace(N), alignof(float));      // before anything is launched
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("distortion_forward", s, M);
     const RayIn in = {w, m, interval, interval_scalar};

@@ -296,15 +296,13 @@ int ngp_sift_interest_mask(const uint8_t* rgb, uint32_t H, uint32_t W, uint32_t 
                            uint8_t* mask, uint32_t* count, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
     SiftGeometry g;
     NGP_REQUIRE(sift_geometry(H, W, g), "sift_interest_mask: H and W must be in [8, 16384] with H * W < 2^32 / 20 (got %u x %u)", H, W);
-    NGP_REQUIRE(rgb && points && mask && count && workspace, "sift_interest_mask: null pointer");
-    NGP_REQUIRE(((uintptr_t)workspace & 3) == 0, "sift_interest_mask: workspace must be 4-byte aligned");
+    NGP_REQUIRE(rgb && points && mask && count, "sift_interest_mask: null pointer");
     NGP_REQUIRE(kernel_size >= 1 && kernel_size <= 255 && dil_iter <= 255, "sift_interest_mask: kernel_size in [1, 255], dil_iter <= 255");
-    if (workspace_bytes < g.total) {
-        set_error("sift_interest_mask: workspace too small (%zu < %zu bytes)", workspace_bytes, g.total);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace("sift_interest_mask", workspace, workspace_bytes, g.total, 4);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(workspace);
+    Carver c(workspace);
+    char* const ws = c.take<char>(g.total);      // SiftGeometry's offsets are into this
     float* base = reinterpret_cast<float*>(ws + g.scratch);
     float* tmp = base + (size_t)g.rows[0] * g.cols[0];
     uint8_t* dtmp = reinterpret_cast<uint8_t*>(ws + g.dilate_tmp);

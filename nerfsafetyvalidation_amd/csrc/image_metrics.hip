@@ -163,6 +163,9 @@ __global__ void __launch_bounds__(64 * kIqSums) k_image_quality_final(const doub
 
 static inline uint32_t iq_tiles(uint32_t H, uint32_t W) { return div_up(H, kIqTileH) * div_up(W, kIqTileW); }
 
+// [B][kIqSums][tiles] partial sums, one per tile and quantity
+static double* iq_layout(Carver& c, uint32_t B, uint32_t H, uint32_t W) { return c.take<double>((size_t)B * kIqSums * iq_tiles(H, W)); }
+
 }  // namespace ngp
 
 using namespace ngp;
@@ -171,7 +174,7 @@ extern "C" {
 
 size_t ngp_image_quality_workspace(uint32_t B, uint32_t H, uint32_t W) {
     if (B == 0 || B > 65535 || H < 6 || W < 6 || H > 32768 || W > 32768) return 0;
-    return (size_t)B * kIqSums * iq_tiles(H, W) * sizeof(double);
+    Carver c; iq_layout(c, B, H, W); return c.bytes();
 }
 
 int ngp_image_quality(const float* pred, const float* target, const float* mask, uint32_t B, uint32_t H, uint32_t W, int64_t stride_b,
@@ -183,11 +186,10 @@ int ngp_image_quality(const float* pred, const float* target, const float* mask,
     NGP_REQUIRE(B >= 1 && B <= 65535, "image_quality: batch size must be in [1, 65535] (got %u)", B);
     NGP_REQUIRE(data_range > 0.0f, "image_quality: data_range must be positive");     // (false for NaN as well)
     NGP_REQUIRE(stride_b >= 0 && stride_c >= 0 && stride_y >= 0 && stride_x >= 0, "image_quality: negative stride");
-    const size_t need = ngp_image_quality_workspace(B, H, W);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) {
-        set_error("image_quality: workspace too small or not 8-byte aligned (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace("image_quality", workspace, workspace_bytes, ngp_image_quality_workspace(B, H, W), 8);
+    if (rc) return rc;
+    Carver c(workspace);
+    double* const partial = iq_layout(c, B, H, W);
     IqParams prm;
     double sum = 0.0;
     for (int k = 0; k < kIqTaps; k++) {
@@ -203,10 +205,10 @@ int ngp_image_quality(const float* pred, const float* target, const float* mask,
     ProfScope prof("image_quality", s, (double)B * H * W);
     const dim3 grid(div_up(W, kIqTileW), div_up(H, kIqTileH), B);
     k_image_quality<<<grid, kIqThreads, 0, s>>>(pred, target, mask, (int)H, (int)W, stride_b, stride_c, stride_y, stride_x, prm, ssim_map,
-                                                (double*)workspace);
-    int rc = check_launch("image_quality");
+                                                partial);
+    rc = check_launch("image_quality");
     if (rc) return rc;
-    k_image_quality_final<<<B, 64 * kIqSums, 0, s>>>((const double*)workspace, iq_tiles(H, W), (double)H * (double)W, stats);
+    k_image_quality_final<<<B, 64 * kIqSums, 0, s>>>(partial, iq_tiles(H, W), (double)H * (double)W, stats);
     return check_launch("image_quality (final)");
 }
 

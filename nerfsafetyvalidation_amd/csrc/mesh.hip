@@ -314,19 +314,16 @@ struct IsoWorkspace {
     uint32_t n_blocks;
 };
 
-static IsoWorkspace iso_carve(void* workspace, uint32_t N) {
+static IsoWorkspace iso_layout(Carver& c, uint32_t N) {
     IsoWorkspace w;
     w.n_blocks = div_up(N, kIsoBlock);
-    uint8_t* base = reinterpret_cast<uint8_t*>(workspace);
-    w.block_tot = reinterpret_cast<unsigned long long*>(base);
-    base += (size_t)w.n_blocks * 16;
-    const size_t n2 = ((size_t)N * 2 + 7) & ~(size_t)7;
-    w.vpre = reinterpret_cast<uint16_t*>(base);
-    w.fpre = reinterpret_cast<uint16_t*>(base + n2);
-    base += 2 * n2;
-    w.flags = base;
-    w.mask = base + N;
-    w.ntri = base + 2 * (size_t)N;
+    w.block_tot = c.take<unsigned long long>((size_t)w.n_blocks * 2);
+    w.vpre = c.take<uint16_t>(N, 8);
+    w.fpre = c.take<uint16_t>(N, 8);
+    w.flags = c.take<uint8_t>(N, 8);
+    w.mask = c.take<uint8_t>(N);
+    w.ntri = c.take<uint8_t>(N);
+    c.pad(64);      // no kernel touches it: kept so that the size stays what it was
     return w;
 }
 
@@ -345,24 +342,21 @@ extern "C" {
 
 size_t ngp_isosurface_workspace(uint32_t X, uint32_t Y, uint32_t Z) {
     if (iso_check_dims("isosurface_workspace", X, Y, Z) != NGP_OK) return 0;
-    const size_t N = (size_t)X * Y * Z;
-    const size_t n2 = (N * 2 + 7) & ~(size_t)7;
-    return (size_t)div_up((uint32_t)N, kIsoBlock) * 16 + 2 * n2 + 3 * N + 64;
+    Carver c; iso_layout(c, X * Y * Z); return c.bytes();
 }
 
 int ngp_isosurface_count(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, void* workspace, size_t workspace_bytes,
                          uint64_t* totals, ngp_stream_t stream) {
     int rc = iso_check_dims("isosurface_count", X, Y, Z);
     if (rc) return rc;
-    NGP_REQUIRE(u && workspace && totals, "isosurface_count: null pointer");
-    NGP_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)totals & 7) == 0, "isosurface_count: workspace and totals must be 8-byte aligned");
-    if (workspace_bytes < ngp_isosurface_workspace(X, Y, Z)) {
-        set_error("isosurface_count: workspace too small (%zu < %zu bytes)", workspace_bytes, ngp_isosurface_workspace(X, Y, Z));
-        return NGP_EWORKSPACE;
-    }
+    NGP_REQUIRE(u && totals, "isosurface_count: null pointer");
+    NGP_REQUIRE(((uintptr_t)totals & 7) == 0, "isosurface_count: totals must be 8-byte aligned");
+    rc = check_workspace("isosurface_count", workspace, workspace_bytes, ngp_isosurface_workspace(X, Y, Z), 8);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const IsoDims D{X, Y, Z, X * Y * Z, Y * Z};
-    const IsoWorkspace w = iso_carve(workspace, D.N);
+    Carver c(workspace);
+    const IsoWorkspace w = iso_layout(c, D.N);
     {
         ProfScope prof("isosurface_count", s, (double)D.N);
         k_iso_flags<<<w.n_blocks, kIsoBlock, 0, s>>>(u, D.N, threshold, w.flags);
@@ -381,17 +375,15 @@ int ngp_isosurface_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, floa
     if (rc) return rc;
     NGP_REQUIRE(V < ((uint64_t)1 << 31) && F < ((uint64_t)1 << 31), "isosurface_emit: V and F must be < 2^31 (got V = %llu, F = %llu)",
                 (unsigned long long)V, (unsigned long long)F);
-    NGP_REQUIRE(u && workspace, "isosurface_emit: null pointer");
+    NGP_REQUIRE(u, "isosurface_emit: null pointer");
     NGP_REQUIRE((V == 0 || vertices) && (F == 0 || faces), "isosurface_emit: null output for a non-empty mesh");
-    NGP_REQUIRE(((uintptr_t)workspace & 7) == 0, "isosurface_emit: workspace must be 8-byte aligned");
-    if (workspace_bytes < ngp_isosurface_workspace(X, Y, Z)) {
-        set_error("isosurface_emit: workspace too small (%zu < %zu bytes)", workspace_bytes, ngp_isosurface_workspace(X, Y, Z));
-        return NGP_EWORKSPACE;
-    }
+    rc = check_workspace("isosurface_emit", workspace, workspace_bytes, ngp_isosurface_workspace(X, Y, Z), 8);
+    if (rc) return rc;
     if (V == 0 && F == 0) return NGP_OK;
     hipStream_t s = (hipStream_t)stream;
     const IsoDims D{X, Y, Z, X * Y * Z, Y * Z};
-    const IsoWorkspace w = iso_carve(const_cast<void*>(workspace), D.N);
+    Carver c(const_cast<void*>(workspace));      // (read only here: ngp_isosurface_count filled it)
+    const IsoWorkspace w = iso_layout(c, D.N);
     ProfScope prof("isosurface_emit", s, (double)D.N);
     k_iso_emit<<<w.n_blocks, kIsoBlock, 0, s>>>(u, w.flags, D, threshold, w.mask, w.ntri, w.vpre, w.fpre, w.block_tot, (uint32_t)V, (uint32_t)F,
                                                 vertices, faces);

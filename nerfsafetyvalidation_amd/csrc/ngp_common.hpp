@@ -10,11 +10,11 @@
 #include <string>
 
 #include "../../include/ngp_hip.h"
+#include "workspace.hpp"
 
 namespace ngp {
 
-// ---- error plumbing -------------------------------------------------------------
-void set_error(const char* fmt, ...);
+// ---- error plumbing (set_error: declared in workspace.hpp) -----------------------
 int check_launch(const char* what);
 
 #define NGP_REQUIRE(cond, ...)                 \
@@ -45,8 +45,10 @@ static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; 
 constexpr uint32_t kMeanOneBlockRays = 16384;      // up to here one 1024-thread workgroup forms the mean: one launch, no workspace
 constexpr uint32_t kMeanOneBlockThreads = 1024;
 constexpr uint32_t kMeanGroupThreads = 256;        // above: 256 values per workgroup into per-64 group sums, then one wave over the groups
-static inline size_t mean_workspace(uint32_t N) { return N <= kMeanOneBlockRays ? 0 : (size_t)div_up(N, 64) * sizeof(float); }
-// *mean = mean of values[0 .. N); mean_workspace(N) bytes of workspace (NGP_EWORKSPACE when it has fewer).  `what` names the caller in errors.
+// [(N + 63) / 64] group sums; nothing up to kMeanOneBlockRays
+static inline float* mean_layout(Carver& c, uint32_t N) { return c.take<float>(N <= kMeanOneBlockRays ? 0 : div_up(N, 64)); }
+static inline size_t mean_workspace(uint32_t N) { Carver c; mean_layout(c, N); return c.bytes(); }
+// *mean = mean of values[0 .. N); mean_workspace(N) bytes of workspace, 4-byte aligned (check_workspace's codes).  `what` names the caller in errors.
 int mean_of_rays(const float* values, uint32_t N, float* mean, void* workspace, size_t workspace_bytes, hipStream_t s, const char* what);
 // the last step alone, for a caller that formed the (N + 63) / 64 group sums in a pass of its own (N > kMeanOneBlockRays)
 int mean_of_groups(const float* groups, uint32_t N, float* mean, hipStream_t s, const char* what);

@@ -739,16 +739,29 @@ int ngp_packbits(const float* grid, uint32_t N, float density_thresh, uint8_t* b
     return check_launch("packbits");
 }
 
-static size_t train_counts_bytes(uint32_t N) {
-    const size_t nblocks = div_up(N ? N : 1, kBlock);
-    return (((size_t)(N + nblocks + 4) * sizeof(uint32_t)) + 15) & ~(size_t)15;
+constexpr uint32_t kTraceMaxRays = 16384, kTraceMaxSteps = 1024;   // (t, dt) trace of the count pass: 8 bytes per possible sample
+
+struct TrainWs {
+    uint32_t *counts, *block_sums, *base;      // [N] samples per ray, [nblocks] per-block sums -> offsets, the two counter bases
+    char *lin, *coarse;                        // the derived copies of the occupancy bits (build_occupancy_lin)
+    float2* trace;                             // [N][kTraceMaxSteps], only up to kTraceMaxRays rays
+    uint32_t nblocks;
+};
+static TrainWs train_layout(Carver& c, uint32_t N) {
+    TrainWs w;
+    w.nblocks = div_up(N ? N : 1, kBlock);
+    w.counts = c.take<uint32_t>(N);
+    w.block_sums = c.take<uint32_t>(w.nblocks);
+    w.base = c.take<uint32_t>(2);
+    c.pad(2 * sizeof(uint32_t));               // two spare words no kernel touches: kept so that the size stays what it was
+    w.lin = c.take<char>(kTrainLinBytes, 16);
+    w.coarse = c.take<char>(kCoarseMaxBytes);
+    w.trace = c.take<float2>(N <= kTraceMaxRays ? (size_t)N * kTraceMaxSteps : 0);
+    return w;
 }
 
-constexpr uint32_t kTraceMaxRays = 16384, kTraceMaxSteps = 1024;   // (t, dt) trace of the count pass: 8 bytes per possible sample
-static size_t train_trace_bytes(uint32_t N) { return N <= kTraceMaxRays ? (size_t)N * kTraceMaxSteps * sizeof(float2) : 0; }
-
 size_t ngp_march_rays_train_workspace(uint32_t N) {
-    return train_counts_bytes(N) + kTrainLinBytes + kCoarseMaxBytes + train_trace_bytes(N);
+    Carver c; train_layout(c, N); return c.bytes();
 }
 
 int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma, uint32_t max_steps,
@@ -759,27 +772,23 @@ int ngp_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t
     NGP_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter, "march_rays_train: null pointer");
     NGP_REQUIRE(C >= 1 && C <= 8 && grid_size_ok(H), "march_rays_train: unsupported cascade/grid size C=%u H=%u (C in [1, 8]; " NGP_GRID_SIZE_RULE ")",
                 C, H);
-    if (!workspace || workspace_bytes < ngp_march_rays_train_workspace(N)) {
-        set_error("march_rays_train: workspace of %zu bytes needed, %zu given", ngp_march_rays_train_workspace(N), workspace_bytes);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace("march_rays_train", workspace, workspace_bytes, ngp_march_rays_train_workspace(N), 16);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t nblocks = div_up(N, kBlock);
-    uint32_t* counts = (uint32_t*)workspace;
-    uint32_t* block_sums = counts + N;
-    uint32_t* base = block_sums + nblocks;
+    Carver carver(workspace);
+    const TrainWs w = train_layout(carver, N);
+    const uint32_t nblocks = w.nblocks;
+    uint32_t *const counts = w.counts, *const block_sums = w.block_sums, *const base = w.base;
     Pcg32 rng;
     rng.seed(42u);  // raymarching.cu:489 hard-coded seed
     ProfScope prof("march_rays_train", s, N);
     // power-of-two grid whose bits fit the workspace: derived copies of the occupancy bits (a few microseconds) and the cheaper probes
     OccupancyLin tl = {};
     const bool lin = N >= 1024 && occupancy_lin_fits(C, H, grid, kTrainLinBytes, kCoarseMaxBytes);
-    char* extra = (char*)workspace + train_counts_bytes(N);      // the two copies, then the trace
-    float2* trace = nullptr;
-    if (lin && train_trace_bytes(N) && max_steps <= kTraceMaxSteps) trace = (float2*)(extra + kTrainLinBytes + kCoarseMaxBytes);
+    float2* const trace = lin && N <= kTraceMaxRays && max_steps <= kTraceMaxSteps ? w.trace : nullptr;
     // both passes: a wave per ray on the step lattice (dt_gamma == 0 only), a lane per ray with the trace replayed, or marching twice
     enum { kWave, kTraced, kLin, kPlain } const form = !lin ? kPlain : (!trace ? kLin : (dt_gamma == 0.0f ? kWave : kTraced));
-    if (lin) tl = build_occupancy_lin(grid, C, H, extra, extra + kTrainLinBytes, s);
+    if (lin) tl = build_occupancy_lin(grid, C, H, w.lin, w.coarse, s);
 #define NGP_COUNT(LIN_, TRACE_)                                                                                                                   \
     k_march_train_count<LIN_, TRACE_><<<nblocks, kBlock, 0, s>>>(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, perturb, rng, \
                                                                  counts, block_sums, tl, trace)

@@ -778,11 +778,16 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
     return check_launch("render_uniform");
 }
 
-// sigma of the coarse pass [N, T], depths and sigma of the fine pass [N, U] x 2 (fp32), the sigma net's outputs of both [N, T + U, 16] (fp16)
-static size_t upsample_workspace_bytes(uint32_t N, uint32_t T, uint32_t U) {
-    const size_t Np = ((size_t)N + 15) / 16 * 16;          // whole groups of sixteen rays
-    return Np * (((size_t)T + 2 * (size_t)U) * sizeof(float) + ((size_t)T + U) * 16 * sizeof(_Float16));
+// group-major arrays over Np rays, whole groups of sixteen (see k_density_x16)
+struct UpsampleWs {
+    float *sc, *zf, *sf;      // sigma of the coarse pass [Np, T]; depths and sigma of the fine pass [Np, U] each
+    _Float16 *gc, *gf;        // the sigma net's outputs of both passes [Np, T, 16], [Np, U, 16]
+};
+static UpsampleWs upsample_layout(Carver& c, uint32_t N, uint32_t T, uint32_t U) {
+    const size_t Np = ((size_t)N + 15) / 16 * 16;
+    return {c.take<float>(Np * T), c.take<float>(Np * U), c.take<float>(Np * U), c.take<_Float16>(Np * T * 16), c.take<_Float16>(Np * U * 16)};
 }
+static size_t upsample_workspace_bytes(uint32_t N, uint32_t T, uint32_t U) { Carver c; upsample_layout(c, N, T, U); return c.bytes(); }
 size_t ngp_render_upsample_workspace(uint32_t N, uint32_t T, uint32_t U) {
     return N >= kUniformX16MinRays ? upsample_workspace_bytes(N, T, U) : 0;
 }
@@ -829,12 +834,10 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     // Large batches: four launches through the caller's scratch (group-major arrays, see k_density_x16).  The two density
     // passes take their tiles ACROSS sixteen neighbouring rays (twice the per-sample rate of tiles along a ray) and keep the sigma
     // net's outputs; the per-ray kernel resamples between them; merge + compositing run across the rays as well, colour net only.
-    const size_t Np = ((size_t)N + 15) / 16 * 16;
-    float* sc = reinterpret_cast<float*>(workspace);
-    float* zf = sc + Np * T;
-    float* sf = zf + Np * U;
-    _Float16* gc = reinterpret_cast<_Float16*>(sf + Np * U);
-    _Float16* gf = gc + Np * T * 16;
+    Carver carver(workspace);
+    const UpsampleWs w = upsample_layout(carver, N, T, U);
+    float *sc = w.sc, *zf = w.zf, *sf = w.sf;
+    _Float16 *gc = w.gc, *gf = w.gf;
     uint32_t gb = div_up(div_up(N, 16), 4);
     if (gb > 1024) gb = 1024;
     auto density = [&](uint32_t n, const float* z_in, float* out, _Float16* geo) {

@@ -191,33 +191,39 @@ __global__ void __launch_bounds__(kFitThreads) k_sigma_fit_reduce(const double* 
     }
 }
 
+struct FitWs {
+    double* part_loss;      // [wgs] one partial loss per workgroup
+    float* part_grad;       // [wgs][kFitPartial] and its partial gradient
+    uint32_t wgs;
+};
+static FitWs fit_layout(Carver& c, uint32_t n, uint32_t max_workgroups) {
+    const uint32_t wgs = fit_workgroups(n, max_workgroups);
+    return {c.take<double>(wgs), c.take<float>((size_t)wgs * kFitPartial), wgs};
+}
+
 static int fit_launch(const float* features, const float* y, uint32_t n, const float* theta, float prior_mean, double prior_var, int mode,
                       uint32_t max_workgroups, void* workspace, size_t workspace_bytes, double* loss, float* grad, float* history,
                       float* min_loss, int32_t* improved, hipStream_t s) {
-    NGP_REQUIRE(features && y && theta && workspace, "sigma_fit: null pointer");
+    NGP_REQUIRE(features && y && theta, "sigma_fit: null pointer");
     NGP_REQUIRE(n >= 1, "sigma_fit: no points");
     NGP_REQUIRE(mode >= 0 && mode <= 2, "sigma_fit: mode must be 0 (loss), 1 (loss + prior gradient) or 2 (loss + full gradient)");
     NGP_REQUIRE(mode == 0 || grad, "sigma_fit: mode %d needs a gradient buffer", mode);
     NGP_REQUIRE(max_workgroups <= kFitMaxWG, "sigma_fit: max_workgroups %u > %u", max_workgroups, kFitMaxWG);
     NGP_REQUIRE(prior_var > 0.0, "sigma_fit: the prior's variance must be positive");
-    NGP_REQUIRE(((uintptr_t)features & 15) == 0 && ((uintptr_t)workspace & 7) == 0, "sigma_fit: features must be 16-byte and the workspace 8-byte aligned");
-    const size_t need = ngp_sigma_fit_workspace(n, max_workgroups);
-    if (workspace_bytes < need) {
-        set_error("sigma_fit: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-        return NGP_EWORKSPACE;
-    }
-    const uint32_t wgs = fit_workgroups(n, max_workgroups);
-    double* part_loss = (double*)workspace;
-    float* part_grad = (float*)(part_loss + wgs);
+    NGP_REQUIRE(((uintptr_t)features & 15) == 0, "sigma_fit: features must be 16-byte aligned");
+    int rc = check_workspace("sigma_fit", workspace, workspace_bytes, ngp_sigma_fit_workspace(n, max_workgroups), 8);
+    if (rc) return rc;
+    Carver c(workspace);
+    const FitWs w = fit_layout(c, n, max_workgroups);
     ProfScope prof(mode == 2 ? "sigma_fit_grad" : "sigma_fit_loss", s, (double)n);
     if (mode == 2)
-        k_sigma_fit<true><<<wgs, kFitThreads, 0, s>>>(features, y, n, theta, part_loss, part_grad);
+        k_sigma_fit<true><<<w.wgs, kFitThreads, 0, s>>>(features, y, n, theta, w.part_loss, w.part_grad);
     else
-        k_sigma_fit<false><<<wgs, kFitThreads, 0, s>>>(features, y, n, theta, part_loss, part_grad);
-    int rc = check_launch("sigma_fit");
+        k_sigma_fit<false><<<w.wgs, kFitThreads, 0, s>>>(features, y, n, theta, w.part_loss, w.part_grad);
+    rc = check_launch("sigma_fit");
     if (rc) return rc;
     const uint32_t grad_blocks = mode == 0 ? 0 : kFitTheta / 64;
-    k_sigma_fit_reduce<<<grad_blocks + 1, kFitThreads, 0, s>>>(part_loss, part_grad, wgs, theta, prior_mean, (float)prior_var, prior_var, mode,
+    k_sigma_fit_reduce<<<grad_blocks + 1, kFitThreads, 0, s>>>(w.part_loss, w.part_grad, w.wgs, theta, prior_mean, (float)prior_var, prior_var, mode,
                                                               grad_blocks, grad, loss, history, min_loss, improved);
     return check_launch("sigma_fit (reduce)");
 }
@@ -230,7 +236,7 @@ extern "C" {
 
 size_t ngp_sigma_fit_workspace(uint32_t n, uint32_t max_workgroups) {
     if (max_workgroups > kFitMaxWG) return 0;
-    return (size_t)fit_workgroups(n, max_workgroups) * (sizeof(double) + kFitPartial * sizeof(float));
+    Carver c; fit_layout(c, n, max_workgroups); return c.bytes();
 }
 
 int ngp_sigma_fit_eval(const float* features, const float* y, uint32_t n, const float* theta, float prior_mean, double prior_var, int mode,

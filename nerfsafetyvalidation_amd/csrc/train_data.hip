@@ -130,16 +130,16 @@ int mean_of_groups(const float* groups, uint32_t N, float* mean, hipStream_t s, 
 
 int mean_of_rays(const float* values, uint32_t N, float* mean, void* workspace, size_t workspace_bytes, hipStream_t s, const char* what) {
     const size_t need = mean_workspace(N);
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("%s: workspace too small (%zu < %zu bytes)", what, workspace ? workspace_bytes : (size_t)0, need);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace(what, workspace, workspace_bytes, need, alignof(float));
+    if (rc) return rc;
     if (!need) {
         k_mean_one_block<<<1, kMeanOneBlockThreads, 0, s>>>(values, N, mean);
         return check_launch(what);
     }
-    k_mean_groups<<<div_up(N, kMeanGroupThreads), kMeanGroupThreads, 0, s>>>(values, N, (float*)workspace);
-    return mean_of_groups((const float*)workspace, N, mean, s, what);
+    Carver c(workspace);
+    float* const groups = mean_layout(c, N);
+    k_mean_groups<<<div_up(N, kMeanGroupThreads), kMeanGroupThreads, 0, s>>>(values, N, groups);
+    return mean_of_groups(groups, N, mean, s, what);
 }
 
 template <typename P>
@@ -210,10 +210,8 @@ int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, ui
     NGP_REQUIRE(pred_dtype == 0 || pred_dtype == 1, "photo_loss_forward: pred dtype must be 0 (f32) or 1 (f16)");
     NGP_REQUIRE(!error_row || inds_coarse, "photo_loss_forward: an error-map row needs inds_coarse");
     const size_t need = ngp_photo_loss_workspace(N);
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("photo_loss_forward: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
-        return NGP_EWORKSPACE;
-    }
+    int rc = check_workspace("photo_loss_forward", workspace, workspace_bytes, need, alignof(float));
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("photo_loss", s, (double)N);
     if (!need) {
@@ -223,14 +221,16 @@ int ngp_photo_loss_forward(const void* pred, int pred_dtype, const float* gt, ui
             k_photo_loss_one_block<_Float16><<<1, kMeanOneBlockThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, mean, error_row, map_len, inds_coarse);
         return check_launch("photo_loss_forward");
     }
+    Carver c(workspace);
+    float* const groups = mean_layout(c, N);
     const uint32_t blocks = div_up(N, kMeanGroupThreads);
     if (pred_dtype == 0)
-        k_photo_loss_groups<float><<<blocks, kMeanGroupThreads, 0, s>>>((const float*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
+        k_photo_loss_groups<float><<<blocks, kMeanGroupThreads, 0, s>>>((const float*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, groups);
     else
-        k_photo_loss_groups<_Float16><<<blocks, kMeanGroupThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, (float*)workspace);
-    int rc = check_launch("photo_loss_forward");
+        k_photo_loss_groups<_Float16><<<blocks, kMeanGroupThreads, 0, s>>>((const _Float16*)pred, gt, N, per_ray, error_row, map_len, inds_coarse, groups);
+    rc = check_launch("photo_loss_forward");
     if (rc) return rc;
-    return mean_of_groups((const float*)workspace, N, mean, s, "photo_loss_forward (final)");
+    return mean_of_groups(groups, N, mean, s, "photo_loss_forward (final)");
 }
 
 int ngp_photo_loss_backward(const void* pred, int pred_dtype, const float* gt, uint32_t N, const float* g, void* grad_pred, ngp_stream_t stream) {

@@ -352,7 +352,7 @@ class NeRFRenderer(nn.Module):
         device = self.density_grid.device
         cams = torch.as_tensor(np.asarray(poses) if not torch.is_tensor(poses) else poses, dtype=torch.float32).to(device).contiguous()
         fx, fy, cx, cy = [float(v) for v in intrinsic]
-        work, nbytes = self._grid_workspace()
+        work, nbytes = _lib.workspace("mark_untrained_grid", cams.shape[0], self.cascade, self.grid_size, device=device)
         _lib.call("mark_untrained_grid", cams, cams.shape[0], fx, fy, cx, cy, float(self.bound), self.cascade, self.grid_size,
                   self.density_grid, work, nbytes, wrote=(self.density_grid,))
 

@@ -146,6 +146,49 @@ def test_backward_plans_answer_as_before_the_refactor(monkeypatch):
         assert lib.ngp_grid_encode_backward_workspace(B, 3, 2, 16, _lib.NGP_F16) == nbytes
 
 
+def test_workspace_sizes_answer_as_before_the_layouts():
+    """Every size function whose entry point carves through csrc/workspace.hpp answers (host arithmetic, no GPU), over the sweep of
+    tests/golden/make_golden_workspaces.py, what the build before the shared layouts answered (tests/golden/workspace_sizes.json) --
+    except the density grid for H < 8, where the layout counts the partial sums the kernels write: there the answer is the listed new
+    value, and no smaller than the bytes ngp_density_grid_update and ngp_density_grid_finish touch.  The size function that is new
+    with the layouts, ngp_mark_untrained_grid_workspace, is checked against its definition."""
+    import importlib.util
+    import json
+    from nerfsafetyvalidation_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_golden_workspaces", os.path.join(ROOT, "tests", "golden", "make_golden_workspaces.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    doc = json.load(open(gen.OUT))
+    assert doc["cases"] == gen.CASES and sorted(doc["answers"]) == sorted(gen.CASES)
+    lib = _lib.lib()
+    got = gen.answers(lib)
+    excepted = {(e["cascade"], e["H"]): e for e in gen.DENSITY_GRID_EXCEPTIONS}
+    assert sorted(excepted) == [(c, H) for c in range(2, 9) for H in (2, 4)]
+    wrong = []
+    for name, shapes in gen.CASES.items():
+        assert len(got[name]) == len(doc["answers"][name]) == len(shapes)
+        for shape, g, w in zip(shapes, got[name], doc["answers"][name]):
+            e = excepted.get(tuple(shape)) if name == "density_grid" else None
+            if e is not None:
+                c, H = shape
+                assert w == e["old"] and e["new"] != e["old"], (shape, w, e)
+                touched = H ** 3 * 8 + c * -(-H ** 3 // 256) * 8
+                if g != e["new"] or g < touched:
+                    wrong.append((name, shape, g, e["new"], touched))
+            elif g != w:
+                wrong.append((name, shape, g, w))
+    assert not wrong, f"{len(wrong)} shapes answer differently, first (function, shape, got, recorded): {wrong[:5]}"
+    # spot values by hand: the refusals answer 0, the thresholds sit where the header says
+    assert lib.ngp_photo_loss_workspace(16384) == 0 and lib.ngp_photo_loss_workspace(16385) == 257 * 4
+    assert lib.ngp_render_upsample_workspace(65535, 4, 2) == 0 and lib.ngp_render_upsample_workspace(65536, 4, 2) == 65536 * (8 * 4 + 6 * 32)
+    assert lib.ngp_isosurface_workspace(2048, 1024, 1024) == 0 and lib.ngp_label_components_workspace(0, 5, 6) == 0
+    assert lib.ngp_density_grid_workspace(8, 2) == 64 + 64 + 64 and lib.ngp_density_grid_workspace(1, 128) == (128 ** 3 + 128 ** 3 // 256) * 8 + 64
+    # ngp_mark_untrained_grid_workspace: nothing up to 2048 cameras (one launch), a word per cell above, 0 for a grid the call refuses
+    for n_cams, cascade, H, want in ((0, 1, 128, 0), (1, 3, 32, 0), (2048, 8, 128, 0), (2049, 3, 32, 3 * 32 ** 3 * 4), (5000, 8, 128, 8 * 128 ** 3 * 4),
+                                     (2049, 1, 2, 32), (2049, 0, 32, 0), (2049, 9, 32, 0), (2049, 3, 48, 0), (2049, 1, 2048, 0)):
+        assert lib.ngp_mark_untrained_grid_workspace(n_cams, cascade, H) == want, (n_cams, cascade, H)
+
+
 def test_signature_table_matches_the_header():
     """Every prototype against its SIGNATURES / _RESTYPES entry: the number of parameters, per parameter the class (pointer, signed or
     unsigned integer, floating point) and the width, the return type (int, size_t, const char*), and the slot the table marks as the
