@@ -506,6 +506,49 @@ NGP_API int ngp_isosurface_count(const float* u, uint32_t X, uint32_t Y, uint32_
 NGP_API int ngp_isosurface_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, const void* workspace,
                                 size_t workspace_bytes, uint64_t V, uint64_t F, float* vertices, int32_t* faces, ngp_stream_t stream);
 
+/* Mesh simplification by vertex clustering with quadric-optimal representatives (csrc/simplify.hip; DESIGN.md "Mesh simplification"
+ * fixes the rule and the summation order; nerfsafetyvalidation_amd/mesh.py's _simplify_numpy defines the result, and these kernels
+ * give its bits).  vertices float [V,3], faces int32 [F,3], cell > 0 and origin (three HOST doubles).  All arithmetic is IEEE double
+ * on the float inputs, one rounding per operation.  A vertex belongs to cell i_a = floor((v_a - o_a) / cell), 0 <= i_a < 2^21, key =
+ * ix << 42 | iy << 21 | iz; the clusters are the distinct keys, numbered in ascending order.  Sorting and scanning between the calls
+ * are the caller's (stable sorts, so that every list is in ascending input index within a cluster); all arrays are device memory:
+ *   ngp_simplify_keys        keys int64 [V].  A non-finite coordinate, a vertex below origin or an index >= 2^21 sets *error (int32,
+ *                            zeroed by the caller; atomicMax) to 1 and the key to 0; a face index outside [0, V) sets it to 2.  The
+ *                            later calls are memory-safe whatever the error; the caller reads the word once, with V' and F', and
+ *                            reads nothing else when it is set.
+ *   ngp_simplify_corners     vcluster int32 [V] (the cluster of every vertex) -> ccluster int32 [3 F], corner 3 f + k's cluster.
+ *   ngp_simplify_accumulate  sorted_keys int64 [V] ascending; vertex_order int64 [V] the vertices sorted by cluster; vertex_start int64
+ *                            [V + 1] the first row of cluster c in it (V for c >= the number of clusters); corner_order int64 [3 F],
+ *                            corner_start int64 [V + 1] the same for the corners -> representatives float [V,3], row c for cluster c.
+ *                            Relative to p_c = o + (i + 1/2) cell: m = the mean of the cluster's vertices; over its corners, with A, B,
+ *                            C the corner's face: n = (B - A) x (C - A), d = -n . (A - p_c), Q_A += n n^T, q_b += d n.  Every sum: 64
+ *                            consecutive ranks by the xor butterfly (offsets 32 .. 1, +0 beyond the list), the groups added in
+ *                            ascending order to a double that starts at +0.  x solves (Q_A + mu I) x = mu m - q_b, mu =
+ *                            NGP_SIMPLIFY_LAMBDA * trace(Q_A), by Cramer's rule; x = m for placement NGP_SIMPLIFY_MEAN, trace == 0, or
+ *                            an x that is not finite or has some |x_a| > cell / 2; x is clamped to +- cell / 2 and the row is
+ *                            float(p_c + x).  A cluster of one vertex keeps that vertex's bits.  One wave per cluster.
+ *   ngp_simplify_faces       keep int32 [F] = 1 iff the face's three clusters differ, referenced int32 [V] = 1 for the clusters of kept
+ *                            faces (zeroed here first).
+ *   ngp_simplify_emit        with the inclusive scans of keep and referenced (int64) and their totals F' and V' read back: the kept
+ *                            faces in input order and rotation, renumbered (duplicates stay); the referenced clusters' rows in
+ *                            order; vertex_map int32 [V], the output vertex of every input vertex or -1.
+ * V < 2^31, 3 F < 2^31, cell finite and > 0 (NGP_EINVAL otherwise, nothing launched).  No float atomics, no workspace, no global state:
+ * the same bits on every call, and calls on different streams do not interact. */
+#define NGP_SIMPLIFY_LAMBDA 1e-3
+#define NGP_SIMPLIFY_QUADRIC 0
+#define NGP_SIMPLIFY_MEAN 1
+NGP_API int ngp_simplify_keys(const float* vertices, uint32_t V, const int32_t* faces, uint32_t F, const double* origin3_host, double cell,
+                              int64_t* keys, int32_t* error, ngp_stream_t stream);
+NGP_API int ngp_simplify_corners(const int32_t* faces, uint32_t F, uint32_t V, const int32_t* vcluster, int32_t* ccluster, ngp_stream_t stream);
+NGP_API int ngp_simplify_accumulate(const float* vertices, uint32_t V, const int32_t* faces, uint32_t F, const double* origin3_host, double cell,
+                                    int placement, const int64_t* sorted_keys, const int64_t* vertex_order, const int64_t* vertex_start,
+                                    const int64_t* corner_order, const int64_t* corner_start, float* representatives, ngp_stream_t stream);
+NGP_API int ngp_simplify_faces(const int32_t* ccluster, uint32_t F, uint32_t V, int32_t* keep, int32_t* referenced, ngp_stream_t stream);
+NGP_API int ngp_simplify_emit(uint32_t V, uint32_t F, const int32_t* vcluster, const int32_t* ccluster, const float* representatives,
+                              const int32_t* keep, const int64_t* keep_scan, const int32_t* referenced, const int64_t* referenced_scan,
+                              uint64_t n_vertices, uint64_t n_faces, float* vertices_out, int32_t* faces_out, int32_t* vertex_map,
+                              ngp_stream_t stream);
+
 /* Rays against a triangle mesh through a uniform grid (DESIGN.md "The ground-truth world"; world.py).  tri_data float [F,12],
  * 16-byte aligned: per triangle the rows (v0, 0), (e1 = v1 - v0, 0), (e2 = v2 - v0, 0).  The grid is host arithmetic of the caller:
  * cell (a, b, c) covers lo + (a, b, c) * cell .. lo + (a + 1, b + 1, c + 1) * cell, 1..256 cells per axis, inv_cell = 1 / cell;

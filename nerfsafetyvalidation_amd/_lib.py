@@ -170,6 +170,11 @@ SIGNATURES = {
     "ngp_isosurface_workspace": [_u32, _u32, _u32],
     "ngp_isosurface_count": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, _vp, _st],
     "ngp_isosurface_emit": [_vp, _u32, _u32, _u32, _f32, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _st],
+    "ngp_simplify_keys": [_vp, _u32, _vp, _u32, C.POINTER(C.c_double), C.c_double, _vp, _vp, _st],
+    "ngp_simplify_corners": [_vp, _u32, _u32, _vp, _vp, _st],
+    "ngp_simplify_accumulate": [_vp, _u32, _vp, _u32, C.POINTER(C.c_double), C.c_double, _int, _vp, _vp, _vp, _vp, _vp, _vp, _st],
+    "ngp_simplify_faces": [_vp, _u32, _u32, _vp, _vp, _st],
+    "ngp_simplify_emit": [_u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _st],
     "ngp_raycast_bin_count": [_vp, _u32, C.POINTER(RaycastGrid), _vp, _st],
     "ngp_raycast_bin_emit": [_vp, _u32, C.POINTER(RaycastGrid), _vp, C.c_uint64, _vp, _vp, _st],
     "ngp_raycast": [_vp, _vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _f32, _f32, _u32, _vp, _vp, _vp, _vp, _st],

@@ -5,7 +5,9 @@
     isosurface         lattice -> (vertices [V,3] float32 in index units, faces [F,3] int32)
                          CUDA tensor: ngp_isosurface_count / ngp_isosurface_emit (csrc/mesh.hip)
                          CPU tensor / numpy array: the same rule and order in numpy (the package's CPU path)
-    extract_geometry   extract_fields + isosurface + the reference's scaling to the bounds
+    simplify           a mesh made coarser by vertex clustering: one vertex per cubic cell, placed by the incident faces' plane quadrics
+                         CUDA tensors: ngp_simplify_* (csrc/simplify.hip); CPU tensors / numpy arrays: the numpy path that defines it
+    extract_geometry   extract_fields + isosurface (+ simplify with simplify_cell > 0) + the reference's scaling to the bounds
     save_mesh          extract_geometry of model.density over model.aabb_infer, written as a binary PLY
     write_ply/read_ply the binary PLY (optionally with uchar vertex colours) and its reader
     mesh_to_world      NeRF axes -> the world frame of collision.py's boxes (the inverse of collision.to_nerf)
@@ -230,6 +232,211 @@ def isosurface(u, threshold):
     return _isosurface_numpy(np.asarray(u), threshold)
 
 
+# ------------------------------------------------------------------------------------------------------------- simplification
+SIMPLIFY_LAMBDA = 1e-3                              # the regularisation towards the mean, as a share of trace(Q_A)
+SIMPLIFY_MAX_INDEX = 1 << 21                        # cell indices per axis: three of them make one int64 key
+_PLACEMENTS = {"quadric": 0, "mean": 1}
+
+
+def _grouped_sum(values, start, count):
+    """THE summation order of simplify (csrc/simplify.hip follows it): values float64 [N], sorted by cluster, cluster c owning the rows
+    start[c] .. start[c] + count[c] -> float64 [C].  A cluster's rows are cut into groups of 64 consecutive ranks (the last padded
+    with +0); a group is summed by the xor butterfly (_fold64); the cluster's sum is 0 + group 0 + group 1 + ... in that order."""
+    C = count.shape[0]
+    groups = -(-count // 64)
+    gstart = np.cumsum(groups) - groups
+    cluster = np.repeat(np.arange(C), count)
+    padded = np.zeros(int(groups.sum()) * 64, dtype=np.float64)
+    padded[gstart[cluster] * 64 + (np.arange(values.shape[0]) - start[cluster])] = values
+    partial = _fold64(padded.reshape(-1, 64), np.add)
+    acc = np.zeros(C, dtype=np.float64)
+    for j in range(int(groups.max()) if C else 0):
+        sel = np.flatnonzero(groups > j)
+        acc[sel] = acc[sel] + partial[gstart[sel] + j]
+    return acc
+
+
+def _simplify_args(n_vertices, n_faces, cell, origin, placement):
+    if placement not in _PLACEMENTS:
+        raise ValueError(f"simplify: placement is 'quadric' or 'mean' (got {placement!r})")
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f"simplify: cell > 0 and finite (got {cell})")
+    if n_vertices >= 2 ** 31 or 3 * n_faces >= 2 ** 31:
+        raise ValueError(f"simplify: V < 2^31 and 3 F < 2^31 (got {n_vertices} vertices, {n_faces} faces)")
+    if origin is not None:
+        origin = [float(o) for o in origin]
+        if len(origin) != 3 or not all(math.isfinite(o) for o in origin):
+            raise ValueError(f"simplify: origin is three finite numbers (got {origin})")
+    return cell, origin
+
+
+_SIMPLIFY_ERRORS = {1: "a vertex is not finite, lies below `origin` or has a cell index >= 2^21", 2: "a face index is outside [0, V)"}
+
+
+def _simplify_numpy(vertices, faces, cell, origin=None, placement="quadric"):
+    """The definition of simplify (its docstring), in IEEE double on the float32 inputs with one rounding per written operation."""
+    v32 = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    V, F = v32.shape[0], faces.shape[0]
+    cell, origin = _simplify_args(V, F, cell, origin, placement)
+    if origin is None:
+        origin = [float(a) for a in v32.min(0)] if V else [0.0, 0.0, 0.0]
+    o = np.asarray(origin, dtype=np.float64)
+    v = v32.astype(np.float64)
+    with np.errstate(all="ignore"):
+        idx = np.floor((v - o[None, :]) / cell)
+        if not ((idx >= 0.0) & (idx < float(SIMPLIFY_MAX_INDEX))).all():          # (false for NaN)
+            raise ValueError("simplify: " + _SIMPLIFY_ERRORS[1])
+    if ((faces < 0) | (faces >= V)).any():
+        raise ValueError("simplify: " + _SIMPLIFY_ERRORS[2])
+    empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.full(V, -1, np.int32))
+    if V == 0 or F == 0:
+        return empty
+
+    # clusters: the distinct cells in ascending (ix, iy, iz); a cluster's vertices in ascending index
+    ii = idx.astype(np.int64)
+    keys = (ii[:, 0] << 42) | (ii[:, 1] << 21) | ii[:, 2]
+    ukeys, cluster, vcount = np.unique(keys, return_inverse=True, return_counts=True)
+    cluster = cluster.reshape(-1)
+    C = ukeys.shape[0]
+    vorder = np.argsort(cluster, kind="stable")
+    vstart = np.cumsum(vcount) - vcount
+    ci = np.stack([ukeys >> 42, (ukeys >> 21) & (SIMPLIFY_MAX_INDEX - 1), ukeys & (SIMPLIFY_MAX_INDEX - 1)], -1).astype(np.float64)
+    pc = o[None, :] + (ci + 0.5) * cell
+
+    # the mean of every cluster's vertices, relative to the cell's centre
+    rel = v[vorder] - pc[cluster[vorder]]
+    m = np.stack([_grouped_sum(rel[:, a], vstart, vcount) for a in range(3)], -1) / vcount.astype(np.float64)[:, None]
+
+    # the plane quadrics of the corners of every cluster, corners in ascending 3 f + k
+    ccluster = cluster[faces.reshape(-1)]
+    corder = np.argsort(ccluster, kind="stable")
+    ccount = np.bincount(ccluster, minlength=C)
+    cstart = np.cumsum(ccount) - ccount
+    fa = faces[corder // 3]
+    pa, pb, pcn = v[fa[:, 0]], v[fa[:, 1]], v[fa[:, 2]]
+    with np.errstate(all="ignore"):
+        e1, e2 = pb - pa, pcn - pa
+        nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        r = pa - pc[ccluster[corder]]
+        d = -((nx * r[:, 0] + ny * r[:, 1]) + nz * r[:, 2])
+        del fa, pa, pb, pcn, e1, e2, r
+        qxx, qxy, qxz, qyy, qyz, qzz, bx, by, bz = (_grouped_sum(t, cstart, ccount) for t in
+                                                    (nx * nx, nx * ny, nx * nz, ny * ny, ny * nz, nz * nz, d * nx, d * ny, d * nz))
+        # (Q_A + mu I) x = mu m - q_b by Cramer's rule, every cofactor written out
+        t = (qxx + qyy) + qzz
+        mu = SIMPLIFY_LAMBDA * t
+        a, b, c, dd, e, f = qxx + mu, qxy, qxz, qyy + mu, qyz, qzz + mu
+        r0, r1, r2 = mu * m[:, 0] - bx, mu * m[:, 1] - by, mu * m[:, 2] - bz
+        c00, c01, c02 = dd * f - e * e, c * e - b * f, b * e - c * dd
+        c11, c12, c22 = a * f - c * c, b * c - a * e, a * dd - b * b
+        det = (a * c00 + b * c01) + c * c02
+        x = np.stack([((c00 * r0 + c01 * r1) + c02 * r2) / det, ((c01 * r0 + c11 * r1) + c12 * r2) / det,
+                      ((c02 * r0 + c12 * r1) + c22 * r2) / det], -1)
+        half = cell / 2.0
+        ok = (np.abs(x) <= half).all(1) & (t != 0.0)                # (false for a NaN or an infinity in x)
+        if _PLACEMENTS[placement] == 1:
+            ok[:] = False
+        x = np.where(ok[:, None], x, m)
+        x = np.minimum(np.maximum(x, -half), half)
+        rep = (pc + x).astype(np.float32)
+    single = vcount == 1
+    rep[single] = v32[vorder[vstart[single]]]
+
+    # faces: survivors in input order and rotation; clusters no survivor references are dropped
+    fc = cluster[faces]
+    keep = (fc[:, 0] != fc[:, 1]) & (fc[:, 1] != fc[:, 2]) & (fc[:, 0] != fc[:, 2])
+    if not keep.any():
+        return empty
+    referenced = np.zeros(C, dtype=bool)
+    referenced[fc[keep].reshape(-1)] = True
+    new_id = (np.cumsum(referenced) - 1).astype(np.int32)
+    return rep[referenced], new_id[fc[keep]], np.where(referenced[cluster], new_id[cluster], np.int32(-1)).astype(np.int32)
+
+
+def _simplify_hip(vertices, faces, cell, origin, placement):
+    device = vertices.device
+    v = vertices.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    f = faces.detach().to(device, torch.int32).reshape(-1, 3).contiguous()
+    V, F = v.shape[0], f.shape[0]
+    cell, origin = _simplify_args(V, F, cell, origin, placement)
+    with torch.cuda.device(device):
+        empty = lambda: (torch.zeros(0, 3, dtype=torch.float32, device=device), torch.zeros(0, 3, dtype=torch.int32, device=device),
+                         torch.full((V,), -1, dtype=torch.int32, device=device))
+        if V == 0 and F == 0:
+            return empty()
+        if origin is None:
+            origin = v.min(0).values.tolist() if V else [0.0, 0.0, 0.0]      # (a host read of its own; pass origin to avoid it)
+        o = (ctypes.c_double * 3)(*origin)
+        state = torch.zeros(3, dtype=torch.int64, device=device)              # V', F', the error word: one host read for all three
+        err = state[2:].view(torch.int32)
+        keys = torch.empty(V, dtype=torch.int64, device=device)
+        _lib.call("simplify_keys", v, V, f, F, o, cell, keys, err)
+        if V == 0 or F == 0:
+            code = int(state[2].item()) & 0xFFFFFFFF
+            if code:
+                raise ValueError("simplify: " + _SIMPLIFY_ERRORS[code])
+            return empty()
+        # plumbing: every list sorted by cluster (stable: ascending index within one), the clusters' first rows
+        skeys, vorder = torch.sort(keys, stable=True)
+        rank = torch.zeros(V, dtype=torch.int64, device=device)
+        rank[1:] = torch.cumsum(skeys[1:] != skeys[:-1], 0)
+        vcluster = torch.empty(V, dtype=torch.int32, device=device)
+        vcluster[vorder] = rank.to(torch.int32)
+        ids = torch.arange(V + 1, dtype=torch.int64, device=device)
+        vstart = torch.searchsorted(rank, ids)                                # (V for the ids past the last cluster)
+        ccluster = torch.empty(3 * F, dtype=torch.int32, device=device)
+        _lib.call("simplify_corners", f, F, V, vcluster, ccluster)
+        csorted, corder = torch.sort(ccluster, stable=True)
+        cstart = torch.searchsorted(csorted.to(torch.int64), ids)
+        rep = torch.empty(V, 3, dtype=torch.float32, device=device)           # (one row per cluster; there are at most V)
+        _lib.call("simplify_accumulate", v, V, f, F, o, cell, _PLACEMENTS[placement], skeys, vorder, vstart, corder, cstart, rep)
+        keep = torch.empty(F, dtype=torch.int32, device=device)
+        referenced = torch.empty(V, dtype=torch.int32, device=device)
+        _lib.call("simplify_faces", ccluster, F, V, keep, referenced)
+        keep_scan, ref_scan = torch.cumsum(keep, 0), torch.cumsum(referenced, 0)         # inclusive, int64
+        state[0], state[1] = ref_scan[-1], keep_scan[-1]
+        n_v, n_f, code = (int(s) for s in state.tolist())
+        if code & 0xFFFFFFFF:
+            raise ValueError("simplify: " + _SIMPLIFY_ERRORS[code & 0xFFFFFFFF])
+        out_v = torch.empty(n_v, 3, dtype=torch.float32, device=device)
+        out_f = torch.empty(n_f, 3, dtype=torch.int32, device=device)
+        vertex_map = torch.empty(V, dtype=torch.int32, device=device)
+        _lib.call("simplify_emit", V, F, vcluster, ccluster, rep, keep, keep_scan, referenced, ref_scan, n_v, n_f, out_v, out_f, vertex_map)
+    return out_v, out_f, vertex_map
+
+
+def simplify(vertices, faces, cell, *, origin=None, placement="quadric"):
+    """Vertex clustering with quadric-optimal representatives (Rossignac-Borrel cells, Lindstrom's placement; DESIGN.md "Mesh
+    simplification"): vertices float32 [V,3], faces int32 [F,3] -> (vertices float32 [V',3], faces int32 [F',3], vertex_map int32 [V]:
+    the output vertex of every input vertex, or -1).  CUDA tensors go through csrc/simplify.hip on the current stream (tensors back; one
+    host read, of V', F' and the error word, plus one of the minimum when origin is None); CPU tensors and numpy arrays through
+    _simplify_numpy, which defines the result -- the HIP path gives the same bits.  All arithmetic is IEEE double on the float32 inputs.
+
+    1. vertex -> cell i_a = floor((v_a - o_a) / cell), o = origin (default: the per-axis float32 minimum); a coordinate on a cell face
+       belongs to the upper cell.  ValueError for cell <= 0, a non-finite coordinate, a vertex below origin, an index >= 2^21, a face
+       index outside [0, V), an unknown placement.
+    2. clusters = the distinct cells in ascending (ix, iy, iz); p_c = o + (i + 1/2) cell.
+    3. per cluster, relative to p_c: m = the mean of its vertices (ascending index); over every corner 3 f + k (ascending) whose vertex
+       lies in it, with A, B, C the face's vertices: n = (B - A) x (C - A), d = -n . (A - p_c), Q_A += n n^T, q_b += d n.  Every sum
+       in _grouped_sum's order.
+    4. t = trace Q_A, mu = SIMPLIFY_LAMBDA t, x solves (Q_A + mu I) x = mu m - q_b (Cramer's rule); x = m instead for
+       placement="mean", t == 0, or an x that is not finite or leaves the cell (some |x_a| > cell / 2); x clamped to +- cell / 2; the
+       vertex is float32(p_c + x).  A cluster of ONE vertex keeps that vertex bit for bit.
+    5. a face survives iff its three clusters differ; survivors keep order and rotation; duplicates stay (a closed surface stays closed).
+    6. clusters without a surviving face are dropped, the rest renumbered in order."""
+    if isinstance(vertices, torch.Tensor):
+        if vertices.is_cuda:
+            return _simplify_hip(vertices, torch.as_tensor(faces), cell, origin, placement)
+        out = _simplify_numpy(vertices.detach().numpy(), torch.as_tensor(faces).detach().cpu().numpy(), cell, origin, placement)
+        return tuple(torch.from_numpy(a) for a in out)
+    return _simplify_numpy(np.asarray(vertices), faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces),
+                           cell, origin, placement)
+
+
 def extract_fields(bound_min, bound_max, resolution, query_func, S=128):
     """query_func on the resolution^3 lattice of torch.linspace(bound_min[d], bound_max[d], resolution) per axis, at most S^3 points
     [n, 3] per call (the reference's chunking, nerf/utils.py:152-167) -> float32 [R,R,R] tensor on the device query_func answers on"""
@@ -281,12 +488,18 @@ def drop_small_components(u, threshold, min_points):
     return np.where(small, np.asarray(thr, dtype=u.dtype), u)
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, min_points=0):
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, min_points=0, simplify_cell=0):
     """-> (vertices [V,3] float64 numpy in the bounds' units, triangles [F,3] int32 numpy): the isosurface of extract_fields, scaled as
     nerf/utils.py:181 scales mcubes' vertices: v / (resolution - 1) * (b_max - b_min) + b_min.  min_points: drop_small_components
-    first (0: the field as it is)."""
+    first (0: the field as it is).  simplify_cell > 0: simplify(..., cell=simplify_cell, origin=(0, 0, 0)) on the surface in index
+    units, before the scaling -- the cell is in lattice steps and the result does not depend on where the bounds lie (0: the surface
+    as it is cut)."""
+    if not simplify_cell >= 0:
+        raise ValueError(f"extract_geometry: simplify_cell >= 0 (got {simplify_cell!r})")
     u = drop_small_components(extract_fields(bound_min, bound_max, resolution, query_func), threshold, min_points)
     v, f = isosurface(u, threshold)
+    if simplify_cell > 0:
+        v, f, _ = simplify(v, f, simplify_cell, origin=(0.0, 0.0, 0.0))
     b_min, b_max = _bounds(bound_min), _bounds(bound_max)
     vertices = v.cpu().numpy().astype(np.float64) / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
     return vertices, f.cpu().numpy()
@@ -364,10 +577,11 @@ def read_ply(path):
     return vrec["p"].astype(np.float32), frec["i"].astype(np.int32), (vrec["c"].copy() if colored else None)
 
 
-def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False, min_points=0):
+def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False, min_points=0, simplify_cell=0):
     """Trainer.save_mesh (nerf/utils.py:533-553): the isosurface sigma = threshold of model.density over model.aabb_infer on a
     resolution^3 lattice, written to save_path as a binary PLY -> (vertices float64 [V,3], triangles int32 [F,3]).  min_points:
-    components of fewer inside lattice points are left out (drop_small_components; 0: none)."""
+    components of fewer inside lattice points are left out (drop_small_components; 0: none).  simplify_cell: the side, in lattice
+    steps, of the cells `simplify` clusters the surface's vertices in (0: no simplification, the file it has always been)."""
     directory = os.path.dirname(save_path)
     if directory:
         os.makedirs(directory, exist_ok=True)
@@ -377,7 +591,8 @@ def save_mesh(model, save_path, resolution=256, threshold=10, fp16=False, min_po
         with torch.no_grad(), torch.autocast(device.type, dtype=torch.float16 if device.type == "cuda" else torch.bfloat16, enabled=fp16):
             return model.density(pts.to(device))["sigma"]
 
-    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], resolution, threshold, query_func, min_points)
+    vertices, triangles = extract_geometry(model.aabb_infer[:3], model.aabb_infer[3:], resolution, threshold, query_func, min_points,
+                                           simplify_cell)
     write_ply(save_path, vertices, triangles)
     return vertices, triangles
 

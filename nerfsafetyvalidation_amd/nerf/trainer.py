@@ -345,13 +345,13 @@ class Trainer(object):
 
         return pred_rgb, pred_depth
 
-    def save_mesh(self, save_path=None, resolution=256, threshold=10):
+    def save_mesh(self, save_path=None, resolution=256, threshold=10, simplify_cell=0):
         from .. import mesh
         if save_path is None:
             save_path = os.path.join(self.workspace, 'meshes', f'{self.name}_{self.epoch}.ply')
         self.log(f"==> Saving mesh to {save_path}")
         os.makedirs(os.path.dirname(save_path), exist_ok=True)
-        mesh.save_mesh(self.model, save_path, resolution=resolution, threshold=threshold, fp16=self.fp16)
+        mesh.save_mesh(self.model, save_path, resolution=resolution, threshold=threshold, fp16=self.fp16, simplify_cell=simplify_cell)
         self.log("==> Finished saving mesh.")
 
     ### ------------------------------
