@@ -207,6 +207,9 @@ int fill_net(const ngp_model* m, const _Float16* packed, NetArgs& na, GridLevels
     na.align_corners = m->align_corners;
     NGP_REQUIRE(m->precision <= NGP_PREC_F16_REF, "ngp_model: unknown precision %u", m->precision);
     na.prec_bits = (m->precision == NGP_PREC_F32 ? 256u : 0u) | (m->precision == NGP_PREC_F16_REF ? 512u : 0u);
+    // the fused gathers address the table with a 32-bit byte offset (table_at)
+    NGP_REQUIRE((uint64_t)m->offsets_host[16] * (na.f32() ? 8u : 4u) < (1ull << 32), "fused renderer: the hash table must be smaller than 4 GiB (%u entries)",
+                (unsigned)m->offsets_host[16]);
     na.cells = nullptr;
     na.cell_steps = 0;
     for (int l = 0; l < 16; l++) na.cell_off[l] = 0;
@@ -237,6 +240,13 @@ int net_variant(const NetArgs& na, const GridLevels& lv) {
     const bool gen = needs_generic(lv);
     if (na.f32()) return gen ? 4 : 3;
     return (gen ? 1 : (na.cells ? 2 : 0)) + (na.hacc() ? 5 : 0);
+}
+
+// 2*bound = 2^k: then (x + bound) * inv_two_bound maps [-bound, bound] onto [0, 1] exactly (inv_two_bound is the exact reciprocal)
+// and a kernel that clamps its positions may drop the encoder's out-of-range test (encoder_unit<CLAMPED>)
+bool clamped_exact(const NetArgs& na) {
+    int e = 0;
+    return na.bound > 0.0f && std::isfinite(na.bound) && frexpf(na.bound, &e) == 0.5f && na.inv_two_bound * (2 * na.bound) == 1.0f;
 }
 
 // the fp32 backward kernels keep at most 1 / 2 hidden layers' activations (NetF32::Tape; nerf/network.py has 0 / 1)

@@ -135,6 +135,68 @@ __device__ __forceinline__ void sh4_quarter(uint32_t q, float x, float y, float 
     }
 }
 
+// ---- the encoder's per-sample arithmetic, shared by every gather below ------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Encoder input (x + bound) / (2 bound) (gridencoder/grid.py:144) and the out-of-range test of gridencoder.cu:107-123: an
+// out-of-range point gathers at the centre (in range) and has its features zeroed by the callers.
+// CLAMPED: a compile-time promise of the call site that (x, y, z) went through clampf(., -bound, bound) AND that 2*bound is a power
+// of two (clamped_exact() on the host).  Then x + bound is in [0, 2 bound] (0 and 2 bound exactly at the ends, rounding is
+// monotone), the multiplication with the power of two 1 / (2 bound) is exact, so u is in [0, 1]; a NaN does not survive the
+// clamp's v_med3_f32.  The test cannot fire and is not compiled: no compares, no selects on u, none on the features.
+template <bool CLAMPED = false>
+__device__ __forceinline__ void encoder_unit(const NetArgs& na, float x, float y, float z, float (&u)[3], bool& oob) {
+    u[0] = (x + na.bound) * na.inv_two_bound; u[1] = (y + na.bound) * na.inv_two_bound; u[2] = (z + na.bound) * na.inv_two_bound;
+    if constexpr (CLAMPED) {
+        oob = false;
+    } else {
+        oob = (u[0] < 0 || u[0] > 1) || (u[1] < 0 || u[1] > 1) || (u[2] < 0 || u[2] > 1);
+        if (oob) { u[0] = 0.5f; u[1] = 0.5f; u[2] = 0.5f; }
+    }
+}
+
+// position along an axis in cells -> (cell, fraction): gridencoder.cu's floorf(p), (uint32_t), p - (float)cell in two instructions.
+// p = fmaf(u, scale, half_off) with u in [0, 1], scale > 0, half_off >= 0, so p >= 0 and finite: truncation IS the floor, and
+// p - floor(p) is exact in fp32 (a suffix of p's significand), which is what v_fract_f32 returns (its clamp below one only acts for
+// negative inputs).  A NaN gives cell 0 and fraction NaN in both forms.
+__device__ __forceinline__ void cell_frac(float p, uint32_t& cell, float& frac) {
+    cell = (uint32_t)p;
+    frac = __builtin_amdgcn_fractf(p);
+}
+
+// the eight corner weights w[idx] = (wx * wy) * wz in the reference's order (gridencoder.cu:150-160; 1 * wx is exact), corner idx
+// bit d set = the upper cell boundary along axis d.  PACKED: the same twelve products in the same order, two per v_pk_mul_f32
+// (the four wx * wy, then the eight * wz) -- a packing, not a re-association.  Only the render loop's tile (net_density_piped) asks
+// for it: there it takes 46 v_mul_f32 out for 23 v_pk_mul_f32 at unchanged registers, while in net_density, the tape and the fp32
+// gather the even-aligned register pairs cost occupancy or scratch in some kernels, so they keep the scalar form.
+template <bool PACKED>
+__device__ __forceinline__ void corner_weights(const float (&fr)[3], float (&w)[8]) {
+    if constexpr (!PACKED) {
+#pragma unroll
+        for (int idx = 0; idx < 8; idx++) {
+            const float wx = (idx & 1) ? fr[0] : 1 - fr[0];
+            const float wy = (idx & 2) ? fr[1] : 1 - fr[1];
+            const float wz = (idx & 4) ? fr[2] : 1 - fr[2];
+            w[idx] = (wx * wy) * wz;
+        }
+        return;
+    }
+    const f32x2 wx = {1 - fr[0], fr[0]};
+    const float wy0 = 1 - fr[1], wy1 = fr[1], wz0 = 1 - fr[2], wz1 = fr[2];
+    const f32x2 xy0 = wx * (f32x2){wy0, wy0}, xy1 = wx * (f32x2){wy1, wy1};
+    const f32x2 w01 = xy0 * (f32x2){wz0, wz0}, w23 = xy1 * (f32x2){wz0, wz0}, w45 = xy0 * (f32x2){wz1, wz1}, w67 = xy1 * (f32x2){wz1, wz1};
+    w[0] = w01[0]; w[1] = w01[1]; w[2] = w23[0]; w[3] = w23[1];
+    w[4] = w45[0]; w[5] = w45[1]; w[6] = w67[0]; w[7] = w67[1];
+}
+
+// entry e of the compact table (hashed / dense levels; e counts from the table's start, the level's offset included): the table's
+// base stays in SGPRs and the lane supplies a 32-bit byte offset (the global_load saddr form), so no 64-bit vector address is formed.
+// fill_net() refuses a table of 4 GiB or more.  (The per-cell records are larger than that and keep 64-bit addresses.)
+template <typename T>
+__device__ __forceinline__ T table_at(const void* table, uint32_t e) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(table) + (size_t)(e * (uint32_t)sizeof(T)));
+}
+
 // fmaf(w, (float)half, acc) with the half taken from the low / high 16 bits of a packed table entry: one v_fma_mix_f32
 // (fp32 arithmetic, the conversion is part of the instruction).  hipcc otherwise converts both halves and uses v_pk_fma_f32.
 __device__ __forceinline__ float fma_mix_lo(float w, uint32_t packed, float acc) {
@@ -151,16 +213,15 @@ __device__ __forceinline__ float fma_mix_hi(float w, uint32_t packed, float acc)
 // HALF_ACC (ngp_model::precision == NGP_PREC_F16_REF, `model.fused_reference_rounding`): the grid_encode operator's arithmetic instead --
 // every product rounded to fp16, fp16 running sum (c10::Half, gridencoder.cu:169-172): the features are then bit-identical to the
 // reference's, at three VALU instructions per corner and feature instead of one.
-template <bool HALF_ACC = false>
+template <bool HALF_ACC = false, bool PACKED = false>
 __device__ __forceinline__ void corners_to_feature(const float (&fr)[3], const uint32_t (&raw)[8], bool oob, _Float16& f0, _Float16& f1) {
     float a0 = 0.0f, a1 = 0.0f;
     half2v hs = {(_Float16)0, (_Float16)0};
+    float cw[8];
+    corner_weights<PACKED>(fr, cw);
 #pragma unroll
     for (int idx = 0; idx < 8; idx++) {
-        const float wx = (idx & 1) ? fr[0] : 1 - fr[0];
-        const float wy = (idx & 2) ? fr[1] : 1 - fr[1];
-        const float wz = (idx & 4) ? fr[2] : 1 - fr[2];
-        const float w = (wx * wy) * wz;
+        const float w = cw[idx];
         if (HALF_ACC) {
             // w * (float)entry in fp32 (x + (-0) = x: the fma with a -0 addend IS the fp32 product, signed zeros included; the
             // conversion of the entry is part of the instruction), rounded to half -- two roundings, as c10::Half's operator* gives,
@@ -177,15 +238,16 @@ __device__ __forceinline__ void corners_to_feature(const float (&fr)[3], const u
 }
 
 // density half: hash-grid encode + sigma net.  Returns sigma (meaningful in q == 0) and the sigma-net outputs 4q..4q+3 as fp16.
-template <int MODE, bool HACC = false>
+template <int MODE, bool HACC = false, bool CLAMPED = false>
 __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* Wlds, const LevelTab& lt, uint32_t lane, float x, float y, float z,
                                             float& sigma, _Float16 (&s16)[4]) {
     const uint32_t q = lane >> 4;
     // encoder input: (x + bound) / (2 bound)  (gridencoder/grid.py:144).  torch evaluates a division by a Python scalar on
     // the GPU as a multiplication with the fp32 reciprocal; identical to the division whenever 2*bound is a power of two.
-    float u0 = (x + na.bound) * na.inv_two_bound, u1 = (y + na.bound) * na.inv_two_bound, u2 = (z + na.bound) * na.inv_two_bound;
-    const bool oob = (u0 < 0 || u0 > 1) || (u1 < 0 || u1 > 1) || (u2 < 0 || u2 > 1);
-    if (oob) { u0 = 0.5f; u1 = 0.5f; u2 = 0.5f; }  // keep the gathers in range; the features are zeroed below (gridencoder.cu:107-123)
+    float u[3];
+    bool oob;
+    encoder_unit<CLAMPED>(na, x, y, z, u, oob);
+    const float u0 = u[0], u1 = u[1], u2 = u[2];
     const float half_off = na.align_corners ? 0.0f : 0.5f;
 
     // ---- 4 levels x 8 corners: issue all 32 gathers, then interpolate (gridencoder.cu:139-175).
@@ -202,11 +264,7 @@ __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* W
         float p[3] = {fmaf(u0, scale, half_off), fmaf(u1, scale, half_off), fmaf(u2, scale, half_off)};
         uint32_t g[3];
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float fl_ = floorf(p[d]);
-            g[d] = (uint32_t)fl_;
-            fr[i][d] = p[d] - (float)g[d];
-        }
+        for (int d = 0; d < 3; d++) cell_frac(p[d], g[d], fr[i][d]);
         if (MODE == 2 && i < 3) {   // levels 0..11 from the per-cell records (compile-time: no second code path in the other kernels)
             const uint32_t S = lt.cell_res[level];
             const uint32_t ci = lt.cell_off[level] + g[0] + S * (g[1] + S * g[2]);
@@ -216,7 +274,7 @@ __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* W
             raw[i][4] = hi.x; raw[i][5] = hi.y; raw[i][6] = hi.z; raw[i][7] = hi.w;
             continue;
         }
-        const uint32_t* tab = na.table + lt.offset[level];
+        const uint32_t off = lt.offset[level];
         const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1};
         const uint32_t t2[2] = {g[2] * a2, g[2] * a2 + a2};
 #pragma unroll
@@ -227,7 +285,7 @@ __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* W
             if (MODE == 1) {
                 if (fl & 2u) e %= lt.size[level];
             }
-            raw[i][idx] = tab[e];
+            raw[i][idx] = table_at<uint32_t>(na.table, off + e);
         }
     }
     half8 feat;
@@ -243,15 +301,12 @@ __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* W
             continue;
         }
         float a0 = 0.0f, a1 = 0.0f;
+        float cw[8];
+        corner_weights<false>(fr[i], cw);     // w = ((1 * wx) * wy) * wz in the reference's order (:150-160)
 #pragma unroll
         for (int idx = 0; idx < 8; idx++) {
-            // w = ((1 * wx) * wy) * wz in the reference's order (:150-160); 1 * wx is exact
-            const float wx = (idx & 1) ? fr[i][0] : 1 - fr[i][0];
-            const float wy = (idx & 2) ? fr[i][1] : 1 - fr[i][1];
-            const float wz = (idx & 4) ? fr[i][2] : 1 - fr[i][2];
-            const float w = (wx * wy) * wz;
-            a0 = fma_mix_lo(w, raw[i][idx], a0);
-            a1 = fma_mix_hi(w, raw[i][idx], a1);
+            a0 = fma_mix_lo(cw[idx], raw[i][idx], a0);
+            a1 = fma_mix_hi(cw[idx], raw[i][idx], a1);
         }
         feat[2 * i] = oob ? (_Float16)0 : (_Float16)a0;
         feat[2 * i + 1] = oob ? (_Float16)0 : (_Float16)a1;
@@ -274,40 +329,34 @@ __device__ __forceinline__ void net_density(const NetArgs& na, const _Float16* W
 // (`pre`).  Order inside a tile: issue this tile's record loads; interpolate the hashed level from `pre` (loaded a tile ago);
 // issue the next tile's hashed gathers into the freed registers; then wait for the records only (vector-memory loads return
 // in order, so the younger gathers stay in flight behind them).
-__device__ __forceinline__ void encoder_unit(const NetArgs& na, float x, float y, float z, float (&u)[3], bool& oob) {
-    u[0] = (x + na.bound) * na.inv_two_bound; u[1] = (y + na.bound) * na.inv_two_bound; u[2] = (z + na.bound) * na.inv_two_bound;
-    oob = (u[0] < 0 || u[0] > 1) || (u[1] < 0 || u[1] > 1) || (u[2] < 0 || u[2] > 1);
-    if (oob) { u[0] = 0.5f; u[1] = 0.5f; u[2] = 0.5f; }
-}
-
+template <bool CLAMPED = false>
 __device__ __forceinline__ void hashed_gather(const NetArgs& na, const LevelTab& lt, uint32_t level, float x, float y, float z, uint32_t (&out)[8]) {
     float u[3];
     bool oob;
-    encoder_unit(na, x, y, z, u, oob);
+    encoder_unit<CLAMPED>(na, x, y, z, u, oob);
     const float half_off = na.align_corners ? 0.0f : 0.5f, scale = lt.scale[level];
-    const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level];
-    const uint32_t g0 = (uint32_t)floorf(fmaf(u[0], scale, half_off)), g1 = (uint32_t)floorf(fmaf(u[1], scale, half_off)),
-                   g2 = (uint32_t)floorf(fmaf(u[2], scale, half_off));
-    const uint32_t* tab = na.table + lt.offset[level];
+    const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], off = lt.offset[level];
+    // (cells only: p >= 0, so the truncation is the floor, see cell_frac)
+    const uint32_t g0 = (uint32_t)fmaf(u[0], scale, half_off), g1 = (uint32_t)fmaf(u[1], scale, half_off), g2 = (uint32_t)fmaf(u[2], scale, half_off);
     const bool hashed = (lt.flags[level] & 1u) != 0;     // (a tiled grid's fine levels are sums wrapped by the mask, not hashes)
     const uint32_t t1[2] = {g1 * a1, g1 * a1 + a1};
     const uint32_t t2[2] = {g2 * a2, g2 * a2 + a2};
 #pragma unroll
     for (int idx = 0; idx < 8; idx++) {
         const uint32_t px = g0 + (idx & 1), ty = t1[(idx >> 1) & 1], tz = t2[(idx >> 2) & 1];
-        out[idx] = tab[(hashed ? (px ^ ty ^ tz) : (px + ty + tz)) & mask];
+        out[idx] = table_at<uint32_t>(na.table, off + ((hashed ? (px ^ ty ^ tz) : (px + ty + tz)) & mask));
     }
 }
 
 // same values and arithmetic as net_density<2>; `pre` holds this tile's hashed-level entries on entry and the next tile's on exit
-template <bool HACC = false>
+template <bool HACC = false, bool CLAMPED = false>
 __device__ __forceinline__ void net_density_piped(const NetArgs& na, const _Float16* Wlds, const LevelTab& lt, uint32_t lane, float x, float y,
                                                   float z, float nx, float ny, float nz, uint32_t (&pre)[8], float& sigma,
                                                   _Float16 (&s16)[4]) {
     const uint32_t q = lane >> 4;
     float u[3];
     bool oob;
-    encoder_unit(na, x, y, z, u, oob);
+    encoder_unit<CLAMPED>(na, x, y, z, u, oob);
     const float half_off = na.align_corners ? 0.0f : 0.5f;
     uint4 rec[3][2];
     float fr[4][3];
@@ -317,11 +366,7 @@ __device__ __forceinline__ void net_density_piped(const NetArgs& na, const _Floa
         const float scale = lt.scale[level];
         uint32_t g[3];
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
+        for (int d = 0; d < 3; d++) cell_frac(fmaf(u[d], scale, half_off), g[d], fr[i][d]);
         if (i < 3) {
             const uint32_t S = lt.cell_res[level];
             const uint4* r = na.cells + (size_t)(lt.cell_off[level] + g[0] + S * (g[1] + S * g[2])) * 2;
@@ -332,16 +377,16 @@ __device__ __forceinline__ void net_density_piped(const NetArgs& na, const _Floa
     half8 feat;
     {
         _Float16 f0, f1;
-        corners_to_feature<HACC>(fr[3], pre, oob, f0, f1);
+        corners_to_feature<HACC, true>(fr[3], pre, oob, f0, f1);
         feat[6] = f0; feat[7] = f1;
     }
     // (unconditional: a branch here makes the compiler wait for ALL outstanding loads at the join; the last tile re-gathers its own entries)
-    hashed_gather(na, lt, q + 12, nx, ny, nz, pre);
+    hashed_gather<CLAMPED>(na, lt, q + 12, nx, ny, nz, pre);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const uint32_t raw[8] = {rec[i][0].x, rec[i][0].y, rec[i][0].z, rec[i][0].w, rec[i][1].x, rec[i][1].y, rec[i][1].z, rec[i][1].w};
         _Float16 f0, f1;
-        corners_to_feature<HACC>(fr[i], raw, oob, f0, f1);
+        corners_to_feature<HACC, true>(fr[i], raw, oob, f0, f1);
         feat[2 * i] = f0; feat[2 * i + 1] = f1;
     }
     const half8* Ws = reinterpret_cast<const half8*>(Wlds);
@@ -356,11 +401,11 @@ __device__ __forceinline__ void net_density_piped(const NetArgs& na, const _Floa
 
 // The gather of net_density on its own: a lane's four levels (q, q+4, q+8, q+12) -> 32 raw corner entries, the interpolation
 // fractions and the out-of-range flag.  (net_density keeps its own copy of these lines: its instruction schedule is tuned.)
-template <int MODE>
+template <int MODE, bool CLAMPED = false>
 __device__ __forceinline__ void fused_gather(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, uint32_t (&raw)[4][8],
                                              float (&fr)[4][3], bool& oob) {
     float u[3];
-    encoder_unit(na, x, y, z, u, oob);
+    encoder_unit<CLAMPED>(na, x, y, z, u, oob);
     const float half_off = na.align_corners ? 0.0f : 0.5f;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -368,11 +413,7 @@ __device__ __forceinline__ void fused_gather(const NetArgs& na, const LevelTab& 
         const float scale = lt.scale[level];
         uint32_t g[3];
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
+        for (int d = 0; d < 3; d++) cell_frac(fmaf(u[d], scale, half_off), g[d], fr[i][d]);
         if (MODE == 2 && i < 3) {
             const uint32_t S = lt.cell_res[level];
             const uint4* rec = na.cells + (size_t)(lt.cell_off[level] + g[0] + S * (g[1] + S * g[2])) * 2;
@@ -381,7 +422,7 @@ __device__ __forceinline__ void fused_gather(const NetArgs& na, const LevelTab& 
             raw[i][4] = hi.x; raw[i][5] = hi.y; raw[i][6] = hi.z; raw[i][7] = hi.w;
             continue;
         }
-        const uint32_t* tab = na.table + lt.offset[level];
+        const uint32_t off = lt.offset[level];
         const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], fl = lt.flags[level];
         const bool hashed = (fl & 1u) != 0;
         const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1}, t2[2] = {g[2] * a2, g[2] * a2 + a2};
@@ -391,7 +432,7 @@ __device__ __forceinline__ void fused_gather(const NetArgs& na, const LevelTab& 
             uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
             e &= mask;
             if (MODE == 1) { if (fl & 2u) e %= lt.size[level]; }
-            raw[i][idx] = tab[e];
+            raw[i][idx] = table_at<uint32_t>(na.table, off + e);
         }
     }
 }
@@ -561,25 +602,20 @@ __device__ __forceinline__ f32x4 mlp32_out(const f32x4* W, uint32_t lane, const 
 }
 
 // a lane's four levels from the fp32 table: 32 eight-byte corner entries, the interpolation fractions, the out-of-range flag
-template <int MODE>
+template <int MODE, bool CLAMPED = false>
 __device__ __forceinline__ void fused_gather32(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, float2 (&raw)[4][8],
                                                float (&fr)[4][3], bool& oob) {
     float u[3];
-    encoder_unit(na, x, y, z, u, oob);
+    encoder_unit<CLAMPED>(na, x, y, z, u, oob);
     const float half_off = na.align_corners ? 0.0f : 0.5f;
-    const float2* table = reinterpret_cast<const float2*>(na.table);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t level = q + 4 * i;
         const float scale = lt.scale[level];
         uint32_t g[3];
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float p = fmaf(u[d], scale, half_off);
-            g[d] = (uint32_t)floorf(p);
-            fr[i][d] = p - (float)g[d];
-        }
-        const float2* tab = table + lt.offset[level];
+        for (int d = 0; d < 3; d++) cell_frac(fmaf(u[d], scale, half_off), g[d], fr[i][d]);
+        const uint32_t off = lt.offset[level];
         const uint32_t a1 = lt.a1[level], a2 = lt.a2[level], mask = lt.mask[level], fl = lt.flags[level];
         const bool hashed = (fl & 1u) != 0;
         const uint32_t t1[2] = {g[1] * a1, g[1] * a1 + a1}, t2[2] = {g[2] * a2, g[2] * a2 + a2};
@@ -589,21 +625,19 @@ __device__ __forceinline__ void fused_gather32(const NetArgs& na, const LevelTab
             uint32_t e = hashed ? (px ^ ty ^ tz) : (px + ty + tz);
             e &= mask;
             if (MODE == 1) { if (fl & 2u) e %= lt.size[level]; }
-            raw[i][idx] = tab[e];
+            raw[i][idx] = table_at<float2>(na.table, off + e);
         }
     }
 }
 // gridencoder.cu:139-175 in fp32: results[ch] += w * grid[index + ch] over the corners in index order (one fma each under nvcc's
 // -fmad; the operator and the oracle write it as fmaf) -- bit-identical to grid_encode's fp32 features
 __device__ __forceinline__ void corners_to_feature32(const float (&fr)[3], const float2 (&raw)[8], bool oob, float& f0, float& f1) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2 acc = {0.0f, 0.0f};                           // both features of a corner in one v_pk_fma_f32 (an IEEE fma per component)
+    float cw[8];
+    corner_weights<false>(fr, cw);
 #pragma unroll
     for (int idx = 0; idx < 8; idx++) {
-        const float wx = (idx & 1) ? fr[0] : 1 - fr[0];
-        const float wy = (idx & 2) ? fr[1] : 1 - fr[1];
-        const float wz = (idx & 4) ? fr[2] : 1 - fr[2];
-        const float w = (wx * wy) * wz;
+        const float w = cw[idx];
         acc = __builtin_elementwise_fma((f32x2){w, w}, (f32x2){raw[idx].x, raw[idx].y}, acc);
     }
     const float a0 = acc[0], a1 = acc[1];
@@ -703,16 +737,17 @@ __device__ __forceinline__ void stage_block(const NetArgs& na, const GridLevels&
 //   color_vjp    colour net forward + backward for one tile: dL/d rgb = G * wsc * sigmoid' -> this lane's part of dL/d dir (through
 //                SH) and dL/d(sigma-net outputs) (through the geometry features)
 // ------------------------------------------------------------------------------------------
-template <int MODE_, bool HACC_ = false>
+template <int MODE_, bool HACC_ = false, bool CLAMPED_ = false>
 struct NetF16 {
     static constexpr int MODE = MODE_;
     static constexpr bool HACC = HACC_;        // the reference's c10::Half corner accumulation (NGP_PREC_F16_REF)
+    static constexpr bool CLAMPED = CLAMPED_;  // `density` only: its callers clamp the position and the host found clamped_exact() (see encoder_unit)
     static constexpr bool kF32 = false;
     typedef _Float16 geo_t;
     static __host__ __device__ size_t w_bytes(const NetArgs& na) { return net_w_bytes_f16(na); }
     static __device__ __forceinline__ void density(const NetArgs& na, const char* W, const LevelTab& lt, uint32_t lane, float x, float y, float z,
                                                    float& sigma, geo_t (&s)[4]) {
-        net_density<MODE, HACC>(na, reinterpret_cast<const _Float16*>(W), lt, lane, x, y, z, sigma, s);
+        net_density<MODE, HACC, CLAMPED>(na, reinterpret_cast<const _Float16*>(W), lt, lane, x, y, z, sigma, s);
     }
     static __device__ __forceinline__ void color(const NetArgs& na, const char* W, uint32_t lane, float dx, float dy, float dz, const geo_t (&s)[4],
                                                  float& cr, float& cg, float& cb) {
@@ -852,17 +887,19 @@ struct NetF16 {
     }
 };
 
-template <int MODE_>
+template <int MODE_, bool CLAMPED_ = false>
 struct NetF32 {
     static constexpr int MODE = MODE_;
+    static constexpr bool CLAMPED = CLAMPED_;  // `density` only, as in NetF16
     static constexpr bool kF32 = true;
     typedef float geo_t;
     static __host__ __device__ size_t w_bytes(const NetArgs& na) { return 2 * net_w_bytes_f16(na); }
+    template <bool CL = false>
     static __device__ __forceinline__ void features(const NetArgs& na, const LevelTab& lt, uint32_t q, float x, float y, float z, float (&feat)[8]) {
         float2 raw[4][8];
         float fr[4][3];
         bool oob;
-        fused_gather32<MODE>(na, lt, q, x, y, z, raw, fr, oob);
+        fused_gather32<MODE, CL>(na, lt, q, x, y, z, raw, fr, oob);
 #pragma unroll
         for (int i = 0; i < 4; i++) corners_to_feature32(fr[i], raw[i], oob, feat[2 * i], feat[2 * i + 1]);
     }
@@ -870,7 +907,7 @@ struct NetF32 {
                                                    float& sigma, geo_t (&s)[4]) {
         const f32x4* Ws = reinterpret_cast<const f32x4*>(W);
         float feat[8];
-        features(na, lt, lane >> 4, x, y, z, feat);
+        features<CLAMPED>(na, lt, lane >> 4, x, y, z, feat);
         f32x4 h[4];
         mlp32_in(Ws, lane, feat, h);
         for (uint32_t k = 0; k < na.sig_mm; k++) mlp32_hidden(Ws + 512 + k * 1024, lane, h);
@@ -1023,6 +1060,7 @@ int fill_net(const ngp_model* m, const _Float16* packed, NetArgs& na, GridLevels
 size_t weights_bytes(const NetArgs& na);
 uint32_t resident_blocks(size_t lds);
 int net_variant(const NetArgs& na, const GridLevels& lv);
+bool clamped_exact(const NetArgs& na);   // 2*bound is a power of two: the kernels that clamp to [-bound, bound] may instantiate CLAMPED
 bool bwd_shape_ok(const NetArgs& na);
 // runs STMT with NET bound to the policy class of `variant`
 #define NGP_WITH_NET(variant, ...)                                           \

@@ -311,7 +311,9 @@ __global__ void __launch_bounds__(256) k_march_ahead(RenderArgs ra, float bound)
     ra.march_counts[entry] = (uint8_t)(emitted | (slow ? 128u : 0u));
 }
 
-template <int MODE, bool HACC = false>
+// CLAMPED: the positions below are clamped to [-bound, bound] and the host found 2*bound a power of two, so the encoder's
+// out-of-range test cannot fire and is not compiled (encoder_unit in fused_net.hpp)
+template <int MODE, bool HACC = false, bool CLAMPED = false>
 __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs na, GridLevels lv, RenderArgs ra) {
     Ctl ctl = *ra.ctl;
     if (ctl.done) return;
@@ -459,7 +461,7 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
                 if (ra.stamps) {   // diagnostics: split the tile into encode+sigma net and colour net, count tile fill
                     const unsigned long long ta = __builtin_amdgcn_s_memtime();
                     _Float16 s16[4];
-                    net_density<MODE, HACC>(na, Wlds, *lt, lane, x, y, z, sg, s16);
+                    net_density<MODE, HACC, CLAMPED>(na, Wlds, *lt, lane, x, y, z, sg, s16);
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                     const unsigned long long tb = __builtin_amdgcn_s_memtime();
                     net_color(na, Wlds, lane, dx, dy, dz, s16, r, g, b);
@@ -478,13 +480,13 @@ __global__ void __launch_bounds__(kThreads, kWavesPerSimd) k_render_iter(NetArgs
                     const float nx = clampf(fmaf(tn, S.od[rn][3], S.od[rn][0]), -na.bound, na.bound);
                     const float ny = clampf(fmaf(tn, S.od[rn][4], S.od[rn][1]), -na.bound, na.bound);
                     const float nz = clampf(fmaf(tn, S.od[rn][5], S.od[rn][2]), -na.bound, na.bound);
-                    if (tile == 0) hashed_gather(na, *lt, (lane >> 4) + 12, x, y, z, pre);
+                    if (tile == 0) hashed_gather<CLAMPED>(na, *lt, (lane >> 4) + 12, x, y, z, pre);
                     _Float16 s16[4];
-                    net_density_piped<HACC>(na, Wlds, *lt, lane, x, y, z, nx, ny, nz, pre, sg, s16);
+                    net_density_piped<HACC, CLAMPED>(na, Wlds, *lt, lane, x, y, z, nx, ny, nz, pre, sg, s16);
                     net_color(na, Wlds, lane, dx, dy, dz, s16, r, g, b);
                 } else {
                     _Float16 s16[4];
-                    net_density<MODE, HACC>(na, Wlds, *lt, lane, x, y, z, sg, s16);
+                    net_density<MODE, HACC, CLAMPED>(na, Wlds, *lt, lane, x, y, z, sg, s16);
                     net_color(na, Wlds, lane, dx, dy, dz, s16, r, g, b);
                 }
                 if (lane < 16 && valid) {
@@ -1055,12 +1057,17 @@ static void fill_render_args(const ngp_render_ctx* ctx, const ngp_model* model, 
     ra.sample_hash = dbg.sample_hash;
 }
 
-// the kernel instantiation of a call: (index recipe) x (corner rounding)
+// the kernel instantiation of a call: (index recipe) x (corner rounding), and for the per-cell-record recipe x (out-of-range test
+// compiled out when 2*bound is a power of two).  Only that recipe gets the third axis: it is the one the render loop is tuned for, and
+// every instantiation costs this unit's compile time.
 typedef void (*IterKernel)(NetArgs, GridLevels, RenderArgs);
 static IterKernel choose_iter_kernel(const NetArgs& na, const GridLevels& lv) {
     static const IterKernel kIter[2][3] = {{k_render_iter<0, false>, k_render_iter<1, false>, k_render_iter<2, false>},
                                            {k_render_iter<0, true>, k_render_iter<1, true>, k_render_iter<2, true>}};
-    return kIter[na.hacc() ? 1 : 0][needs_generic(lv) ? 1 : (na.cells ? 2 : 0)];
+    static const IterKernel kIterClamped[2] = {k_render_iter<2, false, true>, k_render_iter<2, true, true>};
+    const int mode = needs_generic(lv) ? 1 : (na.cells ? 2 : 0);
+    if (mode == 2 && clamped_exact(na)) return kIterClamped[na.hacc() ? 1 : 0];
+    return kIter[na.hacc() ? 1 : 0][mode];
 }
 
 // Enqueues launch number `launched` of a call: the march, the network over its samples, the compaction that publishes its status word.

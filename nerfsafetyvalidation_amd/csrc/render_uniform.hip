@@ -365,7 +365,7 @@ __global__ void __launch_bounds__(256, 4) k_composite_merged_x16(NetArgs na, Gri
 //   5. compositing over the T + U merged samples exactly as k_render_uniform does; a tile that holds a sample with weight > 1e-4
 //      re-evaluates the sigma net for its geometry features (bit-identical to the first evaluation) and runs the colour net.
 // ------------------------------------------------------------------------------------------
-template <int MODE>
+template <int MODE, bool CLAMPED = false>
 __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels lv, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                          const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N, uint32_t T,
                                                          uint32_t U, const float* __restrict__ lin, const float* __restrict__ u_det,
@@ -415,7 +415,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
                 sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
                 float sigma;
                 _Float16 s16[4];
-                net_density<MODE>(na, Wlds, *lt, lane, x, y, z, sigma, s16);
+                net_density<MODE, false, CLAMPED>(na, Wlds, *lt, lane, x, y, z, sigma, s16);
                 if (lane < 16 && valid) { zdst[idx] = zv; sdst[idx] = sigma; }
             }
             NGP_WAVE_SYNC();
@@ -506,7 +506,7 @@ __global__ void __launch_bounds__(256) k_render_upsample(NetArgs na, GridLevels 
                 float x, y, z, s_again;
                 sample_point(r, zv, aabb_lo, aabb_hi, x, y, z);
                 _Float16 s16[4];
-                net_density<MODE>(na, Wlds, *lt, lane, x, y, z, s_again, s16);
+                net_density<MODE, false, CLAMPED>(na, Wlds, *lt, lane, x, y, z, s_again, s16);
                 net_color(na, Wlds, lane, r.dx, r.dy, r.dz, s16, cr, cg, cb);
                 if (!masked) { cr = 0; cg = 0; cb = 0; }
             }
@@ -727,6 +727,22 @@ static uint32_t usable_frame_width(uint32_t frame_width, uint32_t N) {
         case 2: { constexpr int MODE = 2; __VA_ARGS__; } break;    \
         default: { constexpr int MODE = 0; __VA_ARGS__; } break;   \
     }
+// The forward kernels of this unit clamp every position to [-bound, bound] (sample_point), so when 2*bound is a power of two
+// (clamped_exact) they take the instantiation without the encoder's out-of-range test: CL / the third parameter of the NET policy.
+#define NGP_WITH_CLAMPED(clamped, ...)                             \
+    if (clamped) { constexpr bool CL = true; __VA_ARGS__; }        \
+    else { constexpr bool CL = false; __VA_ARGS__; }
+#define NGP_WITH_NET_CLAMPED(variant, ...)                                         \
+    switch (variant) {                                                             \
+        case 0: { using NET = NetF16<0, false, true>; __VA_ARGS__; } break;        \
+        case 1: { using NET = NetF16<1, false, true>; __VA_ARGS__; } break;        \
+        case 2: { using NET = NetF16<2, false, true>; __VA_ARGS__; } break;        \
+        case 3: { using NET = NetF32<0, true>; __VA_ARGS__; } break;               \
+        case 4: { using NET = NetF32<1, true>; __VA_ARGS__; } break;               \
+        case 5: { using NET = NetF16<0, true, true>; __VA_ARGS__; } break;         \
+        case 6: { using NET = NetF16<1, true, true>; __VA_ARGS__; } break;         \
+        default: { using NET = NetF16<2, true, true>; __VA_ARGS__; } break;        \
+    }
 
 extern "C" {
 
@@ -749,6 +765,7 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
     const size_t lds = weights_bytes(na) + sizeof(LevelTab);
     NGP_REQUIRE(lds <= 96 * 1024, "render_uniform: the packed weights need %zu bytes of LDS", lds);
     const int variant = net_variant(na, lv);
+    const bool clamped = clamped_exact(na);     // the kernels below clamp to [-bound, bound]: see NGP_WITH_NET_CLAMPED
     uint32_t blocks = div_up(N, 4);
     if (blocks > resident_blocks(lds)) blocks = resident_blocks(lds);   // each wave strides over rays
     ProfScope prof("render_uniform", s, (double)N * T);
@@ -763,18 +780,26 @@ int ngp_render_uniform(const ngp_model* model, const float* rays_o, const float*
         // of the occupancy (800x800 x 512 samples, fp32: 8.01 -> 7.56 ms)
         const uint32_t gb_cap = resident_blocks(lds);
         if (gb > gb_cap) gb = gb_cap;
-        NGP_WITH_NET(variant, {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NET>), 96 * 1024);
-            k_render_uniform_x16<NET><<<gb, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density,
-                                                           dump_begin, sigmas, rgbs, -model->bound, model->bound, fw, dbg.stamps);
-        });
+#define NGP_LAUNCH_X16                                                                                                                          \
+    {                                                                                                                                           \
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform_x16<NET>), 96 * 1024);                                                \
+        k_render_uniform_x16<NET><<<gb, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density, \
+                                                       dump_begin, sigmas, rgbs, -model->bound, model->bound, fw, dbg.stamps);                 \
+    }
+        if (clamped) { NGP_WITH_NET_CLAMPED(variant, NGP_LAUNCH_X16); }
+        else { NGP_WITH_NET(variant, NGP_LAUNCH_X16); }
+#undef NGP_LAUNCH_X16
         return check_launch("render_uniform");
     }
-    NGP_WITH_NET(variant, {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform<NET>), 96 * 1024);
-        k_render_uniform<NET><<<blocks, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density,
-                                                       dump_begin, sigmas, rgbs, -model->bound, model->bound);
-    });
+#define NGP_LAUNCH_PER_RAY                                                                                                                      \
+    {                                                                                                                                           \
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_uniform<NET>), 96 * 1024);                                                    \
+        k_render_uniform<NET><<<blocks, 256, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, lin, weights_sum, depth, image, aggregated_density, \
+                                                       dump_begin, sigmas, rgbs, -model->bound, model->bound);                                 \
+    }
+    if (clamped) { NGP_WITH_NET_CLAMPED(variant, NGP_LAUNCH_PER_RAY); }
+    else { NGP_WITH_NET(variant, NGP_LAUNCH_PER_RAY); }
+#undef NGP_LAUNCH_PER_RAY
     return check_launch("render_uniform");
 }
 
@@ -818,13 +843,14 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     if (blocks > 1024) blocks = 1024;
     ProfScope prof("render_upsample", s, (double)N * (T + U));
     const int mode = needs_generic(lv) ? 1 : (na.cells ? 2 : 0);
+    const bool clamped = clamped_exact(na);
     const uint32_t fw = usable_frame_width(frame_width, N);
     auto per_ray = [&](const float* sc_in, float* zf_out) {
-        NGP_WITH_MODE(mode, {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<MODE>), 160 * 1024);
-            k_render_upsample<MODE><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
-                                                                    aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
-        });
+        NGP_WITH_MODE(mode, NGP_WITH_CLAMPED(clamped, {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(k_render_upsample<MODE, CL>), 160 * 1024);
+            k_render_upsample<MODE, CL><<<blocks, 64 * waves, lds, s>>>(na, lv, rays_o, rays_d, nears, fars, N, T, U, lin, u, weights_sum, depth, image,
+                                                                        aggregated_density, dump_begin, sigmas, rgbs, -model->bound, model->bound, sc_in, zf_out, fw);
+        }));
     };
     const size_t need = upsample_workspace_bytes(N, T, U);
     if (!(workspace && workspace_bytes >= need && N >= kUniformX16MinRays && !env_set("NGP_UPSAMPLE_PER_RAY"))) {
@@ -841,10 +867,11 @@ int ngp_render_upsample(const ngp_model* model, const float* rays_o, const float
     uint32_t gb = div_up(div_up(N, 16), 4);
     if (gb > 1024) gb = 1024;
     auto density = [&](uint32_t n, const float* z_in, float* out, _Float16* geo) {
-        NGP_WITH_MODE(mode, {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(k_density_x16<NetF16<MODE>>), 96 * 1024);
-            k_density_x16<NetF16<MODE>><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, z_in, out, geo, -model->bound, model->bound, fw);
-        });
+        NGP_WITH_MODE(mode, NGP_WITH_CLAMPED(clamped, {
+            using NET = NetF16<MODE, false, CL>;
+            ensure_dynamic_lds(reinterpret_cast<const void*>(k_density_x16<NET>), 96 * 1024);
+            k_density_x16<NET><<<gb, 256, fixed, s>>>(na, lv, rays_o, rays_d, nears, fars, N, n, lin, z_in, out, geo, -model->bound, model->bound, fw);
+        }));
     };
     density(T, nullptr, sc, gc);
     per_ray(sc, zf);
