@@ -23,6 +23,14 @@ builds the map over a different box (`collision_map_box()`, shape (72, 96, 56)).
 field with the start and granularity of the other box; `SignedDistanceField.from_array(sdf, reference_box())` reproduces that
 (DESIGN.md, "The collision field").
 
+The drone's body ("Body collision"; the rule is world.py's docstring, "The body rule"): `lookup` judges the drone's centre
+point -- a collision only when the centre lies in an occupied cell.  Opt-in, the simulators judge the planner's body box instead:
+
+    BodyBox(lims, margin=0)        the planner's body_lims as half extents and an offset; BodyBox.planner()
+    body_boxes(states, body)       drone states -> the box table [..., 15]; the rule's one rotation (Rodrigues, numpy float64)
+    box_cells(boxes, occupied, box)   per box the lowest occupied cell it overlaps     ngp_box_cells_overlap (HIP); box_cells_numpy
+    SignedDistanceField.occupied / .box_overlap(boxes)   the field's own map (values == 0) and the test against it
+
 Connected components ("Connected components"): what tells a floater -- a blob of density attached to nothing, a phantom
 obstacle in the field above -- from an obstacle.
 
@@ -514,6 +522,36 @@ class SignedDistanceField:
             v = self._dev[device] = torch.from_numpy(self.values).to(device)
         return v
 
+    @property
+    def occupied(self):
+        """the map the field was made from, bool [X, Y, Z] (host): values == 0 -- all-false for a field with no occupied cell"""
+        occ = self._dev.get("occupied")
+        if occ is None:
+            occ = self._dev["occupied"] = np.ascontiguousarray(self.values == 0)
+        return occ
+
+    def _device_occupied(self, device):
+        device = torch.device(device)
+        m = self._dev.get(("occupied", device))
+        if m is None:
+            m = self._dev[("occupied", device)] = torch.from_numpy(self.occupied).to(device)
+        return m
+
+    def box_overlap(self, boxes, device=None):
+        """body boxes float64 [N,15] (world.py's box table; collision.body_boxes) against the field's occupied cells by the body rule
+        -> `cell` int32 [N]: the lowest C-order linear index of an occupied cell each box overlaps, -1 without one.  device: where the
+        test runs -- None: where the boxes are (numpy boxes: the host, box_cells_numpy, an array comes back); a HIP device: csrc/body.hip
+        on the current stream against a cached device copy of the map, the result a tensor there."""
+        if device is None:
+            device = boxes.device if isinstance(boxes, torch.Tensor) else "cpu"
+        device = torch.device(device)
+        if device.type != "cuda":
+            cell = box_cells_numpy(boxes, self.occupied, self.box)
+            return torch.from_numpy(cell) if isinstance(boxes, torch.Tensor) else cell
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return box_cells(boxes, self._device_occupied(device), self.box)
+
     def query(self, points):
         """lookup's index rule for a batch: points [..., 3] tensor -> (values [...] float64, NaN where out of range; in_range [...] bool),
         on the points' device (float64 index arithmetic)"""
@@ -525,6 +563,187 @@ class SignedDistanceField:
         idx = torch.where(ok[..., None], torch.where(idx < 0, idx + n, idx), torch.zeros_like(idx))
         vals = self._device_values(p.device)[idx[..., 0], idx[..., 1], idx[..., 2]]
         return torch.where(ok, vals, torch.full_like(vals, float("nan"))), ok
+
+
+# ------------------------------------------------------------------ the drone's body (world.py's docstring, "The body rule")
+_BODY_CHUNK_PAIRS = 1 << 18                         # (box, candidate cell) pairs per chunk of box_cells_numpy
+ORTHONORMAL_TOL = 1e-6                              # body_boxes refuses an R with max |R^T R - I| above this
+
+
+class BodyBox:
+    """The drone's body as the planner has it (envConfig.json's body_lims): lims [[x0, x1], [y0, y1], [z0, z1]] in the body frame,
+    metres.  half = (hi - lo) / 2 + margin, offset = (hi + lo) / 2 (float64 [3] each); margin >= 0 inflates every half extent."""
+
+    def __init__(self, lims, margin=0.0):
+        lims = np.asarray(lims, np.float64)
+        if lims.shape != (3, 2) or not np.isfinite(lims).all() or (lims[:, 1] < lims[:, 0]).any():
+            raise ValueError(f"BodyBox: lims are [[x0, x1], [y0, y1], [z0, z1]] with lo <= hi (got {lims.tolist()})")
+        if not (float(margin) >= 0.0 and np.isfinite(margin)):
+            raise ValueError(f"BodyBox: margin is a finite length >= 0 (got {margin!r})")
+        self.lims, self.margin = lims, float(margin)
+        self.half = (lims[:, 1] - lims[:, 0]) / 2 + self.margin
+        self.offset = (lims[:, 1] + lims[:, 0]) / 2
+
+    @classmethod
+    def planner(cls, margin=0.0):
+        """the box the planner plans with: rollout.PLANNER_ENV["body_lims"], +-5 x +-5 x +-2 cm"""
+        from .rollout import PLANNER_ENV
+        return cls(PLANNER_ENV["body_lims"], margin)
+
+    def __repr__(self):
+        return f"BodyBox(lims={self.lims.tolist()}, margin={self.margin})"
+
+
+def rodrigues(rot_vec):
+    """rotation vectors float64 [..., 3] -> R [..., 3, 3] = I + sin(t) K + (1 - cos(t)) K K, t = |v|, K the skew matrix of v / t (the
+    identity for t == 0), numpy float64.  The body rule's only rotation: no kernel computes one."""
+    v = np.asarray(rot_vec, np.float64)
+    t = np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])[..., None]
+    with np.errstate(all="ignore"):
+        k = np.where(t > 0, v / np.where(t > 0, t, 1.0), 0.0)
+    K = np.zeros(v.shape[:-1] + (3, 3), np.float64)
+    K[..., 0, 1], K[..., 0, 2] = -k[..., 2], k[..., 1]
+    K[..., 1, 0], K[..., 1, 2] = k[..., 2], -k[..., 0]
+    K[..., 2, 0], K[..., 2, 1] = -k[..., 1], k[..., 0]
+    t = t[..., None]
+    return np.eye(3) + np.sin(t) * K + (1.0 - np.cos(t)) * (K @ K)
+
+
+def body_boxes(states, body):
+    """drone states -> the body rule's box table float64 [..., 15] (numpy).  states [..., 12] (rollout's: xyz 0:3, rotation vector
+    6:9), [..., 6] (xyz, rotation vector) or [..., 18] (the planner's: xyz 0:3, R row-major 6:15, used as given).  R = rodrigues of
+    the rotation vector, the centre xyz + R offset, the half extents body.half.  ValueError when max |R^T R - I| > ORTHONORMAL_TOL
+    (or is not a number)."""
+    s = np.asarray(states.detach().cpu().numpy() if isinstance(states, torch.Tensor) else states, np.float64)
+    if s.ndim < 1 or s.shape[-1] not in (6, 12, 18):
+        raise ValueError(f"body_boxes: states are [..., 12], [..., 6] (xyz, rotation vector) or [..., 18] (with R), got {s.shape}")
+    if s.shape[-1] == 18:
+        R = s[..., 6:15].reshape(s.shape[:-1] + (3, 3))
+    else:
+        R = rodrigues(s[..., 6:9] if s.shape[-1] == 12 else s[..., 3:6])
+    if R.size:
+        err = np.abs(np.swapaxes(R, -1, -2) @ R - np.eye(3)).max()
+        if not err <= ORTHONORMAL_TOL:
+            raise ValueError(f"body_boxes: R is not a rotation, max |R^T R - I| = {err} > {ORTHONORMAL_TOL}")
+    out = np.empty(s.shape[:-1] + (15,), np.float64)
+    out[..., 0:3] = s[..., 0:3] + (R @ body.offset[:, None])[..., 0]
+    out[..., 3:12] = R.reshape(s.shape[:-1] + (9,))
+    out[..., 12:15] = body.half
+    return out
+
+
+def box_cell_overlap(boxes, centre, s):
+    """the body rule's box-cell test for M (box, cell) pairs: boxes float64 [M,15], centre float64 [M,3] the cells' centres (world),
+    s their half-width -> bool [M]"""
+    from . import world as WO
+    with np.errstate(all="ignore"):
+        c, R, h, valid = WO.box_parts(boxes)
+        t = WO.box_frame(c, R, centre)
+        A = np.abs(R)
+        sep = ~valid
+        for a in range(3):
+            sep = sep | (np.abs(t[a]) > h[:, a] + s * ((A[:, 0, a] + A[:, 1, a]) + A[:, 2, a]))
+        for i in range(3):
+            q = (R[:, i, 0] * t[0] + R[:, i, 1] * t[1]) + R[:, i, 2] * t[2]
+            sep = sep | (np.abs(q) > ((h[:, 0] * A[:, i, 0] + h[:, 1] * A[:, i, 1]) + h[:, 2] * A[:, i, 2]) + s)
+        for i in range(3):
+            j, k = (i + 1) % 3, (i + 2) % 3
+            for a in range(3):
+                b, cc = (a + 1) % 3, (a + 2) % 3
+                p = R[:, i, b] * t[cc] - R[:, i, cc] * t[b]
+                r = (h[:, b] * A[:, i, cc] + h[:, cc] * A[:, i, b]) + s * (A[:, j, a] + A[:, k, a])
+                sep = sep | (np.abs(p) > r)
+    return ~sep
+
+
+def box_candidates(boxes, box):
+    """the candidate cells of every body box in the map's GridBox: per axis floor((c_a - E_a - start_a) g) - 1 .. floor((c_a + E_a -
+    start_a) g) + 1 clipped to the map -> (lo int64 [N,3], n int64 [N,3]): the first cell and the number of cells (0: none; an
+    invalid row has none); a NaN bound takes the whole axis"""
+    from . import world as WO
+    c, R, h, valid = WO.box_parts(boxes)
+    start, g, top = np.asarray(box.start, np.float64), np.float64(box.granularity), np.asarray(box.shape, np.float64) - 1.0
+    with np.errstate(all="ignore"):
+        E = WO.box_extent(R, h)
+        l = np.floor(((c - E) - start) * g) - 1.0
+        u = np.floor(((c + E) - start) * g) + 1.0
+        some = ~((u < 0.0) | (l > top)).any(1) & valid
+        first = np.where(l >= 1.0, np.minimum(l, top), 0.0)
+        last = np.where(u <= top - 1.0, np.maximum(u, 0.0), top)
+    first, last = np.nan_to_num(first).astype(np.int64), np.nan_to_num(last).astype(np.int64)
+    return first, np.where(some[:, None], np.maximum(last - first + 1, 0), 0)
+
+
+def box_cells_numpy(boxes, occupied, box, all_cells=False):
+    """the body rule's box-cells test in numpy, chunked over (box, candidate cell) pairs: boxes float64 [N,15], occupied [X,Y,Z]
+    (non-zero = occupied), box the map's GridBox (its start and granularity; the index range is the array's) -> int32 [N]: the lowest
+    C-order linear index of an occupied cell the box overlaps, -1 without one.  all_cells: every cell of the map is every box's
+    candidate (brute force, for small maps: the candidates change no result)"""
+    from . import world as WO
+    b = WO.check_boxes(boxes, "box_cells_numpy")
+    occ = np.ascontiguousarray(np.asarray(occupied) != 0)
+    _check_map(occ, "box_cells_numpy")
+    box = GridBox(box.start, box.granularity, occ.shape)
+    WO.check_voxel_box(box)
+    N = b.shape[0]
+    none = np.iinfo(np.int64).max
+    best = np.full(N, none, np.int64)
+    if N == 0:
+        return np.full(0, -1, np.int32)
+    shape = np.asarray(occ.shape, np.int64)
+    start, g = np.asarray(box.start, np.float64), np.float64(box.granularity)
+    s = np.float64(0.5) / g
+    if all_cells:
+        lo, n = np.zeros((N, 3), np.int64), np.tile(shape, (N, 1))
+    else:
+        lo, n = box_candidates(b, box)
+    counts = n.prod(1)
+    ends = np.cumsum(counts)
+    flat = occ.reshape(-1)
+    for p0 in range(0, int(ends[-1]), _BODY_CHUNK_PAIRS):
+        pair = np.arange(p0, min(int(ends[-1]), p0 + _BODY_CHUNK_PAIRS), dtype=np.int64)
+        i = np.searchsorted(ends, pair, side="right")                              # the first box with ends[i] > pair
+        j = pair - (ends[i] - counts[i])
+        nyz, nz = n[i, 1] * n[i, 2], n[i, 2]
+        ijk = np.stack([lo[i, 0] + j // nyz, lo[i, 1] + (j % nyz) // nz, lo[i, 2] + j % nz], 1)
+        cell = (ijk[:, 0] * shape[1] + ijk[:, 1]) * shape[2] + ijk[:, 2]
+        keep = flat[cell]                                                          # only an occupied cell can be the answer
+        i, ijk, cell = i[keep], ijk[keep], cell[keep]
+        centre = start + (ijk.astype(np.float64) + 0.5) / g
+        hit = box_cell_overlap(b[i], centre, s)
+        np.minimum.at(best, i[hit], cell[hit])
+    return np.where(best == none, -1, best).astype(np.int32)
+
+
+def box_cells(boxes, occupied, box):
+    """the free function that dispatches: boxes [N,15] (float64; tensor or numpy), occupied [X,Y,Z] (a map: bool or uint8, non-zero =
+    occupied), box the map's GridBox -> int32 [N] by the body rule.  A map on a HIP device goes through ngp_box_cells_overlap on the
+    current stream and the result stays there (no host read); a host map through box_cells_numpy (a tensor comes back for a tensor
+    map, an array for an array)."""
+    from . import world as WO
+    if not (isinstance(occupied, torch.Tensor) and occupied.is_cuda):
+        host = occupied.detach().numpy() if isinstance(occupied, torch.Tensor) else occupied
+        cell = box_cells_numpy(boxes, host, box)
+        return torch.from_numpy(cell) if isinstance(occupied, torch.Tensor) else cell
+    _check_map(occupied, "box_cells")
+    dev = occupied.device
+    m = occupied.detach()
+    m = (m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).to(torch.uint8)).contiguous()
+    grid = GridBox(box.start, box.granularity, tuple(m.shape))
+    WO.check_voxel_box(grid)
+    b = boxes.detach() if isinstance(boxes, torch.Tensor) else torch.from_numpy(WO.check_boxes(boxes, "box_cells"))
+    if b.dim() != 2 or b.shape[1] != 15:
+        raise ValueError(f"box_cells: the box table is [N,15] (centre, R row-major, half extents), got {tuple(b.shape)}")
+    b = b.to(dev, torch.float64).contiguous()
+    N = b.shape[0]
+    if N >= 2 ** 31:
+        raise ValueError("box_cells: N must be < 2^31")
+    cell = torch.empty(N, dtype=torch.int32, device=dev)
+    if N:
+        import ctypes
+        with torch.cuda.device(dev):
+            _lib.call("box_cells_overlap", m, ctypes.byref(WO._voxel_box_struct(grid, [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])), b, N, cell)
+    return cell
 
 
 SDF_WORLD = "world"
@@ -540,3 +759,19 @@ def resolve_sdf(sdf, world, who):
     if world is None:
         raise ValueError(f"{who}: sdf={SDF_WORLD!r} needs world= (a world.MeshWorld: the mesh the ground-truth field is built from)")
     return SignedDistanceField.from_mesh(world, reference_box())
+
+
+def check_body(body, exact, sdf, world, who):
+    """the `body` / `exact` keywords of the rollout entry points against the resolved `sdf` and `world`: None passes (with exact
+    unset); a BodyBox needs a map -- the analytic stand-in (sdf=None) has none -- and exact=True needs world="""
+    if body is None:
+        if exact:
+            raise ValueError(f"{who}: exact=True selects the body's test and needs body= (a collision.BodyBox)")
+        return
+    if not isinstance(body, BodyBox):
+        raise ValueError(f"{who}: body is None or a collision.BodyBox (got {type(body).__name__})")
+    if exact and world is None:
+        raise ValueError(f"{who}: exact=True tests the body against the world's triangles and needs world= (a world.MeshWorld)")
+    if sdf is None:
+        raise ValueError(f"{who}: body= needs sdf= (a collision.SignedDistanceField or {SDF_WORLD!r}): the analytic stand-in has no map "
+                         "of occupied cells, and no field for the centre's value")

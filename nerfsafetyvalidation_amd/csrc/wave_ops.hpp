@@ -24,6 +24,16 @@ __device__ __forceinline__ T wave_sum_lane0(T v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
 }
+// Smallest value of a group, the same in every lane of it (integers, or floats without NaN: the order then decides nothing).
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+    for (int off = W / 2; off > 0; off >>= 1) {
+        const T u = __shfl_xor(v, off, W);
+        v = u < v ? u : v;
+    }
+    return v;
+}
 // The four quads of sixteen lanes added up: lane l ends with lanes l % 16 + {0, 16, 32, 48}.  Order: xor 16, then xor 32.
 template <typename T>
 __device__ __forceinline__ T quad_sum(T v) {

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import rollout as RO
-from .collision import PLANNER_ROT, SDF_WORLD, reference_box, resolve_sdf, to_nerf
+from .collision import PLANNER_ROT, SDF_WORLD, check_body, reference_box, resolve_sdf, to_nerf
 
 REPLAY_ROW_WIDTH = 22       # replay_MC.py:81-103,134: sim, step, noise x12, collision value, xyz, step loglik, cumulative loglik, collided (+ ever collided)
 REPLAY_CEM_ROW_WIDTH = 23   # replay_CEM.py:142: the population in front
@@ -226,7 +226,7 @@ def group_rows(rows):
 
 
 def run_replay(rows, model, intrinsics, H, W, *, world, sdf=SDF_WORLD, seed=0, planner_cfg=None, estimator_cfg=None, render_kwargs=None,
-               in_flight=3, autocast=True, start=0, start_k=0, counts=None, views=None, steps=None):
+               in_flight=3, autocast=True, start=0, start_k=0, counts=None, views=None, steps=None, body=None, exact=False):
     """replay_MC / replay_CEM: every recorded simulation of `rows` again, with its recorded noise, in the true world -> ReplayResult.
 
     rows: run_rollout's array (width ROW_WIDTH) or run_cem's (width CEM_ROW_WIDTH); any other width is a ValueError.
@@ -245,7 +245,11 @@ def run_replay(rows, model, intrinsics, H, W, *, world, sdf=SDF_WORLD, seed=0, p
     counts: a ReplayCounts to continue from (it is not modified); it replaces the reference's counts.pkl, no pickle file is written.
     views: None, or a directory: one PNG per replayed simulation -- also those that did not collide, as replay_MC.py:119-121 -- named
     failure_{sim}_{step}.png, with {population}_ in front of {sim} for CEM rows (viz_failures_blend.py:108-111); step is the
-    colliding step, or the last one; the picture is failure_view's default overview at the frame size H x W.  The counting follows the module docstring, quirk included."""
+    colliding step, or the last one; the picture is failure_view's default overview at the frame size H x W.  The counting follows the module docstring, quirk included.
+    body / exact: None, or the collision.BodyBox the replay's verdicts are judged with (RolloutSimulator's `body`: against the field's
+    occupied cells, or with exact=True against the world's triangles).  It applies to both verdicts of a confusion matrix: the world's
+    is judged here; the NeRF's is the recorded one, so `rows` must come from a stress run with the SAME body (like seed, planner_cfg
+    and estimator_cfg) for the matrices to compare like with like."""
     from .world import MeshWorld
     cem, data = group_rows(rows)
     if world is None:
@@ -255,6 +259,7 @@ def run_replay(rows, model, intrinsics, H, W, *, world, sdf=SDF_WORLD, seed=0, p
     if model is None and (planner_cfg is not None or estimator_cfg is not None):
         raise ValueError("run_replay: the planner and the estimator need the NeRF (model=)")
     sdf = resolve_sdf(sdf, world, "run_replay")
+    check_body(body, exact, sdf, world, "run_replay")
     device = next(model.parameters()).device if model is not None else getattr(world, "device", torch.device("cpu"))
 
     def by_position(table, first, what):
@@ -274,7 +279,8 @@ def run_replay(rows, model, intrinsics, H, W, *, world, sdf=SDF_WORLD, seed=0, p
     def one(task):
         pop, s = task
         sim = ReplaySimulator(model, intrinsics, H, W, int(steps), seed=seed, render_kwargs=render_kwargs, planner_cfg=planner_cfg,
-                              initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg, world=world, noises=data[pop][s][0], population=pop)
+                              initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg, world=world, body=body, exact=exact, noises=data[pop][s][0],
+                              population=pop)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast and device.type == "cuda"):
             out = sim.run(s)
         return (out, sim.plans), sim.frames

@@ -235,7 +235,8 @@ class RolloutSimulator:
     Gaussian-approximation UQ per step) and MonteCarlo.validate's bookkeeping."""
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
-                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None):
+                 planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None,
+                 body=None, exact=False):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
         sdf: None (the analytic stand-in, scene_collision), a collision.SignedDistanceField the collision check looks up, or "world":
@@ -248,10 +249,18 @@ class RolloutSimulator:
         1e-3 -- and BayesianLaplace.fit's, e.g. n_steps, likelihood_gradient, lm_solver).
         world: None (the NeRF is its own world: render #1 is the sensor image), or a world.MeshWorld: the true world
         (BlenderSimulator.py:82,102).  Every step its frame of the true pose is kept as self.world_image (uint8 [H,W,3] numpy) and,
-        with estimator_cfg, is the estimator's sensor image; shared and read-only between simulations."""
+        with estimator_cfg, is the estimator's sensor image; shared and read-only between simulations.
+        body: None (the reference's verdict: the centre point's field value, today's rows byte for byte, nothing new launched), or a
+        collision.BodyBox (BodyBox.planner(): the planner's body_lims): the collided column carries the verdict of that box at the
+        step's interpolated poses, by world.py's body rule -- exact=False against the occupied cells of `sdf` (any field: a NeRF-density
+        one or sdf="world"), exact=True against the triangles of `world` (needs world=).  Columns 14 and 15:18 stay the centre's field
+        value and position; self.body_hits keeps, per step, the `cell` (or `prim`) of each interpolated pose (int32 [n_interp], -1:
+        free).  The analytic stand-in (sdf=None) has no map: a body with it is a ValueError."""
         self.world, self.world_image = world, None
-        from .collision import resolve_sdf
+        from .collision import check_body, resolve_sdf
         sdf = resolve_sdf(sdf, world, "RolloutSimulator")
+        check_body(body, exact, sdf, world, "RolloutSimulator")
+        self.body, self.exact, self.body_hits = body, bool(exact), []
         if uq_method not in (UQ_GAUSSIAN, UQ_LAPLACE):
             raise ValueError(f"Unrecognized uncertainty quantification method {uq_method}")
         self.uq_method, self.uq_kwargs, self.last_trace = uq_method, dict(uq_kwargs or {}), None
@@ -391,6 +400,18 @@ class RolloutSimulator:
                 return rmv
             return self.uncertainty(out)[1]
 
+    def judge_body(self, states):
+        """the body's verdict at interpolated states [n, 6] (xyz, rotation vector) -> int32 [n] numpy: the overlapped triangle
+        (exact) or occupied cell of each pose, -1 where the body is free; one call, on the simulator's device"""
+        from .collision import body_boxes
+        boxes = body_boxes(states, self.body)
+        if self.exact:
+            hits = self.world.box_overlap(boxes)["prim"]
+        else:
+            device = self.device if self.device is not None else getattr(self.world, "device", None)
+            hits = self.sdf.box_overlap(boxes, device=device if device is not None and device.type == "cuda" else None)
+        return np.asarray(hits.cpu().numpy() if isinstance(hits, torch.Tensor) else hits, np.int32)
+
     def collision(self, xyz):
         """-> (collided, value): the SDF lookup (value None: outside the field, keep the previous value) or the analytic stand-in"""
         if self.sdf is not None:
@@ -428,7 +449,7 @@ class RolloutSimulator:
         self.reset_estimator(sim, state)
         history = [state.numpy().astype(np.float64)]
         rows = []
-        self.poses, self.actions = [], []
+        self.poses, self.actions, self.body_hits = [], [], []
         for k in range(self.steps):
             noise = self.draw_noise(sim, k)
             action = self.action(k, state)
@@ -444,11 +465,18 @@ class RolloutSimulator:
             x = np.arange(hist.shape[0])
             xn = np.linspace(0, hist.shape[0] - 1, hist.shape[0] * self.n_interp)
             interp = np.stack([np.interp(xn, x, hist[:, i]) for i in range(3)], -1)[-self.n_interp:]
+            hits = None
+            if self.body is not None:                          # the same np.interp rule on the rotation vector: one judgement of all poses
+                turn = np.stack([np.interp(xn, x, hist[:, i]) for i in range(6, 9)], -1)[-self.n_interp:]
+                hits = self.judge_body(np.concatenate([interp, turn], -1))
+                self.body_hits.append(hits)
             collided, value, where = False, 9999.0, interp[-1]
-            for p in interp:
+            for i, p in enumerate(interp):
                 collided, v = self.collision(p)
                 if v is not None:                              # None: NerfSimulator.py:145's IndexError branch keeps the value
                     value = v
+                if hits is not None:                           # the body's verdict; value and position stay the centre's
+                    collided = bool(hits[i] >= 0)
                 where = p
                 if collided:
                     break
@@ -501,7 +529,7 @@ def gather_rows(results, n_simulations, steps, width, world_size=1, group=None, 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
                 render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None,
-                uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None):
+                uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None, body=None, exact=False):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
@@ -509,9 +537,12 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     (SignedDistanceField.from_mesh over reference_box(), built once here; a ValueError without world=).  estimator_cfg: None, or nav.estimator_config()'s
     dict (with planner_cfg: every simulation's planner replans from the reference's NeRF state estimate; eager estimator steps).
     uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged).  world: None, or the
-    world.MeshWorld every simulation's sensor looks at (RolloutSimulator's `world`; shared, read-only)."""
-    from .collision import resolve_sdf
+    world.MeshWorld every simulation's sensor looks at (RolloutSimulator's `world`; shared, read-only).  body / exact: None (the
+    centre point's verdict, the rows as they always were) or the collision.BodyBox every simulation's collisions are judged with
+    (RolloutSimulator's `body`: against sdf's occupied cells, or with exact=True against world's triangles)."""
+    from .collision import check_body, resolve_sdf
     sdf = resolve_sdf(sdf, world, "run_rollout")
+    check_body(body, exact, sdf, world, "run_rollout")
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -521,7 +552,7 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
                                    planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg,
-                                   uq_method=uq_method, uq_kwargs=uq_kwargs, world=world)
+                                   uq_method=uq_method, uq_kwargs=uq_kwargs, world=world, body=body, exact=exact)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
@@ -544,7 +575,8 @@ def run_validation(stress_test, *args, simulator=SIM_NERF, **kwargs):
     'Cross Entropy Method' -> cem.run_cem(*args, **kwargs); anything else is an error (the reference prints and exits).  `simulator`
     is envConfig.json's key of that name: 'NerfSimulator' (the default: the NeRF is its own world) or 'BlenderSimulator' (the sensor
     looks at the true world: needs world=, a world.MeshWorld); anything else is an error.  With world=, sdf="world" judges the
-    collisions of either loop against the mesh's own field, not against the NeRF's."""
+    collisions of either loop against the mesh's own field, not against the NeRF's; body= (a collision.BodyBox) judges them for the
+    drone's body box instead of its centre point (exact=True: against the mesh's triangles)."""
     if simulator not in (SIM_NERF, SIM_BLENDER):
         raise ValueError(f"Unrecognized simulator {simulator}")
     if simulator == SIM_BLENDER and kwargs.get("world") is None:

@@ -12,8 +12,8 @@ nerf.utils.get_rays (so a world frame and a NeRF frame of one pose are pixel-ali
 A mesh on a HIP device goes through csrc/raycast.hip (a uniform grid, one lane per ray) on the current stream; a CPU tensor or a numpy
 array through numpy: brute force over all triangles, chunked -- the package's CPU implementation, as mesh.isosurface has one.
 
-This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip, csrc/closest.hip and
-DESIGN.md point here, and a change to a rule is made in this text, in the numpy path and in the kernel.
+This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip, csrc/closest.hip, csrc/body.hip
+and DESIGN.md point here, and a change to a rule is made in this text, in the numpy path and in the kernel.
 
 The hit rule; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
     per triangle v0, e1 = v1 - v0, e2 = v2 - v0;  p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det, s = o - v0,
@@ -65,6 +65,57 @@ The voxelisation rule (written here once, implemented in voxelize_numpy and in c
     Candidates: the result is defined over all cells of the box; an implementation may test any superset of the overlapping cells.
     Both test, per axis, the cells floor((min_k w_ka - start_a) g) - 1 .. floor((max_k w_ka - start_a) g) + 1, clipped to the box
     (face_candidates); voxelize_numpy(all_cells=True) tests every cell of the box instead, and gives the same map.
+
+The world also judges a BODY, not only a point (DESIGN.md "Body collision"): the reference's verdict, SignedDistanceField.lookup's
+value < 1 / granularity, is true only when the drone's CENTRE lies in an occupied cell (the field is a distance transform in whole cells:
+a neighbour's value is exactly 1 / granularity, not below it).  A rotor arm through a pillar is then no failure.  Opt-in, a stress test
+judges the planner's body box instead (collision.BodyBox, body_boxes), against the mesh's triangles or against a map's occupied cells.
+
+        .box_overlap(boxes, rot=PLANNER_ROT)                           -> {"prim": int32 [N]} on the world's device
+    box_overlap_numpy(boxes, vertices_world, faces)                    -> the same, numpy: brute force over all (box, face) pairs
+    collision.box_cells(boxes, occupied, box)                          -> int32 [N]; collision.box_cells_numpy is its numpy path
+
+A HIP world / a map on a HIP device goes through csrc/body.hip (one wave per box) on the current stream, anything else through the
+numpy paths; the two agree bit for bit.
+
+The body rule (written here once; box_tri_overlap / collision.box_cell_overlap and csrc/body.hip implement it):
+    The box table: boxes float64 [N,15]; a row is the centre c (3), R row-major (9) and the half extents h (3).  The COLUMNS of R
+    are the box's axes in the world frame (the frame of collision.GridBox and of the rollout's states).  No kernel and no numpy
+    path computes a rotation: R comes from collision.body_boxes, the one place Rodrigues' formula is evaluated for this rule.
+    Everything is float64, one IEEE rounding per operation, no contraction, with the a . b and a x b of the voxelisation rule.
+    A row with a non-finite entry or a negative half extent overlaps nothing.  Every inequality below is evaluated as written: "all
+    p_k > r" is three comparisons, not a minimum, so a NaN (the overflow of an absurd box) fails it and separates nothing.
+    Into the box's frame: x' = R^T (x - c), summed as x'_a = (R_0a d_0 + R_1a d_1) + R_2a d_2 with d = x - c.
+    Box against a triangle -- exact and closed.  The world vertices are formed as the voxelisation forms them (the exact float32
+        vertices through the signed permutation rot, no rounding), taken to the box's frame, v_k' (k = 0, 1, 2), and tested by the
+        voxelisation's rule (a) with one half-width per axis; the edges e0 = v1' - v0', e1 = v2' - v1', e2 = v0' - v2' and the normal
+        n = e0 x e1 are those of the v_k':
+            box axis a       separates iff  all v'_ka > h_a  or  all v'_ka < -h_a
+            the normal       separates iff  |n . v_0'| > (h_x |n_x| + h_y |n_y|) + h_z |n_z|
+            a = u_i x e_j    separates iff  all p_k > r  or  all p_k < -r,  p_k = a_b v'_kb + a_c v'_kc,  r = h_b |a_b| + h_c |a_c|
+        over the two components b < c that are not identically zero (u_0 x e = (0, -ez, ey), u_1 x e = (ez, 0, -ex), u_2 x e =
+        (-ey, ex, 0)).  Strict inequalities: touching is overlap; a zero axis separates nothing (a zero-area face is decided by the
+        remaining axes).  prim of a box = the LOWEST index of an overlapping face, or -1 -- the minimum, so that a triangle listed
+        in several grid cells is harmless: no deduplication, no atomics.
+        The grid only chooses candidates: an implementation may test any superset of the overlapping triangles, and no result
+        depends on the grid.  csrc/body.hip takes the grid cells reached by the box's world bounds c_a -+ E_a, E_a = (|R_a0| h_0 +
+        |R_a1| h_1) + |R_a2| h_2, permuted into the mesh's axes, rounded outward to float32 and grown by the binning's growth; the
+        cell arithmetic floor((x - lo) * inv_cell) is non-decreasing in x and binning applies the same to a triangle's grown bounds,
+        so a triangle that shares a point with the box's bounds is listed in a cell of the range (the argument in full: body.hip).
+    Box against a map's cells.  occupied bool [X,Y,Z] on a GridBox; cell (i, j, k) is the cube with the centre m = start +
+        ((i, j, k) + 0.5) / g and the half-width s = 0.5 / g (the voxelisation's cell).  It overlaps the box iff the closed 15-axis
+        box-box separating-axis test finds no separating axis, evaluated in the box's frame, where the box is axis-aligned and the
+        cell's axis i is ROW i of R; with t = m' (the centre in the box's frame) and A_ia = |R_ia|:
+            box axis a            separates iff  |t_a| > h_a + s ((A_0a + A_1a) + A_2a)
+            cell axis i           separates iff  |(R_i0 t_0 + R_i1 t_1) + R_i2 t_2| > ((h_0 A_i0 + h_1 A_i1) + h_2 A_i2) + s
+            u_a x (row i)         separates iff  |R_ib t_c - R_ic t_b| > (h_b A_ic + h_c A_ib) + s (A_ja + A_ka)
+        with (a, b, c) and (i, j, k) cyclic: b = a + 1, c = a + 2, j = i + 1, k = i + 2 (mod 3).  Strict inequalities; a zero cross
+        axis separates nothing.  (The last term uses (row i x row j) = +- row k, true of a rotation; R is used as given.)
+        cell of a box = the LOWEST C-order linear index (i Y + j) Z + k of an occupied overlapping cell, or -1.  Cells outside the
+        array do not exist: the part of a body that sticks out of the map touches nothing, as the IndexError branch of the reference's
+        lookup has it.  lookup's wrap of a negative index (numpy's indexing) is NOT reproduced here.
+        Candidates: any superset; both paths take, per axis, the cells floor((c_a - E_a - start_a) g) - 1 .. floor((c_a + E_a -
+        start_a) g) + 1 clipped to the map; collision.box_cells_numpy(all_cells=True) tests every cell, and gives the same result.
 
 The world can also be drawn with analytic primitives in it -- the replay's failure view (replay.failure_view; DESIGN.md "Failure
 replay"), in the place of the Blender scene of validation/utils/viz_failures_blend.py:
@@ -677,6 +728,94 @@ def voxelize_numpy(vertices_world, faces, box, all_cells=False):
     return occ
 
 
+# ------------------------------------------------------------------------------------------------------------- the body (numpy)
+_BODY_CHUNK_PAIRS = 1 << 18                         # (box, face) pairs per chunk of box_overlap_numpy
+
+
+def check_boxes(boxes, who="box_overlap"):
+    """the box table as float64 [N,15] numpy (a copy of nothing: a view where it can be); ValueError for another shape or N >= 2^31"""
+    b = np.ascontiguousarray(boxes.detach().cpu().numpy() if isinstance(boxes, torch.Tensor) else boxes, np.float64)
+    if b.size == 0 and (b.ndim < 2 or b.shape[-1] in (0, 15)):
+        return b.reshape(0, 15)
+    if b.ndim != 2 or b.shape[1] != 15:
+        raise ValueError(f"{who}: the box table is [N,15] (centre, R row-major, half extents), got {b.shape}")
+    if b.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: N must be < 2^31")
+    return b
+
+
+def box_parts(boxes):
+    """boxes float64 [M,15] -> (c [M,3], R [M,3,3], h [M,3], valid bool [M]: every entry finite and no half extent negative)"""
+    c, R, h = boxes[:, 0:3], boxes[:, 3:12].reshape(-1, 3, 3), boxes[:, 12:15]
+    return c, R, h, np.isfinite(boxes).all(1) & (h >= 0).all(1)
+
+
+def box_frame(c, R, x):
+    """the body rule's x' = R^T (x - c): c [M,3], R [M,3,3], x [M,3] -> three [M] arrays, (R_0a d_0 + R_1a d_1) + R_2a d_2"""
+    d = [x[:, k] - c[:, k] for k in range(3)]
+    return [(R[:, 0, a] * d[0] + R[:, 1, a] * d[1]) + R[:, 2, a] * d[2] for a in range(3)]
+
+
+def box_extent(R, h):
+    """the half extent of the boxes' world bounds, E_a = (|R_a0| h_0 + |R_a1| h_1) + |R_a2| h_2 -> [M,3]"""
+    A = np.abs(R)
+    return (A[:, :, 0] * h[:, 0:1] + A[:, :, 1] * h[:, 1:2]) + A[:, :, 2] * h[:, 2:3]
+
+
+def box_tri_overlap(boxes, tri):
+    """the body rule's box-triangle test for M (box, face) pairs: boxes float64 [M,15], tri float64 [M, vertex, axis] (world) -> bool [M]"""
+    out = np.zeros(boxes.shape[0], dtype=bool)
+    with np.errstate(all="ignore"):
+        c, R, h, valid = box_parts(boxes)
+        p = np.stack([np.stack(box_frame(c, R, tri[:, k]), -1) for k in range(3)], 1)                  # [M, vertex, axis]
+        idx = np.nonzero(valid & ~((p > h[:, None, :]).all(1) | (p < -h[:, None, :]).all(1)).any(1))[0]    # the three box axes
+        p, h = p[idx], h[idx]
+        e = np.stack([p[:, 1] - p[:, 0], p[:, 2] - p[:, 1], p[:, 0] - p[:, 2]], 1)                     # [M', edge, axis]
+        n = _cross([e[:, 0, a] for a in range(3)], [e[:, 1, a] for a in range(3)])
+        d = _dot(n, [p[:, 0, a] for a in range(3)])
+        sep = np.abs(d) > (h[:, 0] * np.abs(n[0]) + h[:, 1] * np.abs(n[1])) + h[:, 2] * np.abs(n[2])
+        for j in range(3):
+            ex, ey, ez = e[:, j, 0], e[:, j, 1], e[:, j, 2]
+            for a1, a2, c1, c2 in ((-ez, ey, 1, 2), (ez, -ex, 0, 2), (-ey, ex, 0, 1)):                 # u_0 x e, u_1 x e, u_2 x e
+                q = a1[:, None] * p[:, :, c1] + a2[:, None] * p[:, :, c2]
+                r = (h[:, c1] * np.abs(a1) + h[:, c2] * np.abs(a2))[:, None]
+                sep |= (q > r).all(1) | (q < -r).all(1)
+    out[idx] = ~sep
+    return out
+
+
+def box_overlap_numpy(boxes, vertices_world, faces):
+    """the body rule's box-triangle test in numpy, brute force over all (box, face) pairs, chunked: boxes float64 [N,15],
+    vertices_world float32 [V,3] (the world frame: vertices_to_world), faces integer [F,3] -> {"prim": int32 [N]}: the lowest
+    index of an overlapping face, -1 without one"""
+    b = check_boxes(boxes, "box_overlap_numpy")
+    vw = np.ascontiguousarray(vertices_world, _f32).reshape(-1, 3)
+    fc = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    N, F = b.shape[0], fc.shape[0]
+    prim = np.full(N, -1, np.int32)
+    if N == 0 or F == 0:
+        return {"prim": prim}
+    tri = vw[fc].astype(np.float64)
+    chunk = max(1, _BODY_CHUNK_PAIRS // F)
+    for i0 in range(0, N, chunk):
+        part = b[i0:i0 + chunk]
+        c, R, h, valid = box_parts(part)
+        # the three box axes for every pair of the chunk, by broadcasting (box_frame's arithmetic); the few pairs they do not separate
+        # go through the whole test
+        keep = np.repeat(valid[:, None], F, 1)
+        with np.errstate(all="ignore"):
+            d = [[tri[None, :, k, j] - c[:, None, j] for j in range(3)] for k in range(3)]
+            for a in range(3):
+                p = [(R[:, None, 0, a] * d[k][0] + R[:, None, 1, a] * d[k][1]) + R[:, None, 2, a] * d[k][2] for k in range(3)]
+                ha = h[:, None, a]
+                keep &= ~(((p[0] > ha) & (p[1] > ha) & (p[2] > ha)) | ((p[0] < -ha) & (p[1] < -ha) & (p[2] < -ha)))
+        bi, fi = np.nonzero(keep)
+        hit = np.zeros(keep.shape, dtype=bool)
+        hit[bi, fi] = box_tri_overlap(part[bi], tri[fi])
+        prim[i0:i0 + part.shape[0]] = np.where(hit.any(1), hit.argmax(1), -1)
+    return {"prim": prim}
+
+
 def _voxel_box_struct(box, rot):
     axis, sign = signed_permutation(rot)
     b = _lib.VoxelBox()
@@ -781,6 +920,33 @@ class MeshWorld:
                 _lib.call("voxelize_mark", self.vertices, self.n_vertices, self.faces, self.n_faces, ctypes.byref(b), ends, base,
                           min(int(pairs_per_launch), pairs - base), occ)
         return occ.view(torch.bool)
+
+    # ---- the body
+    def box_overlap(self, boxes, rot=PLANNER_ROT):
+        """boxes float64 [N,15] (the module's box table, world frame: collision.body_boxes) -> {"prim": int32 [N]}, the lowest index
+        of a triangle each box overlaps by the module's body rule, -1 without one -- a tensor on the world's device (a numpy array
+        for numpy boxes on a CPU world).  rot: the signed permutation that collision.to_nerf applied to the world's vertices
+        (ValueError otherwise).  A HIP world runs csrc/body.hip on the current stream (one launch, no host read); a CPU world
+        box_overlap_numpy."""
+        tensors = isinstance(boxes, torch.Tensor)
+        axis, sign = signed_permutation(rot)
+        if self.device.type != "cuda":
+            prim = box_overlap_numpy(check_boxes(boxes, "MeshWorld.box_overlap"), vertices_to_world(self.vertices.numpy(), rot), self.faces.numpy())["prim"]
+            return {"prim": torch.from_numpy(prim) if tensors else prim}
+        b = boxes.detach() if tensors else torch.from_numpy(check_boxes(boxes, "MeshWorld.box_overlap"))
+        if b.dim() != 2 or b.shape[1] != 15:
+            raise ValueError(f"MeshWorld.box_overlap: the box table is [N,15] (centre, R row-major, half extents), got {tuple(b.shape)}")
+        b = b.to(self.device, torch.float64).contiguous()
+        N = b.shape[0]
+        if N >= 2 ** 31:
+            raise ValueError("MeshWorld.box_overlap: N must be < 2^31")
+        prim = torch.empty(N, dtype=torch.int32, device=self.device)
+        if N:
+            axis_c, sign_c = (ctypes.c_int32 * 3)(*[int(a) for a in axis]), (ctypes.c_int32 * 3)(*[int(s) for s in sign])
+            with torch.cuda.device(self.device):
+                _lib.call("box_mesh_overlap", b, N, ctypes.byref(self._grid_c), self.cell_start, self.pair_tri, self.pairs, self.tri_verts,
+                          self.n_faces, ctypes.cast(axis_c, ctypes.c_void_p), ctypes.cast(sign_c, ctypes.c_void_p), prim)
+        return {"prim": prim}
 
     # ---- the closest point of the surface
     def closest(self, points, max_distance=float("inf"), coherent=None, tested=False):
