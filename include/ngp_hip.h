@@ -60,8 +60,9 @@ typedef void* ngp_stream_t;
  *   101: ngp_network_density has a `geo_feat` argument, ngp_model has `precision` (both were added under 100, unrecorded).
  *   102: ngp_mark_untrained_grid_workspace is new; ngp_density_grid_update, ngp_density_grid_finish, ngp_uq_stats and
  *        ngp_mark_untrained_grid return NGP_EWORKSPACE, no longer NGP_EINVAL, for a workspace that is too small.
- *   103: ngp_box_mesh_overlap and ngp_box_cells_overlap are new. */
-#define NGP_ABI_VERSION 103
+ *   103: ngp_box_mesh_overlap and ngp_box_cells_overlap are new.
+ *   104: ngp_box_mesh_clearance and ngp_box_cells_clearance are new. */
+#define NGP_ABI_VERSION 104
 
 /* Caller-owned workspaces.  Every `workspace` / `workspace_bytes` pair below is checked by one rule, against the size its
  * ngp_*_workspace() function answers (which the entry point carves with the very code that measured it):
@@ -629,6 +630,23 @@ NGP_API int ngp_box_mesh_overlap(const double* boxes, uint64_t N, const ngp_rayc
                                  const int32_t* sign3_host, int32_t* prim, ngp_stream_t stream);
 NGP_API int ngp_box_cells_overlap(const uint8_t* map, const ngp_voxel_box* box, const double* boxes, uint64_t N, int32_t* cell,
                                   ngp_stream_t stream);
+
+/* The gap between the body box and the nearest obstacle (csrc/clearance.hip; MeshWorld.box_clearance, collision.box_cells_clearance),
+ * by "The clearance rule" of nerfsafetyvalidation_amd/world.py's docstring: float64, one IEEE operation per step.  The arguments of
+ * the two entry points above, and:
+ *   max_distance  a length > 0 or +inf: a distance above it is not accepted.  It also bounds the candidates; no result depends on them.
+ *   distance      double [N], device, 8-byte aligned: the distance from the box to the nearest triangle (occupied cell), 0 where they
+ *                 overlap, +inf where nothing lies within max_distance or the row is invalid.
+ *   prim / cell   int32 [N]: the lowest index among the nearest, -1 with distance +inf; it is `hit` wherever hit >= 0.
+ *   hit           int32 [N]: what ngp_box_mesh_overlap's prim (ngp_box_cells_overlap's cell) is for the same box -- the same test.
+ * N == 0 launches nothing.  NGP_EINVAL, with a message and nothing launched, when N >= 2^31, when max_distance is NaN or <= 0, or when
+ * a pointer is null with N > 0.  One wave per box; no atomics, no workspace, no global state. */
+NGP_API int ngp_box_mesh_clearance(const double* boxes, uint64_t N, const ngp_raycast_grid* grid, const int32_t* cell_start,
+                                   const int32_t* pair_tri, uint64_t P, const float* tri_verts, uint32_t F, const int32_t* axis3_host,
+                                   const int32_t* sign3_host, double max_distance, double* distance, int32_t* prim, int32_t* hit,
+                                   ngp_stream_t stream);
+NGP_API int ngp_box_cells_clearance(const uint8_t* map, const ngp_voxel_box* box, const double* boxes, uint64_t N, double max_distance,
+                                    double* distance, int32_t* cell, int32_t* hit, ngp_stream_t stream);
 
 /* Rays against a list of analytic primitives, merged by depth with a mesh cast (csrc/overlay.hip): the replay's failure view.
  * The table: 8 floats per primitive, kind, a.xyz, b.xyz, r -- kind 0 a capsule with the axis a-b and the radius r, kind 1 an

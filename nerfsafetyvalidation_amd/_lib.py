@@ -29,7 +29,7 @@ NGP_SCHED_NO_FORECAST = 1                                        # ngp_render_ct
 NGP_EDT_INF = 0x7FFFFFFF                                         # ngp_edt_sq: no occupied cell
 NGP_COMPONENTS_TILE = (4, 4, 16)                                 # NGP_COMPONENTS_TILE_X / _Y / _Z: the tile ngp_label_components labels in LDS
 
-ABI_VERSION = 103                                               # NGP_ABI_VERSION of the header this table mirrors; lib() compares
+ABI_VERSION = 104                                               # NGP_ABI_VERSION of the header this table mirrors; lib() compares
 
 _vp, _u32, _f32, _int, _sz = C.c_void_p, C.c_uint32, C.c_float, C.c_int, C.c_size_t
 
@@ -183,6 +183,8 @@ SIGNATURES = {
     "ngp_voxelize_mark": [_vp, _u32, _vp, _u32, C.POINTER(VoxelBox), _vp, C.c_uint64, C.c_uint64, _vp, _st],
     "ngp_box_mesh_overlap": [_vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _vp, _vp, _vp, _st],
     "ngp_box_cells_overlap": [_vp, C.POINTER(VoxelBox), _vp, C.c_uint64, _vp, _st],
+    "ngp_box_mesh_clearance": [_vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _vp, _vp, C.c_double, _vp, _vp, _vp, _st],
+    "ngp_box_cells_clearance": [_vp, C.POINTER(VoxelBox), _vp, C.c_uint64, C.c_double, _vp, _vp, _vp, _st],
     "ngp_overlay_cast": [_vp, _vp, C.c_uint64, _vp, _vp, _u32, _f32, _vp, _u32, _vp, _vp, _vp, _st],
     "ngp_overlay_shade": [_vp, _vp, _vp, C.c_uint64, _vp, _u32, _f32, _vp, _vp, _st],
     "ngp_closest_point": [_vp, C.c_uint64, C.POINTER(RaycastGrid), _vp, _vp, C.c_uint64, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _st],

@@ -196,20 +196,21 @@ def best_solution(q, simulator, sim):
 
 def run_cem(model, intrinsics, H, W, steps, m=10, m_elite=5, kmax=5, seed=0, q=None, start_k=0, sdf=None, best_solution=False, rank=0,
             world_size=1, group=None, in_flight=3, render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None,
-            estimator_cfg=None, uq_method=RO.UQ_GAUSSIAN, uq_kwargs=None, world=None, body=None, exact=False):
+            estimator_cfg=None, uq_method=RO.UQ_GAUSSIAN, uq_kwargs=None, world=None, body=None, exact=False, clearance=None):
     """CrossEntropyMethod.optimize() with every population run like run_rollout's simulations.  m, m_elite, kmax: validate.py:39's
     10, 5, 5.  q: the proposal to start from (default: the target p); with start_k it is the reference's `--k` resume.  sdf: a
     collision.SignedDistanceField, REQUIRED (the analytic 0 / 9999 stand-in gives CEM nothing to rank), or "world": the ground-truth
     field of `world`'s mesh (SignedDistanceField.from_mesh over reference_box(), built once here; a ValueError without world=).  The other keywords are
-    run_rollout's (world: the world.MeshWorld every simulation's sensor looks at, or None; body / exact: the collision.BodyBox the collisions are judged with, or None); the refit needs every rank's rows, so gather=False is only accepted on one rank.
+    run_rollout's (world: the world.MeshWorld every simulation's sensor looks at, or None; body / exact: the collision.BodyBox the collisions are judged with, or None; clearance: None, or the cap D of the body's gap that then is the value `adjusted`, the risk and the elite are built from); the refit needs every rank's rows, so gather=False is only accepted on one rank.
     Returns (rows [total, CEM_ROW_WIDTH] float64 in (population, simulation, step) order, result, this rank's counters).  result:
     means / covs / q (the final proposal), population_scores / elite_scores (the two series the reference plots, :209,220),
     elite_indices, refit_info and the refitted population_means / population_covs per population, stopped_early (None, or the population whose refit gave no valid q -- the
     reference's ValueError branch, :264-271; q is then the last valid one), and with best_solution=True best_solution's triple
     (simulation number m, i.e. seeded seed + m; every rank runs it, it is one simulation and deterministic)."""
-    from .collision import check_body, resolve_sdf
+    from .collision import check_body, check_clearance, resolve_sdf
     sdf = resolve_sdf(sdf, world, "run_cem")
     check_body(body, exact, sdf, world, "run_cem")
+    check_clearance(clearance, body, "run_cem")
     if sdf is None:
         raise ValueError("run_cem: sdf is required (the analytic stand-in's 0 / 9999 gives the Cross Entropy Method nothing to rank)")
     if not 0 < m_elite <= m:
@@ -229,7 +230,8 @@ def run_cem(model, intrinsics, H, W, steps, m=10, m_elite=5, kmax=5, seed=0, q=N
     def make(population, q_k):
         return CEMSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
                             planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg, uq_method=uq_method,
-                            uq_kwargs=uq_kwargs, world=world, body=body, exact=exact, p=p, q=q_k, population=population)
+                            uq_kwargs=uq_kwargs, world=world, body=body, exact=exact, clearance=clearance, p=p, q=q_k,
+                            population=population)
 
     result = {"population_scores": [], "elite_scores": [], "elite_indices": [], "refit_info": [], "population_means": [],
               "population_covs": [], "stopped_early": None}

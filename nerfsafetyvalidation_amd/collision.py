@@ -31,6 +31,15 @@ point -- a collision only when the centre lies in an occupied cell.  Opt-in, the
     box_cells(boxes, occupied, box)   per box the lowest occupied cell it overlaps     ngp_box_cells_overlap (HIP); box_cells_numpy
     SignedDistanceField.occupied / .box_overlap(boxes)   the field's own map (values == 0) and the test against it
 
+and, with clearance=, score a step by the gap between that box and the nearest obstacle instead of the centre's field value (DESIGN.md,
+"Body clearance"; world.py's docstring, "The clearance rule"):
+
+    box_cells_clearance(boxes, occupied, box, max_distance)   per box the distance to the nearest occupied cell, that cell and the
+                                                              verdict's cell             ngp_box_cells_clearance (HIP); box_cells_clearance_numpy
+    box_cell_distance2(boxes, centre, s)                      the rule's squared distance per (box, cell) pair
+    SignedDistanceField.box_clearance(boxes, max_distance)    the same against the field's own map
+    trajectory_clearance(states, body, world= / sdf=, exact=, max_distance=)   re-score recorded poses [n, 6] in one call
+
 Connected components ("Connected components"): what tells a floater -- a blob of density attached to nothing, a phantom
 obstacle in the field above -- from an obstacle.
 
@@ -552,6 +561,21 @@ class SignedDistanceField:
             device = torch.device("cuda", torch.cuda.current_device())
         return box_cells(boxes, self._device_occupied(device), self.box)
 
+    def box_clearance(self, boxes, max_distance, device=None):
+        """body boxes float64 [N,15] against the field's occupied cells by the clearance rule -> {"distance" float64 [N], "cell" int32
+        [N], "hit" int32 [N]} (hit: box_overlap's cell).  device: box_overlap's rule -- None: where the boxes are (numpy boxes: the
+        host, box_cells_clearance_numpy, arrays come back); a HIP device: csrc/clearance.hip on the current stream against the cached
+        device copy of the map, the results tensors there."""
+        if device is None:
+            device = boxes.device if isinstance(boxes, torch.Tensor) else "cpu"
+        device = torch.device(device)
+        if device.type != "cuda":
+            out = box_cells_clearance_numpy(boxes, self.occupied, self.box, max_distance)
+            return {k: torch.from_numpy(v) for k, v in out.items()} if isinstance(boxes, torch.Tensor) else out
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return box_cells_clearance(boxes, self._device_occupied(device), self.box, max_distance)
+
     def query(self, points):
         """lookup's index rule for a batch: points [..., 3] tensor -> (values [...] float64, NaN where out of range; in_range [...] bool),
         on the points' device (float64 index arithmetic)"""
@@ -656,15 +680,15 @@ def box_cell_overlap(boxes, centre, s):
     return ~sep
 
 
-def box_candidates(boxes, box):
+def box_candidates(boxes, box, reach=0.0):
     """the candidate cells of every body box in the map's GridBox: per axis floor((c_a - E_a - start_a) g) - 1 .. floor((c_a + E_a -
     start_a) g) + 1 clipped to the map -> (lo int64 [N,3], n int64 [N,3]): the first cell and the number of cells (0: none; an
-    invalid row has none); a NaN bound takes the whole axis"""
+    invalid row has none); a NaN bound takes the whole axis.  reach: the clearance rule's max_distance, E_a + reach in E_a's place"""
     from . import world as WO
     c, R, h, valid = WO.box_parts(boxes)
     start, g, top = np.asarray(box.start, np.float64), np.float64(box.granularity), np.asarray(box.shape, np.float64) - 1.0
     with np.errstate(all="ignore"):
-        E = WO.box_extent(R, h)
+        E = WO.box_extent(R, h) + np.float64(reach)
         l = np.floor(((c - E) - start) * g) - 1.0
         u = np.floor(((c + E) - start) * g) + 1.0
         some = ~((u < 0.0) | (l > top)).any(1) & valid
@@ -746,6 +770,170 @@ def box_cells(boxes, occupied, box):
     return cell
 
 
+# ------------------------------------------------------------------ the body's clearance (world.py's docstring, "The clearance rule")
+def _box_cell_terms(boxes, centre, s):
+    """-> (d2 float64 [M] by the clearance rule's box-cell part, +inf for an invalid row; overlap bool [M] by the body rule)"""
+    from . import world as WO
+    inf = np.float64(np.inf)
+    with np.errstate(all="ignore"):
+        c, R, h, valid = WO.box_parts(boxes)
+        over = box_cell_overlap(boxes, centre, s)
+        hh = [h[:, a] for a in range(3)]
+        best = np.full(boxes.shape[0], inf)
+        for m in range(8):                                                         # the cell's corners against the box
+            x = np.stack([centre[:, i] + (s if (m >> i) & 1 else -s) for i in range(3)], 1)
+            best = WO._take_smaller(best, WO.clamp_gap2(WO.box_frame(c, R, x), hh))
+        for m in range(8):                                                         # the box's corners against the cell
+            o = [hh[a] if (m >> a) & 1 else -hh[a] for a in range(3)]
+            y = [(c[:, i] + ((R[:, i, 0] * o[0] + R[:, i, 1] * o[1]) + R[:, i, 2] * o[2])) - centre[:, i] for i in range(3)]
+            best = WO._take_smaller(best, WO.clamp_gap2(y, [s, s, s]))
+        for i in range(3):                                                         # the cell's edges against the box's edges
+            j, k = (i + 1) % 3, (i + 2) % 3
+            for m in range(4):
+                x0 = np.empty_like(centre)
+                x0[:, i], x0[:, j], x0[:, k] = centre[:, i] - s, centre[:, j] + (s if m & 1 else -s), centre[:, k] + (s if m & 2 else -s)
+                x1 = x0.copy()
+                x1[:, i] = centre[:, i] + s
+                q0, q1 = WO.box_frame(c, R, x0), WO.box_frame(c, R, x1)
+                best = WO.box_edges_segment_d2(hh, q0, [q1[a] - q0[a] for a in range(3)], best)
+    return np.where(valid, np.where(over, 0.0, best), inf), over & valid
+
+
+def box_cell_distance2(boxes, centre, s):
+    """the clearance rule's squared distance for M (box, cell) pairs: boxes float64 [M,15], centre float64 [M,3] the cells' centres
+    (world), s their half-width -> float64 [M]: 0 where the body rule says overlap, else the smallest of the 160 candidates; +inf
+    for an invalid row"""
+    return _box_cell_terms(np.ascontiguousarray(boxes, np.float64), np.asarray(centre, np.float64), np.float64(s))[0]
+
+
+def _cell_skip(boxes, centre, s, limit2):
+    """the rule's lower-bound skip for (box, cell) pairs: True where the cell's bounds in the box's frame prove d2 > limit2"""
+    from . import world as WO
+    with np.errstate(all="ignore"):
+        c, R, h, _ = WO.box_parts(boxes)
+        t = WO.box_frame(c, R, centre)
+        A = np.abs(R)
+        rho = [s * ((A[:, 0, a] + A[:, 1, a]) + A[:, 2, a]) for a in range(3)]
+        lb2, m = WO.frame_gap2([t[a] - rho[a] for a in range(3)], [t[a] + rho[a] for a in range(3)], [h[:, a] for a in range(3)])
+        return lb2 > limit2 + WO.CLEARANCE_SKIP * (limit2 + m * m)
+
+
+def box_cells_clearance_numpy(boxes, occupied, box, max_distance, all_cells=False):
+    """the clearance rule against a map in numpy, chunked over (box, candidate cell) pairs: box_cells_numpy's arguments and
+    max_distance (a length > 0 or +inf) -> {"distance" float64 [N] (+inf: no occupied cell within max_distance), "cell" int32 [N]
+    (-1), "hit" int32 [N]: box_cells_numpy's cell}.  all_cells: every cell of the map is every box's candidate."""
+    from . import world as WO
+    max_distance = WO.check_max_distance(max_distance, "box_cells_clearance_numpy")
+    b = WO.check_boxes(boxes, "box_cells_clearance_numpy")
+    occ = np.ascontiguousarray(np.asarray(occupied) != 0)
+    _check_map(occ, "box_cells_clearance_numpy")
+    box = GridBox(box.start, box.granularity, occ.shape)
+    WO.check_voxel_box(box)
+    N = b.shape[0]
+    inf, none = np.float64(np.inf), np.iinfo(np.int64).max
+    best, arg, hit = np.full(N, inf), np.full(N, none, np.int64), np.full(N, none, np.int64)
+    out = {"distance": np.full(N, inf), "cell": np.full(N, -1, np.int32), "hit": np.full(N, -1, np.int32)}
+    if N == 0:
+        return out
+    shape = np.asarray(occ.shape, np.int64)
+    start, g = np.asarray(box.start, np.float64), np.float64(box.granularity)
+    s = np.float64(0.5) / g
+    limit2 = np.float64(max_distance) * np.float64(max_distance)
+    if all_cells:
+        lo, n = np.zeros((N, 3), np.int64), np.tile(shape, (N, 1))
+        n = np.where(WO.box_parts(b)[3][:, None], n, 0)
+    else:
+        lo, n = box_candidates(b, box, max_distance)
+    counts = n.prod(1)
+    ends = np.cumsum(counts)
+    flat = occ.reshape(-1)
+    for p0 in range(0, int(ends[-1]), _BODY_CHUNK_PAIRS):
+        pair = np.arange(p0, min(int(ends[-1]), p0 + _BODY_CHUNK_PAIRS), dtype=np.int64)
+        i = np.searchsorted(ends, pair, side="right")
+        j = pair - (ends[i] - counts[i])
+        nyz, nz = n[i, 1] * n[i, 2], n[i, 2]
+        ijk = np.stack([lo[i, 0] + j // nyz, lo[i, 1] + (j % nyz) // nz, lo[i, 2] + j % nz], 1)
+        cell = (ijk[:, 0] * shape[1] + ijk[:, 1]) * shape[2] + ijk[:, 2]
+        keep = flat[cell]
+        i, ijk, cell = i[keep], ijk[keep], cell[keep]
+        centre = start + (ijk.astype(np.float64) + 0.5) / g
+        keep = ~_cell_skip(b[i], centre, s, limit2)
+        i, cell, centre = i[keep], cell[keep], centre[keep]
+        d2, over = _box_cell_terms(b[i], centre, s)
+        np.minimum.at(hit, i[over], cell[over])
+        order = np.lexsort((cell, d2, i))                                          # per box: the smallest d2, then the lowest cell
+        i, cell, d2 = i[order], cell[order], d2[order]
+        head = np.r_[True, i[1:] != i[:-1]] if i.size else np.zeros(0, bool)
+        i, cell, d2 = i[head], cell[head], d2[head]
+        better = (d2 < best[i]) | ((d2 == best[i]) & (cell < arg[i]))
+        best[i[better]], arg[i[better]] = d2[better], cell[better]
+    with np.errstate(all="ignore"):
+        distance = np.sqrt(best)
+        ok = (best < inf) & (distance <= max_distance)
+    hit = np.where(hit == none, -1, hit)
+    out["distance"] = np.where(ok, distance, inf)
+    out["cell"] = np.where(hit >= 0, hit, np.where(ok, arg, -1)).astype(np.int32)
+    out["hit"] = hit.astype(np.int32)
+    return out
+
+
+def _clearance_boxes(boxes, dev, who):
+    from . import world as WO
+    b = boxes.detach() if isinstance(boxes, torch.Tensor) else torch.from_numpy(WO.check_boxes(boxes, who))
+    if b.dim() != 2 or b.shape[1] != 15:
+        raise ValueError(f"{who}: the box table is [N,15] (centre, R row-major, half extents), got {tuple(b.shape)}")
+    if b.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: N must be < 2^31")
+    return b.to(dev, torch.float64).contiguous()
+
+
+def box_cells_clearance(boxes, occupied, box, max_distance):
+    """the free function that dispatches, as box_cells does: -> {"distance" float64 [N], "cell" int32 [N], "hit" int32 [N]} by the
+    clearance rule.  A map on a HIP device goes through ngp_box_cells_clearance on the current stream and the results stay there; a
+    host map through box_cells_clearance_numpy (tensors come back for a tensor map, arrays for an array)."""
+    from . import world as WO
+    max_distance = WO.check_max_distance(max_distance, "box_cells_clearance")
+    if not (isinstance(occupied, torch.Tensor) and occupied.is_cuda):
+        host = occupied.detach().numpy() if isinstance(occupied, torch.Tensor) else occupied
+        out = box_cells_clearance_numpy(boxes, host, box, max_distance)
+        return {k: torch.from_numpy(v) for k, v in out.items()} if isinstance(occupied, torch.Tensor) else out
+    _check_map(occupied, "box_cells_clearance")
+    dev = occupied.device
+    m = occupied.detach()
+    m = (m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).to(torch.uint8)).contiguous()
+    grid = GridBox(box.start, box.granularity, tuple(m.shape))
+    WO.check_voxel_box(grid)
+    b = _clearance_boxes(boxes, dev, "box_cells_clearance")
+    N = b.shape[0]
+    out = {"distance": torch.empty(N, dtype=torch.float64, device=dev), "cell": torch.empty(N, dtype=torch.int32, device=dev),
+           "hit": torch.empty(N, dtype=torch.int32, device=dev)}
+    if N:
+        import ctypes
+        with torch.cuda.device(dev):
+            _lib.call("box_cells_clearance", m, ctypes.byref(WO._voxel_box_struct(grid, [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])), b, N,
+                      max_distance, out["distance"], out["cell"], out["hit"])
+    return out
+
+
+def trajectory_clearance(states, body, *, world=None, sdf=None, exact=False, max_distance):
+    """re-score recorded poses: interpolated drone states [n, 6] (xyz, rotation vector; body_boxes' other layouts too), body a BodyBox
+    -> the clearance rule's dict for the n body boxes, in one call: exact=False against the occupied cells of `sdf` (a
+    SignedDistanceField; on `world`'s device when that is a HIP world) -> {"distance", "cell", "hit"}; exact=True against `world`'s
+    triangles -> {"distance", "prim", "hit"}"""
+    if not isinstance(body, BodyBox):
+        raise ValueError(f"trajectory_clearance: body is a collision.BodyBox (got {type(body).__name__})")
+    boxes = body_boxes(states, body)
+    boxes = boxes.reshape(-1, 15)
+    if exact:
+        if world is None:
+            raise ValueError("trajectory_clearance: exact=True measures against the world's triangles and needs world= (a world.MeshWorld)")
+        return world.box_clearance(boxes, max_distance)
+    if not isinstance(sdf, SignedDistanceField):
+        raise ValueError("trajectory_clearance: sdf= is a collision.SignedDistanceField (or exact=True with world=)")
+    device = getattr(world, "device", None)
+    return sdf.box_clearance(boxes, max_distance, device=device if device is not None and device.type == "cuda" else None)
+
+
 SDF_WORLD = "world"
 
 
@@ -775,3 +963,16 @@ def check_body(body, exact, sdf, world, who):
     if sdf is None:
         raise ValueError(f"{who}: body= needs sdf= (a collision.SignedDistanceField or {SDF_WORLD!r}): the analytic stand-in has no map "
                          "of occupied cells, and no field for the centre's value")
+
+
+def check_clearance(clearance, body, who):
+    """the `clearance` keyword of the rollout entry points: None passes; otherwise a finite length > 0 (the cap D of the step's
+    value), which needs body= -> None or the float"""
+    if clearance is None:
+        return None
+    d = float(clearance)
+    if not (d > 0.0 and np.isfinite(d)):
+        raise ValueError(f"{who}: clearance is None or a finite length > 0 in metres (got {clearance!r})")
+    if body is None:
+        raise ValueError(f"{who}: clearance= measures the gap between the body and the obstacles and needs body= (a collision.BodyBox)")
+    return d

@@ -236,7 +236,7 @@ class RolloutSimulator:
 
     def __init__(self, model, intrinsics, H, W, steps, seed=0, render_kwargs=None, num_interpolated_points=4, renders_per_step=2,
                  planner_cfg=None, initial_plan=None, sdf=None, estimator_cfg=None, uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None,
-                 body=None, exact=False):
+                 body=None, exact=False, clearance=None):
         """planner_cfg: None (the hover stand-in) or planner_config()'s dict: the reference's planner steers the drone.
         initial_plan: the plan after reset when the caller has computed it already (run_rollout: once per rollout).
         sdf: None (the analytic stand-in, scene_collision), a collision.SignedDistanceField the collision check looks up, or "world":
@@ -255,12 +255,19 @@ class RolloutSimulator:
         step's interpolated poses, by world.py's body rule -- exact=False against the occupied cells of `sdf` (any field: a NeRF-density
         one or sdf="world"), exact=True against the triangles of `world` (needs world=).  Columns 14 and 15:18 stay the centre's field
         value and position; self.body_hits keeps, per step, the `cell` (or `prim`) of each interpolated pose (int32 [n_interp], -1:
-        free).  The analytic stand-in (sdf=None) has no map: a body with it is a ValueError."""
+        free).  The analytic stand-in (sdf=None) has no map: a body with it is a ValueError.
+        clearance: None (column 14 stays the centre's field value; nothing new launched), or a finite length D > 0 in metres (needs
+        body=): the step's n_interp boxes go through ONE clearance call (world.py's clearance rule; against the same geometry as the
+        verdict) in the place of the overlap call.  The verdict is its `hit`, so the collided column is what body= alone gives; column
+        14 -- and through it the Cross Entropy Method's adjusted value and risk -- is the smallest min(distance, D) over the poses the
+        walk visits (up to and including the first hit): 0.0 on a collision, D in open space.  self.body_clearance keeps, per step,
+        the distances of the interpolated poses (float64 [n_interp], +inf beyond D)."""
         self.world, self.world_image = world, None
-        from .collision import check_body, resolve_sdf
+        from .collision import check_body, check_clearance, resolve_sdf
         sdf = resolve_sdf(sdf, world, "RolloutSimulator")
         check_body(body, exact, sdf, world, "RolloutSimulator")
         self.body, self.exact, self.body_hits = body, bool(exact), []
+        self.clearance, self.body_clearance = check_clearance(clearance, body, "RolloutSimulator"), []
         if uq_method not in (UQ_GAUSSIAN, UQ_LAPLACE):
             raise ValueError(f"Unrecognized uncertainty quantification method {uq_method}")
         self.uq_method, self.uq_kwargs, self.last_trace = uq_method, dict(uq_kwargs or {}), None
@@ -412,6 +419,19 @@ class RolloutSimulator:
             hits = self.sdf.box_overlap(boxes, device=device if device is not None and device.type == "cuda" else None)
         return np.asarray(hits.cpu().numpy() if isinstance(hits, torch.Tensor) else hits, np.int32)
 
+    def measure_body(self, states):
+        """the body's clearance at interpolated states [n, 6] (xyz, rotation vector), capped at self.clearance -> {"distance" float64
+        [n] (0 on a hit, +inf beyond the cap), "hit" int32 [n]: judge_body's answer} numpy; one call, on the simulator's device"""
+        from .collision import body_boxes
+        boxes = body_boxes(states, self.body)
+        if self.exact:
+            out = self.world.box_clearance(boxes, self.clearance)
+        else:
+            device = self.device if self.device is not None else getattr(self.world, "device", None)
+            out = self.sdf.box_clearance(boxes, self.clearance, device=device if device is not None and device.type == "cuda" else None)
+        host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else a                          # noqa: E731
+        return {"distance": np.asarray(host(out["distance"]), np.float64), "hit": np.asarray(host(out["hit"]), np.int32)}
+
     def collision(self, xyz):
         """-> (collided, value): the SDF lookup (value None: outside the field, keep the previous value) or the analytic stand-in"""
         if self.sdf is not None:
@@ -449,7 +469,7 @@ class RolloutSimulator:
         self.reset_estimator(sim, state)
         history = [state.numpy().astype(np.float64)]
         rows = []
-        self.poses, self.actions, self.body_hits = [], [], []
+        self.poses, self.actions, self.body_hits, self.body_clearance = [], [], [], []
         for k in range(self.steps):
             noise = self.draw_noise(sim, k)
             action = self.action(k, state)
@@ -465,10 +485,15 @@ class RolloutSimulator:
             x = np.arange(hist.shape[0])
             xn = np.linspace(0, hist.shape[0] - 1, hist.shape[0] * self.n_interp)
             interp = np.stack([np.interp(xn, x, hist[:, i]) for i in range(3)], -1)[-self.n_interp:]
-            hits = None
+            hits, gaps, gap = None, None, self.clearance
             if self.body is not None:                          # the same np.interp rule on the rotation vector: one judgement of all poses
                 turn = np.stack([np.interp(xn, x, hist[:, i]) for i in range(6, 9)], -1)[-self.n_interp:]
-                hits = self.judge_body(np.concatenate([interp, turn], -1))
+                if self.clearance is None:
+                    hits = self.judge_body(np.concatenate([interp, turn], -1))
+                else:                                          # one clearance call in the overlap call's place: its hit is the verdict
+                    measured = self.measure_body(np.concatenate([interp, turn], -1))
+                    hits, gaps = measured["hit"], measured["distance"]
+                    self.body_clearance.append(gaps)
                 self.body_hits.append(hits)
             collided, value, where = False, 9999.0, interp[-1]
             for i, p in enumerate(interp):
@@ -477,9 +502,13 @@ class RolloutSimulator:
                     value = v
                 if hits is not None:                           # the body's verdict; value and position stay the centre's
                     collided = bool(hits[i] >= 0)
+                if gaps is not None:                           # the body's gap at the poses the walk visits, capped
+                    gap = min(gap, float(min(gaps[i], self.clearance)))
                 where = p
                 if collided:
                     break
+            if gaps is not None:
+                value = gap
             rows.append(self.write_row(sim, k, noise, value, where, sigma_d, collided))
             if collided:
                 break
@@ -529,7 +558,7 @@ def gather_rows(results, n_simulations, steps, width, world_size=1, group=None, 
 
 def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, world_size=1, group=None, in_flight=3,
                 render_kwargs=None, autocast=True, gather=True, renders_per_step=2, planner_cfg=None, sdf=None, estimator_cfg=None,
-                uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None, body=None, exact=False):
+                uq_method=UQ_GAUSSIAN, uq_kwargs=None, world=None, body=None, exact=False, clearance=None):
     """Monte-Carlo rollout sharded over ranks.  Returns (rows [total, ROW_WIDTH] float64 in simulation order -- every rank's when
     `gather`, else this rank's -- and a dict of this rank's counters).  planner_cfg: None, or planner_config()'s dict (the
     reference's planner steers every simulation; its initial plan is computed once here).  sdf: None (the analytic stand-in) or
@@ -539,10 +568,13 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     uq_method / uq_kwargs: RolloutSimulator's (the default is the Gaussian approximation, rows unchanged).  world: None, or the
     world.MeshWorld every simulation's sensor looks at (RolloutSimulator's `world`; shared, read-only).  body / exact: None (the
     centre point's verdict, the rows as they always were) or the collision.BodyBox every simulation's collisions are judged with
-    (RolloutSimulator's `body`: against sdf's occupied cells, or with exact=True against world's triangles)."""
-    from .collision import check_body, resolve_sdf
+    (RolloutSimulator's `body`: against sdf's occupied cells, or with exact=True against world's triangles).  clearance: None, or
+    a finite length D > 0 (needs body=): column 14 is the body's gap to the nearest obstacle, capped at D (RolloutSimulator's
+    `clearance`), not the centre's field value."""
+    from .collision import check_body, check_clearance, resolve_sdf
     sdf = resolve_sdf(sdf, world, "run_rollout")
     check_body(body, exact, sdf, world, "run_rollout")
+    check_clearance(clearance, body, "run_rollout")
     device = next(model.parameters()).device
     lo, hi = shard_range(n_simulations, rank, world_size)
     sims = list(range(lo, hi))
@@ -552,7 +584,8 @@ def run_rollout(model, intrinsics, H, W, n_simulations, steps, seed=0, rank=0, w
     def one(sim):
         sim_obj = RolloutSimulator(model, intrinsics, H, W, steps, seed=seed, render_kwargs=render_kwargs, renders_per_step=renders_per_step,
                                    planner_cfg=planner_cfg, initial_plan=plan0, sdf=sdf, estimator_cfg=estimator_cfg,
-                                   uq_method=uq_method, uq_kwargs=uq_kwargs, world=world, body=body, exact=exact)
+                                   uq_method=uq_method, uq_kwargs=uq_kwargs, world=world, body=body, exact=exact,
+                                   clearance=clearance)
         with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
             rows = sim_obj.run(sim)
         return rows, sim_obj.frames
@@ -576,7 +609,8 @@ def run_validation(stress_test, *args, simulator=SIM_NERF, **kwargs):
     is envConfig.json's key of that name: 'NerfSimulator' (the default: the NeRF is its own world) or 'BlenderSimulator' (the sensor
     looks at the true world: needs world=, a world.MeshWorld); anything else is an error.  With world=, sdf="world" judges the
     collisions of either loop against the mesh's own field, not against the NeRF's; body= (a collision.BodyBox) judges them for the
-    drone's body box instead of its centre point (exact=True: against the mesh's triangles)."""
+    drone's body box instead of its centre point (exact=True: against the mesh's triangles), and clearance=D scores them with the
+    body's gap to the nearest obstacle instead of the centre's field value."""
     if simulator not in (SIM_NERF, SIM_BLENDER):
         raise ValueError(f"Unrecognized simulator {simulator}")
     if simulator == SIM_BLENDER and kwargs.get("world") is None:

@@ -12,8 +12,8 @@ nerf.utils.get_rays (so a world frame and a NeRF frame of one pose are pixel-ali
 A mesh on a HIP device goes through csrc/raycast.hip (a uniform grid, one lane per ray) on the current stream; a CPU tensor or a numpy
 array through numpy: brute force over all triangles, chunked -- the package's CPU implementation, as mesh.isosurface has one.
 
-This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip, csrc/closest.hip, csrc/body.hip
-and DESIGN.md point here, and a change to a rule is made in this text, in the numpy path and in the kernel.
+This docstring is the specification of every rule below; csrc/raycast.hip, csrc/overlay.hip, csrc/voxelize.hip, csrc/closest.hip, csrc/body.hip,
+csrc/clearance.hip and DESIGN.md point here, and a change to a rule is made in this text, in the numpy path and in the kernel.
 
 The hit rule; both paths implement it in float32 with one rounding per operation, so they agree bit for bit:
     per triangle v0, e1 = v1 - v0, e2 = v2 - v0;  p = d x e2, det = e1 . p, reject det == 0, inv = 1 / det, s = o - v0,
@@ -116,6 +116,72 @@ The body rule (written here once; box_tri_overlap / collision.box_cell_overlap a
         lookup has it.  lookup's wrap of a negative index (numpy's indexing) is NOT reproduced here.
         Candidates: any superset; both paths take, per axis, the cells floor((c_a - E_a - start_a) g) - 1 .. floor((c_a + E_a -
         start_a) g) + 1 clipped to the map; collision.box_cells_numpy(all_cells=True) tests every cell, and gives the same result.
+
+The verdict says whether the body touches; a stress test that adapts -- the Cross Entropy Method's risk -- wants to know HOW NEAR it came
+(DESIGN.md "Body clearance"): the gap between the body box and the nearest obstacle, continuous in the pose, zero exactly when the
+verdict says collision, measured on the verdict's geometry.  Opt-in (clearance= on the simulators):
+
+        .box_clearance(boxes, max_distance=inf, rot=PLANNER_ROT)       -> {"distance" float64 [N], "prim" int32 [N], "hit" int32 [N]}
+    box_clearance_numpy(boxes, vertices_world, faces, max_distance)    -> the same, numpy: brute force over all (box, face) pairs
+    box_tri_distance2(boxes, tri)                                      -> the rule's squared distance per (box, face) pair
+    collision.box_cells_clearance(boxes, occupied, box, max_distance)  -> {"distance", "cell", "hit"}; box_cells_clearance_numpy is its
+                                                                          numpy path, collision.box_cell_distance2 the pair's d2
+    collision.trajectory_clearance(states, body, world= / sdf=, ...)   -> the same for recorded drone states [n, 6]
+
+A HIP world / a map on a HIP device goes through csrc/clearance.hip (one wave per box) on the current stream, anything else through the
+numpy paths; the two agree bit for bit.
+
+The clearance rule (written here once; box_tri_distance2 / collision.box_cell_distance2 and csrc/clearance.hip implement it):
+    The body rule's box table, frame and arithmetic: float64, one IEEE rounding per operation, correctly rounded / and sqrt, no
+    contraction, a . b = (a_0 b_0 + a_1 b_1) + a_2 b_2.  Everything happens in the box's frame (x' = R^T (x - c), as above), where the
+    box is the axis-aligned [-h, h].  Per pair a squared distance d2: the smallest of a fixed list of candidates, starting from
+    +inf, a candidate replacing the best so far only when strictly smaller -- so a NaN never replaces, and the order of the
+    candidates decides nothing.  clamp01(x): x = 0 unless x >= 0, then x = 1 unless x <= 1 (a NaN becomes 0).
+    A point against the box, gap2(x, h):  g_a = |x_a| - h_a where that is > 0, else 0;  d2 = (g_0^2 + g_1^2) + g_2^2.
+    A box edge against a segment, edge2(a, sb, sc; q0, q1): the box edge along axis a through (sb h_b, sc h_c) (b = a + 1, c = a + 2
+        mod 3; sb, sc = -1 or +1) is p1 + s L u_a, 0 <= s <= 1, with p1_a = -h_a, p1_b = sb h_b, p1_c = sc h_c, L = h_a + h_a; the
+        segment is q0 + t w, w = q1 - q0.  The clamped closed form, with the box edge's dots reduced to their one non-zero term:
+            r = p1 - q0;  A = L L,  e = w . w,  f = w . r,  c = L r_a,  b = L w_a,  den = A e - b b
+            s0 = clamp01((b f - c e) / den) when den > 0, else 0            (parallel or degenerate: any s is as near; 0 is taken)
+            t0 = (b s0 + f) / e;   low = (e == 0) or not (t0 >= 0);   high = not low and t0 > 1
+            t  = 0 when low, 1 when high, else t0                           (e == 0: the segment is a point, t = 0; a NaN t0 is low)
+            s  = s0 when neither, else 0 when A == 0, else clamp01((-c when low, b - c when high) / A)       (A == 0: the edge is a point)
+            d_a = (p1_a + L s) - (q0_a + w_a t),  d_b = p1_b - (q0_b + w_b t),  d_c likewise;  d2 = (d_0^2 + d_1^2) + d_2^2
+        The twelve box edges: a = 0, 1, 2 and (sb, sc) = (-, -), (+, -), (-, +), (+, +).
+    Box against a triangle, on the body rule's v_k' (the exact float32 vertices taken to float64, in the box's frame):
+        d2 = 0 if the body rule's closed 13-axis test says overlap.  Otherwise the smallest of 47 candidates:
+            1. the 3 vertices against the box: gap2(v_k', h)
+            2. the 8 box corners (+-h_0, +-h_1, +-h_2) against the triangle, by the closest-point rule's d2 (interior candidate, then
+               the three segments; closest_terms in float64, defined for zero-area faces), with the v_k' as its vertices
+            3. the 3 triangle edges v0' -> v1', v1' -> v2', v2' -> v0' against the 12 box edges: edge2
+        Two disjoint convex bodies are nearest at a vertex-face or an edge-edge pair -- an edge-face or face-face contact holds
+        one of those -- so the candidates are complete; penetration is the overlap test's case (no depth: an overlapping body is 0).
+    Box against a map's cell (the body rule's cell: centre m, half-width s = 0.5 / g, axes the world's):
+        d2 = 0 if the body rule's closed 15-axis test says overlap.  Otherwise the smallest of 160 candidates:
+            1. the 8 cell corners x = m + (+-s, +-s, +-s) against the box: gap2(x', h)
+            2. the 8 box corners against the cell: y_i = (c_i + ((R_i0 o_0 + R_i1 o_1) + R_i2 o_2)) - m_i with o_a = +-h_a;
+               gap2(y, (s, s, s))
+            3. the 12 cell edges -- along world axis i from x0 to x1, x0_i = m_i - s, x1_i = m_i + s, the other two coordinates
+               m_j +- s, m_k +- s -- as segments x0' -> x1' against the 12 box edges: edge2
+    Per box:
+        hit  = the lowest index of a candidate that overlaps, or -1: box_overlap's prim / box_cells' cell -- the same test function.
+        d2   = the smallest over the box's candidates; an equal d2 goes to the lowest index, and where hit >= 0 the index is hit.
+        distance = sqrt(d2), accepted iff distance <= max_distance (+inf is allowed; NaN or a value <= 0 is a ValueError).
+        A box with no accepted candidate, or an invalid row (a non-finite entry, a negative half extent): distance = +inf, prim (cell)
+        = hit = -1.  Cells outside the array do not exist.
+    Candidates: any superset; no result depends on them.  csrc/clearance.hip takes body.hip's ranges with E_a + max_distance in E_a's
+        place: for the mesh the grid cells reached by c_a -+ (E_a + max_distance) after the same outward rounding, growth and cell
+        arithmetic (a triangle within max_distance of the box has a point within max_distance of the box's bounds on every axis); for a
+        map the cells floor((c_a -+ (E_a + max_distance) - start_a) g) -+ 1, clipped.
+        The skip.  A pair may be left out when the gap between its bounds and the box proves that it can neither win, nor tie, nor be
+        accepted: with lo_a .. hi_a the bounds of the triangle's v_k' (of the cell: t_a -+ s ((A_0a + A_1a) + A_2a)) in the box's frame,
+        lb2 = gap2-style (max(lo_a - h_a, -h_a - hi_a, 0) per axis), m = sum_a (max(|lo_a|, |hi_a|) + h_a) and `bound` the smaller of
+        max_distance^2 and any d2 found so far for the box, the pair is skipped iff lb2 > bound + 2^-40 (bound + m^2).  Every
+        candidate is the squared distance of a point of the box and a point of the triangle (cell) computed with a few roundings of
+        coordinates no larger than m, so it is at least lb2 less 2^-47 (d2 + m^2): the margin is 2^7 times the rounding.  Every
+        min and max of the bounds (and of the closest-point rule's box2) is numpy's: a NaN operand is the result, in the kernels too
+        (not fmin / fmax, which drop it), so a NaN coordinate reaches the comparison, fails it, and never skips.  An overlapping pair has lb2 within that rounding of 0 and is never skipped.  The numpy paths skip on
+        max_distance^2 only (brute force otherwise), the kernels on both; all_cells=True tests every cell of the map.
 
 The world can also be drawn with analytic primitives in it -- the replay's failure view (replay.failure_view; DESIGN.md "Failure
 replay"), in the place of the Blender scene of validation/utils/viz_failures_blend.py:
@@ -357,13 +423,11 @@ def cast_numpy(o, d, tri_data, t_min=0.0, t_max=np.inf):
     return out
 
 
-def closest_terms(p, tri, dtype=_f32):
-    """the closest-point rule's d2 and closest point for every (point, triangle) before acceptance: p [R,3], tri [F,3,3] (the exact
-    vertices) -> (d2 [R,F] (+inf: no candidate), point 3 x [R,F]) of `dtype` (float32: the rule itself; float64: the same formulas,
-    for error measurements)"""
-    p, T = np.asarray(p, dtype), np.asarray(tri, dtype)
-    pc = [p[:, None, k] for k in range(3)]
-    v0, v1, v2 = [[T[None, :, j, k] for k in range(3)] for j in range(3)]
+def closest_pair_terms(pc, v0, v1, v2, dtype=_f32, want_point=True):
+    """the closest-point rule's candidates for operands that broadcast against each other: pc, v0, v1, v2 lists of three arrays of
+    `dtype` (the point, the exact vertices) -> (d2 (+inf: no candidate), point: three arrays, or None without want_point).  The one
+    copy of the rule's arithmetic: closest_terms evaluates it on all (point, triangle) pairs in float32, the clearance rule per
+    (corner, triangle) pair in float64."""
     inf, zero, one = dtype(np.inf), dtype(0), dtype(1)
     with np.errstate(all="ignore"):
         e1, e2 = [v1[k] - v0[k] for k in range(3)], [v2[k] - v0[k] for k in range(3)]
@@ -376,8 +440,10 @@ def closest_terms(p, tri, dtype=_f32):
              for k in range(3)]
         box2, plane2 = _dot(g, g), (sn * sn) / nn
         d2 = np.where(inside, np.where(plane2 >= box2, plane2, box2), inf)
-        w = sn / nn
-        point = [np.where(inside, pc[k] - w * n[k], zero) for k in range(3)]
+        point = None
+        if want_point:
+            w = sn / nn
+            point = [np.where(inside, pc[k] - w * n[k], zero) for k in range(3)]
         s1 = [pc[k] - v1[k] for k in range(3)]
         e12 = [v2[k] - v1[k] for k in range(3)]
         for ap, a, ab, end in ((s, v0, e1, v1), (s, v0, e2, v2), (s1, v1, e12, v2)):
@@ -389,7 +455,19 @@ def closest_terms(p, tri, dtype=_f32):
             sd = _dot(r, r)
             take = sd < d2
             d2 = np.where(take, sd, d2)
-            point = [np.where(take, np.where(t == one, end[k], a[k] + t * ab[k]), point[k]) for k in range(3)]
+            if want_point:
+                point = [np.where(take, np.where(t == one, end[k], a[k] + t * ab[k]), point[k]) for k in range(3)]
+    return d2, point
+
+
+def closest_terms(p, tri, dtype=_f32):
+    """the closest-point rule's d2 and closest point for every (point, triangle) before acceptance: p [R,3], tri [F,3,3] (the exact
+    vertices) -> (d2 [R,F] (+inf: no candidate), point 3 x [R,F]) of `dtype` (float32: the rule itself; float64: the same formulas,
+    for error measurements)"""
+    p, T = np.asarray(p, dtype), np.asarray(tri, dtype)
+    pc = [p[:, None, k] for k in range(3)]
+    v0, v1, v2 = [[T[None, :, j, k] for k in range(3)] for j in range(3)]
+    d2, point = closest_pair_terms(pc, v0, v1, v2, dtype)
     return d2.astype(dtype), [c.astype(dtype) for c in point]
 
 
@@ -816,6 +894,166 @@ def box_overlap_numpy(boxes, vertices_world, faces):
     return {"prim": prim}
 
 
+# ------------------------------------------------------------------------------------------------------ the clearance (numpy)
+CLEARANCE_SKIP = 2.0 ** -40                         # the margin of the clearance rule's lower-bound skip (the docstring's "Candidates")
+
+
+def _clamp01(x):
+    x = np.where(x >= 0, x, 0.0)
+    return np.where(x <= 1, x, 1.0)
+
+
+def _take_smaller(best, cand):
+    return np.where(cand < best, cand, best)
+
+
+def check_max_distance(max_distance, who):
+    """the clearance rule's max_distance as a float: +inf is allowed, NaN or a value <= 0 is a ValueError"""
+    d = float(max_distance)
+    if not d > 0.0:
+        raise ValueError(f"{who}: max_distance is a length > 0 or +inf (got {max_distance!r})")
+    return d
+
+
+def clamp_gap2(x, h):
+    """the clearance rule's point-box candidate: x three [M] arrays (box frame), h three [M] half extents (arrays or scalars) ->
+    (g_0^2 + g_1^2) + g_2^2, g_a = |x_a| - h_a where that is > 0, else 0"""
+    g = []
+    for a in range(3):
+        d = np.abs(x[a]) - h[a]
+        g.append(np.where(d > 0, d, 0.0))
+    return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
+
+
+def point_tri_d2(pc, v0, v1, v2):
+    """the closest-point rule's d2 (closest_pair_terms, float64) for M (point, triangle) PAIRS: four lists of three [M] arrays"""
+    return closest_pair_terms(pc, v0, v1, v2, np.float64, want_point=False)[0]
+
+
+def box_edge_segment_d2(h, a, sb, sc, q0, w):
+    """the clearance rule's segment-segment candidate, in the box's frame: the box edge along axis a through (sb h_b, sc h_c) (b, c =
+    a + 1, a + 2 mod 3; sb, sc = -1.0 or 1.0) against the segment q0 + t w, 0 <= t <= 1.  h, q0, w: three [M] arrays each -> d2 [M]"""
+    b_, c_ = (a + 1) % 3, (a + 2) % 3
+    p1 = [None] * 3
+    p1[a], p1[b_], p1[c_] = -h[a], sb * h[b_], sc * h[c_]
+    L = h[a] + h[a]
+    r = [p1[k] - q0[k] for k in range(3)]
+    A, e, f = L * L, _dot(w, w), _dot(w, r)
+    c, b = L * r[a], L * w[a]
+    den = A * e - b * b
+    s0 = np.where(den > 0, _clamp01((b * f - c * e) / den), 0.0)
+    t0 = (b * s0 + f) / e
+    low = (e == 0) | ~(t0 >= 0)
+    high = ~low & (t0 > 1)
+    t = np.where(low, 0.0, np.where(high, 1.0, t0))
+    s1 = np.where(A == 0, 0.0, _clamp01(np.where(low, -c, b - c) / A))
+    s = np.where(low | high, s1, s0)
+    d = [None] * 3
+    d[a] = (p1[a] + L * s) - (q0[a] + w[a] * t)
+    d[b_] = p1[b_] - (q0[b_] + w[b_] * t)
+    d[c_] = p1[c_] - (q0[c_] + w[c_] * t)
+    return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+
+
+def box_edges_segment_d2(h, q0, w, best):
+    """`best` lowered by the twelve box edges (axis a = 0, 1, 2; then (sb, sc) = (-,-), (+,-), (-,+), (+,+)) against one segment"""
+    for a in range(3):
+        for m in range(4):
+            best = _take_smaller(best, box_edge_segment_d2(h, a, 1.0 if m & 1 else -1.0, 1.0 if m & 2 else -1.0, q0, w))
+    return best
+
+
+def frame_gap2(lo, hi, h):
+    """the lower bound of the clearance rule's skip: the squared gap between the bounds lo_a..hi_a (box frame, three [M] arrays each)
+    and the box, and the scale m = sum_a (max(|lo_a|, |hi_a|) + h_a) its margin is taken from -> (lb2 [M], m [M])"""
+    g, m = [], 0.0
+    for a in range(3):
+        g.append(np.maximum(np.maximum(lo[a] - h[a], -h[a] - hi[a]), 0.0))
+        m = m + (np.maximum(np.abs(lo[a]), np.abs(hi[a])) + h[a])
+    return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2], m
+
+
+def _box_tri_terms(boxes, tri):
+    """-> (d2 float64 [M] by the clearance rule, +inf for an invalid row; overlap bool [M] by the body rule)"""
+    inf = np.float64(np.inf)
+    with np.errstate(all="ignore"):
+        c, R, h, valid = box_parts(boxes)
+        over = box_tri_overlap(boxes, tri)
+        hh = [h[:, a] for a in range(3)]
+        p = [box_frame(c, R, tri[:, k]) for k in range(3)]                                              # p[vertex][axis]
+        best = np.full(boxes.shape[0], inf)
+        for k in range(3):                                                                              # 1. the vertices against the box
+            best = _take_smaller(best, clamp_gap2(p[k], hh))
+        for m in range(8):                                                                              # 2. the corners against the triangle
+            corner = [hh[a] if (m >> a) & 1 else -hh[a] for a in range(3)]
+            best = _take_smaller(best, point_tri_d2(corner, p[0], p[1], p[2]))
+        for j in range(3):                                                                              # 3. the edges against the edges
+            q0, q1 = p[j], p[(j + 1) % 3]
+            best = box_edges_segment_d2(hh, q0, [q1[a] - q0[a] for a in range(3)], best)
+    return np.where(valid, np.where(over, 0.0, best), inf), over & valid
+
+
+def box_tri_distance2(boxes, tri):
+    """the clearance rule's squared distance for M (box, face) pairs: boxes float64 [M,15], tri float64 [M, vertex, axis] (world) ->
+    float64 [M]: 0 where the body rule says overlap, else the smallest of the 47 candidates; +inf for an invalid row"""
+    return _box_tri_terms(np.ascontiguousarray(boxes, np.float64), np.asarray(tri, np.float64))[0]
+
+
+def _clearance_result(d2, over, index, max_distance):
+    """per box from its pairs: d2, over [n, C], index int64 [n, C] or [C] the candidates' indices in ascending order along C ->
+    the rule's per-box result (distance, index, hit)"""
+    n = d2.shape[0]
+    index = np.broadcast_to(index, d2.shape)
+    rows = np.arange(n)
+    if d2.shape[1] == 0:
+        return np.full(n, np.inf), np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    best = d2.min(1)
+    first = np.argmax(d2 == best[:, None], 1)
+    hit = np.where(over.any(1), index[rows, np.argmax(over, 1)], -1)
+    with np.errstate(all="ignore"):
+        distance = np.sqrt(best)
+        ok = (best < np.inf) & (distance <= max_distance)
+    prim = np.where(hit >= 0, hit, np.where(ok, index[rows, first], -1))
+    return np.where(ok, distance, np.inf), prim.astype(np.int32), hit.astype(np.int32)
+
+
+def box_clearance_numpy(boxes, vertices_world, faces, max_distance=np.inf):
+    """the clearance rule against a mesh in numpy, brute force over all (box, face) pairs, chunked: boxes float64 [N,15],
+    vertices_world float32 [V,3] (the world frame), faces integer [F,3] -> {"distance" float64 [N] (+inf: nothing within
+    max_distance), "prim" int32 [N] (-1), "hit" int32 [N]: box_overlap_numpy's prim}.  The only pairs left out are those the rule's
+    lower-bound skip proves beyond max_distance."""
+    max_distance = check_max_distance(max_distance, "box_clearance_numpy")
+    b = check_boxes(boxes, "box_clearance_numpy")
+    vw = np.ascontiguousarray(vertices_world, _f32).reshape(-1, 3)
+    fc = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    N, F = b.shape[0], fc.shape[0]
+    out = {"distance": np.full(N, np.inf), "prim": np.full(N, -1, np.int32), "hit": np.full(N, -1, np.int32)}
+    if N == 0 or F == 0:
+        return out
+    tri = vw[fc].astype(np.float64)
+    limit2 = np.float64(max_distance) * np.float64(max_distance)
+    chunk = max(1, _BODY_CHUNK_PAIRS // F)
+    for i0 in range(0, N, chunk):
+        part = b[i0:i0 + chunk]
+        c, R, h, valid = box_parts(part)
+        with np.errstate(all="ignore"):
+            d = [[tri[None, :, k, j] - c[:, None, j] for j in range(3)] for k in range(3)]
+            lo, hi = [], []
+            for a in range(3):
+                p = [(R[:, None, 0, a] * d[k][0] + R[:, None, 1, a] * d[k][1]) + R[:, None, 2, a] * d[k][2] for k in range(3)]
+                lo.append(np.minimum(p[0], np.minimum(p[1], p[2])))
+                hi.append(np.maximum(p[0], np.maximum(p[1], p[2])))
+            lb2, m = frame_gap2(lo, hi, [h[:, None, a] for a in range(3)])
+            keep = valid[:, None] & ~(lb2 > limit2 + CLEARANCE_SKIP * (limit2 + m * m))
+        bi, fi = np.nonzero(keep)
+        d2 = np.full(keep.shape, np.inf)
+        over = np.zeros(keep.shape, dtype=bool)
+        d2[bi, fi], over[bi, fi] = _box_tri_terms(part[bi], tri[fi])
+        sl = slice(i0, i0 + part.shape[0])
+        out["distance"][sl], out["prim"][sl], out["hit"][sl] = _clearance_result(d2, over, np.arange(F), max_distance)
+    return out
+
+
 def _voxel_box_struct(box, rot):
     axis, sign = signed_permutation(rot)
     b = _lib.VoxelBox()
@@ -947,6 +1185,36 @@ class MeshWorld:
                 _lib.call("box_mesh_overlap", b, N, ctypes.byref(self._grid_c), self.cell_start, self.pair_tri, self.pairs, self.tri_verts,
                           self.n_faces, ctypes.cast(axis_c, ctypes.c_void_p), ctypes.cast(sign_c, ctypes.c_void_p), prim)
         return {"prim": prim}
+
+    def box_clearance(self, boxes, max_distance=float("inf"), rot=PLANNER_ROT):
+        """boxes float64 [N,15] (box_overlap's table) -> {"distance" float64 [N], "prim" int32 [N], "hit" int32 [N]} by the module's
+        clearance rule: the distance from each box to the nearest triangle (0 where they overlap, +inf where none lies within
+        max_distance), the lowest index among the nearest (-1) and box_overlap's prim.  max_distance: a length > 0 or +inf
+        (ValueError otherwise).  Tensors on the world's device (numpy arrays for numpy boxes on a CPU world).  A HIP world runs
+        csrc/clearance.hip on the current stream (one launch, no host read); a CPU world box_clearance_numpy."""
+        tensors = isinstance(boxes, torch.Tensor)
+        max_distance = check_max_distance(max_distance, "MeshWorld.box_clearance")
+        axis, sign = signed_permutation(rot)
+        if self.device.type != "cuda":
+            out = box_clearance_numpy(check_boxes(boxes, "MeshWorld.box_clearance"), vertices_to_world(self.vertices.numpy(), rot), self.faces.numpy(),
+                                      max_distance)
+            return {k: torch.from_numpy(v) for k, v in out.items()} if tensors else out
+        b = boxes.detach() if tensors else torch.from_numpy(check_boxes(boxes, "MeshWorld.box_clearance"))
+        if b.dim() != 2 or b.shape[1] != 15:
+            raise ValueError(f"MeshWorld.box_clearance: the box table is [N,15] (centre, R row-major, half extents), got {tuple(b.shape)}")
+        b = b.to(self.device, torch.float64).contiguous()
+        N = b.shape[0]
+        if N >= 2 ** 31:
+            raise ValueError("MeshWorld.box_clearance: N must be < 2^31")
+        out = {"distance": torch.empty(N, dtype=torch.float64, device=self.device), "prim": torch.empty(N, dtype=torch.int32, device=self.device),
+               "hit": torch.empty(N, dtype=torch.int32, device=self.device)}
+        if N:
+            axis_c, sign_c = (ctypes.c_int32 * 3)(*[int(a) for a in axis]), (ctypes.c_int32 * 3)(*[int(s) for s in sign])
+            with torch.cuda.device(self.device):
+                _lib.call("box_mesh_clearance", b, N, ctypes.byref(self._grid_c), self.cell_start, self.pair_tri, self.pairs, self.tri_verts,
+                          self.n_faces, ctypes.cast(axis_c, ctypes.c_void_p), ctypes.cast(sign_c, ctypes.c_void_p), max_distance,
+                          out["distance"], out["prim"], out["hit"])
+        return out
 
     # ---- the closest point of the surface
     def closest(self, points, max_distance=float("inf"), coherent=None, tested=False):
